@@ -7,10 +7,13 @@ in an HBM bank larger than the Infinity Cache) -> 2-ear FFT convolution with the
 (reference: soundspaces/simulator.py:608-701 + soundspaces/tasks/nav.py:86-100, cache-miss path).
 Workload = BASELINE.json's metric shape: 128 envs, 16 kHz, 1-s clips, 2-channel RIRs of 1 s.
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
       N>1 without a torch.distributed environment: bench.py re-launches itself as N ranks (python -m
       torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1, one rank per GPU over RCCL - the
       reference's own launcher shape, ss_baselines/av_nav/single_node.sh:8-11); under torchrun it checks WORLD_SIZE == N.
+      --dump-outputs DIR: after the timed steps, the arrays the last timed step wrote (spectrogram, and audiogoal / logmel /
+      gccphat where the step writes them) as DIR/<name>.npy, float32; inputs are seeded, so the same arguments give the same
+      inputs in every run.  A plain run does only the headline; --full adds everything listed below.
 
 `value` (round 6) is the DEPENDENT-step figure: one env group; per step ss_ctx_observe renders into
 rollouts.observations['spectrogram'][step + 1], a one-workgroup kernel on the caller's stream consumes those rows (the policy's
@@ -21,14 +24,18 @@ waits for every step.
 
 N>1: every rank renders its own 128 envs (weak scaling, units are independent; --scaling strong splits 128 envs over the
 ranks, BASELINE configs[3]), each rank's consumer reads its own slab (DD-PPO) and the per-rank spectrogram slabs are all-gathered
-over RCCL on a side stream (the exchange step BASELINE.json names) in chunks of --gather-every steps; the same run also times
-`exchange_none` (no collective: the reference's arrangement), `allgather`, `gather` (peer copies to one learner) and the per-step
-gather and reports them beside the headline.  Rank 0 prints ONE JSON line.
+over RCCL on a side stream (the exchange step BASELINE.json names) in chunks of --gather-every steps; with --full the same run
+also times `exchange_none` (no collective: the reference's arrangement), `allgather`, `gather` (peer copies to one learner) and
+the per-step gather and reports them beside the headline.  Rank 0 prints ONE JSON line.
 
-The line also carries, measured in the same run: per-step GPU time distribution (HIP events per step), the convolution
+A plain run: set-up, spin-up + warm-up, the timed steps, --dump-outputs, the line (headline fields and `config`).  With --full
+the line also carries, measured in the same run: `pipelined`, `dependent.*`, `preplanned_single_stream`, `ctx_single_stream`,
+`sustained`, `host_us_per_call`, the rooflines, per-step GPU time distribution (HIP events per step), the convolution
 kernel alone on both bank forms (`roofline_conv_only`, `roofline_conv_only_spectral`: the figure BASELINE's >= 40 % target is
 defined on), the other RIR-bank format, the PLUGIN PATH (simulator state -> planning -> descriptor upload -> launch -> rollout
-rows, all inside the timed region) and the CPU oracle on the host cores this process may use.
+rows, all inside the timed region) and the CPU oracle on the host cores this process may use.  Runs longer than
+MAX_DISTINCT_STEPS steps cycle over that many distinct prepared steps (at the headline shape the other steps of one cycle read
+tens of GiB of bank rows before a step comes round again: its rows are long out of the Infinity Cache).
 """
 import argparse
 import json
@@ -43,6 +50,32 @@ for p in (ROOT, os.path.join(ROOT, "sound-spaces_amd")):
         sys.path.insert(0, p)
 
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec (/opt/skills/guides/MI355X_MICROARCH.md)
+MAX_DISTINCT_STEPS = 4096      # prepared steps (unit columns, descriptors) held at once; longer runs cycle over them
+DUMP_BYTES = 60 << 20          # --dump-outputs: payload cap; larger outputs are cut to one seeded sample of units
+
+
+class Cycle(list):
+    """A list indexed modulo its length: step k of a run reads prepared step k % len."""
+
+    def __getitem__(self, k):
+        return list.__getitem__(self, k % len(self))
+
+
+def dump_outputs(outputs, path):
+    """{name: CPU tensor [units, ...]} of one step -> path/<name>.npy (float32).  Over DUMP_BYTES in all, every array keeps the
+    same units: a sorted sample drawn with a fixed seed.  -> (names, units kept)"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrs = {k: v.numpy().astype(np.float32, copy=False) for k, v in outputs.items()}
+    n = next(iter(arrs.values())).shape[0]
+    total = sum(a.nbytes for a in arrs.values())
+    if total > DUMP_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(n, n * DUMP_BYTES // total, replace=False))
+        arrs = {k: a[keep] for k, a in arrs.items()}
+        n = len(keep)
+    for k, a in arrs.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a))
+    return sorted(arrs), n
 
 
 def bytes_per_unit(sr, rir_len, t4):
@@ -505,12 +538,20 @@ def main():
                     help="timed regions of --steps steps each for the headline pass (value = the median region); 0 = auto: 25 "
                          "when --steps <= 50 (a 20-step region is 0.5 ms), else 1")
     ap.add_argument("--sustain", type=float, default=2.0,
-                    help="seconds of the headline loop run once more, untimed for `value`, after the timed regions (reported as "
+                    help="(--full) seconds of the headline loop run once more, untimed for `value`, after the timed regions (reported as "
                          "`sustained`: long enough for once-a-second utilisation samplers to see the load); 0 = off")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: CPU baseline, pipelined / two-group / host-sync / single-stream "
+                         "passes, rooflines, the other bank form, exchange arrangements (N>1), plugin path, sustained run, "
+                         "host time per call; off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the arrays the last timed step produced as DIR/<name>.npy (float32, at "
+                         "most 60 MiB in all: a seeded sample of units when larger)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-plugin-path", action="store_true", help="skip the plugin-path (boundary) measurement")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the conv-only / spectral-bank / 2-stream side measurements")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-plugin-path", action="store_true", help="(--full) skip the plugin-path (boundary) measurement")
+    ap.add_argument("--no-secondary", action="store_true", help="(--full) skip the conv-only / spectral-bank / 2-stream side "
+                                                                "measurements")
     ap.add_argument("--rir-bank", choices=["auto", "spectral", "time"], default="auto",
                     help="format of the HBM-resident RIR bank the headline loop reads: 'time' = the reference's time-domain "
                          "samples (the format SURVEY 8(d) defines the metric and its algorithmic bytes on); 'spectral' = block "
@@ -581,6 +622,8 @@ def main():
     assert world == args.gpus, f"--gpus {args.gpus} but WORLD_SIZE={world}: launch with --nproc-per-node {args.gpus}"
     if args.dry_run:
         return dry_run(args, rank, world)
+    assert args.dump_outputs is None or world == 1, "--dump-outputs: one rank (--gpus 1)"
+    secondary = args.full and not args.no_secondary
     sr = args.sr
     if args.scaling == "strong":
         assert args.envs % world == 0, "--scaling strong: --envs must divide by the number of ranks"
@@ -590,7 +633,7 @@ def main():
     N = n_env * args.rotations                               # units per GPU per step
 
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline:                # rank 0 of ANY world size: an N > 1 line carries it too (the
+    if rank == 0 and args.full and not args.no_cpu_baseline:  # rank 0 of ANY world size: an N > 1 line carries it too (the
         cpu = cpu_baseline(sr, args.cpu_seconds, args.workload, feats, args.rotations)   # other ranks wait at the first barrier);
                                                           # before any CUDA context exists (fork-safe); the CONFIG's own shape
 
@@ -668,8 +711,8 @@ def main():
             return r.plan([UnitRequest(int(s), int(t), int(h), dis_sound=int(d), dis_rir=int(hd))
                            for s, t, h, d, hd in zip(c["sound"], c["t0"], c["rir"], c["dis_sound"], c["dis_rir"])])
         return r.plan_arrays(c["sound"][::rot], np.zeros(n_env, np.int64), c["rir"][::rot], rotations=rot)
-    cols = [draw_cols() for _ in range(total)]
-    descs = [plan_of(c) for c in cols]
+    cols = [draw_cols() for _ in range(min(total, MAX_DISTINCT_STEPS))]
+    descs = Cycle(plan_of(c) for c in cols) if args.full else None   # (pre-planned descriptors: the --full passes only)
     # the untimed spin-up has steps OF ITS OWN: cycling over the timed region's steps would re-read the timed region's bank
     # rows dozens of times before the clock starts ("8(d)'s bank-larger-than-the-Infinity-Cache guarantee is void")
     spin_cols = [draw_cols() for _ in range(16)]
@@ -682,7 +725,7 @@ def main():
     for i in range(len(r.sources)):
         ctx.add_source(f"sound{i}", r.sources._host[i])
     ctx.set_rir_bank(bank, lengths_dev)
-    preps, spin_preps = [ctx.prepare(**c) for c in cols], [ctx.prepare(**c) for c in spin_cols]
+    preps, spin_preps = Cycle(ctx.prepare(**c) for c in cols), [ctx.prepare(**c) for c in spin_cols]
     feat_sets = None
     if feats:
         assert fused and sr <= P.KB, "--features: rows of one block (16 kHz)"
@@ -700,7 +743,7 @@ def main():
     spin_steps = args.spinup_steps if args.spinup_steps >= 0 else max(64, 1500 * 128 // max(N, 128) * 16000 // sr)
 
     def run_loop(S, gather_every, spectral, per_step_events=False, lanes=0, regions=1, sustain_s=0.0, dependent=0,
-                 host_sync=False, exchange=None):
+                 host_sync=False, exchange=None, capture=False):
         """warm-up + EXACTLY args.steps timed steps bracketed by barrier + synchronize -> (elapsed s, GPU ms per step from
         HIP events on the launch stream: the region average, or the per-step list with per_step_events; note).
         lanes = 0: pre-planned descriptors through the stateless entry points on S torch streams (kernel-rate passes; with
@@ -721,7 +764,8 @@ def main():
         sampler - group B renders while group A's policy runs: a context and a caller stream PER GROUP (each chain is plain
         in-order work on its own stream: no cross-stream events at all; ss_ctx_set_chip_share(2) makes each group's launch take
         half the chip so the two run side by side).  host_sync: the host also WAITS
-        for every token before it issues the next step of that group (a trainer that reads its actions back: actions.item())."""
+        for every token before it issues the next step of that group (a trainer that reads its actions back: actions.item()).
+        capture (dependent, one rank): copies what the last timed step wrote to the host, into last_outputs."""
         r.rirs.spectra = spectra if spectral else None
         if dependent:
             lanes = 1                                              # (two groups: two single-stream contexts, see below)
@@ -808,7 +852,8 @@ def main():
                     c_.set_chip_share(G)
 
             def split(cl):
-                return [[ctxs[g].prepare(**{kk: vv[lo:hi] for kk, vv in c.items()}) for g, (lo, hi) in enumerate(bounds)] for c in cl]
+                return Cycle([ctxs[g].prepare(**{kk: vv[lo:hi] for kk, vv in c.items()}) for g, (lo, hi) in enumerate(bounds)]
+                             for c in cl)
             dep_preps = preps if G == 1 else split(cols)
             dep_spin = spin_preps if G == 1 else split(spin_cols)
             assert G == 1 or feat_sets is None, "dependent groups > 1: without the extension features"
@@ -834,6 +879,15 @@ def main():
                             torch.cuda.current_stream(dev).synchronize()
                         else:
                             cs[g].synchronize()
+
+            def outputs_of(k):                                     # what step k wrote (the pointers step() hands the library)
+                out = {"spectrogram": roll[1 + k % T_roll]}
+                if roll_ag is not None:
+                    out["audiogoal"] = roll_ag[k & 1]
+                if feat_sets is not None:
+                    lm, _, _, gc = feat_sets[k % 4]["keep"]
+                    out.update({nm: t_ for nm, t_ in (("logmel", lm), ("gccphat", gc)) if t_ is not None})
+                return out
         elif use_ctx and cx is None:                               # the lean loop: one bound call per step, nothing else
             sg_ptrs = [b_.data_ptr() for b_ in sg_buf]
             ag_ptrs = [None if b_ is None else b_.data_ptr() for b_ in ag_bufs]
@@ -914,7 +968,10 @@ def main():
             if evs:
                 region_ev.append([evs[i].elapsed_time(evs[i + 1]) for i in range(args.steps)] if per_step_events
                                  else [evs[0].elapsed_time(evs[1]) / args.steps])
-        if use_ctx and cx is None and world == 1:
+        if capture:                                                # (after the fence: the step is complete)
+            last_outputs.clear()
+            last_outputs.update({nm: t_.to("cpu", copy=True) for nm, t_ in outputs_of(k0 + args.steps - 1).items()})
+        if args.full and use_ctx and cx is None and world == 1:
             # host time of ONE product-path call (planner + window cache + descriptor ring + launch inside ss_ctx_observe, plus
             # the bound Python call): each call timed on its own, launch queue kept shallow.  Small steps are bound by THIS,
             # not by the kernel (a 32-env launch on two lanes is 10 us of GPU time per step: profiles/r5/kbench_lanes.txt)
@@ -982,8 +1039,9 @@ def main():
     last_regions = []
     last_sustained = {}
     last_host = [None]
+    last_outputs = {}
     spectra = None
-    if args.spectral or not args.no_secondary:
+    if args.spectral or secondary:
         r.rirs.build_spectra()
         spectra = r.rirs.spectra
     exchanging = world > 1 and args.exchange != "none"
@@ -1000,26 +1058,32 @@ def main():
         return {"value": round(world * N * args.steps / e, 1), "ms_per_step": round(1e3 * e / args.steps, 5)}
     # ---- headline (round 6): the product path in the TRAINER-SHAPED loop - one env group, step k+1 ordered behind the consumer
     # of step k's observation (run_loop: dependent), writing into rollouts.observations['spectrogram'][step + 1]; exchange on
-    # when there are ranks.  The pipelined figure (independent steps on LANES internal streams: what r1-r5 reported as `value`)
-    # is measured right after it and reported as `pipelined`.
-    elapsed, head_ev, exchange_note = run_loop(1, G_head, args.spectral, regions=REGIONS, sustain_s=args.sustain, dependent=1)
+    # when there are ranks.  With --full the pipelined figure (independent steps on LANES internal streams: what r1-r5 reported as
+    # `value`) is measured right after it and reported as `pipelined`.
+    elapsed, head_ev, exchange_note = run_loop(1, G_head, args.spectral, regions=REGIONS, sustain_s=args.sustain if args.full else 0.0,
+                                               dependent=1, capture=args.dump_outputs is not None)
     head_regions = list(last_regions)
     head_sustained = dict(last_sustained)
     head_host_us = last_host[0]
+    dumped = None
+    if args.dump_outputs is not None:
+        names, kept = dump_outputs(last_outputs, args.dump_outputs)
+        dumped = {"dir": args.dump_outputs, "arrays": names, "units": kept, "step": args.warmup + REGIONS * args.steps - 1}
     side = {}
-    e_p, _, _ = run_loop(1, G_head, args.spectral, lanes=LANES, regions=REGIONS)
-    pipe_regions = list(last_regions)
-    side["pipelined"] = dict(rate(e_p), lanes=LANES, independent_groups_presumed=LANES, host_us_per_call=last_host[0],
-                             note=f"consecutive steps issued with NO dependency between them on {LANES} internal streams of the "
-                                  f"library (ss_ctx_set_overlap): realisable only by a caller that has {LANES} independent env "
-                                  "groups of this size in flight; r1-r5 reported this figure as `value`",
-                             **({} if len(pipe_regions) < 2 else
-                                {"spread": {k_: round(world * N * args.steps / float(np.quantile(pipe_regions, q_)), 1)
-                                            for k_, q_ in (("min", 1.0), ("p10", 0.9), ("p90", 0.1), ("max", 0.0))}}))
+    if args.full:
+        e_p, _, _ = run_loop(1, G_head, args.spectral, lanes=LANES, regions=REGIONS)
+        pipe_regions = list(last_regions)
+        side["pipelined"] = dict(rate(e_p), lanes=LANES, independent_groups_presumed=LANES, host_us_per_call=last_host[0],
+                                 note=f"consecutive steps issued with NO dependency between them on {LANES} internal streams of the "
+                                      f"library (ss_ctx_set_overlap): realisable only by a caller that has {LANES} independent env "
+                                      "groups of this size in flight; r1-r5 reported this figure as `value`",
+                                 **({} if len(pipe_regions) < 2 else
+                                    {"spread": {k_: round(world * N * args.steps / float(np.quantile(pipe_regions, q_)), 1)
+                                                for k_, q_ in (("min", 1.0), ("p10", 0.9), ("p90", 0.1), ("max", 0.0))}}))
     dep = {"groups": 1, "envs_per_group": n_env, "consumer": "one-workgroup kernel per step and group on the caller's stream "
            "(libss_bench.so: stands in for actor_critic.act, ppo_trainer.py:133-150); the next step is ordered behind it",
            "writes_into": "rollouts.observations['spectrogram'][step + 1] ([17, N, 65, T4, 2], 16 slots cycled)"}
-    if world == 1 and not args.no_secondary:
+    if world == 1 and secondary:
         if N % 2 == 0 and not feats:
             e2, _, _ = run_loop(1, 0, args.spectral, regions=REGIONS, dependent=2)
             dep["two_groups"] = dict(rate(e2), envs_per_group=n_env // 2 if rot == 1 else f"{N // 2} units",
@@ -1028,17 +1092,18 @@ def main():
         eh, _, _ = run_loop(1, 0, args.spectral, regions=REGIONS, dependent=1, host_sync=True)
         dep["host_sync"] = dict(rate(eh), note="as `value`, and the host also waits for every step's token before it issues the "
                                                "next step (a trainer that reads its actions back: actions.item())")
-    side["dependent"] = dep
+    if args.full:
+        side["dependent"] = dep
     step_dist = None
     # ---- the kernel's own rate: pre-planned descriptors, ONE stream - per-launch durations are separable only without
     # overlap, and this is the average the rocprofv3 kernel trace of the same command reports for the kernel
     per_step = None
     kernel_pass = "preplanned_single_stream"
-    if rank == 0 or world > 1:
+    if args.full and (rank == 0 or world > 1):
         e_k, per_step, _ = run_loop(1, 0, args.spectral, regions=REGIONS)
         side["preplanned_single_stream"] = dict(rate(e_k), note="stateless entry point, descriptors planned outside the timed "
                                                 "region, one stream: the kernel rate (r1 / r2 headline protocol)")
-    if world == 1 and not args.no_secondary:
+    if world == 1 and secondary:
         _, ps, _ = run_loop(1, 0, args.spectral, per_step_events=True)
         step_dist = dist_of(ps)
         step_dist["note"] = "separate single-stream pass with one HIP event record per step (the records themselves add 2-3 us per step)"
@@ -1049,7 +1114,7 @@ def main():
         # call (~7 us of host): the smaller of the two event averages is the one that is bound by the kernel
         if per_step and ps_ctx and float(np.mean(ps_ctx)) < float(np.mean(per_step)):
             per_step, kernel_pass = ps_ctx, "ctx_single_stream"
-    if world > 1 and not args.no_secondary:
+    if world > 1 and secondary:
         #  every exchange arrangement from ONE run of `bench.py --gpus N`, same dependent-step protocol:
         #   exchange_none  no collective (the reference's DD-PPO arrangement: every rank's learner consumes its own slab)
         #   allgather      RCCL all_gather_into_tensor of the step slabs, a chunk of --gather-every steps at a time
@@ -1065,7 +1130,7 @@ def main():
                 side[key] = dict(rate(e_x), **({"note": note_x} if note_x else {}))
             except Exception as ex_:                               # one arrangement failing must not take the line down
                 side[key] = {"value": None, "note": f"{type(ex_).__name__}: {ex_}"}
-    if world == 1 and not args.no_secondary:
+    if world == 1 and secondary:
         eo, _, _ = run_loop(1, 0, not args.spectral, lanes=LANES)  # the other RIR bank format: pipelined, dependent, kernel rate
         ed, _, _ = run_loop(1, 0, not args.spectral, regions=REGIONS, dependent=1)
         _, ps_o, _ = run_loop(1, 0, not args.spectral)
@@ -1081,7 +1146,7 @@ def main():
     # ---- secondary measurement: the convolution kernel alone (audiogoal written), same inputs -------------
     conv_ms = None
     conv_ms_other = None
-    if rank == 0 and not args.no_secondary:
+    if rank == 0 and secondary:
         ag = torch.empty((N, 2, sr), dtype=torch.float32, device=dev)
 
         def conv_alone():
@@ -1163,24 +1228,27 @@ def main():
                                "caller's stream (the policy's stand-in); step k+1 is ordered behind it.  One stream, nothing "
                                f"overlaps.  `pipelined` = the r1-r5 protocol ({LANES} internal streams, independent steps)",
                        "streams": 1, "pipelined_streams": LANES, "kernel": kname, "features": feats or None},
-            "roofline": {"bound": "hbm", "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": None, "kernel": kname,
-                         "bytes_per_unit": bpu, "units_per_launch": N, "avg_launch_ms": round(kernel_ms, 5),
-                         "pass": f"single-stream pass of the same run over the same steps ({kernel_pass}): per-launch durations are only "
-                                 "separable without overlap; HIP events around its timed region (for kernels shorter than the host's "
-                                 "issue rate - small steps - the pass with the leaner host side is taken)",
-                         "dependent_achieved": round(bpu * N / (elapsed / args.steps) / 1e9, 1),
-                         "dependent_frac": round(bpu * N / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 4),
-                         "pipeline_achieved": round(bpu * N / (e_p / args.steps) / 1e9, 1),
-                         "pipeline_frac": round(bpu * N / (e_p / args.steps) / 1e9 / HBM_PEAK_GBS, 4)},
         }
-        trs = [measured_traffic(N, sr, k_) for k_ in traffic_kernels]
-        if all(t_ is not None for t_ in trs):
-            out["roofline"]["traffic"] = sum(t_["bytes"] for t_ in trs)
-            out["roofline"]["traffic_detail"] = trs[0] if len(trs) == 1 else dict(zip(traffic_kernels, trs))
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
+        if args.full:
+            out["roofline"] = {"bound": "hbm", "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": None, "kernel": kname,
+                               "bytes_per_unit": bpu, "units_per_launch": N, "avg_launch_ms": round(kernel_ms, 5),
+                               "pass": f"single-stream pass of the same run over the same steps ({kernel_pass}): per-launch durations are "
+                                       "only separable without overlap; HIP events around its timed region (for kernels shorter than the "
+                                       "host's issue rate - small steps - the pass with the leaner host side is taken)",
+                               "dependent_achieved": round(bpu * N / (elapsed / args.steps) / 1e9, 1),
+                               "dependent_frac": round(bpu * N / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 4),
+                               "pipeline_achieved": round(bpu * N / (e_p / args.steps) / 1e9, 1),
+                               "pipeline_frac": round(bpu * N / (e_p / args.steps) / 1e9 / HBM_PEAK_GBS, 4)}
+            trs = [measured_traffic(N, sr, k_) for k_ in traffic_kernels]
+            if all(t_ is not None for t_ in trs):
+                out["roofline"]["traffic"] = sum(t_["bytes"] for t_ in trs)
+                out["roofline"]["traffic_detail"] = trs[0] if len(trs) == 1 else dict(zip(traffic_kernels, trs))
         if step_dist:
             out["gpu_ms_per_step"] = step_dist
-        if fused and sr <= P.KB:
+        if args.full and fused and sr <= P.KB:
             # FFT convolution sits at the FP32 ridge (~20 FLOP/B), so the vector-FP32 roofline is reported
             # beside the declared HBM one.  Algorithmic FLOPs per env-step (radix-2 real-FFT count 2.5 N log2 N):
             # conv 5.1 MFLOP + STFT 2.3 MFLOP @16 kHz; peak = 157.3 TFLOP/s dense FP32 vector (packed FMA) on MI355X.
@@ -1210,12 +1278,12 @@ def main():
                     "avg_launch_ms": round(co, 5), "actual_bytes_per_unit": act, "actual_achieved": round(a4, 1),
                     "actual_frac": round(a4 / HBM_PEAK_GBS, 4)}
         out.update(side)
-        if fused and sr > P.KB:
+        if args.full and fused and sr > P.KB:
             flops = (23.1e6 + 6.4e6) * N                      # SURVEY 8(d) @44.1 kHz: conv 23.1 MFLOP + STFT 6.4 MFLOP per unit
             tf = flops / (kernel_ms * 1e-3) / 1e12
             out["roofline_valu"] = {"bound": "valu-fp32", "achieved": round(tf, 2), "peak": 157.3, "unit": "TFLOP/s",
                                     "frac": round(tf / 157.3, 4), "flops_per_unit": 29.5e6}
-        if world == 1 and not args.no_plugin_path and sr <= P.KB and rot == 1 and not savi:
+        if world == 1 and args.full and not args.no_plugin_path and sr <= P.KB and rot == 1 and not savi:
             srcs = [r.sources._host[i] for i in range(len(r.sources))]
             out["plugin_path"] = measure_plugin_path(torch, np, dev, sr, n_env, bank, args.sounds, srcs,
                                                      min(args.steps, 400), min(args.warmup, 50),

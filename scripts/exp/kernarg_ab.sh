@@ -2,7 +2,7 @@ cd "$GRAFT_REPO_ROOT"
 for R in 1 2; do
 for V in unset 0 1; do
   if [ $V = unset ]; then unset HIP_FORCE_DEV_KERNARG; else export HIP_FORCE_DEV_KERNARG=$V; fi
-  timeout 600 python bench.py --no-cpu-baseline --no-plugin-path > /tmp/b_$V.json 2>/dev/null
+  timeout 600 python bench.py --full --no-cpu-baseline --no-plugin-path > /tmp/b_$V.json 2>/dev/null
   python - $V <<'PY'
 import json,sys
 d=json.loads(open(f'/tmp/b_{sys.argv[1]}.json').read().strip().splitlines()[-1])

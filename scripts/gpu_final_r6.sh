@@ -14,11 +14,11 @@ timeout 300 python -m pytest tests/test_context.py -m gpu -q -s -k "observe_feat
 bash scripts/gpu_profile_r6.sh > /tmp/profile_pass.log 2>&1; echo "profile rc=$?"
 cp /tmp/pytest_final.log "$OUT/pytest_gpu.log"; cp /tmp/profile_pass.log "$OUT/profile_pass.log"; cp /tmp/features_vs_oracle.txt "$OUT/features_vs_oracle.txt"
 mkdir -p profiles/r6; cp "$OUT/traffic.json" profiles/r6/traffic.json
-timeout 900 python bench.py --steps 20 --warmup 5 > "$OUT/bench_headline_driver_protocol.json" 2> "$OUT/bench_headline_driver_protocol.err"; echo "driver-protocol rc=$?"
-timeout 900 python bench.py > "$OUT/bench_headline.json" 2> "$OUT/bench_headline.err"; echo "headline rc=$?"
-timeout 900 python bench.py --rir-bank time --no-plugin-path > "$OUT/bench_headline_time.json" 2> "$OUT/bench_headline_time.err"
-timeout 900 python bench.py --config cfg2 --steps 40 --warmup 5 --no-plugin-path > "$OUT/bench_cfg2.json" 2> "$OUT/bench_cfg2.err"
-timeout 900 python bench.py --config cfg4 --steps 100 --no-plugin-path > "$OUT/bench_cfg4.json" 2> "$OUT/bench_cfg4.err"
+timeout 900 python bench.py --full --steps 20 --warmup 5 > "$OUT/bench_headline_driver_protocol.json" 2> "$OUT/bench_headline_driver_protocol.err"; echo "driver-protocol rc=$?"
+timeout 900 python bench.py --full > "$OUT/bench_headline.json" 2> "$OUT/bench_headline.err"; echo "headline rc=$?"
+timeout 900 python bench.py --full --rir-bank time --no-plugin-path > "$OUT/bench_headline_time.json" 2> "$OUT/bench_headline_time.err"
+timeout 900 python bench.py --full --config cfg2 --steps 40 --warmup 5 --no-plugin-path > "$OUT/bench_cfg2.json" 2> "$OUT/bench_cfg2.err"
+timeout 900 python bench.py --full --config cfg4 --steps 100 --no-plugin-path > "$OUT/bench_cfg4.json" 2> "$OUT/bench_cfg4.err"
 timeout 900 python scripts/bench_dataset.py > "$OUT/dataset.json" 2> "$OUT/dataset.err"; echo "dataset rc=$?"; cat "$OUT/dataset.json"
 timeout 600 python scripts/bench_loader.py --out "$OUT/loader.json" > "$OUT/loader.log" 2>&1; echo "loader rc=$?"
 # SS2.0 deferred: the live-column path and, on the SAME box, round 4's per-request walk (alternating: host speed differs box to box)

@@ -11,7 +11,7 @@ for cfg in cfg3 cfg1 headline; do
   for fence in 1 0; do
     if [ $fence = 1 ]; then export SS_HIP_ALWAYS_FENCE=1; else unset SS_HIP_ALWAYS_FENCE; fi
     echo "== $cfg always_fence=$fence rep=$rep" >> $OUT/host_profile.txt
-    timeout 300 python bench.py --config $cfg --no-cpu-baseline --no-plugin-path --no-secondary --regions 5 --sustain 0 \
+    timeout 300 python bench.py --full --config $cfg --no-cpu-baseline --no-plugin-path --no-secondary --regions 5 --sustain 0 \
         2>> $OUT/host_profile.txt | python -c "import sys,json; d=json.loads(sys.stdin.readline()); print(json.dumps({k:d[k] for k in ('value','ms_per_step','host_us_per_call')}))" >> $OUT/host_profile.txt
   done
 done

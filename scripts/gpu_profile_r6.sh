@@ -8,6 +8,7 @@
 set -u
 cd "$GRAFT_REPO_ROOT"; mkdir -p gpurun_out; export TMPDIR=/tmp
 OUT="$GRAFT_REPO_ROOT/gpurun_out/prof_r6"
+REPO=$PWD                                         # (bench.py for the runs that start in /tmp)
 rm -rf "$OUT"; mkdir -p "$OUT"
 declare -A CFG
 CFG[headline]=""
@@ -30,11 +31,11 @@ for NAME in headline headline_driver_protocol headline_time cfg1 cfg1_time cfg2 
   ARGS=${CFG[$NAME]}
   EXTRA=""; case "$NAME" in cfg4_no_features|headline_time|cfg1_time|cfg4_time|cfg2_time|replica44k_5|replica44k_10_time) EXTRA="--no-cpu-baseline";; esac
   [ "$NAME" = headline ] || [ "$NAME" = headline_driver_protocol ] || EXTRA="$EXTRA --no-plugin-path"
-  timeout 900 python bench.py $ARGS $EXTRA > "$OUT/bench_$NAME.json" 2> "$OUT/bench_$NAME.err" || echo "bench $NAME failed"
+  timeout 900 python bench.py --full $ARGS $EXTRA > "$OUT/bench_$NAME.json" 2> "$OUT/bench_$NAME.err" || echo "bench $NAME failed"
   [ "$NAME" = headline_driver_protocol ] && continue
   case "$NAME" in cfg4_no_features|cfg1_time|cfg4_time) continue;; esac
   D="$OUT/trace_$NAME"
-  ( cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$D" -o trace -- python $GRAFT_REPO_ROOT/bench.py $ARGS --no-cpu-baseline --no-plugin-path --no-secondary --streams 1 --regions 1 --sustain 0 > "$OUT/bench_under_rocprof_$NAME.json" 2>/dev/null )
+  ( cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$D" -o trace -- python $REPO/bench.py --full $ARGS --no-cpu-baseline --no-plugin-path --no-secondary --streams 1 --regions 1 --sustain 0 > "$OUT/bench_under_rocprof_$NAME.json" 2>/dev/null )
   python - "$D" > "$OUT/stats_$NAME.txt" <<'PY'
 import csv, glob, os, sys
 print("# rocprofv3 --kernel-trace --stats, bench.py single-stream run (--no-secondary --streams 1): kernels of libss_hip.so")
@@ -47,7 +48,7 @@ PY
 done
 for NAME in headline headline_time cfg1 cfg2 cfg2_time cfg4 replica44k_10; do
   ARGS=${CFG[$NAME]}
-  CMD="python $GRAFT_REPO_ROOT/bench.py $ARGS --no-cpu-baseline --no-plugin-path --no-secondary --streams 1 --spinup-steps 0 --regions 1 --sustain 0"
+  CMD="python $REPO/bench.py --full $ARGS --no-cpu-baseline --no-plugin-path --no-secondary --streams 1 --spinup-steps 0 --regions 1 --sustain 0"
   D="$OUT/pmc_$NAME"
   i=0
   for PMC in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR" \
@@ -156,7 +157,7 @@ for cfg in ("headline", "headline_time", "cfg1", "cfg2", "cfg2_time", "cfg4", "r
                         "factor measured in the SAME pass script on a known byte count in the kernel's dominant access pattern "
                         "(scripts/calib_traffic.hip; factors under 'calibration')"}
 src_hash = open("sound-spaces_amd/csrc/.libss_hip.kernelhash").read().strip()     # device code only (build.py::kernel_hash)
-json.dump({"source_hash": src_hash, "command": "bench.py [--config cfg2|cfg4] --no-cpu-baseline --no-plugin-path --no-secondary --streams 1 --spinup-steps 0 --regions 1 --sustain 0",
+json.dump({"source_hash": src_hash, "command": "bench.py --full [--config cfg2|cfg4] --no-cpu-baseline --no-plugin-path --no-secondary --streams 1 --spinup-steps 0 --regions 1 --sustain 0",
            "calibration": calib, "kernels": kernels}, open(os.path.join(out, "traffic.json"), "w"), indent=1)
 print(json.dumps({"calibration": calib, "kernels": kernels}, indent=1))
 PY
