@@ -350,6 +350,32 @@ def synth_rir(rng, sr, length=None, n=1):
     return out
 
 
+def synth_rir_blocks(rng, sr, length, n=1, block=16384):
+    """An RIR in which every partition block of ``block`` taps (planning.KB) is audible, unlike the decaying
+    ``synth_rir``.  Per ear and block: a noise floor with its own gain g in [0.3, 1] (0.05 g N(0,1)), signed
+    impulses of magnitude 0.5-1 at the block's first and last tap (so an off-by-one at a block seam moves an O(1)
+    tap) and at one random interior tap; the ears draw independently; peak-normalised to 0.5.  The last block is
+    ragged when ``length % block != 0`` (down to one tap).  ``sr`` is unused (kept for symmetry with synth_rir).
+    Returns float32 [n, 2, length] (planar)."""
+    del sr
+    L = int(length)
+    out = np.zeros((n, 2, L), dtype=np.float32)
+    for i in range(n):
+        for c in range(2):
+            h = np.zeros(L)
+            for lo in range(0, L, block):
+                hi = min(L, lo + block)
+                h[lo:hi] = rng.uniform(0.3, 1.0) * 0.05 * rng.standard_normal(hi - lo)
+                amp = rng.uniform(0.5, 1.0, size=3) * rng.choice([-1.0, 1.0], size=3)
+                h[lo] = amp[0]
+                h[hi - 1] = amp[1]                     # (a one-tap block: the same tap)
+                if hi - lo > 2:
+                    h[rng.integers(lo + 1, hi - 1)] = amp[2]
+            out[i, c] = h
+        out[i] *= 0.5 / np.abs(out[i]).max()
+    return out
+
+
 def synth_sources(rng, sr, k=4, seconds=1):
     """float32 [k, seconds*sr] white noise in U(-1, 1)."""
     return rng.uniform(-1.0, 1.0, size=(k, seconds * sr)).astype(np.float32)

@@ -28,6 +28,14 @@ TOL = 1e-4
 RATES = [16000, 16000, 16000, 44100, 44100, 48000, 22050, 32000, 8000, 11025]
 
 
+def synth_any_rir(rng, sr, L):
+    """[2, L]: about one RIR in four has every partition block audible (synth_rir_blocks), the rest decay (synth_rir), whose
+    blocks after the first one or two lie below the parity tolerance."""
+    if rng.random() < 0.25:
+        return O.synth_rir_blocks(rng, sr, L, n=1)[0]
+    return O.synth_rir(rng, sr, length=L, n=1)[0]
+
+
 def draw_trial(rng):
     sr = int(rng.choice(RATES))
     n_src = int(rng.integers(1, 5))
@@ -49,7 +57,7 @@ def draw_trial(rng):
         if kind == 0:                                          # a few taps (synth_rir's decay model needs a real length)
             rirs.append((rng.standard_normal((L, 2)) * 0.3).astype(np.float32))
             continue
-        h = O.synth_rir(rng, sr, length=L, n=1)[0]             # [2, L]
+        h = synth_any_rir(rng, sr, L)                          # [2, L]
         rirs.append(np.ascontiguousarray(h.T).astype(np.float32))
     n_units = int(rng.choice([1, 2, 3, 5, 7, 10, 16, 31, 32, 33, 42, 43, 64, 96, 97, 128, 150, 257, 400, 700, 1100],
                              p=None))
@@ -85,7 +93,7 @@ def draw_continuous(rng):
     rirs = []
     for _ in range(n_rir):
         L = int(rng.uniform(1.0, 2.0) * sr) if rng.integers(0, 5) == 0 else int(rng.uniform(0.02, 1.0) * sr)
-        rirs.append(np.ascontiguousarray(O.synth_rir(rng, sr, length=L, n=1)[0].T).astype(np.float32))
+        rirs.append(np.ascontiguousarray(synth_any_rir(rng, sr, L).T).astype(np.float32))
     n_units = int(rng.choice([1, 2, 3, 5, 10, 16, 33, 42, 64, 97, 128]))
     if sr >= 32000:
         n_units = min(n_units, 64)

@@ -153,3 +153,75 @@ def test_float32_vs_float64_headroom():
     a32 = O.compute_audiogoal(d["source"], d["rir"], 16000)
     a64 = O.compute_audiogoal(d["source"].astype(np.float64), d["rir"].astype(np.float64), 16000)
     assert O.relerr(a32, a64) < 2e-6
+
+
+# ---- synth_rir_blocks and the multi-block sensitivity guard (tests/rir_guard.py) ----------------------------------------
+def _four_second_inputs():
+    """The inputs of test_hostsim.py::test_four_second_rir_four_partition_blocks (seed 11)."""
+    rng = np.random.default_rng(11)
+    sr, L = 16000, 64000
+    src = O.synth_sources(rng, sr, k=1, seconds=5)[0]
+    h = O.synth_rir(rng, sr, length=L, n=1)[0]
+    h *= np.exp(-np.arange(L) / 30000.0)[None, :].astype(np.float32)
+    return sr, src, np.ascontiguousarray(h.T)
+
+
+@pytest.mark.parametrize("L", [16385, 40001, 64000])
+def test_synth_rir_blocks_shape_edges_and_peak(L):
+    """Every block, the one-tap and the ragged last block included, starts and ends with an impulse of 0.5-1 before the
+    normalisation; ears drawn independently; peak 0.5."""
+    h = O.synth_rir_blocks(np.random.default_rng(L), 16000, L, n=2)
+    assert h.shape == (2, 2, L) and h.dtype == np.float32
+    for i in range(2):
+        assert np.isclose(np.abs(h[i]).max(), 0.5)
+        assert not np.array_equal(h[i, 0], h[i, 1])
+        for c in range(2):
+            scale = np.abs(h[i, c]).max()
+            for lo in range(0, L, 16384):
+                hi = min(L, lo + 16384)
+                for k in (lo, hi - 1):
+                    assert abs(h[i, c, k]) >= 0.25 * scale       # >= 0.5 of a peak that is <= 1 (impulses) or a noise tap
+    assert not np.array_equal(O.synth_rir_blocks(np.random.default_rng(0), 16000, L), h[:1])
+
+
+def test_guard_accepts_synth_rir_blocks_and_sums_blocks_exactly():
+    import rir_guard as G
+    rng = np.random.default_rng(2)
+    sr = 16000
+    src = O.synth_sources(rng, sr, k=1, seconds=5)[0]
+    h = G.wav(O.synth_rir_blocks(rng, sr, 64000)[0])
+    term = G.Term(src, h, t0=4 * sr, out_len=sr)
+    ref, = G.check([term])
+    parts, full, _ = term.blocks()
+    assert parts.shape == (4, 2, sr)
+    assert np.abs(parts.sum(axis=0) - full).max() <= 1e-9 * np.abs(full).max()          # (a)
+    np.testing.assert_allclose(ref, O.compute_audiogoal(src.astype(np.float64), h.astype(np.float64), sr, audio_index=4),
+                               rtol=0, atol=1e-9 * np.abs(ref).max())
+    # SS2.0 step with wrap-around, and a one-tap last block
+    h1 = G.wav(O.synth_rir_blocks(rng, sr, 16385)[0])
+    ref2, = G.check([G.Term(src, h1, "cont", sr=sr, sample_index=78000, step_time=0.25)])
+    np.testing.assert_allclose(ref2, O.convolve_with_rir(src.astype(np.float64), h1.astype(np.float64), sr, 78000, 0.25),
+                               rtol=0, atol=1e-9 * np.abs(ref2).max())
+
+
+def test_guard_rejects_the_decaying_rirs_of_the_four_block_test():
+    """Documents the gap the guard closes: with synth_rir's decay the later blocks of this test's 64000-tap RIR cannot
+    move its output by 1e-2 of peak (float32: by nothing at all), so dropping them would pass."""
+    import rir_guard as G
+    sr, src, h = _four_second_inputs()
+    units = [G.Term(src, h, "cont", sr=sr, sample_index=70000, step_time=0.25), G.Term(src, h, t0=4 * sr, out_len=sr)]
+    with pytest.raises(AssertionError, match="block 1 .* reaches only"):
+        G.check(units)
+    # the same windows with an audible RIR pass
+    G.check([G.Term(src, G.wav(O.synth_rir_blocks(np.random.default_rng(3), sr, 64000)[0]), t0=4 * sr, out_len=sr)])
+
+
+def test_guard_rejects_a_window_too_short_for_the_rir():
+    """A 16-block RIR rendered from a 5-s clip: the window never reaches back to blocks 5-15."""
+    import rir_guard as G
+    rng = np.random.default_rng(4)
+    sr = 16000
+    src = O.synth_sources(rng, sr, k=1, seconds=5)[0]
+    h = G.wav(O.synth_rir_blocks(rng, sr, 1 << 18)[0])
+    with pytest.raises(AssertionError, match="block 5 "):
+        G.check([G.Term(src, h, t0=4 * sr, out_len=sr)])
