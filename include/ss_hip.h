@@ -253,7 +253,12 @@ int ss_ctx_add_source_len(ss_ctx* ctx, int len);   /* planner-only registration 
 int ss_ctx_set_rir_bank(ss_ctx* ctx, const float* rir, const int* rir_len, long long rir_unit_stride,
                         int rir_chan_stride, int rir_elem_stride, int rir_cap);
 /* Optional spectral form (ss_rir_spectra_f32) of the bank given to ss_ctx_set_rir_bank: steps without a cross-fade then
- * run the *_spec_* kernels.  hspec = NULL: back to the time-domain kernels.  Borrowed pointer. */
+ * run the *_spec_* kernels.  hspec = NULL: back to the time-domain kernels.  Borrowed pointer.
+ * SPECTRAL-ONLY binding (a bank that keeps no time-domain rows, filled by ss_bank_scatter_spectra_f32):
+ *   ss_ctx_set_rir_bank(ctx, NULL, rir_len, 0, 0, 1, rir_cap);  ss_ctx_set_rir_spectra(ctx, hspec, ceil(rir_cap / kB));
+ * Steps then always read the spectra; a step whose route reads time-domain rows (a cross-fade) is refused with SS_EINVAL
+ * before any upload or launch.  The in-call loaders (ss_miss_loader with bank = NULL, stage_desc not needed) write the
+ * new rows' spectra and lengths with one k_stage_spectra launch. */
 int ss_ctx_set_rir_spectra(ss_ctx* ctx, const float* hspec, int h_blocks);
 /* The bank as length buckets (see ss_rir_bucket; replaces the two calls above for such banks; the descriptor array is copied,
  * the device pointers are borrowed).  Call again whenever a bucket is (re)allocated. */
@@ -395,7 +400,7 @@ typedef struct ss_miss_loader {
     int pair_cap;                    /* ... with room for pair_cap entries; ss_request_tables.n_pairs is updated                */
     int* free_slots;                 /* stack of free bank entries: the call pops free_slots[n_free - 1], ...                   */
     int n_free;                      /* in: entries on the stack; out: entries left                                             */
-    float* bank;                     /* DEVICE: planar time-domain bank [entries][2][cap]                                        */
+    float* bank;                     /* DEVICE: planar time-domain bank [entries][2][cap]; NULL on a spectral-only context       */
     long long bank_unit_stride;      /* floats between entries                                                                   */
     int bank_chan_stride, cap;
     int* dev_len;                    /* DEVICE: rir_len table of the bank                                                        */
@@ -468,6 +473,18 @@ int ss_wav_read_rirs_f32(const char* const* paths, int n, float* dst, long long 
  * device at all there) for what follows ss_wav_read_rirs_f32 / ss_rows_gather_f32.  Returns 0 / SS_EINVAL / -hipError_t. */
 int ss_bank_scatter_rows_f32(const float* staged, long long staged_row_stride, const int* slots, const int* lens, int n,
                              float* bank, long long unit_stride, int chan_stride, int cap, int* bank_len, void* stream);
+/* The same hop for a SPECTRAL-ONLY bank (no time-domain rows, see ss_ctx_set_rir_spectra): n staged rows -> the block spectra
+ * H'_b = 2 rFFT(block b) of both ears in entry slots[i] of hspec [entries][2][h_blocks][ss_spec_floats()] - item order and
+ * scale exactly those of ss_rir_spectra_f32, whose output over the scattered planar rows they equal bit for bit - and lens[i]
+ * into bank_len[slots[i]] (bank_len may be NULL), ONE launch (k_stage_spectra: one workgroup per row and block).  Row i
+ * starts at staged + i * staged_row_stride floats: wav layout [frames][2] (planar = 0; staged_row_stride even) or planar
+ * [2][staged_row_stride / 2] (planar = 1; staged_row_stride a multiple of 4); `staged` 8-byte aligned.  A row holds
+ * cap = min(staged_row_stride / 2, h_blocks * kB) frames; lens[i] is clamped to [0, cap] and frames at or beyond it are
+ * not read (zero).  `staged`, `slots`, `lens`: pinned host or device memory as for ss_bank_scatter_rows_f32 (pageable host
+ * memory is refused: SS_EINVAL); hspec / bank_len are device memory.  Asynchronous on `stream`.
+ * Returns 0 / SS_EINVAL / -hipError_t. */
+int ss_bank_scatter_spectra_f32(const float* staged, long long staged_row_stride, int planar, const int* slots, const int* lens,
+                                int n, float* hspec, int h_blocks, int* bank_len, void* stream);
 /* n HOST arrays -> n rows of a (pinned) staging block: row i = src[i][0 .. n_floats[i]) followed by zeros up to row_floats,
  * rows row_stride floats apart, on up to n_threads plain threads.  The live RIRs of a SoundSpaces 2.0 step (one new RIR per
  * env and step from the ray tracer, soundspaces/continuous_simulator.py:419) travel to the bank this way: one block, one

@@ -1191,6 +1191,12 @@ static int ctx_observe_on(ss_ctx* h, const ss_units* units, int n, float* audiog
     SS_PROF_MARK(2);                                           // ring slot: group event synchronise
     rc = ssctx::plan_units(c, units, n, hd, &res);
     if (rc) return rc;                                         // (refused before the cache or the ring was touched)
+    // a spectral-only bank (spectra bound, no rows: ss_ctx_set_rir_bank(ctx, NULL, ...) + ss_ctx_set_rir_spectra) cannot serve a
+    // step whose route reads the time-domain rows (a cross-fade): refused before any upload or launch, the plan's keys given back
+    if (!c.rir && c.buckets.empty() && (!c.hspec || (res.flags & SS_FLAG_CROSSFADE))) {
+        ssctx::cache_rollback(c);
+        return SS_EINVAL;
+    }
     SS_PROF_MARK(3);                                           // planner
     c.ring_k = (k + 1) % ssctx::kRing;                         // the slot is taken from here on, whatever happens next
     // The slot's group is released by an event recorded behind the group's last launch (overlap mode: behind each lane's
@@ -1611,7 +1617,10 @@ static int loader_load_paths(ssctx::Context& c, ss_miss_loader* ld, const char* 
                              int n_slots, bool spectral, hipStream_t st) {
     const int hb = (ld->cap + ssk::kB - 1) / ssk::kB;
     if (k <= 0 || k > ld->stage_rows || k > ld->loaded_cap) return 1;
-    if (spectral && (!ld->stage_desc || c.h_blocks != hb || !c.hspec)) return 1;
+    // a spectral-only bank (no rows: ld->bank == NULL) takes its block spectra straight from the staged rows (k_stage_spectra)
+    const bool spec_only = !ld->bank;
+    if (spec_only && (!spectral || c.rir)) return 1;
+    if (spectral && ((!spec_only && !ld->stage_desc) || c.h_blocks != hb || !c.hspec)) return 1;
     // entries: free ones first, then - if the caller lent its recency arrays - the least recently used occupied ones
     std::vector<int> victims;
     if (k > ld->n_free) {
@@ -1630,7 +1639,7 @@ static int loader_load_paths(ssctx::Context& c, ss_miss_loader* ld, const char* 
     std::vector<int> take(k);                                  // the entries the k new rows go to, in order
     for (int i = 0; i < k; ++i)
         take[i] = i < ld->n_free ? ld->free_slots[ld->n_free - 1 - i] : victims[i - ld->n_free];
-    if (spectral) {                                            // (window offsets are int32 words from the bank's base)
+    if (spectral && !spec_only) {                              // (window offsets are int32 words from the bank's base)
         for (int i = 0; i < k; ++i)
             if ((static_cast<long long>(take[i]) + 1) * ld->bank_unit_stride >= (1LL << 31)) return 1;
     }
@@ -1665,9 +1674,17 @@ static int loader_load_paths(ssctx::Context& c, ss_miss_loader* ld, const char* 
         if (last_used && slot < n_slots) last_used[slot] = tick;
     }
     ld->n_loaded = k;
-    int rc = ss_bank_scatter_rows_f32(ld->stage, 2LL * ld->cap, ld->stage_slot, ld->stage_len, k, ld->bank, ld->bank_unit_stride,
+    int rc = 0;
+    if (spec_only) {                                           // staged rows -> block spectra + lengths, one launch
+        rc = ss_bank_scatter_spectra_f32(ld->stage, 2LL * ld->cap, 0, ld->stage_slot, ld->stage_len, k, const_cast<float*>(c.hspec),
+                                         hb, ld->dev_len, st);
+        if (rc == 0 && ld->spec_stale)
+            for (int i = 0; i < k; ++i) ld->spec_stale[ld->stage_slot[i]] = 0;
+    } else {
+        rc = ss_bank_scatter_rows_f32(ld->stage, 2LL * ld->cap, ld->stage_slot, ld->stage_len, k, ld->bank, ld->bank_unit_stride,
                                       ld->bank_chan_stride, ld->cap, ld->dev_len, st);
-    if (rc == 0 && spectral) {
+    }
+    if (rc == 0 && spectral && !spec_only) {
         // the new rows' block spectra H'_i = 2 rFFT(block i), straight into the spectral bank (scatter form of k_source_windows;
         // the descriptors are read from the pinned block in place)
         int w = 0;
@@ -1704,8 +1721,9 @@ static int serve_pose_misses(ss_ctx* h, const long long* recs, int n, ss_request
                              int n_miss, hipStream_t st, bool spectral) {
     ssctx::Context& c = h->c;
     const int hb = (ld && ld->cap > 0) ? (ld->cap + ssk::kB - 1) / ssk::kB : 1;
-    if (spectral && (!ld || !ld->stage_desc || c.h_blocks != hb)) return 1;
-    if (!ld || !ld->table_dirs || !ld->pair_keys || !ld->pair_slots || !ld->free_slots || !ld->bank || !ld->dev_len ||
+    const bool spec_only = ld && !ld->bank && !c.rir && c.hspec && spectral;       // spectral-only bank: no rows, no descriptors
+    if (spectral && (!ld || (!spec_only && !ld->stage_desc) || c.h_blocks != hb)) return 1;
+    if (!ld || !ld->table_dirs || !ld->pair_keys || !ld->pair_slots || !ld->free_slots || (!ld->bank && !spec_only) || !ld->dev_len ||
         !ld->host_len || !ld->clipped || !ld->stage || !ld->stage_slot || !ld->stage_len || !ld->loaded_key || !ld->loaded_slot ||
         !ld->loaded_frames || ld->cap < 2 || (ld->cap & 1) || tb->pair_keys != ld->pair_keys || tb->pair_slots != ld->pair_slots)
         return 1;
@@ -1779,7 +1797,8 @@ int ss_ctx_load_rir_files(ss_ctx* h, ss_miss_loader* ld, const char* const* path
     ld->n_loaded = 0; ld->n_evicted = 0;
     if (k == 0) return 0;
     ssctx::Context& c = h->c;
-    if (!ld->free_slots || !ld->bank || !ld->dev_len || !ld->host_len || !ld->clipped || !ld->stage || !ld->stage_slot ||
+    const bool spec_only = !ld->bank && !c.rir && c.hspec && c.buckets.empty();     // spectral-only bank (see loader_load_paths)
+    if (!ld->free_slots || (!ld->bank && !spec_only) || !ld->dev_len || !ld->host_len || !ld->clipped || !ld->stage || !ld->stage_slot ||
         !ld->stage_len || !ld->loaded_slot || !ld->loaded_frames || ld->cap < 2 || (ld->cap & 1) || c.rir != ld->bank)
         return 1;
     // (rows of a store that keeps the spectral form get their block spectra right away: whichever form the next launch reads)
@@ -1974,6 +1993,44 @@ extern "C" int ss_bank_scatter_rows_f32(const float* staged, long long staged_ro
         ssk::ScatterRowsParams q = p;
         q.staged += static_cast<size_t>(lo) * staged_row_stride; q.slots += lo; q.lens += lo;
         hipLaunchKernelGGL(ssk::k_scatter_rows, dim3((cap + 511) / 512, m), dim3(256), 0, static_cast<hipStream_t>(stream), q);
+    }
+    return hip_err(hipGetLastError());
+}
+
+// the kernel dereferences these: pageable host memory would be a GPU memory fault (the process dies), not an error code -
+// refuse anything the runtime does not know as device-accessible (pinned / registered host, device, managed)
+static bool device_accessible(const void* ptr) {
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, ptr) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return attr.type == hipMemoryTypeHost || attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged;
+}
+
+// Staged rows (wav or planar layout, pinned host or device memory) -> block spectra of a spectral-only bank + its lengths, one
+// launch (k_stage_spectra).  Both staging forms are accepted; which is faster depends on the number of rows: a workgroup that
+// pulls its 128 KiB block over the host link waits at the link's latency, which a handful of rows hides and dozens do not
+// (profiles/r7, one sequential run, noisy: 1 row pulled 123 us against 130 us copied first, 32 rows 487 against 368 us per 128-env
+// miss step).  The Python
+// stores pull blocks of <= RirStore.spectra_pull_rows rows and copy larger ones; the in-call loaders pull (their steps load few).
+extern "C" int ss_bank_scatter_spectra_f32(const float* staged, long long staged_row_stride, int planar, const int* slots,
+                                           const int* lens, int n, float* hspec, int h_blocks, int* bank_len, void* stream) {
+    if (n == 0) return 0;
+    if (!staged || !slots || !lens || !hspec || n < 0 || h_blocks < 1 || staged_row_stride < 2) return SS_EINVAL;
+    // 8-byte loads: pairs of frames (planar: of one ear, the second ear half a row further) or both ears of a frame (wav)
+    if ((reinterpret_cast<size_t>(staged) & 7) || (staged_row_stride & (planar ? 3 : 1))) return SS_EINVAL;
+    for (const void* ptr : {static_cast<const void*>(staged), static_cast<const void*>(slots), static_cast<const void*>(lens)})
+        if (!device_accessible(ptr)) return SS_EINVAL;
+    ssk::StageSpecParams p;
+    int rc = get_tables(&p.tb);
+    if (rc) return rc;
+    const long long frames = staged_row_stride / 2, hb_frames = static_cast<long long>(h_blocks) * ssk::kB;
+    p.staged = staged; p.slots = slots; p.lens = lens; p.hspec = reinterpret_cast<ssk::f32x4*>(hspec); p.bank_len = bank_len;
+    p.staged_stride = staged_row_stride; p.planar = planar ? 1 : 0; p.h_blocks = h_blocks;
+    p.cap = static_cast<int>(std::min(frames, hb_frames));
+    for (int lo = 0; lo < n; lo += 65535) {                    // (grid.y limit)
+        const int m = n - lo < 65535 ? n - lo : 65535;
+        ssk::StageSpecParams q = p;
+        q.staged += static_cast<size_t>(lo) * staged_row_stride; q.slots += lo; q.lens += lo;
+        hipLaunchKernelGGL(ssk::k_stage_spectra, dim3(h_blocks, m), dim3(ssk::kT), 0, static_cast<hipStream_t>(stream), q);
     }
     return hip_err(hipGetLastError());
 }

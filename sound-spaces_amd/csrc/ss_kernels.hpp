@@ -2460,4 +2460,98 @@ __global__ __launch_bounds__(256) void k_scatter_rows(ScatterRowsParams p) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// k_stage_spectra: the miss path of a SPECTRAL-ONLY bank (no time-domain rows).  n staged rows -> the block spectra
+// H'_b = 2*rFFT_{2kB}(row[b*kB : (b+1)*kB]) of both ears, straight into entry slots[i] of the spectral bank, and the rows'
+// lengths into its length table: one launch where a bank that keeps rows takes two (k_scatter_rows, then k_source_windows
+// over the new rows), and no time-domain row in between.  Grid (h_blocks, n), one 1024-thread workgroup per (row, block).
+// Staged rows: wav layout ([frames][2]: one 8-byte load is both ears of a frame) or planar ([2][stride/2]); pinned host memory
+// (the workgroups pull their block over the host link themselves) or device memory.  Frames at or beyond the row's length are
+// not read: they are zero.  One transform takes 136 KiB of the CU's 160 KiB of LDS, so the ears are transformed one after the
+// other, the second one's 16 samples per thread waiting in registers.  Item order and scale are those of k_source_windows
+// with scale = 1 (ss_rir_spectra_f32), and so are the instructions (pass1_fwd_lo): the spectra are bit-identical to that path
+// over the scattered planar rows.
+struct StageSpecParams {
+    const float* staged;       // row i at staged + i * staged_stride
+    const int* slots;          // [n] bank entries
+    const int* lens;           // [n] frames of row i (clamped to [0, cap])
+    f32x4* hspec;              // [entries][2][h_blocks][kSpecComplex / 2]
+    int* bank_len;             // [entries] (may be nullptr)
+    Tables tb;
+    long long staged_stride;   // floats
+    int planar;                // 0: [frames][2]; 1: [2][staged_stride / 2]
+    int cap;                   // frames a row may hold: min(staged_stride / 2, h_blocks * kB)
+    int h_blocks;
+};
+
+// pass1_fwd<false> of a block whose packed samples m = t + 1024*a, a < 8, are already in registers (an RIR block has <= kB
+// real samples: the upper half is zero).  The zeros are opaque to the compiler, so the instructions are those of
+// k_source_windows over the same samples.
+__device__ __forceinline__ void pass1_fwd_lo(c32* lds, c32 wbase, int t, const c32 (&lo)[8]) {
+    c32 x[16];
+#pragma unroll
+    for (int a = 0; a < 16; ++a) {
+        if (a < 8) x[a] = lo[a & 7];
+        else { x[a] = mk2(0.f, 0.f); SSK_OPAQUE2(x[a]); }
+    }
+    fft16<false>(x);
+    c32 w = wbase;
+    SSK_OPAQUE2(w);
+    twiddle16<false>(x, w);
+    c32* base = lds + t + (t >> 6);
+#pragma unroll
+    for (int a = 0; a < 16; ++a) lds_st(base + 1040 * a, x[a]);
+}
+
+// one ear's block (packed samples in registers) -> its stored spectrum at o (kernel order, k_source_windows with scale 1)
+__device__ __forceinline__ void stage_block_spectrum(c32* lds, const ThreadTw& tw, int t, const c32 (&lo)[8], f32x4* o) {
+    pass1_fwd_lo(lds, tw.p1, t, lo);
+    fwd_passes(lds, tw, t);
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        c32 v[8];
+        item_load_fwd(lds, s ? tw.i1 : tw.i0, t + 1024 * s, v);
+#pragma unroll
+        for (int h = 0; h < 4; ++h) o[(s * 4 + h) * 1024] = mk4(v[2 * h], v[2 * h + 1]);
+    }
+}
+
+__global__ __launch_bounds__(1024) void k_stage_spectra(StageSpecParams p) {
+    __shared__ c32 lds[kLdsComplex];
+    const int t = threadIdx.x, b = blockIdx.x, i = blockIdx.y;
+    const int slot = __builtin_amdgcn_readfirstlane(p.slots[i]);
+    const int len = min(max(__builtin_amdgcn_readfirstlane(p.lens[i]), 0), p.cap);
+    if (b == 0 && t == 0 && p.bank_len) p.bank_len[slot] = len;
+    const int nv = min(max(len - b * kB, 0), kB);        // frames of this block that hold samples
+    const float* row = p.staged + (size_t)i * p.staged_stride + (p.planar ? (size_t)b * kB : 2 * (size_t)b * kB);
+    const size_t half = (size_t)(p.staged_stride >> 1);  // planar: offset of the second ear
+    c32 xl[8], xr[8];
+#pragma unroll
+    for (int a = 0; a < 8; ++a) {
+        const int j = 2 * (t + 1024 * a);                // frames j, j + 1 of the block: packed sample a of both ears
+        c32 l = mk2(0.f, 0.f), r = mk2(0.f, 0.f);
+        if (p.planar) {
+            if (j + 1 < nv) { l = *reinterpret_cast<const c32*>(row + j); r = *reinterpret_cast<const c32*>(row + half + j); }
+            else if (j < nv) { l.x = row[j]; r.x = row[half + j]; }
+        } else {
+            if (j < nv) {
+                const c32 f0 = *reinterpret_cast<const c32*>(row + 2 * j);                // (L, R) of frame j
+                l.x = f0.x; r.x = f0.y;
+                if (j + 1 < nv) {
+                    const c32 f1 = *reinterpret_cast<const c32*>(row + 2 * j + 2);        // ... of frame j + 1
+                    l.y = f1.x; r.y = f1.y;
+                }
+            }
+        }
+        xl[a] = l;
+        xr[a] = r;
+    }
+    const ThreadTw tw = load_thread_tw(p.tb.twM, p.tb.twItem, t);
+    const size_t ear_f4 = (size_t)p.h_blocks * (kSpecComplex / 2);
+    f32x4* o = p.hspec + (size_t)slot * 2 * ear_f4 + (size_t)b * (kSpecComplex / 2) + t;
+    stage_block_spectrum(lds, tw, t, xl, o);
+    lds_barrier();                                       // every item read of the first ear before the second one's pass 1
+    stage_block_spectrum(lds, tw, t, xr, o + ear_f4);
+}
+
 }  // namespace ssk

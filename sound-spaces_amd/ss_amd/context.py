@@ -128,6 +128,16 @@ class AudioContext:
         self.rir_cap = int(cap)
         self._spectra = None
 
+    def set_rir_spectra_only(self, hspec, lengths, cap: int) -> None:
+        """A SPECTRAL-ONLY bank (``RirStore(spectral="only")``: block spectra hspec [R,2,ceil(cap/KB),SPEC_FLOATS] and CUDA int32
+        lengths [R], no time-domain rows): ss_ctx_set_rir_bank(ctx, NULL, lengths, 0, 0, 1, cap) + ss_ctx_set_rir_spectra.  Every
+        step reads the spectra; a cross-faded step (it would read rows) is refused by the library with SS_EINVAL."""
+        _lib.check(self.lib.ss_ctx_set_rir_bank(self._h, None, lengths.data_ptr(), 0, 0, 1, int(cap)), "ss_ctx_set_rir_bank")
+        self._bank = (None, lengths)
+        self.rir_cap = int(cap)
+        _lib.check(self.lib.ss_ctx_set_rir_spectra(self._h, hspec.data_ptr(), int(hspec.shape[2])), "ss_ctx_set_rir_spectra")
+        self._spectra = hspec
+
     def set_rir_buckets(self, bank, spectral: bool = False) -> None:
         """A length-bucketed bank (``ss_amd.renderer.BucketedRirBank``; include/ss_hip.h ``ss_ctx_set_rir_buckets``):
         steps whose units all sit in bucket 0 keep the loop-free kernel, long RIRs live in buckets of their own.

@@ -236,6 +236,27 @@ def rir_spectra_into(rir_bank: torch.Tensor, hspec: torch.Tensor, first: int = 0
                                                   cap, _stream(rir_bank)), "ss_rir_spectra_f32")
 
 
+def scatter_spectra_into(staged: torch.Tensor, planar: bool, slots: torch.Tensor, lens: torch.Tensor, n: int,
+                         hspec: torch.Tensor, bank_len: torch.Tensor) -> None:
+    """Rows [0, n) of a staging block -> block spectra of entries slots[i] of the spectral-only bank hspec [R,2,hb,SPEC_FLOATS]
+    and lens[i] into bank_len[slots[i]] (ss_bank_scatter_spectra_f32: one launch on the current stream of hspec's device).
+    staged: float32 [*, cap, 2] (wav layout) or [*, 2, cap] (planar), pinned host or device memory; slots / lens: int32, pinned
+    host or device memory.  The caller keeps all three alive and unchanged until the launch has run."""
+    _chk(hspec, torch.float32, "hspec"); _chk(bank_len, torch.int32, "bank_len")
+    for t, dt, name in ((staged, torch.float32, "staged"), (slots, torch.int32, "slots"), (lens, torch.int32, "lens")):
+        if not (t.is_cuda or t.is_pinned()):
+            raise ValueError(f"{name}: pinned host or device memory expected (the kernel reads it in place)")
+        if t.dtype != dt or not t.is_contiguous():
+            raise ValueError(f"{name}: expected contiguous {dt}, got {t.dtype} contiguous={t.is_contiguous()}")
+    assert staged.dim() == 3 and staged.shape[2 if not planar else 1] == 2 and hspec.dim() == 4 and staged.shape[0] >= n
+    if n == 0:
+        return
+    with torch.cuda.device(hspec.device):
+        _lib.check(_lib.load().ss_bank_scatter_spectra_f32(staged.data_ptr(), staged[0].numel(), int(bool(planar)), slots.data_ptr(),
+                                                           lens.data_ptr(), n, hspec.data_ptr(), hspec.shape[2], bank_len.data_ptr(),
+                                                           _stream(hspec)), "ss_bank_scatter_spectra_f32")
+
+
 def rir_spectra(rir_bank: torch.Tensor) -> torch.Tensor:
     R, _, cap = rir_bank.shape
     hspec = torch.empty((R, 2, ceil_div(cap, KB), SPEC_FLOATS), dtype=torch.float32, device=rir_bank.device)

@@ -18,7 +18,7 @@ from __future__ import annotations
 
 import os
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -61,20 +61,30 @@ class SourceBank:
 
 class RirBank:
     """Binaural RIRs, planar float32 ``[R, 2, cap]`` on the device, rows zero beyond their own length
-    (the precondition of ss_fftconv_binaural_f32)."""
+    (the precondition of ss_fftconv_binaural_f32).
 
-    def __init__(self, data: torch.Tensor, lengths: torch.Tensor):
+    A SPECTRAL-ONLY bank (``RirStore(spectral="only")``) keeps no time-domain rows: ``data`` is then a zero-size
+    ``[R, 2, 0]`` tensor (``len(bank)`` still counts the entries), ``cap`` is given (the rows' capacity that ``spectra``
+    ``[R, 2, ceil(cap/KB), SPEC_FLOATS]`` was built for) and ``spectral_only`` is True: only the *_spec_* kernels read it."""
+
+    def __init__(self, data: torch.Tensor, lengths: torch.Tensor, cap: Optional[int] = None):
         assert data.dim() == 3 and data.shape[1] == 2 and data.dtype == torch.float32 and data.is_contiguous()
         assert lengths.dtype == torch.int32 and lengths.shape == (data.shape[0],)
+        assert cap is None or data.shape[2] == 0, "cap is only given for a spectral-only bank (no rows)"
         self.data, self.lengths = data, lengths
-        self.cap = int(data.shape[2])
+        self.cap = int(data.shape[2]) if cap is None else int(cap)
         self.spectra: Optional[torch.Tensor] = None      # [R, 2, ceil(cap/KB), SPEC_FLOATS]: see build_spectra()
+
+    @property
+    def spectral_only(self) -> bool:
+        return self.data.shape[2] == 0 and self.cap > 0
 
     def build_spectra(self) -> torch.Tensor:
         """Spectral form of the bank (ss_rir_spectra_f32): the forward FFT of every RIR block, done once here instead
         of once per step and unit (the reference redoes it inside every fftconvolve call, simulator.py:630).  With it
         the renderer runs k_conv_spec (no forward FFT; 2x the bytes per RIR).  For banks whose entries change after
         this call, call it again (or use RirStore(spectral=True), which keeps the two forms in step)."""
+        assert not self.spectral_only, "a spectral-only bank has no rows to transform"
         self.spectra = ops.rir_spectra(self.data)
         return self.spectra
 
@@ -378,6 +388,7 @@ class BatchedAudioRenderer:
         xfade = bool(plan.flags & ops.FLAG_CROSSFADE)
         spectral = (self.rirs.spectra is not None if not isinstance(self.rirs, BucketedRirBank) else bool(self.rirs.spectra)) \
             and not xfade and self._spectral_for(N, not (plan.flags & ops.FLAG_NO_DISTRACTOR))
+        self._check_rows(spectral)
         need_ag = (want_audiogoal or audiogoal_out is not None or
                    (self.out_len > P.KB and not P.wide_one_block(self.out_len, self.n_valid, spectral)
                     and (xfade or self.n_valid <= P.KB or self.out_len > 3 * P.KB)))
@@ -398,8 +409,16 @@ class BatchedAudioRenderer:
                                self.out_len, self.pad_mode, flags=plan.flags)
         return (ag if (want_audiogoal or audiogoal_out is not None) else None), sg
 
+    def _check_rows(self, spectral: bool) -> None:
+        if not spectral and getattr(self.rirs, "spectral_only", False):
+            raise ValueError("this RIR bank keeps block spectra only (spectral-only): a cross-faded step, or one the "
+                             "spectral_max_units policy sends to the time-domain rows, cannot be rendered from it")
+
     def render_audiogoal(self, plan: Plan, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """AudioGoalSensor-only configurations (soundspaces/tasks/nav.py:37-60)."""
+        if not isinstance(self.rirs, BucketedRirBank):
+            self._check_rows(self.rirs.spectra is not None and not (plan.flags & ops.FLAG_CROSSFADE) and
+                             self._spectral_for(len(plan), not (plan.flags & ops.FLAG_NO_DISTRACTOR)))
         if out is None:
             out = torch.empty((len(plan), 2, self.out_len), dtype=torch.float32, device=self.device)
         if isinstance(self.rirs, BucketedRirBank):
@@ -450,12 +469,24 @@ class RirStore:
     pair: SURVEY 8(f)2), loaded and evicted together; ``slot()`` then returns the first slot of the group."""
 
     def __init__(self, slots: int, cap: int, device, truncate_to: Optional[int] = None, max_cap: int = 1 << 18,
-                 on_grow=None, group: int = 1, spectral: bool = False):
+                 on_grow=None, group: int = 1, spectral: Union[bool, str] = False):
         cap += cap & 1
         assert slots % group == 0
         self.device = torch.device(device)
-        self.bank = RirBank(torch.zeros((slots, 2, cap), dtype=torch.float32, device=self.device),
-                            torch.zeros((slots,), dtype=torch.int32, device=self.device))
+        # spectral="only": the block spectra and the lengths, NO time-domain rows (RirBank.spectral_only: bank.data is a zero-size
+        # [slots, 2, 0] tensor).  Every upload path stages the rows and transforms them on their way in (ss_bank_scatter_spectra_f32,
+        # one launch): 1.49x the entries of a both-forms store per byte of HBM at 16 kHz, 1.45x at 44.1 kHz.  Only the *_spec_*
+        # kernels can read such a bank: no cross-fade (SS2.0), no small-step policy, no time-domain fallback - hence no CPU store.
+        if isinstance(spectral, str) and spectral != "only":
+            raise ValueError(f"RirStore: spectral must be False, True or 'only', not {spectral!r}")
+        self.spectral_only = spectral == "only"
+        if self.spectral_only and self.device.type != "cuda":
+            raise ValueError("RirStore(spectral='only') needs a GPU device: the spectral-only bank has no CPU fallback")
+        lengths = torch.zeros((slots,), dtype=torch.int32, device=self.device)
+        if self.spectral_only:
+            self.bank = RirBank(torch.zeros((slots, 2, 0), dtype=torch.float32, device=self.device), lengths, cap=cap)
+        else:
+            self.bank = RirBank(torch.zeros((slots, 2, cap), dtype=torch.float32, device=self.device), lengths)
         self.slots, self.cap, self.group = slots, cap, group
         self.truncate_to, self.max_cap, self.on_grow = truncate_to, max_cap, on_grow
         # called before ANYTHING this store writes to the bank on the device (rows, lengths, block spectra, a reallocation): the
@@ -487,8 +518,9 @@ class RirStore:
         self._clipped = np.zeros((slots,), bool)              # the stored row is shorter than its RIR (truncate_to)
         # spectral=True keeps the block spectra of every row next to it (RirBank.spectra, ss_rir_spectra_f32): rows
         # (re)loaded since the last sync_spectra() are transformed there, once, instead of once per step and unit
-        self.spectral = spectral
+        self.spectral = bool(spectral)
         self._stale = np.zeros((slots,), bool)
+        self._stale_mark = not self.spectral_only               # (a spectral-only store's rows are transformed as they arrive)
         if spectral and self.device.type == "cuda":
             self.bank.spectra = torch.zeros((slots, 2, P.ceil_div(cap, P.KB), P.SPEC_FLOATS), dtype=torch.float32,
                                             device=self.device)
@@ -553,6 +585,22 @@ class RirStore:
             raise ValueError(f"RIR of {n} samples exceeds RirStore.max_cap = {self.max_cap}")
         self._about_to_write()
         new_cap = min(self.max_cap + (self.max_cap & 1), -(-n // 2048) * 2048)
+        if self.spectral_only:
+            # H'_i depends on block i of the row alone and rows are zero beyond their length: the old blocks stay valid, the new
+            # ones are the spectra of zero blocks - exact, no row needed (and none is kept)
+            old = self.bank.spectra
+            spectra = torch.zeros((self.slots, 2, P.ceil_div(new_cap, P.KB), P.SPEC_FLOATS), dtype=torch.float32,
+                                  device=self.device)
+            spectra[:, :, :old.shape[2]] = old
+            self.bank = RirBank(torch.zeros((self.slots, 2, 0), dtype=torch.float32, device=self.device), self.bank.lengths,
+                                cap=new_cap)
+            self.bank.spectra = spectra
+            self.cap = new_cap
+            self._stage = None
+            self.grown += 1
+            if self.on_grow is not None:
+                self.on_grow(self.bank)
+            return
         data = torch.zeros((self.slots, 2, new_cap), dtype=torch.float32, device=self.device)
         data[:, :, :self.cap] = self.bank.data
         self.bank = RirBank(data, self.bank.lengths)
@@ -586,14 +634,16 @@ class RirStore:
         n = self._kept_len(r.shape[1])
         self._clipped[slot] = n < r.shape[1]
         self._ensure_cap(n)
-        if self.defer_uploads:
+        if self.defer_uploads or self.spectral_only:
             # batched mode (AudioEngine): the row crosses PCIe with the step's other new rows, as ONE pinned block and ONE
             # H2D copy, when the engine flushes before its launch (flush_uploads).  SoundSpaces 2.0 hands every env a new
             # RIR every step (continuous_simulator.py:419): 128 single-row copies + 128 one-element length fills per step
             # were the whole cost of its batched and deferred modes
             self._pending[slot] = (r, n)
             self.host_len[slot] = n
-            self._stale[slot] = True
+            self._stale[slot] = self._stale_mark
+            if not self.defer_uploads:                          # (spectral-only: rows reach the bank through the staged transform)
+                self.flush_uploads()
             return
         row_t, row, k = self._stage_row()
         row[:, :n] = r[:, :n]
@@ -664,6 +714,13 @@ class RirStore:
                 continue
             k = len(which)
             sl = [slots[j] for j in which]
+            if self.spectral_only:                             # staged rows -> block spectra + lengths, one launch per block
+                pidx, plen = self._pinned_meta("_flush_meta_" + blk_name, k)
+                pidx.numpy()[:k] = sl
+                plen.numpy()[:k] = lens[which]
+                self._scatter_spectra(getattr(self, blk_name), not transpose, pidx, plen, k)
+                self._dev_len[np.asarray(sl)] = lens[which]
+                continue
             dev_blk = getattr(self, blk_name)[:k].to(self.device, non_blocking=True)
             if transpose:
                 dev_blk = dev_blk.permute(0, 2, 1)                 # [k, cap, 2] -> [k, 2, cap]: transposed by the scatter kernel
@@ -739,13 +796,13 @@ class RirStore:
         self._dev_len[sl_np] = lens32
         self.host_len[sl_np] = lens32
         self._clipped[sl_np] = lens < full
-        self._stale[sl_np] = True
+        self._stale[sl_np] = self._stale_mark
 
     def sync_spectra(self) -> int:
         """spectral stores: transform the rows loaded since the last call (contiguous runs, one ss_rir_spectra_f32 each;
         synchronous - this is bank-load work, steady-state steps find nothing to do).  Returns the rows transformed."""
         self.flush_uploads()
-        if not self.spectral or self.bank.spectra is None or not self._stale.any():
+        if not self.spectral or self.spectral_only or self.bank.spectra is None or not self._stale.any():
             return 0
         self._about_to_write()
         idx = np.flatnonzero(self._stale)
@@ -870,14 +927,22 @@ class RirStore:
                     torch.cuda.synchronize(self.device)          # (a scatter may still be reading the old block)
                 d["stage"] = torch.zeros((L.stage_rows, self.cap, 2), dtype=torch.float32, pin_memory=True)
                 L.stage = d["stage"].data_ptr()
-                d["stage_desc"] = torch.zeros((L.stage_rows * 2 * P.ceil_div(self.cap, P.KB) * 5,), dtype=torch.int32, pin_memory=True)
-                L.stage_desc = d["stage_desc"].data_ptr() if self.spectral else None
+                if self.spectral_only:                           # (no rows: the library transforms the staged rows directly)
+                    d["stage_desc"], L.stage_desc = None, None
+                else:
+                    d["stage_desc"] = torch.zeros((L.stage_rows * 2 * P.ceil_div(self.cap, P.KB) * 5,), dtype=torch.int32,
+                                                  pin_memory=True)
+                    L.stage_desc = d["stage_desc"].data_ptr() if self.spectral else None
             d["bank"], d["cap"] = bank.data, self.cap
-            L.bank, L.bank_unit_stride, L.bank_chan_stride, L.cap = bank.data.data_ptr(), bank.data.stride(0), bank.data.stride(1), self.cap
+            if self.spectral_only:                               # ss_miss_loader.bank = NULL: the context's spectra are written
+                L.bank, L.bank_unit_stride, L.bank_chan_stride, L.cap = None, 0, 0, self.cap
+            else:
+                L.bank, L.bank_unit_stride, L.bank_chan_stride, L.cap = (bank.data.data_ptr(), bank.data.stride(0),
+                                                                         bank.data.stride(1), self.cap)
             L.dev_len = bank.lengths.data_ptr()
         L.host_len, L.clipped = self.host_len.ctypes.data, self._clipped.ctypes.data
         L.used, L.use_seq = self._used.ctypes.data, self._use_seq.ctypes.data      # (eviction inside the call: _take_slots' policy)
-        L.spec_stale = self._stale.ctypes.data if self.spectral else None
+        L.spec_stale = self._stale.ctypes.data if self.spectral and not self.spectral_only else None
         L.keep = -1 if self.truncate_to is None else int(self.truncate_to)
         if d["dirs"] is not table_dirs or len(table_dirs) != L.n_table_dirs:
             d["dirs"] = table_dirs
@@ -1017,13 +1082,19 @@ class RirStore:
                     r, n = rows[j * G + g], kept[j * G + g]
                     stage_np[j * G + g, :, :n] = r[:, :n]
                     slots.append(sl + g)
-            idx = torch.as_tensor(slots, dtype=torch.long, device=self.device)
             self._about_to_write()
-            self.bank.data.index_copy_(0, idx, stage.to(self.device, non_blocking=True))
-            self.bank.lengths.index_copy_(0, idx, torch.from_numpy(lens).to(self.device))
+            if self.spectral_only:
+                pidx, plen = self._pinned_meta("_many_meta", len(slots))
+                pidx.numpy()[:len(slots)] = slots
+                plen.numpy()[:len(slots)] = lens
+                self._scatter_spectra(stage, True, pidx, plen, len(slots))
+            else:
+                idx = torch.as_tensor(slots, dtype=torch.long, device=self.device)
+                self.bank.data.index_copy_(0, idx, stage.to(self.device, non_blocking=True))
+                self.bank.lengths.index_copy_(0, idx, torch.from_numpy(lens).to(self.device))
             self._dev_len[np.asarray(slots)] = lens
             self.host_len[np.asarray(slots)] = lens
-            self._stale[np.asarray(slots)] = True
+            self._stale[np.asarray(slots)] = self._stale_mark
             self._clipped[np.asarray(slots)] = [n < r.shape[1] for n, r in zip(kept, rows)]
             if self.device.type == "cuda":
                 torch.cuda.current_stream(self.device).synchronize()   # the pinned block dies with this scope
@@ -1048,6 +1119,8 @@ class RirStore:
             self.bank.data.index_copy_(0, idx, stage[:n_rows].permute(0, 2, 1))
             self.bank.lengths.index_copy_(0, idx, plen[:n_rows])
             return None
+        if self.spectral_only:
+            return self._scatter_spectra(stage, False, pidx, plen, n_rows)
         from . import _lib
         data = self.bank.data
         di = self.device.index if self.device.index is not None else torch.cuda.current_device()
@@ -1065,6 +1138,35 @@ class RirStore:
             return launch()
         with torch.cuda.device(di):
             return launch()
+
+    def _pinned_meta(self, attr: str, k: int):
+        """(slots, lengths): two pinned int32 tensors of >= k entries kept under `attr` (the kernels read them in place)"""
+        meta = getattr(self, attr, None)
+        if meta is None or meta[0].shape[0] < k:
+            meta = tuple(torch.zeros((max(k, 64),), dtype=torch.int32, pin_memory=True) for _ in range(2))
+            setattr(self, attr, meta)
+        return meta
+
+    # spectral-only stores: the transform pulls a pinned block of at most this many rows over the host link itself; larger
+    # blocks cross in one H2D copy first.  One workgroup per (row, block) reads its 128 KiB at the link's latency: 128-env miss
+    # steps (load_files + step, profiles/r7: one sequential run, noisy) with 1 / 6 / 32 new rows took 123 / 200 / 487 us pulled
+    # against 130 / 185 / 368 us copied (the both-forms store: 139 / 203 / 370 us)
+    spectra_pull_rows = 4
+
+    def _scatter_spectra(self, stage, planar: bool, pidx, plen, n_rows: int):
+        """spectral-only stores: rows [0, n_rows) of the pinned staging block `stage` ([*, cap, 2] wav layout, or [*, 2, cap]
+        with planar) -> block spectra of bank entries pidx[i] and their lengths plen[i] (ss_bank_scatter_spectra_f32: one
+        launch, k_stage_spectra).  The kernel pulls small pinned blocks itself (``spectra_pull_rows``), larger ones and every
+        block with ``scatter_from_host`` False go through one H2D copy first.  Returns the event behind the launch (the block
+        may be refilled after it)."""
+        self._about_to_write()
+        pull = self.scatter_from_host and n_rows <= self.spectra_pull_rows
+        src = stage if pull else stage[:n_rows].to(self.device, non_blocking=True)
+        with torch.cuda.device(self.device):
+            ops.scatter_spectra_into(src, planar, pidx, plen, n_rows, self.bank.spectra, self.bank.lengths)
+            ev = torch.cuda.Event()
+            ev.record()
+        return ev
 
     def _file_stage(self, k: int):
         """pinned [_FILE_CHUNK, cap, 2] staging block k & 1 (wav layout), free to be overwritten"""
@@ -1174,7 +1276,7 @@ class RirStore:
             self._fstage_ev[c & 1] = self._scatter_staged(stage, pidx, plen, n_rows)
             self._dev_len[sl_np] = lens
             self.host_len[sl_np] = lens
-            self._stale[sl_np] = True
+            self._stale[sl_np] = self._stale_mark
             self._clipped[sl_np] = lens < full
         for i, key in enumerate(keys):
             if out[i] < 0:
@@ -1197,6 +1299,8 @@ class BucketedRirStore:
     def __init__(self, slots: Sequence[int], caps: Sequence[int], device, truncate_to: Optional[int] = None,
                  max_cap: int = 1 << 18, on_grow=None, group: int = 1, spectral: bool = False):
         assert len(slots) == len(caps) and 1 <= len(caps) <= 4 and list(caps) == sorted(caps)
+        if spectral == "only":
+            raise ValueError("BucketedRirStore: spectral='only' (a spectral-only bank) is not supported with length buckets")
         self.device = torch.device(device)
         self.group, self.on_grow, self.spectral = group, on_grow, spectral
         self.first = [int(v) for v in np.cumsum([0] + list(slots[:-1]))]
@@ -1433,7 +1537,7 @@ class AudioEngine:
     use, longer RIRs grow the bank (RirStore)."""
 
     def __init__(self, sampling_rate: int, device="cuda", rir_slots: int = 4096, rir_cap: Optional[int] = None,
-                 rir_max_cap: int = 1 << 18, rir_group: int = 1, rir_spectral: Optional[bool] = None,
+                 rir_max_cap: int = 1 << 18, rir_group: int = 1, rir_spectral: Union[None, bool, str] = None,
                  rir_buckets: Optional[Sequence[Tuple[int, int]]] = None, spectral_hbm_fraction: float = 0.5,
                  spectral_max_units: int = 0, **renderer_kwargs):
         """rir_spectral: keep the RIR rows' block spectra in HBM as well (2x the bytes per row) and run k_conv_spec /
@@ -1448,7 +1552,22 @@ class AudioEngine:
         from the spectral rows) - what it costs is HBM (rows + spectra = 3 x the rows) and one transform per loaded row, which is why
         it is tied to `spectral_hbm_fraction`.  `spectral_max_units` > 0 restores a per-launch choice: launches of more units than
         that (without distractor terms) read the time-domain rows, and the block spectra of freshly loaded rows are only built
-        when a launch needs them."""
+        when a launch needs them.
+
+        rir_spectral="only": the block spectra WITHOUT the time-domain rows (RirStore(spectral="only")): the fast kernels of a
+        static bank at ~1.5x the entries per byte of HBM (INTEGRATION.md "Spectral-only RIR banks").  Refused (ValueError) with
+        step_time / wrap (SS2.0: live RIRs and the cross-fade read rows), rir_buckets and spectral_max_units > 0."""
+        if isinstance(rir_spectral, str):
+            if rir_spectral != "only":
+                raise ValueError(f"rir_spectral must be None, True, False or 'only', not {rir_spectral!r}")
+            if renderer_kwargs.get("step_time") is not None or renderer_kwargs.get("wrap"):
+                raise ValueError("rir_spectral='only' cannot serve SoundSpaces 2.0 (step_time / wrap): live RIRs and the "
+                                 "cross-fade need time-domain rows")
+            if rir_buckets:
+                raise ValueError("rir_spectral='only' does not support length-bucketed banks (rir_buckets)")
+            if spectral_max_units > 0:
+                raise ValueError("rir_spectral='only' keeps no time-domain rows for the spectral_max_units policy to send "
+                                 "large steps to")
         self.renderer = BatchedAudioRenderer(sampling_rate, device=device, **renderer_kwargs)
         self._native_readers: Dict[int, tuple] = {}              # rir_file_slot: id(reader) -> (stock wav reader?, lenient?, reader)
         self._file_loader = None                                 # RirStore.miss_loader dict of rir_file_slot (ss_ctx_load_rir_files)
@@ -1461,6 +1580,7 @@ class AudioEngine:
                 self.spectral_max_units = int(spectral_max_units)
         self.renderer.spectral_max_units = self.spectral_max_units
         self.rir_spectral = bool(rir_spectral) and not full
+        self.rir_spectral_only = rir_spectral == "only"
         if rir_buckets:
             # length-bucketed bank: [(slots, cap samples), ...] ascending, e.g. [(4096, 16000), (256, 49152), (64, 65536)]
             self.store = BucketedRirStore([b[0] for b in rir_buckets], [b[1] for b in rir_buckets], self.renderer.device,
@@ -1471,7 +1591,8 @@ class AudioEngine:
             return
         self.store = RirStore(rir_slots, rir_cap or sampling_rate, self.renderer.device,
                               truncate_to=None if full else int(sampling_rate), max_cap=rir_max_cap,
-                              on_grow=self.renderer.set_rir_bank, group=rir_group, spectral=rir_spectral and not full)
+                              on_grow=self.renderer.set_rir_bank, group=rir_group,
+                              spectral="only" if self.rir_spectral_only else bool(rir_spectral) and not full)
         self.store.defer_uploads = True            # single-row uploads of a step travel as one block (flushed before every launch)
         self.renderer.set_rir_bank(self.store.bank)
 
@@ -1541,6 +1662,10 @@ class AudioEngine:
                 self._ctx_bank = now
             return ctx
         if n_sync or cur is None or cur[0] is not bank.data or cur[1] is not bank.spectra:   # two data_ptr() calls per step)
+            if bank.spectral_only:                               # (no rows: the context's spectral-only binding)
+                ctx.set_rir_spectra_only(bank.spectra, bank.lengths, bank.cap)
+                self._ctx_bank = (bank.data, bank.spectra)
+                return ctx
             ctx.set_rir_bank(bank.data, bank.lengths)
             if bank.spectra is not None and self.store.spectral:
                 ctx.set_rir_spectra(bank.spectra)
