@@ -89,7 +89,10 @@ int ss_fftconv_binaural_f32(const float* spec, const float* rir, const int* rir_
                             long long rir_unit_stride, int rir_chan_stride, int rir_elem_stride,
                             int rir_cap, int n_valid, int out_len, int flags, void* stream);
 
-/* Spectrogram of x [n_units, 2, len] -> out [n_units, 65, ceil((1+len/160)/4), 2] (channel-last). */
+/* Spectrogram of x [n_units, 2, len] -> out [n_units, 65, ceil((1+len/160)/4), 2] (channel-last).
+ * Any len >= 1 (len <= 0: SS_EINVAL).  Centre padding (256 samples at each end) with SS_PAD_REFLECT follows
+ * np.pad(mode="reflect") at EVERY length: padded position i reads sample (i mod 2(len-1)) folded back at len-1, so rows
+ * shorter than 257 samples are reflected more than once and a row of one sample is repeated - what librosa.stft computes. */
 int ss_spectrogram_f32(const float* x, float* out, int n_units, int len, int pad_mode, void* stream);
 
 /* Fused observation: convolution + spectrogram in ONE launch for rows of up to 3*kB samples (16 kHz: 1 block; 44.1 /
@@ -104,7 +107,9 @@ int ss_spectrogram_f32(const float* x, float* out, int n_units, int len, int pad
  * Small steps of such rows (rows x output blocks <= the launch's share of the CUs: <= 42 units at 44.1 kHz) are rendered by one
  * workgroup per OUTPUT BLOCK (k_obs_blocks): the samples in front of a block boundary are handed to the next block's workgroup
  * through a per-(device, stream) area of 1.3 MB whose flags carry a launch counter - such a launch must not be replayed from a
- * captured hipGraph (the counter would repeat; the library itself never captures). */
+ * captured hipGraph (the counter would repeat; the library itself never captures).
+ * out_len >= 257 (SS_EINVAL below, here and in the *_spec_ / *_buckets_ / 32 forms): the fused kernels reflect the centre
+ * padding once.  Shorter rows: ss_fftconv_binaural_f32, then ss_spectrogram_f32 (any length). */
 int ss_audio_obs_f32(const float* spec, const float* rir, const int* rir_len, const int* unit_desc,
                      float* audiogoal, float* spectrogram, int n_units,
                      long long rir_unit_stride, int rir_chan_stride, int rir_elem_stride,
@@ -161,7 +166,8 @@ int ss_audio_obs_buckets_f32(const float* spec, const ss_rir_bucket* buckets, in
  *   logmel      [n_units, n_mels, T, 2]         as ss_logmel_f32  (n_mels <= 64; larger banks: ss_logmel_f32)
  *   gccphat     [n_units, 2*max_lag+1, T]       as ss_gccphat_f32
  * (NULL = not wanted; at least one).  Same arguments and results as the three stand-alone entry points, which each re-read
- * the waveform and redo the STFT. */
+ * the waveform and redo the STFT: any len >= 1, reflect padding as np.pad at every length (see ss_spectrogram_f32),
+ * 1 <= n_mels <= 64, 1 <= max_lag <= 32, both eps > 0; SS_EINVAL outside. */
 int ss_audio_features_f32(const float* x, int n_units, int len, int pad_mode, float* spectrogram, float* logmel,
                           const int* mel_start, const float* mel_w, int n_mels, int max_len, float mel_eps,
                           float* gccphat, int max_lag, float gcc_eps, void* stream);
@@ -179,14 +185,16 @@ int ss_audio_obs32_f32(const float* spec32, const float* rir, const int* rir_len
                        int rir_cap, int n_valid, int out_len, int pad_mode, void* stream);
 
 /* av_wan Intensity sensor (ss_baselines/av_wan/avwan_sensors.py:91-100) on audiogoal [n_units, 2, len]:
- * onset = min over ears of the first sample > 0.1*max, out[n] = mean(x[:, onset:onset+num_frame]**2). */
+ * onset = min over ears of the first sample > 0.1*max, out[n] = mean(x[:, onset:onset+num_frame]**2) over the samples that
+ * exist (rows may be shorter than num_frame).  len >= 1, num_frame >= 1. */
 int ss_intensity_f32(const float* audiogoal, float* out, int n_units, int len, int num_frame, void* stream);
 
 /* EXTENSION (no counterpart in the reference; BASELINE.json north_star "log-mel"): log-mel spectrogram of
  * x [n_units, 2, len] -> out [n_units, n_mels, 1 + len/160, 2] (channel-last, no pooling):
  *   out = log( sum_k W[j][k] * |STFT(x)[k]|^2 + eps ), STFT framing exactly as ss_spectrogram_f32.
  * The filter bank is band-sparse: band j covers bins mel_start[j] .. mel_start[j] + max_len - 1 with weights
- * mel_w[j*max_len + i] (zero padded).  n_mels <= 128; max_len a multiple of 4, <= 64 (32 bands at 48 kHz; 20-band banks are wider); n_mels*max_len <= 4096;
+ * mel_w[j*max_len + i] (zero padded).  1 <= n_mels <= 128; eps > 0; any len >= 1 (reflect padding as np.pad at every length,
+ * see ss_spectrogram_f32); max_len a multiple of 4, <= 64 (32 bands at 48 kHz; 20-band banks are wider); n_mels*max_len <= 4096;
  * mel_start[j] a multiple of 4 in [0, 256] (pad the band with leading zero weights; the kernel reads 16 bytes at a
  * time and sees zeros beyond bin 256); mel_w 16-byte aligned.  mel_start's range is the caller's responsibility. */
 int ss_logmel_f32(const float* x, float* out, int n_units, int len, int pad_mode, const int* mel_start,
@@ -195,7 +203,8 @@ int ss_logmel_f32(const float* x, float* out, int n_units, int len, int pad_mode
 /* EXTENSION (no counterpart in the reference; BASELINE.json configs[4] "GCC-PHAT"): generalised cross-correlation
  * with phase transform between the two ears, per STFT frame (framing exactly as ss_spectrogram_f32):
  *   G[k] = X_left[k] conj(X_right[k]);  g = irfft(G / (|G| + eps), 512);  out[n][i][t] = g[(i - max_lag) mod 512]
- * x [n_units, 2, len] -> out [n_units, 2*max_lag + 1, 1 + len/160].  1 <= max_lag <= 32, eps > 0. */
+ * x [n_units, 2, len] -> out [n_units, 2*max_lag + 1, 1 + len/160].  1 <= max_lag <= 32 (0 and 33: SS_EINVAL), eps > 0,
+ * any len >= 1 (reflect padding as np.pad at every length, see ss_spectrogram_f32). */
 int ss_gccphat_f32(const float* x, float* out, int n_units, int len, int pad_mode, int max_lag, float eps,
                    void* stream);
 

@@ -304,9 +304,8 @@ __global__ __launch_bounds__(256, 2) void k_features(FeatParams p) {     // two 
                 for (int i = t; i < 2 * kSegLen; i += 256) {
                     const int c = i >= kSegLen, n = s0 + i - c * kSegLen;
                     if (n >= 0 && n < len) continue;
-                    int m = n < 0 ? -n : 2 * (len - 1) - n;                       // reflect, excluding the edge sample
-                    const bool ok = p.pad_mode == 0 && m >= 0 && m < len;
-                    const float v = ok ? row0[(size_t)c * len + m] : 0.f;        // (frames that reach further are not live)
+                    // reflect as np.pad does (period 2(len-1), at every length), or zeros
+                    const float v = p.pad_mode == 0 ? row0[(size_t)c * len + reflect_index(n, len)] : 0.f;
                     segw[(c ? 0 : kSegLen) + (i - c * kSegLen)] = v;
                 }
             }

@@ -516,7 +516,7 @@ int ss_spectrogram_f32(const float* x, float* out, int n_units, int len, int pad
 
 static int spectrogram_of_rows(const float* x, float* out, int n_units, int len, int n_valid, int pad_mode, void* stream) {
     if (n_units == 0) return 0;
-    if (!x || !out || n_units < 0 || len < ssk::kNfft / 2 + 1) return SS_EINVAL;   // reflect pad needs len > 256
+    if (!x || !out || n_units < 0 || len < 1) return SS_EINVAL;   // any length: the centre padding folds as np.pad does
     if (pad_mode != SS_PAD_REFLECT && pad_mode != SS_PAD_CONSTANT) return SS_EINVAL;
     ssk::SpecParams p;
     int rc = get_tables(&p.tb);
@@ -542,7 +542,7 @@ static int spectrogram_of_rows(const float* x, float* out, int n_units, int len,
 int ss_logmel_f32(const float* x, float* out, int n_units, int len, int pad_mode, const int* mel_start,
                   const float* mel_w, int n_mels, int max_len, float eps, void* stream) {
     if (n_units == 0) return 0;
-    if (!x || !out || !mel_start || !mel_w || n_units < 0 || len < ssk::kNfft / 2 + 1) return SS_EINVAL;
+    if (!x || !out || !mel_start || !mel_w || n_units < 0 || len < 1) return SS_EINVAL;
     if (pad_mode != SS_PAD_REFLECT && pad_mode != SS_PAD_CONSTANT) return SS_EINVAL;
     if (n_mels < 1 || n_mels > ssk::kMelMaxBands || max_len < 4 || max_len > ssk::kMelMaxLen || (max_len & 3) ||
         n_mels * max_len > ssk::kMelTableFloats || !(eps > 0.f) || (reinterpret_cast<size_t>(mel_w) & 15))
@@ -571,7 +571,7 @@ int ss_logmel_f32(const float* x, float* out, int n_units, int len, int pad_mode
 int ss_gccphat_f32(const float* x, float* out, int n_units, int len, int pad_mode, int max_lag, float eps,
                    void* stream) {
     if (n_units == 0) return 0;
-    if (!x || !out || n_units < 0 || len < ssk::kNfft / 2 + 1) return SS_EINVAL;
+    if (!x || !out || n_units < 0 || len < 1) return SS_EINVAL;
     if (pad_mode != SS_PAD_REFLECT && pad_mode != SS_PAD_CONSTANT) return SS_EINVAL;
     if (max_lag < 1 || max_lag > ssk::kGccMaxLag || !(eps > 0.f)) return SS_EINVAL;
     ssk::GccParams p;
@@ -596,7 +596,7 @@ int ss_audio_features_f32(const float* x, int n_units, int len, int pad_mode, fl
                           const int* mel_start, const float* mel_w, int n_mels, int max_len, float mel_eps, float* gccphat,
                           int max_lag, float gcc_eps, void* stream) {
     if (n_units == 0) return 0;
-    if (!x || n_units < 0 || len < ssk::kNfft / 2 + 1 || (!spectrogram && !logmel && !gccphat)) return SS_EINVAL;
+    if (!x || n_units < 0 || len < 1 || (!spectrogram && !logmel && !gccphat)) return SS_EINVAL;
     if (pad_mode != SS_PAD_REFLECT && pad_mode != SS_PAD_CONSTANT) return SS_EINVAL;
     if (logmel && (!mel_start || !mel_w || n_mels < 1 || n_mels > ssk::kFeatMaxMels || max_len < 4 ||
                    max_len > ssk::kFeatMaxLen || (max_len & 3) || n_mels * max_len > ssk::kFeatMelTable || !(mel_eps > 0.f) ||

@@ -385,6 +385,25 @@ __host__ __device__ constexpr int live_blocks(int n_valid, int len, int t4) {
 constexpr int kSegFrames = 16, kSegLen = kHop * (kSegFrames - 1) + kNfft;     // 2912 samples
 constexpr int kSegQuads = kSegLen / 4;                                         // 728 float4 per ear
 
+// librosa / np.pad(mode="reflect") centre padding at ANY row length: position i of the padded row reads sample
+// (i mod 2(len-1)), folded back at len-1 - the row keeps reflecting, however short it is (a frame reaches 256 samples past
+// each end; rows under 257 samples are crossed more than once).  len == 1 has period 0: every position reads sample 0.
+// Branch-free (no exec-mask bookkeeping in kernels that sit at their SGPR limit): the quotient comes from a float product with
+// a reciprocal rounded DOWN by 2^-20, so it is the true quotient or one less and one conditional subtraction finishes the
+// remainder.  That holds where it matters - a quotient above 1 needs a position beyond one period, and positions stay within
+// len + kSegLen of the row, so then both are below 2^13 and exact in float; on longer rows the true quotient is 0 or 1 and the
+// rounding of a large i (2^-24) stays inside the 2^-20.  The two min() are the conditional subtraction (a negative difference is
+// a huge unsigned) and the fold at len-1 (period - r < r exactly when r >= len).  Edge paths only.
+__host__ __device__ __forceinline__ int reflect_index(int i, int len) {
+    const int period = 2 * (len - 1) > 1 ? 2 * (len - 1) : 1;      // (len 1: every position mod 1 = 0)
+    const float rcp = (1.f / static_cast<float>(period)) * (1.f - 1.f / 1048576.f);
+    i = i < 0 ? -i : i;                                             // the fold is even in i
+    unsigned r = static_cast<unsigned>(i - static_cast<int>(static_cast<float>(i) * rcp) * period);    // in [0, 2 period)
+    r = r < r - static_cast<unsigned>(period) ? r : r - static_cast<unsigned>(period);
+    const int a = static_cast<int>(r), b = period - a;
+    return a < b ? a : b;
+}
+
 // the (up to) 3 float4 of the two-ear segment of group g that thread t stages: quad e4 = t + 512 k.
 // Interior groups (the segment lies inside the row; workgroup-uniform test) take a path WITHOUT per-lane branches:
 // three unconditional 16-byte loads from clamped addresses and nothing that touches the loaded values.  With the per-lane
@@ -394,19 +413,22 @@ constexpr int kSegQuads = kSegLen / 4;                                         /
 __device__ __forceinline__ void spec_seg_load(const SpecParams& p, const float* row0, int g, int t, f32x4 (&r)[3]) {
     const int s0 = kHop * kSegFrames * g - kNfft / 2;
     const bool vec_ok = !(p.len & 3) && !(reinterpret_cast<size_t>(row0) & 15);
-    if (vec_ok && s0 >= 0 && s0 + kSegLen <= p.len) {
+    if (s0 >= 0 && s0 + kSegLen <= p.len) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             const int e4 = t + 512 * k;
             const int e = e4 < 2 * kSegQuads ? e4 : 0;      // clamp: the load is unconditional
             const int c = e >= kSegQuads, n = s0 + 4 * (e - c * kSegQuads);
-            // no select on the loaded value (it would force the wait here): quads >= 2*kSegQuads are never stored
-            r[k] = *reinterpret_cast<const f32x4*>(row0 + (size_t)c * p.len + n);
+            const float* q = row0 + (size_t)c * p.len + n;
+            // no select on the loaded value (it would force the wait here): quads >= 2*kSegQuads are never stored.
+            // Rows of odd length / unaligned base (workgroup-uniform): the same samples by 4-byte loads
+            if (vec_ok) r[k] = *reinterpret_cast<const f32x4*>(q);
+            else r[k] = f32x4{q[0], q[1], q[2], q[3]};
         }
         return;
     }
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {                           // first / last group of a row, odd lengths, unaligned rows
+    for (int k = 0; k < 3; ++k) {                           // first / last group of a row: the centre padding
         const int e4 = t + 512 * k;
         const int c = e4 >= kSegQuads, n = s0 + 4 * (e4 - c * kSegQuads);
         const float* row = row0 + (size_t)c * p.len;
@@ -419,7 +441,7 @@ __device__ __forceinline__ void spec_seg_load(const SpecParams& p, const float* 
 #pragma unroll
             for (int u = 0; u < 4; ++u) {                   // librosa centre padding, resolved once per sample
                 int i = n + u;
-                if (p.pad_mode == 0) { i = i < 0 ? -i : i; i = i >= p.len ? 2 * (p.len - 1) - i : i; }
+                if (p.pad_mode == 0) i = reflect_index(i, p.len);
                 const bool ok = i >= 0 && i < p.len;
                 const float q = row[ok ? i : 0];
                 v[u] = ok ? q : 0.f;
@@ -1935,6 +1957,9 @@ __device__ __forceinline__ void rows_stft_phase(c32* lds, const ConvParams& p, i
     // (a wait that ran out - the producer never came: not reachable under the launcher's "grid fits the chip" rule - poisons the
     //  block's first frames instead of rendering them from stale samples: NaN in the observation, not a plausible wrong value)
     if (GLOBAL_TAIL && j > 0 && t < ctx) buf[t] = tail_ok ? ld_agent(tail_in + t) : __builtin_nanf("");
+    // a last block of fewer than 257 samples: the right padding below mirrors INTO the context that was just loaded
+    // (workgroup-uniform test; without GLOBAL_TAIL the context is in place before the barrier above)
+    if (GLOBAL_TAIL && j > 0 && last && len - base <= kNfft / 2) lds_barrier();
     if (j == 0 && t < kNfft / 2) yl[-1 - t] = p.pad_mode == 0 ? yl[1 + t] : 0.f;              // left centre padding
     if (last && t >= 256 && t < 256 + kNfft / 2) {        // right centre padding: sample len + k = sample len - 2 - k
         const int k = t - 256;

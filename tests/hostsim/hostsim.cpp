@@ -404,6 +404,7 @@ int hs_spectrogram(const float* x, float* out, int n_units, int len, int pad_mod
     p.len = len; p.n_frames = 1 + len / ssk::kHop; p.t4 = (p.n_frames + 3) / 4; p.pad_mode = pad_mode;
     p.live = g_spec_n_valid >= 0 ? ssk::live_blocks(g_spec_n_valid, len, p.t4) : p.t4;
     g_spec_n_valid = -1;
+    if (len < 1) return -2;                             // (the entry points' own argument checks, here and below)
     const int groups = (p.t4 + 3) / 4;
     p.gpw = gpw < 1 ? 1 : gpw > groups ? groups : gpw;
     const int chunks = (groups + p.gpw - 1) / p.gpw;
@@ -422,7 +423,7 @@ int hs_logmel(const float* x, float* out, int n_units, int len, int pad_mode, co
     p.x = x; p.out = out; p.tb = host_tables(); p.start = start; p.w = w;
     p.len = len; p.n_frames = 1 + len / ssk::kHop; p.pad_mode = pad_mode;
     p.n_mels = n_mels; p.max_len = max_len; p.eps = eps;
-    if (n_mels > ssk::kMelMaxBands || max_len > ssk::kMelMaxLen || (max_len & 3) || n_mels * max_len > ssk::kMelTableFloats) return -2;
+    if (len < 1 || n_mels < 1 || n_mels > ssk::kMelMaxBands || max_len > ssk::kMelMaxLen || (max_len & 3) || n_mels * max_len > ssk::kMelTableFloats) return -2;
     const int groups = (p.n_frames + ssk::kSegFrames - 1) / ssk::kSegFrames;
     p.gpw = gpw < 1 ? 1 : gpw > groups ? groups : gpw;
     const int chunks = (groups + p.gpw - 1) / p.gpw;
@@ -439,7 +440,7 @@ int hs_gccphat(const float* x, float* out, int n_units, int len, int pad_mode, i
     ssk::GccParams p;
     p.x = x; p.out = out; p.tb = host_tables();
     p.len = len; p.n_frames = 1 + len / ssk::kHop; p.pad_mode = pad_mode; p.max_lag = max_lag; p.eps = eps;
-    if (max_lag < 1 || max_lag > ssk::kGccMaxLag) return -2;
+    if (len < 1 || max_lag < 1 || max_lag > ssk::kGccMaxLag) return -2;
     const int groups = (p.n_frames + ssk::kSegFrames - 1) / ssk::kSegFrames;
     p.gpw = gpw < 1 ? 1 : gpw > groups ? groups : gpw;
     const int chunks = (groups + p.gpw - 1) / p.gpw;
@@ -459,7 +460,8 @@ int hs_features(const float* x, int n_units, int len, int pad_mode, float* sgram
     p.len = len; p.n_frames = 1 + len / ssk::kHop; p.t4 = (p.n_frames + 3) / 4; p.pad_mode = pad_mode;
     p.n_mels = mel ? n_mels : 0; p.max_len = mel ? max_len : 4; p.max_lag = gcc ? max_lag : 1;
     p.mel_eps = mel_eps; p.gcc_eps = gcc_eps;
-    if (mel && (n_mels > ssk::kFeatMaxMels || max_len > ssk::kFeatMaxLen || (max_len & 3) || n_mels * max_len > ssk::kFeatMelTable)) return -2;
+    if (len < 1 || (!sgram && !mel && !gcc)) return -2;
+    if (mel && (n_mels < 1 || n_mels > ssk::kFeatMaxMels || max_len > ssk::kFeatMaxLen || (max_len & 3) || n_mels * max_len > ssk::kFeatMelTable)) return -2;
     if (gcc && (max_lag < 1 || max_lag > ssk::kGccMaxLag)) return -2;
     const int groups = (p.n_frames + ssk::kSegFrames - 1) / ssk::kSegFrames;
     p.n_units = n_units;

@@ -41,7 +41,8 @@ def test_argument_checks_return_einval_without_a_gpu():
     assert lib.ss_fftconv_binaural_f32(one, one, one, one, one, 2, 32000, 16000, 1, 16000, 16001, 16000, 0, null) == -1   # n_valid > out_len
     assert lib.ss_fftconv_binaural_f32(one, one, one, one, one, 2, 32000, 16000, 0, 16000, 16000, 16000, 0, null) == -1   # elem stride 0
     assert lib.ss_fftconv_binaural_f32(one, one, one, one, one, 0, 32000, 16000, 1, 16000, 16000, 16000, 0, null) == 0
-    assert lib.ss_spectrogram_f32(one, one, 1, 100, 0, null) == -1                       # shorter than the reflect pad
+    assert lib.ss_spectrogram_f32(one, one, 1, 0, 0, null) == -1                         # no samples (any len >= 1 is served:
+    assert lib.ss_spectrogram_f32(one, one, 1, -100, 0, null) == -1                      #  the reflect pad folds as np.pad does)
     assert lib.ss_spectrogram_f32(one, one, 1, 16000, 7, null) == -1                     # unknown pad mode
     assert lib.ss_audio_obs_f32(one, one, one, one, null, null, 1, 32000, 16000, 1, 16000, 16000, 16000, 0, 0, null) == -1
     assert lib.ss_intensity_f32(one, one, 1, 16000, 0, null) == -1
@@ -55,7 +56,9 @@ def test_argument_checks_return_einval_without_a_gpu():
     assert lib.ss_logmel_f32(one, one, 0, 16000, 0, one, one, 64, 24, f(1e-6), null) == 0           # empty batch
     assert lib.ss_gccphat_f32(one, one, 1, 16000, 0, 33, f(1e-8), null) == -1                       # max_lag > 32
     assert lib.ss_gccphat_f32(one, one, 1, 16000, 0, 0, f(1e-8), null) == -1
-    assert lib.ss_gccphat_f32(one, one, 1, 100, 0, 8, f(1e-8), null) == -1                          # too short
+    assert lib.ss_gccphat_f32(one, one, 1, 0, 0, 8, f(1e-8), null) == -1                            # no samples
+    assert lib.ss_logmel_f32(one, one, 1, 0, 0, one, one, 64, 24, f(1e-6), null) == -1
+    assert lib.ss_logmel_f32(one, one, 1, 16000, 0, one, one, 0, 24, f(1e-6), null) == -1           # no bands
     assert lib.ss_gccphat_f32(one, null, 1, 16000, 0, 8, f(1e-8), null) == -1
 
 
@@ -82,7 +85,7 @@ def test_header_is_plain_c(tmp_path):
         'int main(void) {\n'
         '  /* argument checks only: no device needed */\n'
         '  if (ss_block_len() != 16384 || ss_spec_floats() != 32768) return 1;\n'
-        '  if (ss_spectrogram_f32((const float*)16, (float*)16, 1, 100, SS_PAD_REFLECT, 0) != SS_EINVAL) return 2;\n'
+        '  if (ss_spectrogram_f32((const float*)16, (float*)16, 1, 0, SS_PAD_REFLECT, 0) != SS_EINVAL) return 2;\n'
         '  if (ss_gccphat_f32((const float*)16, (float*)16, 1, 16000, SS_PAD_CONSTANT, 99, 1e-8f, 0) != SS_EINVAL) return 3;\n'
         '  if (ss_fftconv_binaural_f32(0, 0, 0, 0, 0, 0, 0, 0, 1, 0, 0, 1, SS_FLAG_NO_DISTRACTOR, 0) != 0) return 4;\n'
         '  return 0;\n'
