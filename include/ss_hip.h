@@ -61,7 +61,8 @@ int ss_version(void);
 int ss_init(void);
 /* Rows longer than kB (44.1 kHz) make the library keep a scratch per (device, stream) for the block spectra of the rows in
  * flight (96 MiB per stream at 44.1 kHz without distractors), allocated by the stream's first such call (not inside a
- * hipGraph capture: warm the stream up first).  This frees all of them (after a device synchronise). */
+ * hipGraph capture: warm the stream up first).  This frees all of them (after a device synchronise), and the contexts'
+ * waveform scratches of ss_ctx_observe_features (which grow again on demand). */
 int ss_release_scratch(void);
 
 /* Source-window spectra.  win_desc[w] = {src_offset, src_len, start, wrap} (int32 x4):
@@ -132,6 +133,25 @@ int ss_fftconv_binaural_spec_f32(const float* spec, const float* hspec, const in
 int ss_audio_obs_spec_f32(const float* spec, const float* hspec, const int* rir_len, const int* unit_desc,
                           float* audiogoal, float* spectrogram, int n_units, int h_blocks, int n_valid, int out_len,
                           int pad_mode, int flags, void* stream);
+
+/* Log-mel observation in ONE launch, without a waveform buffer (EXTENSION): the fused kernels' STFT phase goes on from the
+ * power spectrum to the mel bands, logmel[n, j, tf, c] = exactly what ss_logmel_f32 of the row ss_audio_obs_f32 writes would
+ * give (samples >= n_valid zero, centre padding by pad_mode), and - when `spectrogram` is given - the pooled spectrogram of the
+ * same frames (equal to ss_audio_obs_f32's to rounding).  `logmel` [n, n_mels, 1 + out_len/160, 2] is required; `audiogoal`
+ * and `spectrogram` may each be NULL (an audiogoal buffer is written as by ss_audio_obs_f32).  mel arguments as
+ * ss_audio_features_f32: n_mels <= 64, max_len <= 64 and a multiple of 4, n_mels * max_len <= 3072, mel_start[j] multiples of 4
+ * in [0, 256], mel_w 16-byte aligned, mel_eps > 0.  Served shapes: rows of one partition block, 257 <= out_len <= kB (16 kHz),
+ * without SS_FLAG_CROSSFADE; any RIR length and distractor terms are fine.  Everything else is SS_EINVAL from the argument
+ * checks, before a device is touched: this level owns no scratch to fall back on (ss_ctx_observe_features does). */
+int ss_audio_obs_logmel_f32(const float* spec, const float* rir, const int* rir_len, const int* unit_desc,
+                            float* audiogoal, float* spectrogram, float* logmel, const int* mel_start, const float* mel_w,
+                            int n_mels, int max_len, float mel_eps, int n_units, long long rir_unit_stride,
+                            int rir_chan_stride, int rir_elem_stride, int rir_cap, int n_valid, int out_len, int pad_mode,
+                            int flags, void* stream);
+int ss_audio_obs_logmel_spec_f32(const float* spec, const float* hspec, const int* rir_len, const int* unit_desc,
+                                 float* audiogoal, float* spectrogram, float* logmel, const int* mel_start,
+                                 const float* mel_w, int n_mels, int max_len, float mel_eps, int n_units, int h_blocks,
+                                 int n_valid, int out_len, int pad_mode, int flags, void* stream);
 
 /* ---- Length-bucketed RIR bank ------------------------------------------------------------------------
  * The reference's RIRs are variable-length wav files (soundspaces/README.md:38-42, read at simulator.py:615-618; SS2.0's
@@ -277,10 +297,21 @@ int ss_ctx_set_rir_buckets(ss_ctx* ctx, const ss_rir_bucket* buckets, int n_buck
 int ss_ctx_observe(ss_ctx* ctx, const ss_units* units, int n, float* audiogoal, float* spectrogram, void* stream);
 /* One step plus its STFT-derived extension features (BASELINE.json configs[4]: savi, "GCC-PHAT + log-mel fused sensor"): as
  * ss_ctx_observe, then ss_audio_features_f32 over the step's waveform on the SAME stream (in overlap mode: the same internal
- * lane), so the features need no join of their own.  audiogoal must be given (the features read it); logmel / gccphat of
- * `f` may each be NULL.  When a spectrogram is asked for as well it is pooled by the feature kernel (which holds every
- * frame's spectrum of both ears anyway) and the convolution launch runs without its fused STFT phase: 96.5 instead of 108 us
- * per 256-env savi step. */
+ * lane), so the features need no join of their own.  logmel / gccphat of `f` may each be NULL (not both).  With an audiogoal
+ * buffer and a spectrogram asked for as well, the spectrogram is pooled by the feature kernel (which holds every frame's
+ * spectrum of both ears anyway) and the convolution launch runs without its fused STFT phase: 96.5 instead of 108 us per
+ * 256-env savi step.
+ * audiogoal == NULL is accepted for log-mel without GCC-PHAT (f->logmel != NULL, f->gccphat == NULL; GCC-PHAT reads both ears'
+ * waveform and stays SS_EINVAL without a buffer); spectrogram may then be NULL too.  Such a step takes
+ *   - ONE fused launch (ss_audio_obs_logmel_f32 / _spec_f32; no waveform anywhere) when its rows are one partition block
+ *     (257 <= sr <= kB: 16 kHz), the step has no cross-fade, the bank is a single allocation of either form (also the
+ *     spectral-only binding) and its unit count lies inside ss_ctx_set_logmel_policy's range;
+ *   - otherwise (44.1 / 48 kHz rows, cross-faded steps, bucketed banks, unit counts outside the range) the route ss_ctx_observe
+ *     takes with an audiogoal buffer, into a waveform scratch the CONTEXT owns ([n, 2, sr] floats per overlap lane, grown on
+ *     demand, freed with the context and by ss_release_scratch; a growth needed while the stream is being captured is refused
+ *     with SS_EINVAL: warm the stream up first), then ss_audio_features_f32 over it: bit for bit ss_ctx_observe +
+ *     ss_audio_features_f32.
+ * Calls that pass an audiogoal buffer take exactly the route described first. */
 typedef struct ss_features {
     float* logmel;            /* [n, n_mels, 1 + sr/160, 2] or NULL */
     const int* mel_start;     /* device, [n_mels]          (ss_logmel_f32's band-sparse filter bank) */
@@ -293,6 +324,10 @@ typedef struct ss_features {
 } ss_features;
 int ss_ctx_observe_features(ss_ctx* ctx, const ss_units* units, int n, float* audiogoal, float* spectrogram,
                             const ss_features* f, void* stream);
+/* Which log-mel steps without a waveform buffer take the fused launch: those of min_units <= n <= max_units units (and a shape
+ * it serves, see above).  Default: the range in which the fused launch measured faster than the two launches it replaces
+ * (profiles/r7/kbench_obs_logmel.txt).  (1, INT_MAX): whenever the shape allows; max_units < min_units: never. */
+int ss_ctx_set_logmel_policy(ss_ctx* ctx, int min_units, int max_units);
 /* Overlap mode.  ss_ctx_set_overlap(ctx, n), n = 2 .. 4: consecutive ss_ctx_observe calls run on n internal streams in turn
  * (2: the head of step k+1 under the tail of step k; 3 - 4: for steps of few rows, where several launches fit the chip side by
  * side - fused rows are then split over fewer workgroups, ConvParams::parts_log2 - and the caller has that many to issue), each

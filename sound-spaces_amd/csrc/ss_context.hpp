@@ -113,6 +113,8 @@ struct Context {
     int n_lanes = 1, lane_next = 0;
     void* miss_ev = nullptr;            // hipEvent_t behind the last scatter of ss_ctx_observe_requests_load (its staging block is reused)
     int spectral_max_units = 0;         // ss_ctx_set_spectral_policy: one-block rows take the spectral bank only for steps of <= this many units (0: always)
+    // ss_ctx_set_logmel_policy: log-mel steps without a waveform buffer take the fused launch for min <= units <= max
+    int mel_fused_min_units = 1, mel_fused_max_units = 0x7fffffff;
     int chip_share = 0;                 // ss_ctx_set_chip_share: launch sources the chip is shared with (0: the lane count)
     hipStream_t lane_stream[kLanes] = {};
     bool lane_dirty[kLanes] = {};                 // work issued on the lane since ev_lane was last recorded

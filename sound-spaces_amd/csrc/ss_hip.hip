@@ -367,6 +367,78 @@ int launch_obs_rows(ssk::ConvParams p, int n_units, int flags, int n_cus, hipStr
     return hip_err(hipGetLastError());
 }
 
+// ---- log-mel form of the fused one-block kernels (k_conv / k_conv_spec <.., MEL>): one workgroup per row, no unit table ----
+// the mel arguments of the fused entries: the limits of ss_audio_features_f32
+inline bool mel_args_ok(const float* logmel, const int* mel_start, const float* mel_w, int n_mels, int max_len, float eps) {
+    return logmel && mel_start && mel_w && n_mels >= 1 && n_mels <= ssk::kFeatMaxMels && max_len >= 4 &&
+           max_len <= ssk::kFeatMaxLen && !(max_len & 3) && n_mels * max_len <= ssk::kFeatMelTable && eps > 0.f &&
+           !(reinterpret_cast<size_t>(mel_w) & 15);
+}
+// rows the log-mel form serves: one partition block, long enough for the reflect padding, no cross-fade
+inline bool obs_logmel_shape_ok(int out_len, int flags) {
+    return out_len >= ssk::kNfft / 2 + 1 && out_len <= ssk::kB && !(flags & SS_FLAG_CROSSFADE);
+}
+
+int launch_conv_mel(ssk::ConvParams p, const ssk::MelArgs& m, int n_units, int flags, hipStream_t st) {
+    p.nb_y = 1;
+    p.parts_log2 = 0;
+    const bool simple = (flags & SS_FLAG_NO_DISTRACTOR) && p.rir_cap <= ssk::kB && p.n_buckets == 1;
+    const dim3 grid(2 * n_units), block(ssk::kT);
+    if (simple) hipLaunchKernelGGL((ssk::k_conv<true, true, false, false, false, true>), grid, block, 0, st, p, m);
+    else hipLaunchKernelGGL((ssk::k_conv<true, false, false, false, false, true>), grid, block, 0, st, p, m);
+    return hip_err(hipGetLastError());
+}
+
+int launch_conv_spec_mel(ssk::ConvParams p, const ssk::MelArgs& m, int n_units, int flags, hipStream_t st) {
+    p.nb_y = 1;
+    p.parts_log2 = 0;
+    const bool simple = (flags & SS_FLAG_NO_DISTRACTOR) && p.h_blocks == 1 && p.n_buckets == 1;
+    const dim3 grid(2 * n_units), block(ssk::kT);
+    if (simple) hipLaunchKernelGGL((ssk::k_conv_spec<true, true, false, true>), grid, block, 0, st, p, m);
+    else hipLaunchKernelGGL((ssk::k_conv_spec<true, false, false, true>), grid, block, 0, st, p, m);
+    return hip_err(hipGetLastError());
+}
+
+// Waveform scratch of the contexts: ss_ctx_observe_features without an audiogoal buffer, on the shapes the log-mel form does
+// not serve, renders into [n, 2, sr] floats the library owns - one buffer per (context, overlap lane), grown on demand, freed
+// with the context (drop_wave_scratch) and by ss_release_scratch.  A growth needed while the stream is being captured is
+// refused (an allocation cannot be part of a capture: warm the stream up first).
+struct WaveScratch { float* ptr = nullptr; size_t floats = 0; int dev = 0; };
+std::map<std::pair<const void*, int>, WaveScratch> g_wave_scratch;
+
+int get_wave_scratch(const void* owner, int lane, hipStream_t st, size_t floats, float** out) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    WaveScratch& b = g_wave_scratch[std::make_pair(owner, lane)];
+    if (b.floats < floats) {
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(st, &cap) != hipSuccess) { (void)hipGetLastError(); return SS_EINVAL; }
+        if (cap != hipStreamCaptureStatusNone) return SS_EINVAL;
+        hipError_t e = hipGetDevice(&b.dev);
+        if (e != hipSuccess) return hip_err(e);
+        if (b.ptr) {
+            e = hipDeviceSynchronize();                         // earlier steps may still read the old buffer
+            if (e != hipSuccess) return hip_err(e);
+            (void)hipFree(b.ptr);
+            b.ptr = nullptr; b.floats = 0;
+        }
+        e = hipMalloc(reinterpret_cast<void**>(&b.ptr), floats * sizeof(float));
+        if (e != hipSuccess) { b.ptr = nullptr; return hip_err(e); }
+        b.floats = floats;
+    }
+    *out = b.ptr;
+    return 0;
+}
+
+// the context is going away (its streams have been synchronised by the caller or belong to the caller)
+void drop_wave_scratch(const void* owner) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    for (auto it = g_wave_scratch.begin(); it != g_wave_scratch.end();) {
+        if (it->first.first != owner) { ++it; continue; }
+        if (it->second.ptr) { (void)hipDeviceSynchronize(); (void)hipFree(it->second.ptr); }
+        it = g_wave_scratch.erase(it);
+    }
+}
+
 template <bool FUSE>
 int launch_conv32(ssk::ConvParams& p, int n_units, hipStream_t st) {
     const dim3 grid(2 * n_units), block(ssk::kT32);
@@ -410,6 +482,16 @@ int ss_release_scratch(void) {
         kv.second.tails = nullptr;
     }
     for (auto it = g_sync.begin(); it != g_sync.end();) it = it->second.tails ? std::next(it) : g_sync.erase(it);
+    for (auto& kv : g_wave_scratch) {                           // the contexts' waveform scratches (grown again on demand)
+        if (!kv.second.ptr) continue;
+        e = hipSetDevice(kv.second.dev);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e != hipSuccess) { rc = hip_err(e); continue; }
+        (void)hipFree(kv.second.ptr);
+        kv.second.ptr = nullptr;
+        kv.second.floats = 0;
+    }
+    for (auto it = g_wave_scratch.begin(); it != g_wave_scratch.end();) it = it->second.ptr ? std::next(it) : g_wave_scratch.erase(it);
     (void)hipSetDevice(cur);
     return rc;
 }
@@ -669,6 +751,28 @@ int ss_audio_obs_f32(const float* spec, const float* rir, const int* rir_len, co
     return spectrogram_of_rows(audiogoal, spectrogram, n_units, out_len, n_valid, pad_mode, stream);
 }
 
+// Log-mel observation in ONE launch, no waveform buffer needed (k_conv<.., MEL>): rows of one partition block only.  Every
+// argument is checked before a device is touched - this level owns no scratch to fall back on.
+int ss_audio_obs_logmel_f32(const float* spec, const float* rir, const int* rir_len, const int* unit_desc, float* audiogoal,
+                            float* spectrogram, float* logmel, const int* mel_start, const float* mel_w, int n_mels, int max_len,
+                            float mel_eps, int n_units, long long rir_unit_stride, int rir_chan_stride, int rir_elem_stride,
+                            int rir_cap, int n_valid, int out_len, int pad_mode, int flags, void* stream) {
+    if (n_units == 0) return 0;
+    if (n_units < 0 || !mel_args_ok(logmel, mel_start, mel_w, n_mels, max_len, mel_eps)) return SS_EINVAL;
+    if (pad_mode != SS_PAD_REFLECT && pad_mode != SS_PAD_CONSTANT) return SS_EINVAL;
+    if (!obs_logmel_shape_ok(out_len, flags)) return SS_EINVAL;
+    ssk::ConvParams p;
+    int n_cus = 1;
+    int rc = fill_conv(p, &n_cus, spec, rir, rir_len, unit_desc, rir_unit_stride, rir_chan_stride, rir_elem_stride,
+                       rir_cap, n_valid, out_len);
+    if (rc) return rc;
+    p.pad_mode = pad_mode;
+    p.out = audiogoal;
+    p.sgram = spectrogram;
+    const ssk::MelArgs m{logmel, mel_start, mel_w, n_mels, max_len, mel_eps};
+    return launch_conv_mel(p, m, n_units, flags, static_cast<hipStream_t>(stream));
+}
+
 // ---- 512-thread FFT core (ss_kernels32.hpp): loop-free rows only; spectra in that core's own register order ----------
 int ss_source_windows32_f32(const float* src, const int* win_desc, float* spec_out, int n_windows, void* stream) {
     if (n_windows == 0) return 0;
@@ -898,6 +1002,28 @@ int ss_audio_obs_spec_f32(const float* spec, const float* hspec, const int* rir_
     return spectrogram_of_rows(audiogoal, spectrogram, n_units, out_len, n_valid, pad_mode, stream);
 }
 
+// ss_audio_obs_logmel_f32 from the spectral bank (k_conv_spec<.., MEL>)
+int ss_audio_obs_logmel_spec_f32(const float* spec, const float* hspec, const int* rir_len, const int* unit_desc, float* audiogoal,
+                                 float* spectrogram, float* logmel, const int* mel_start, const float* mel_w, int n_mels,
+                                 int max_len, float mel_eps, int n_units, int h_blocks, int n_valid, int out_len, int pad_mode,
+                                 int flags, void* stream) {
+    if (n_units == 0) return 0;
+    if (n_units < 0 || !hspec || h_blocks < 1 || !mel_args_ok(logmel, mel_start, mel_w, n_mels, max_len, mel_eps)) return SS_EINVAL;
+    if (pad_mode != SS_PAD_REFLECT && pad_mode != SS_PAD_CONSTANT) return SS_EINVAL;
+    if (!obs_logmel_shape_ok(out_len, flags)) return SS_EINVAL;
+    ssk::ConvParams p;
+    int n_cus = 1;
+    int rc = fill_conv(p, &n_cus, spec, nullptr, rir_len, unit_desc, 0, 0, 1, 0, n_valid, out_len, false);
+    if (rc) return rc;
+    p.pad_mode = pad_mode;
+    p.hspec = reinterpret_cast<const ssk::f32x4*>(hspec);
+    p.h_blocks = h_blocks;
+    p.out = audiogoal;
+    p.sgram = spectrogram;
+    const ssk::MelArgs m{logmel, mel_start, mel_w, n_mels, max_len, mel_eps};
+    return launch_conv_spec_mel(p, m, n_units, flags, static_cast<hipStream_t>(stream));
+}
+
 // ---- context API (include/ss_hip.h): planner + window-spectra cache + descriptor ring inside the library --------------
 struct ss_ctx { ssctx::Context c; };
 
@@ -926,6 +1052,7 @@ static void ctx_free_device(ssctx::Context& c) {
     if (c.h_win) (void)hipHostFree(c.h_win);
     if (c.ag_scratch) (void)hipFree(c.ag_scratch);
     c.ag_scratch = nullptr; c.ag_cap = 0;
+    drop_wave_scratch(&c);
     if (c.ev_made)
         for (int k = 0; k < ssctx::kRing / ssctx::kGroup; ++k) (void)hipEventDestroy(c.ev_done[k]);
     if (c.ev_xstream) (void)hipEventDestroy(c.ev_xstream);
@@ -1121,8 +1248,11 @@ static int ctx_ensure_pool(ssctx::Context& c, hipStream_t st) {
 // One step: plan the units (host), compute the missing source-window spectra, render.  `units` are HOST arrays.
 // audiogoal / spectrogram are DEVICE buffers [n,2,sr] / [n,65,T4,2]; either may be NULL (not both).
 // `lane` >= 0: the step runs on internal stream `lane` of the overlap mode (stream == c.lane_stream[lane])
+// `mel` != NULL (then audiogoal == NULL): a log-mel step without a waveform buffer (ss_ctx_observe_features) - the log-mel form
+// of the fused kernels where it serves the step, else this step's route into the context's waveform scratch followed by
+// ss_audio_features_f32 on the same stream.
 static int ctx_observe_on(ss_ctx* h, const ss_units* units, int n, float* audiogoal, float* spectrogram, void* stream,
-                          int lane) {
+                          int lane, const ss_features* mel = nullptr) {
     ssctx::Context& c = h->c;
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipError_t e;
@@ -1247,6 +1377,15 @@ static int ctx_observe_on(ss_ctx* h, const ss_units* units, int n, float* audiog
                           !(c.spectral_max_units > 0 && c.rir && c.out_len <= ssk::kB && n > c.spectral_max_units &&
                             (res.flags & SS_FLAG_NO_DISTRACTOR));
     const int nbh_bank = spectral ? c.h_blocks : (c.rir_cap > 0 ? ssctx::ceil_div(c.rir_cap, c.kb) : 1);
+    // log-mel without a waveform buffer: one fused launch for one-block rows of a single-allocation bank in a step without a
+    // cross-fade, inside the units range the measured policy gives (ss_ctx_set_logmel_policy); everything else renders into the
+    // context's own waveform scratch and runs the feature kernel over it
+    const bool mel_fused = mel && c.buckets.empty() && obs_logmel_shape_ok(c.out_len, res.flags) &&
+                           n >= c.mel_fused_min_units && n <= c.mel_fused_max_units;
+    if (mel && !mel_fused) {
+        rc = get_wave_scratch(&c, lane < 0 ? 0 : lane, st, static_cast<size_t>(n) * 2 * c.out_len, &audiogoal);
+        if (rc) return fail(rc);
+    }
     if (spectrogram && !audiogoal && c.out_len > ssk::kB && !wide_one_block_ok(c.out_len, c.n_valid, res.flags, spectral) &&
         !obs_rows_ok(c.out_len, c.n_valid, nbh_bank, res.flags, spectral, true)) {  // cross-faded / very long rows hand over through memory (the context's own buffer)
         const size_t need = static_cast<size_t>(n) * 2 * c.out_len;
@@ -1265,7 +1404,14 @@ static int ctx_observe_on(ss_ctx* h, const ss_units* units, int n, float* audiog
     SS_PROF_MARK(4);                                           // new windows (upload + k_source_windows), descriptor upload
     g_host_desc = no_tab ? nullptr : hd;                       // (see fill_unit_tab; cleared right after the dispatch below)
     g_launch_share = c.chip_share > 0 ? c.chip_share : c.n_lanes;
-    if (!c.buckets.empty()) {
+    if (mel_fused) {
+        rc = spectral ? ss_audio_obs_logmel_spec_f32(c.pool, c.hspec, c.rir_len, dd, nullptr, spectrogram, mel->logmel, mel->mel_start,
+                                                     mel->mel_w, mel->n_mels, mel->max_len, mel->mel_eps, n, c.h_blocks, c.n_valid,
+                                                     c.out_len, c.pad_mode, res.flags, stream)
+                      : ss_audio_obs_logmel_f32(c.pool, c.rir, c.rir_len, dd, nullptr, spectrogram, mel->logmel, mel->mel_start,
+                                                mel->mel_w, mel->n_mels, mel->max_len, mel->mel_eps, n, c.rir_us, c.rir_cs, c.rir_es,
+                                                c.rir_cap, c.n_valid, c.out_len, c.pad_mode, res.flags, stream);
+    } else if (!c.buckets.empty()) {
         const int nb = static_cast<int>(c.buckets.size());
         rc = spectrogram ? ss_audio_obs_buckets_f32(c.pool, c.buckets.data(), nb, c.rir_len, dd, audiogoal, spectrogram, n,
                                                     c.n_valid, c.out_len, c.pad_mode, res.flags, stream)
@@ -1286,6 +1432,9 @@ static int ctx_observe_on(ss_ctx* h, const ss_units* units, int n, float* audiog
     g_host_desc = nullptr;
     g_launch_share = 1;
     SS_PROF_MARK(5);                                           // the launch entry (unit table + hipLaunchKernel)
+    if (!rc && mel && !mel_fused)                              // scratch route: the features of the waveform just rendered
+        rc = ss_audio_features_f32(audiogoal, n, c.out_len, c.pad_mode, nullptr, mel->logmel, mel->mel_start, mel->mel_w,
+                                   mel->n_mels, mel->max_len, mel->mel_eps, nullptr, 1, 1.f, stream);
     if (rc) return fail(rc);
     // (overlap mode: a group's ticks alternate between the lanes; each lane records its half after ITS last tick)
     rc = close_slot();
@@ -1328,6 +1477,13 @@ int ss_ctx_set_overlap(ss_ctx* h, int n_streams) {
 int ss_ctx_set_spectral_policy(ss_ctx* h, int max_units) {
     if (!h || max_units < 0) return SS_EINVAL;
     h->c.spectral_max_units = max_units;
+    return 0;
+}
+
+int ss_ctx_set_logmel_policy(ss_ctx* h, int min_units, int max_units) {
+    if (!h || min_units < 0 || max_units < 0) return SS_EINVAL;
+    h->c.mel_fused_min_units = min_units;
+    h->c.mel_fused_max_units = max_units;
     return 0;
 }
 
@@ -1392,13 +1548,18 @@ static bool features_take_spectrogram(const ss_features* f, const float* audiogo
 
 static int ctx_observe_any(ss_ctx* h, const ss_units* units, int n, float* audiogoal, float* spectrogram, const ss_features* f,
                            void* stream) {
-    if (!h || n < 0 || (!audiogoal && !spectrogram)) return SS_EINVAL;
-    if (f && (!audiogoal || (!f->logmel && !f->gccphat))) return SS_EINVAL;
+    if (!h || n < 0 || (!audiogoal && !spectrogram && !(f && f->logmel))) return SS_EINVAL;
+    if (f && !f->logmel && !f->gccphat) return SS_EINVAL;
+    // without a waveform buffer: log-mel (and the pooled spectrogram) only - GCC-PHAT reads both ears' waveform
+    const bool mel_only = f && !audiogoal;
+    if (mel_only && (f->gccphat || !mel_args_ok(f->logmel, f->mel_start, f->mel_w, f->n_mels, f->max_len, f->mel_eps)))
+        return SS_EINVAL;
     if (n == 0) return 0;
     ssctx::Context& c = h->c;
     if ((!c.rir && !c.hspec && c.buckets.empty()) || !c.rir_len || !c.src_dev) return SS_EINVAL;
     const bool sg_late = features_take_spectrogram(f, audiogoal, spectrogram);
     if (c.n_lanes <= 1) {
+        if (mel_only) return ctx_observe_on(h, units, n, nullptr, spectrogram, stream, -1, f);
         const int rc = ctx_observe_on(h, units, n, audiogoal, sg_late ? nullptr : spectrogram, stream, -1);
         return rc ? rc : ctx_features_on(h, n, audiogoal, sg_late ? spectrogram : nullptr, f, stream);
     }
@@ -1433,6 +1594,7 @@ static int ctx_observe_any(ss_ctx* h, const ss_units* units, int n, float* audio
     SS_PROF_MARK(0);                                           // input fence: caller's stream -> lane
     SS_PROF_CALL();
     c.lane_dirty[lane] = true;
+    if (mel_only) return ctx_observe_on(h, units, n, nullptr, spectrogram, c.lane_stream[lane], lane, f);
     const int rc = ctx_observe_on(h, units, n, audiogoal, sg_late ? nullptr : spectrogram, c.lane_stream[lane], lane);
     return rc ? rc : ctx_features_on(h, n, audiogoal, sg_late ? spectrogram : nullptr, f, c.lane_stream[lane]);
 }

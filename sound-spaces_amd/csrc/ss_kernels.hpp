@@ -592,6 +592,144 @@ __device__ __forceinline__ void stft_power(c32* sc, int lane, c32 wq, const c32*
     wave_sync();
 }
 
+__device__ __forceinline__ float mel_log(float v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_logf(v) * 0.69314718055994531f;
+#else
+    return logf(v);
+#endif
+}
+
+// One pooled block (4 frames) of ONE ear for the log-mel form of the fused observation kernels (fused_stft_phase<.., MEL>):
+// the two radix-16 passes and the Hermitian split of stft_block / stft_power, then
+//   * the power spectra of the 4 frames -> the wave's scratch (kPowStride floats per frame, zero tail, 16-byte stores as in
+//     ear_power_features), and the filter bank with lane = BAND: lane j walks the max_len bins of band j once, every weight
+//     quad (global memory: the table is 12 KiB shared by every workgroup of the launch - L1 / L2 hits - and does not fit the
+//     LDS these kernels have left) meets the four frames' power quads (LDS) -> mv[f] = log(sum + eps), frame 4 b + f;
+//   * want_sg (wave-uniform): the pooled magnitudes from the SAME |X|^2 values, through the partial sums and the gather of
+//     stft_block (identical arithmetic) -> store(row, value).
+// Lanes >= n_mels work on a clamped band; the caller drops their mv.
+template <class STORE>
+__device__ __forceinline__ void stft_block_mel(c32* sc, int lane, c32 wq, const c32* tw512, c32 (&x)[16], int start,
+                                               const f32x4* wj, int steps, float eps, bool want_sg, float (&mv)[4], STORE store) {
+    const int f = lane >> 4, q = lane & 15;
+    c32* fr = sc + f * kFrameStride;
+    c32* fn = sc + f * kNatStride;
+    fft16<false>(x);
+    SSK_OPAQUE2(wq);
+    twiddle16<false>(x, wq);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) lds_st(fr + r * 17 + q, x[r]);
+    wave_sync();
+#pragma unroll
+    for (int r = 0; r < 16; ++r) x[r] = lds_ld(fr + q * 17 + r);
+    fft16<false>(x);
+    wave_sync();
+#pragma unroll
+    for (int s = 0; s < 16; ++s) lds_st(fn + q + posN(16 * s), x[s]);
+    wave_sync();
+    f32x4 k01[2], k23[2], p01[2], p23[2], w01[2], w23[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int b = q + 16 * i;
+        const f32x4* zk4 = reinterpret_cast<const f32x4*>(fn + posN(4 * b));
+        const f32x4* zp4 = reinterpret_cast<const f32x4*>(fn + posN(252 - 4 * b));
+        const f32x4* w4 = reinterpret_cast<const f32x4*>(tw512 + posN(4 * b));
+        k01[i] = zk4[0]; k23[i] = zk4[1]; p01[i] = zp4[0]; p23[i] = zp4[1]; w01[i] = w4[0]; w23[i] = w4[1];
+    }
+    const c32 prev0 = mk2(row_ror1(p01[0].x, lane), row_ror1(p01[0].y, lane));
+    const c32 prev1 = mk2(row_ror1(p01[1].x, lane), row_ror1(p01[1].y, lane));
+    float p128 = 0.f;
+    if (q == 0) { const c32 z = fn[posN(128)]; p128 = z.x * z.x + z.y * z.y; }
+    wave_sync();                                         // every lane holds its Z values: the scratch may be overwritten
+    float px[2][4], py[2][4];                            // |2 X[k]|^2, |2 X[256 - k]|^2, k = 4 b + e
+    float dsum[2] = {0.f, 0.f}, m0[2] = {0.f, 0.f}, m123[2] = {0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const c32 ptop = i == 0 ? (q == 0 ? k01[0].xy : prev0) : (q == 0 ? prev0 : prev1);
+        const c32 zk[4] = {k01[i].xy, k01[i].zw, k23[i].xy, k23[i].zw};
+        const c32 zp[4] = {ptop, p23[i].zw, p23[i].xy, p01[i].zw};
+        const c32 ww[4] = {w01[i].xy, w01[i].zw, w23[i].xy, w23[i].zw};
+        float d = 0.f, m = 0.f;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const c32 P = add_conj(zk[e], zp[e]), Q = sub_conj(zk[e], zp[e]);
+            const c32 wQ = cmul(Q, ww[e]);
+            const c32 m2 = mag2(xy_re(P, wQ), xy_im(P, wQ));
+            px[i][e] = m2.x;
+            py[i][e] = m2.y;
+            if (want_sg) {
+                d += fast_sqrt(m2.x);
+                const float my = fast_sqrt(m2.y);
+                if (e == 0) m0[i] = 0.5f * my; else m += my;
+            }
+        }
+        dsum[i] = 0.5f * d;
+        m123[i] = 0.5f * m;
+    }
+    float* pw = reinterpret_cast<float*>(sc) + f * kPowStride;
+    {   // natural-order power spectra by 16-byte stores: see ear_power_features (ss_features.hpp) for the mirror half
+        const float n0 = row_rol1(py[0][0], lane), n1 = row_rol1(py[1][0], lane), n128 = row_rol1(q == 0 ? 4.f * p128 : 0.f, lane);
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int b = q + 16 * i;
+            *reinterpret_cast<f32x4*>(pw + 4 * b) = f32x4{0.25f * px[i][0], 0.25f * px[i][1], 0.25f * px[i][2], 0.25f * px[i][3]};
+            const float nxt = i == 0 ? (q == 15 ? n1 : n0) : (q == 15 ? n128 : n1);
+            *reinterpret_cast<f32x4*>(pw + 252 - 4 * b) = f32x4{0.25f * nxt, 0.25f * py[i][3], 0.25f * py[i][2], 0.25f * py[i][1]};
+        }
+        if (q == 0) pw[256] = 0.25f * py[0][0];
+        for (int k = 257 + q; k < kPowStride; k += 16) pw[k] = 0.f;
+    }
+    wave_sync();
+    {
+        const f32x4* pj = reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(sc) + start);
+        constexpr int fs = kPowStride / 4;               // quads between two frames' spectra
+        c32 acc[4] = {mk2(0.f, 0.f), mk2(0.f, 0.f), mk2(0.f, 0.f), mk2(0.f, 0.f)};
+        f32x4 a = wj[0];
+        for (int i = 0; i < steps; ++i) {
+            const f32x4 an = wj[i + 1 < steps ? i + 1 : i];      // next weight quad in flight under this step's math
+            const f32x4 b0 = pj[i], b1 = pj[fs + i], b2 = pj[2 * fs + i], b3 = pj[3 * fs + i];
+            acc[0] = acc[0] + mk2(a.x * b0.x, a.y * b0.y); acc[1] = acc[1] + mk2(a.x * b1.x, a.y * b1.y);
+            acc[2] = acc[2] + mk2(a.x * b2.x, a.y * b2.y); acc[3] = acc[3] + mk2(a.x * b3.x, a.y * b3.y);
+            acc[0] = acc[0] + mk2(a.z * b0.z, a.w * b0.w); acc[1] = acc[1] + mk2(a.z * b1.z, a.w * b1.w);
+            acc[2] = acc[2] + mk2(a.z * b2.z, a.w * b2.w); acc[3] = acc[3] + mk2(a.z * b3.z, a.w * b3.w);
+            a = an;
+        }
+#pragma unroll
+        for (int g = 0; g < 4; ++g) mv[g] = mel_log(acc[g].x + acc[g].y + eps);
+    }
+    wave_sync();                                          // the power spectra are dead
+    if (want_sg) {                                        // the tail of stft_block: partial sums -> gather -> log1p
+        float* ps = reinterpret_cast<float*>(sc);
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            ps[f * kPsStride + q + 16 * i] = dsum[i];
+            ps[f * kPsStride + 32 + q + 16 * i] = m0[i];
+            ps[f * kPsStride + 64 + q + 16 * i] = m123[i];
+        }
+        if (q == 0) ps[f * kPsStride + 96] = fast_sqrt(p128);
+        if (q == 1) ps[f * kPsStride + 97] = 0.f;
+        wave_sync();
+        const int r = lane;
+        const bool lo = r < 32, mid = r == 32;
+        const int oa = lo ? r : mid ? 64 + 31 : 64 + 63 - r;
+        const int ob = lo ? 97 : mid ? 96 : 32 + 64 - r;
+        float a[4], b[4];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) { a[g] = ps[g * kPsStride + oa]; b[g] = ps[g * kPsStride + ob]; }
+        float v = 0.f;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) v += a[g] + b[g];
+        store(r, fast_log1p(v * (1.0f / 16.0f)));
+        if (lane == 0) {
+            float v64 = 0.f;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) v64 += ps[g * kPsStride + 32];
+            store(64, fast_log1p(v64 * (1.0f / 16.0f)));
+        }
+    }
+}
+
 __global__ __launch_bounds__(512) void k_logmel(MelParams p) {
     alignas(16) __shared__ c32 sc[8 * kWaveScratch];
     __shared__ float res[kMelMaxBands * 32];                // [n_mels][16 frames][2 ears]
@@ -945,10 +1083,21 @@ struct ConvParams {
 // to the TAB instantiations only (k_conv<.., SIMPLE, .., TAB>, k_conv_spec<.., SIMPLE, TAB>, k_conv32<.., TAB>): every
 // other launch keeps a kernarg block of a few hundred bytes (inside ConvParams the 2 KiB went up with every
 // launch of every kernel and sat next to the 4 KiB kernarg limit).
-template <bool TAB>
+// MEL (the log-mel instantiations of the fused kernels, never together with TAB): the same second argument carries the mel
+// filter bank and the log-mel output instead - ConvParams, and with it every other instantiation's arguments, stays as it is.
+template <bool TAB, bool MEL = false>
 struct UnitTab { };
 template <>
-struct UnitTab<true> { int tab[kTabWords * kTabUnits]; };
+struct UnitTab<true, false> { int tab[kTabWords * kTabUnits]; };
+template <>
+struct UnitTab<false, true> {
+    float* logmel;         // [N][n_mels][n_frames][2]
+    const int* start;      // [n_mels]: first bin of band j (a multiple of 4, <= 256)
+    const float* w;        // [n_mels][max_len], 16-byte aligned, zero padded
+    int n_mels, max_len;   // n_mels <= 64; max_len <= 64, a multiple of 4
+    float eps;
+};
+using MelArgs = UnitTab<false, true>;
 static_assert(sizeof(ConvParams) <= 512, "ConvParams is passed by value to every conv kernel: keep it small");
 static_assert(sizeof(ConvParams) + sizeof(UnitTab<true>) + 64 <= 4096, "kernel arguments of the TAB instantiations");
 
@@ -1131,9 +1280,17 @@ constexpr int kResFloats = kBins4 * 26;     // pooled spectrogram of one ear (<=
 // pooled blocks [part * per, (part + 1) * per) of a row belong to workgroup `part` of its 2^parts_log2 (ConvParams::parts_log2)
 __host__ __device__ constexpr int part_blocks(int t4, int parts_log2) { return (t4 + (1 << parts_log2) - 1) >> parts_log2; }
 
-template <bool WIDE = false>
+// MEL (log-mel form; one workgroup per row, not WIDE): every pooled block also yields the log-mel values of its four frames
+// (stft_block_mel) - lane j of a wave keeps band j of its two blocks in eight registers; when every wave is done the big buffer
+// is dead and collects the ear's [n_mels][n_frames] values (26 KiB at 64 bands: s_res could not hold them), which then leave as
+// whole rows of logmel[unit][j][.][ear]: consecutive lanes, consecutive frames, every other float of a contiguous range.  The
+// pooled spectrogram is optional there (p.sgram may be null).
+constexpr int kMelResStride = 4 * 26;       // floats per band of the collected log-mel values (frames of 26 blocks)
+template <bool WIDE = false, bool MEL = false>
 __device__ __forceinline__ void fused_stft_phase(c32* lds, const ConvParams& p, int t, int unit, int ch, const c32 (&y)[8],
-                                                 const float* s_win, const c32* s_tw512, c32 wq, float* s_res, int part = 0) {
+                                                 const float* s_win, const c32* s_tw512, c32 wq, float* s_res, int part = 0,
+                                                 const UnitTab<false, MEL>& mel = UnitTab<false, MEL>()) {
+    static_assert(!(WIDE && MEL), "the log-mel form serves one-block rows");
     // The row goes to LDS with librosa's centre padding materialised around it (256 samples on each side), so that
     // every frame is an aligned, branch-free read.  (With the padding resolved per sample at load time, the three
     // waves that own the first / last frames ran a ~300-instruction edge path on top of their two blocks; two of them
@@ -1196,6 +1353,41 @@ __device__ __forceinline__ void fused_stft_phase(c32* lds, const ConvParams& p, 
     // stores row r of out[unit][r][block][ear] - 64 lanes, 64 different cache lines, 4 bytes each, 26 times per workgroup.
     // From s_res, 32 threads per pooled row write its blocks: every other float of a contiguous range.
     const int rs = WIDE ? 26 : p.t4;                        // row stride of s_res
+    if constexpr (MEL) {
+        const MelArgs& m = mel;
+        const bool want_sg = p.sgram != nullptr;
+        const int jb = min(lane, m.n_mels - 1);             // this lane's band (lanes >= n_mels: clamped, dropped below)
+        const int start = m.start[jb];
+        const f32x4* wj = reinterpret_cast<const f32x4*>(m.w + jb * m.max_len);
+        const float quiet = mel_log(m.eps);                 // blocks that are not computed: zero power in every band
+        float mv0[4] = {quiet, quiet, quiet, quiet}, mv1[4] = {quiet, quiet, quiet, quiet};
+        c32* sc = lds + wv * kWaveScratch;
+        if (one)
+            stft_block_mel(sc, lane, wq, s_tw512, x0, start, wj, m.max_len >> 2, m.eps, want_sg, mv0,
+                           [&](int b, float v) { s_res[b * rs + bw] = v; });
+        if (two) {
+            wave_sync();
+            stft_block_mel(sc, lane, wq, s_tw512, x1, start, wj, m.max_len >> 2, m.eps, want_sg, mv1,
+                           [&](int b, float v) { s_res[b * rs + bw + 16] = v; });
+        }
+        lds_barrier();                                      // every wave's scratch is dead: the buffer collects the bands
+        float* res = reinterpret_cast<float*>(lds);
+        if (lane < m.n_mels) {
+            if (bw < p.t4) *reinterpret_cast<f32x4*>(res + lane * kMelResStride + 4 * bw) = f32x4{mv0[0], mv0[1], mv0[2], mv0[3]};
+            if (bw + 16 < p.t4)
+                *reinterpret_cast<f32x4*>(res + lane * kMelResStride + 4 * (bw + 16)) = f32x4{mv1[0], mv1[1], mv1[2], mv1[3]};
+        }
+        lds_barrier();
+        float* om = m.logmel + (size_t)unit * m.n_mels * p.n_frames * 2 + ch;
+        for (int j = wv; j < m.n_mels; j += kT / 64)
+            for (int tf = lane; tf < p.n_frames; tf += 64) om[2 * ((size_t)j * p.n_frames + tf)] = res[j * kMelResStride + tf];
+        if (!want_sg) return;
+        float* o = p.sgram + (size_t)unit * kBins4 * p.t4 * 2 + ch;     // (s_res: complete since the first barrier above)
+        const int k = t & 31;
+        if (k < p.t4)
+            for (int b = t >> 5; b < kBins4; b += kT / 32) o[2 * (b * p.t4 + k)] = k < live ? s_res[b * p.t4 + k] : 0.f;
+        return;
+    }
     if (one)
         stft_block(lds + wv * kWaveScratch, lane, wq, s_tw512, x0, [&](int b, float v) { s_res[b * rs + bw] = v; });
     if (two) {
@@ -1223,9 +1415,10 @@ __device__ __forceinline__ void fused_stft_phase(c32* lds, const ConvParams& p, 
 // of that result (at most two packed pairs per thread) are kept in registers, then the row is convolved with the
 // current RIR (term 0) and the head of the row becomes prev*(fade-n)/fade + cur*n/fade.  One launch, and in the
 // fused kernel the spectrogram is taken from the blended row without it ever leaving the CU.
-template <bool FUSE, bool SIMPLE, bool XFADE = false, bool TAB = false, bool WIDE = false>
-__global__ __launch_bounds__(1024) void k_conv(ConvParams p, UnitTab<TAB> ut = UnitTab<TAB>()) {
+template <bool FUSE, bool SIMPLE, bool XFADE = false, bool TAB = false, bool WIDE = false, bool MEL = false>
+__global__ __launch_bounds__(1024) void k_conv(ConvParams p, UnitTab<TAB, MEL> ut = UnitTab<TAB, MEL>()) {
     static_assert(!(SIMPLE && XFADE), "the cross-fade needs the two-term loop kernel");
+    static_assert(!MEL || (FUSE && !XFADE && !TAB && !WIDE), "log-mel: the plain fused kernels (launched with parts_log2 = 0)");
     static_assert(!WIDE || (FUSE && !SIMPLE), "WIDE: fused loop kernel for rows of which only block 0 is rendered");
     static_assert(!TAB || SIMPLE, "the unit table serves the loop-free kernel");
     __shared__ c32 lds[FUSE && 16 * kWaveScratch > kLdsComplex ? 16 * kWaveScratch : kLdsComplex];
@@ -1392,7 +1585,8 @@ __global__ __launch_bounds__(1024) void k_conv(ConvParams p, UnitTab<TAB> ut = U
     if (FUSE) {
         if (t < kNfft) s_win[t] = win_v;                    // visible to the STFT phase after its first barrier
         if (t < 256) s_tw512[posN(t)] = tw512_v;
-        fused_stft_phase<WIDE>(lds, p, t, ounit, ch, y, s_win, s_tw512, wq, s_res, part);
+        if constexpr (MEL) fused_stft_phase<false, true>(lds, p, t, ounit, ch, y, s_win, s_tw512, wq, s_res, 0, ut);
+        else fused_stft_phase<WIDE>(lds, p, t, ounit, ch, y, s_win, s_tw512, wq, s_res, part);
     }
 }
 
@@ -1437,9 +1631,10 @@ __device__ __forceinline__ void spec_block_product(const f32x4* spec, int t, con
         }
 }
 
-template <bool FUSE, bool SIMPLE, bool TAB = false>
-__global__ __launch_bounds__(1024) void k_conv_spec(ConvParams p, UnitTab<TAB> ut = UnitTab<TAB>()) {
+template <bool FUSE, bool SIMPLE, bool TAB = false, bool MEL = false>
+__global__ __launch_bounds__(1024) void k_conv_spec(ConvParams p, UnitTab<TAB, MEL> ut = UnitTab<TAB, MEL>()) {
     static_assert(!TAB || SIMPLE, "the unit table serves the loop-free kernel");
+    static_assert(!MEL || (FUSE && !TAB), "log-mel: the plain fused kernels (launched with parts_log2 = 0)");
     __shared__ c32 lds[FUSE && 16 * kWaveScratch > kLdsComplex ? 16 * kWaveScratch : kLdsComplex];
     const int t = threadIdx.x;
     // 1-D grid of 2N * nb_y workgroups.  With several output blocks per row (44.1 kHz: 3) the blocks of one row sit NEXT
@@ -1560,7 +1755,8 @@ __global__ __launch_bounds__(1024) void k_conv_spec(ConvParams p, UnitTab<TAB> u
     if (FUSE) {
         if (t < kNfft) s_win[t] = win_v;
         if (t < 256) s_tw512[posN(t)] = tw512_v;
-        fused_stft_phase(lds, p, t, ounit, ch, y, s_win, s_tw512, wq, s_res, part);
+        if constexpr (MEL) fused_stft_phase<false, true>(lds, p, t, ounit, ch, y, s_win, s_tw512, wq, s_res, 0, ut);
+        else fused_stft_phase(lds, p, t, ounit, ch, y, s_win, s_tw512, wq, s_res, part);
     }
 }
 

@@ -17,7 +17,7 @@ EXPORTS = ("ss_block_len", "ss_spec_floats", "ss_version", "ss_init", "ss_source
            "ss_audio_obs_buckets_f32", "ss_ctx_set_rir_buckets", "ss_release_scratch",
            "ss_source_windows32_f32", "ss_audio_obs32_f32", "ss_ctx_observe_requests", "ss_ctx_requests_units", "ss_audio_features_f32", "ss_ctx_observe_features",
            "ss_wav_read_rirs_f32", "ss_rows_gather_f32", "ss_bank_scatter_rows_f32", "ss_ctx_set_chip_share", "ss_ctx_set_spectral_policy", "ss_ctx_observe_requests_load", "ss_ctx_load_rir_files",
-           "ss_bank_scatter_spectra_f32")
+           "ss_bank_scatter_spectra_f32", "ss_audio_obs_logmel_f32", "ss_audio_obs_logmel_spec_f32", "ss_ctx_set_logmel_policy")
 
 
 class SsRirBucket(ctypes.Structure):
@@ -119,6 +119,11 @@ def load() -> ctypes.CDLL:
     lib.ss_rir_spectra_f32.argtypes = [vp, vp, c_int, c_ll, c_int, c_int, vp]
     lib.ss_fftconv_binaural_spec_f32.argtypes = [vp, vp, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, vp]
     lib.ss_audio_obs_spec_f32.argtypes = [vp, vp, vp, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, vp]
+    lib.ss_audio_obs_logmel_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, c_int, c_int, ctypes.c_float, c_int, c_ll, c_int, c_int,
+                                            c_int, c_int, c_int, c_int, c_int, vp]
+    lib.ss_audio_obs_logmel_spec_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, c_int, c_int, ctypes.c_float, c_int, c_int, c_int,
+                                                 c_int, c_int, c_int, vp]
+    lib.ss_ctx_set_logmel_policy.argtypes = [vp, c_int, c_int]
     lib.ss_source_windows32_f32.argtypes = [vp, vp, vp, c_int, vp]
     lib.ss_audio_obs32_f32.argtypes = [vp, vp, vp, vp, vp, vp, c_int, c_ll, c_int, c_int, c_int, c_int, c_int, c_int, vp]
     lib.ss_audio_features_f32.argtypes = [vp, c_int, c_int, c_int, vp, vp, vp, vp, c_int, c_int, ctypes.c_float, vp, c_int,

@@ -175,6 +175,13 @@ class AudioContext:
         rows, smaller ones the spectral rows (ss_ctx_set_spectral_policy); 0 = the spectral form whenever it is set."""
         _lib.check(self.lib.ss_ctx_set_spectral_policy(self._h, int(max_units)), "ss_ctx_set_spectral_policy")
 
+    def set_logmel_policy(self, min_units: int, max_units: int) -> None:
+        """Log-mel steps without a waveform buffer (``observe(logmel_out=...)`` with ``audiogoal_out=None``) of ``min_units`` ..
+        ``max_units`` units take the one-launch fused kernel where the shape allows it (one-block rows, no cross-fade,
+        single-allocation bank); all other steps render into the context's own waveform scratch and run the feature kernel over
+        it (ss_ctx_set_logmel_policy).  (1, 2**31 - 1): fused whenever possible; (1, 0): never."""
+        _lib.check(self.lib.ss_ctx_set_logmel_policy(self._h, int(min_units), int(max_units)), "ss_ctx_set_logmel_policy")
+
     def set_chip_share(self, n_sources: int) -> None:
         """This context is one of ``n_sources`` launch sources kept busy at once (e.g. two env groups stepped alternately, each
         with its own context and stream): its small steps split their rows over 1 / n_sources of the chip (ss_ctx_set_chip_share)."""
@@ -205,9 +212,13 @@ class AudioContext:
         return u, n, cols
 
     def observe(self, sound, t0, rir, spectrogram_out=None, audiogoal_out=None, dis_sound=None, dis_rir=None,
-                last_rir=None, wrap=None, last_wrap=None, stream: Optional[int] = None) -> None:
+                last_rir=None, wrap=None, last_wrap=None, stream: Optional[int] = None, logmel_out=None, mel_start=None,
+                mel_w=None, mel_eps: float = 1e-6) -> None:
         """Render one step into the given CUDA tensors ([n,65,T4,2] and / or [n,2,sr], float32, contiguous) on the
-        current torch stream (or `stream`, a raw hipStream_t).  rir < 0 = silent unit."""
+        current torch stream (or `stream`, a raw hipStream_t).  rir < 0 = silent unit.
+        ``logmel_out`` [n, n_mels, 1 + sr // 160, 2] (with ``mel_start`` int32 [n_mels], ``mel_w`` float32 [n_mels, max_len]:
+        ``planning.mel_filterbank_sparse``) adds the step's log-mel (ss_ctx_observe_features); it needs no ``audiogoal_out`` and
+        no ``spectrogram_out``."""
         import torch
         u, n, keep = self._units(sound, t0, rir, dis_sound, dis_rir, last_rir, wrap, last_wrap)
         sg = ag = None
@@ -220,12 +231,24 @@ class AudioContext:
             assert audiogoal_out.is_cuda and audiogoal_out.dtype == torch.float32 and audiogoal_out.is_contiguous()
             assert tuple(audiogoal_out.shape) == (n, 2, self.sr)
             ag, dev = audiogoal_out.data_ptr(), audiogoal_out.device
+        feat = None
+        if logmel_out is not None:
+            assert logmel_out.is_cuda and logmel_out.dtype == torch.float32 and logmel_out.is_contiguous()
+            assert mel_start is not None and mel_w is not None and mel_start.dtype == torch.int32 and mel_w.dtype == torch.float32
+            assert mel_start.is_contiguous() and mel_w.is_contiguous() and mel_start.shape == (mel_w.shape[0],)
+            assert tuple(logmel_out.shape) == (n, mel_w.shape[0], 1 + self.sr // 160, 2)
+            feat = self.features(logmel_out, mel_start, mel_w, mel_eps)
+            dev = logmel_out.device
         if dev is None:
-            raise ValueError("observe: pass spectrogram_out and / or audiogoal_out")
+            raise ValueError("observe: pass spectrogram_out, audiogoal_out and / or logmel_out")
         if stream is None:
             stream = torch._C._cuda_getCurrentRawStream(dev.index if dev.index is not None else torch.cuda.current_device())
         with torch.cuda.device(dev):
-            _lib.check(self.lib.ss_ctx_observe(self._h, ctypes.byref(u), n, ag, sg, stream), "ss_ctx_observe")
+            if feat is not None:
+                _lib.check(self.lib.ss_ctx_observe_features(self._h, ctypes.byref(u), n, ag, sg, feat["ref"], stream),
+                           "ss_ctx_observe_features")
+            else:
+                _lib.check(self.lib.ss_ctx_observe(self._h, ctypes.byref(u), n, ag, sg, stream), "ss_ctx_observe")
 
     def prepare(self, sound, t0, rir, dis_sound=None, dis_rir=None, last_rir=None, wrap=None, last_wrap=None):
         """Unit columns converted ONCE into the ss_units struct ``observe_prepared`` takes (callers that replay known steps -
@@ -255,7 +278,8 @@ class AudioContext:
         return dict(f=f, ref=ctypes.byref(f), keep=(logmel_out, mel_start, mel_w, gccphat_out))
 
     def observe_prepared_features(self, prep, spectrogram_ptr, audiogoal_ptr, stream: int, features) -> None:
-        """``observe_prepared`` + the step's log-mel / GCC-PHAT on the same stream (``ss_ctx_observe_features``)."""
+        """``observe_prepared`` + the step's log-mel / GCC-PHAT on the same stream (``ss_ctx_observe_features``).  A log-mel-only
+        feature set needs no waveform: ``audiogoal_ptr`` (and ``spectrogram_ptr``) may then be None."""
         rc = self.lib.ss_ctx_observe_features(self._h, prep["ref"], prep["n"], audiogoal_ptr, spectrogram_ptr, features["ref"],
                                               stream)
         if rc != 0:

@@ -294,6 +294,56 @@ def audio_obs_spec_into(spec, hspec, rir_len, unit_desc, audiogoal, spectrogram_
                    "ss_audio_obs_spec_f32")
 
 
+# ---- log-mel observation in one launch (no waveform buffer) ---------------------------------------------------------
+def _obs_logmel_args(unit_desc, audiogoal, spectrogram_out, logmel_out, mel_start, mel_w, out_len):
+    _chk(unit_desc, torch.int32, "unit_desc"); _chk(logmel_out, torch.float32, "logmel_out")
+    _chk(mel_start, torch.int32, "mel_start"); _chk(mel_w, torch.float32, "mel_w")
+    N = unit_desc.shape[0]
+    n_mels, max_len = mel_w.shape
+    assert mel_start.shape == (n_mels,) and tuple(logmel_out.shape) == (N, n_mels, 1 + out_len // 160, 2)
+    ag_ptr = sg_ptr = None
+    if audiogoal is not None:
+        _chk(audiogoal, torch.float32, "audiogoal")
+        assert tuple(audiogoal.shape) == (N, 2, out_len)
+        ag_ptr = audiogoal.data_ptr()
+    if spectrogram_out is not None:
+        _chk(spectrogram_out, torch.float32, "spectrogram_out")
+        assert tuple(spectrogram_out.shape) == (N,) + spectrogram_shape(out_len)
+        sg_ptr = spectrogram_out.data_ptr()
+    return N, n_mels, max_len, ag_ptr, sg_ptr
+
+
+def audio_obs_logmel_into(spec, rir_bank, rir_len, unit_desc, audiogoal, spectrogram_out, logmel_out, mel_start, mel_w,
+                          n_valid: int, out_len: int, mel_eps: float = 1e-6, pad_mode="reflect", interleaved: bool = False,
+                          flags: int = 0) -> None:
+    """EXTENSION: log-mel observation in ONE launch (``ss_audio_obs_logmel_f32``): convolution -> framing -> window -> rFFT ->
+    |.|^2 -> mel bands -> log on the row a workgroup holds in LDS; the waveform needs no buffer.  ``audiogoal`` and
+    ``spectrogram_out`` may each be None.  Rows of one partition block (257 <= out_len <= KB) without a cross-fade only; mel
+    arguments as ``audio_features_into``; anything else is refused (invalid argument)."""
+    _chk(spec, torch.float32, "spec"); _chk(rir_bank, torch.float32, "rir_bank"); _chk(rir_len, torch.int32, "rir_len")
+    N, n_mels, max_len, ag_ptr, sg_ptr = _obs_logmel_args(unit_desc, audiogoal, spectrogram_out, logmel_out, mel_start, mel_w, out_len)
+    us, cs, es, cap = _bank_strides(rir_bank, interleaved)
+    with torch.cuda.device(spec.device):
+        _lib.check(_lib.load().ss_audio_obs_logmel_f32(spec.data_ptr(), rir_bank.data_ptr(), rir_len.data_ptr(), unit_desc.data_ptr(),
+                                                       ag_ptr, sg_ptr, logmel_out.data_ptr(), mel_start.data_ptr(), mel_w.data_ptr(),
+                                                       int(n_mels), int(max_len), float(mel_eps), N, us, cs, es, cap, n_valid,
+                                                       out_len, _PAD[pad_mode], flags, _stream(spec)), "ss_audio_obs_logmel_f32")
+
+
+def audio_obs_logmel_spec_into(spec, hspec, rir_len, unit_desc, audiogoal, spectrogram_out, logmel_out, mel_start, mel_w,
+                               n_valid: int, out_len: int, mel_eps: float = 1e-6, pad_mode="reflect", flags: int = 0) -> None:
+    """``audio_obs_logmel_into`` from the spectral RIR bank (``ss_audio_obs_logmel_spec_f32``)."""
+    _chk(spec, torch.float32, "spec"); _chk(hspec, torch.float32, "hspec"); _chk(rir_len, torch.int32, "rir_len")
+    assert hspec.dim() == 4
+    N, n_mels, max_len, ag_ptr, sg_ptr = _obs_logmel_args(unit_desc, audiogoal, spectrogram_out, logmel_out, mel_start, mel_w, out_len)
+    with torch.cuda.device(spec.device):
+        _lib.check(_lib.load().ss_audio_obs_logmel_spec_f32(spec.data_ptr(), hspec.data_ptr(), rir_len.data_ptr(), unit_desc.data_ptr(),
+                                                            ag_ptr, sg_ptr, logmel_out.data_ptr(), mel_start.data_ptr(),
+                                                            mel_w.data_ptr(), int(n_mels), int(max_len), float(mel_eps), N,
+                                                            hspec.shape[2], n_valid, out_len, _PAD[pad_mode], flags, _stream(spec)),
+                   "ss_audio_obs_logmel_spec_f32")
+
+
 # ---- length-bucketed RIR bank (SURVEY 8(f)2) ------------------------------------------------------------------------
 def bucket_array(banks, firsts, spectral: bool):
     """ctypes array of ss_rir_bucket for per-bucket (data [n,2,cap], spectra or None) tensors; keep it alive with the
