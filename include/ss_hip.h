@@ -30,6 +30,8 @@
 #ifndef SS_HIP_H
 #define SS_HIP_H
 
+#include <stddef.h>
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -152,6 +154,28 @@ int ss_audio_obs_logmel_spec_f32(const float* spec, const float* hspec, const in
                                  float* audiogoal, float* spectrogram, float* logmel, const int* mel_start,
                                  const float* mel_w, int n_mels, int max_len, float mel_eps, int n_units, int h_blocks,
                                  int n_valid, int out_len, int pad_mode, int flags, void* stream);
+
+/* The same for rows of 2 or 3 partition blocks (kB < out_len <= 3 kB: 44.1 / 48 kHz, the reference's Replica rate; EXTENSION):
+ * the log-mel form of the fused row kernels (k_obs_rows / k_obs_blocks), the STFT phase behind every output block emits the
+ * frames it completes.  Arguments and outputs as ss_audio_obs_logmel_f32 / _spec_f32 (which keep refusing rows longer than kB);
+ * `audiogoal` and `spectrogram` may each be NULL and ANY combination of the three outputs is ONE launch - at this level the
+ * caller chose the entry.  A waveform buffer is written exactly as ss_audio_obs_f32 / _spec_f32 write it on the same kernel.
+ * Units that are silent or whose RIR is empty, and the frames of pooled blocks behind n_valid, come out as log(mel_eps) (exact
+ * zeros in the pooled spectrogram).  Served shapes: kB < out_len <= 3 kB, 0 <= n_valid <= out_len, at most 16 RIR blocks
+ * (rir_cap <= 16 kB / 1 <= h_blocks <= 16), no SS_FLAG_CROSSFADE, mel arguments under the limits above.  Everything else is
+ * SS_EINVAL from the argument checks, before a device is touched.  The choice between the two kernels, the per-stream stash and
+ * hand-off area are those of ss_audio_obs_f32 on such rows; like there, a launch that takes the one-workgroup-per-output-block
+ * kernel (small steps: the whole grid fits the chip) must NOT be replayed from a captured graph - its hand-off flags carry the
+ * launch's epoch. */
+int ss_audio_obs_logmel_rows_f32(const float* spec, const float* rir, const int* rir_len, const int* unit_desc,
+                                 float* audiogoal, float* spectrogram, float* logmel, const int* mel_start,
+                                 const float* mel_w, int n_mels, int max_len, float mel_eps, int n_units,
+                                 long long rir_unit_stride, int rir_chan_stride, int rir_elem_stride, int rir_cap, int n_valid,
+                                 int out_len, int pad_mode, int flags, void* stream);
+int ss_audio_obs_logmel_rows_spec_f32(const float* spec, const float* hspec, const int* rir_len, const int* unit_desc,
+                                      float* audiogoal, float* spectrogram, float* logmel, const int* mel_start,
+                                      const float* mel_w, int n_mels, int max_len, float mel_eps, int n_units, int h_blocks,
+                                      int n_valid, int out_len, int pad_mode, int flags, void* stream);
 
 /* ---- Length-bucketed RIR bank ------------------------------------------------------------------------
  * The reference's RIRs are variable-length wav files (soundspaces/README.md:38-42, read at simulator.py:615-618; SS2.0's
@@ -306,7 +330,10 @@ int ss_ctx_observe(ss_ctx* ctx, const ss_units* units, int n, float* audiogoal, 
  *   - ONE fused launch (ss_audio_obs_logmel_f32 / _spec_f32; no waveform anywhere) when its rows are one partition block
  *     (257 <= sr <= kB: 16 kHz), the step has no cross-fade, the bank is a single allocation of either form (also the
  *     spectral-only binding) and its unit count lies inside ss_ctx_set_logmel_policy's range;
- *   - otherwise (44.1 / 48 kHz rows, cross-faded steps, bucketed banks, unit counts outside the range) the route ss_ctx_observe
+ *   - ONE fused launch as well (ss_audio_obs_logmel_rows_f32 / _spec_f32) when its rows are 2 or 3 partition blocks (44.1 /
+ *     48 kHz), under the same conditions, and its unit count lies inside ss_ctx_set_logmel_rows_policy's range - which is empty
+ *     by default: the fused values equal the next route's to rounding (1e-4 of the largest value), not bit for bit;
+ *   - otherwise (44.1 / 48 kHz rows by default, cross-faded steps, bucketed banks, unit counts outside the range) the route ss_ctx_observe
  *     takes with an audiogoal buffer, into a waveform scratch the CONTEXT owns ([n, 2, sr] floats per overlap lane, grown on
  *     demand, freed with the context and by ss_release_scratch; a growth needed while the stream is being captured is refused
  *     with SS_EINVAL: warm the stream up first), then ss_audio_features_f32 over it: bit for bit ss_ctx_observe +
@@ -328,6 +355,12 @@ int ss_ctx_observe_features(ss_ctx* ctx, const ss_units* units, int n, float* au
  * it serves, see above).  Default: the range in which the fused launch measured faster than the two launches it replaces
  * (profiles/r7/kbench_obs_logmel.txt).  (1, INT_MAX): whenever the shape allows; max_units < min_units: never. */
 int ss_ctx_set_logmel_policy(ss_ctx* ctx, int min_units, int max_units);
+/* The same for rows of 2 or 3 partition blocks (44.1 / 48 kHz).  ss_ctx_set_logmel_policy keeps its meaning (one-block rows
+ * only).  Default: never (max_units < min_units) - see above; profiles/r7/NOTES.md names the range the measurements support. */
+int ss_ctx_set_logmel_rows_policy(ss_ctx* ctx, int min_units, int max_units);
+/* Bytes of waveform scratch the context currently holds over all overlap lanes (the scratch route above): 0 after creation and
+ * after ss_release_scratch. */
+size_t ss_ctx_wave_scratch_bytes(const ss_ctx* ctx);
 /* Overlap mode.  ss_ctx_set_overlap(ctx, n), n = 2 .. 4: consecutive ss_ctx_observe calls run on n internal streams in turn
  * (2: the head of step k+1 under the tail of step k; 3 - 4: for steps of few rows, where several launches fit the chip side by
  * side - fused rows are then split over fewer workgroups, ConvParams::parts_log2 - and the caller has that many to issue), each

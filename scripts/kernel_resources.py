@@ -16,6 +16,8 @@ def main(extra):
         subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only",
                                "-Wno-unused-command-line-argument", "ss_hip.hip", "-o", asm] + extra, cwd=CSRC)
         t = open(asm).read()
+    # (the metadata keys of a kernel are sorted: its static LDS size stands in front of its name)
+    lds = {n: int(v) for v, n in re.findall(r"\.group_segment_fixed_size:\s+(\d+)\n(?:.*\n){1,12}?\s+\.name:\s+(\S+)\n", t)}
     for m in re.finditer(r"\.name:\s+(\S+)\n((?:.*\n)*?)\s+\.wavefront_size", t):
         name, body = m.group(1), m.group(2)
 
@@ -23,8 +25,8 @@ def main(extra):
             r = re.search(r"\." + k + r":\s+(\d+)", body)
             return int(r.group(1)) if r else -1
         dn = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip()
-        print(f"{dn[:100]:100s} vgpr {g('vgpr_count'):4d} sgpr {g('sgpr_count'):4d} lds {g('group_segment_fixed_size'):7d} "
-              f"vspill {g('vgpr_spill_count')} sspill {g('sgpr_spill_count')}")
+        print(f"{dn[:100]:100s} vgpr {g('vgpr_count'):4d} sgpr {g('sgpr_count'):4d} lds {lds.get(name, -1):7d} "
+              f"scratch {g('private_segment_fixed_size')} vspill {g('vgpr_spill_count')} sspill {g('sgpr_spill_count')}")
 
 
 if __name__ == "__main__":

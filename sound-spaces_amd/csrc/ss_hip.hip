@@ -296,8 +296,10 @@ inline bool obs_rows_ok(int out_len, int n_valid, int nbh_max, int flags, bool s
 // per OUTPUT BLOCK of a row instead of one per row (k_obs_blocks) - while the whole grid fits the launch's share of the chip at
 // one workgroup per CU, which is also what makes the kernel's inter-workgroup hand-off safe.  Spare CUs go to parts (the STFT
 // phase of a block split 2 / 4 / 8 ways).  Returns 1 when the launch does not qualify (the caller falls through to k_obs_rows).
-template <bool SPECTRAL>
-int launch_obs_blocks(ssk::ConvParams p, int n_units, int flags, int n_cus, hipStream_t st) {
+// MEL: the log-mel instantiations (ss_audio_obs_logmel_rows_f32 / _spec_f32), same rule, same hand-off area.
+template <bool SPECTRAL, bool MEL = false>
+int launch_obs_blocks(ssk::ConvParams p, int n_units, int flags, int n_cus, hipStream_t st,
+                      const ssk::UnitTab<false, MEL>& mel = ssk::UnitTab<false, MEL>()) {
     static const bool off = ab_flag("SS_HIP_NO_OBS_BLOCKS");   // (A/B builds only)
     const int n_rows = 2 * n_units, nb = (p.out_len + ssk::kB - 1) / ssk::kB;
     const int budget = n_cus / (g_launch_share > 1 ? g_launch_share : 1);
@@ -316,15 +318,18 @@ int launch_obs_blocks(ssk::ConvParams p, int n_units, int flags, int n_cus, hipS
     int rc = get_block_sync(st, &tails, &fl, &epoch);
     if (rc) return rc;
     const int grid = (n_rows * nb) << k;
-    hipLaunchKernelGGL((ssk::k_obs_blocks<SPECTRAL>), dim3(grid), dim3(ssk::kT), 0, st, p, n_rows, tails, fl, epoch);
+    if constexpr (MEL) hipLaunchKernelGGL((ssk::k_obs_blocks<SPECTRAL, true>), dim3(grid), dim3(ssk::kT), 0, st, p, n_rows, tails, fl, epoch, mel);
+    else hipLaunchKernelGGL((ssk::k_obs_blocks<SPECTRAL>), dim3(grid), dim3(ssk::kT), 0, st, p, n_rows, tails, fl, epoch);
     return hip_err(hipGetLastError());
 }
 
-template <bool SPECTRAL>
-int launch_obs_rows(ssk::ConvParams p, int n_units, int flags, int n_cus, hipStream_t st) {
+template <bool SPECTRAL, bool MEL = false>
+int launch_obs_rows(ssk::ConvParams p, int n_units, int flags, int n_cus, hipStream_t st,
+                    const ssk::UnitTab<false, MEL>& mel = ssk::UnitTab<false, MEL>()) {
     const int n_rows = 2 * n_units;
+    if (MEL && ((flags & SS_FLAG_CROSSFADE) || p.n_buckets != 1)) return SS_EINVAL;      // (the log-mel form: plain rows, one allocation)
     {
-        const int rc = launch_obs_blocks<SPECTRAL>(p, n_units, flags, n_cus, st);
+        const int rc = launch_obs_blocks<SPECTRAL, MEL>(p, n_units, flags, n_cus, st, mel);
         if (rc != 1) return rc;
     }
     // small steps (the reference steps 5-10 envs per GPU at this rate): a row on 2 / 4 / 8 CUs, each rendering the row and
@@ -360,6 +365,10 @@ int launch_obs_rows(ssk::ConvParams p, int n_units, int flags, int n_cus, hipStr
             hipLaunchKernelGGL((ssk::k_obs_rows<false, true>), dim3(grid), dim3(ssk::kT), 0, st, p, n_rows);
             return hip_err(hipGetLastError());
         }
+    }
+    if constexpr (MEL) {
+        hipLaunchKernelGGL((ssk::k_obs_rows<SPECTRAL, false, false, true>), dim3(grid), dim3(ssk::kT), 0, st, p, n_rows, mel);
+        return hip_err(hipGetLastError());
     }
     // one bank allocation (every launch but those of a length-bucketed store): the instantiation without the bucket descriptors
     if (p.n_buckets == 1) hipLaunchKernelGGL((ssk::k_obs_rows<SPECTRAL, false, false>), dim3(grid), dim3(ssk::kT), 0, st, p, n_rows);
@@ -773,6 +782,34 @@ int ss_audio_obs_logmel_f32(const float* spec, const float* rir, const int* rir_
     return launch_conv_mel(p, m, n_units, flags, static_cast<hipStream_t>(stream));
 }
 
+// rows the log-mel form of k_obs_rows / k_obs_blocks serves: 2 or 3 partition blocks (44.1 / 48 kHz), plain steps, at most 16
+// RIR blocks (obs_rows_ok without a cross-fade; a waveform buffer changes nothing here: the caller chose the entry)
+inline bool obs_logmel_rows_shape_ok(int out_len, int n_valid, int nbh_max, int flags) {
+    return !(flags & SS_FLAG_CROSSFADE) && n_valid >= 0 && obs_rows_ok(out_len, n_valid, nbh_max, flags);
+}
+
+// Log-mel observation of rows of 2 or 3 partition blocks in ONE launch (k_obs_blocks<.., MEL> for small steps, else
+// k_obs_rows<.., MEL>: launch_obs_rows' own choice, hand-off area and stash).  Every argument is checked before a device is touched.
+int ss_audio_obs_logmel_rows_f32(const float* spec, const float* rir, const int* rir_len, const int* unit_desc, float* audiogoal,
+                                 float* spectrogram, float* logmel, const int* mel_start, const float* mel_w, int n_mels,
+                                 int max_len, float mel_eps, int n_units, long long rir_unit_stride, int rir_chan_stride,
+                                 int rir_elem_stride, int rir_cap, int n_valid, int out_len, int pad_mode, int flags, void* stream) {
+    if (n_units == 0) return 0;
+    if (n_units < 0 || !mel_args_ok(logmel, mel_start, mel_w, n_mels, max_len, mel_eps)) return SS_EINVAL;
+    if (pad_mode != SS_PAD_REFLECT && pad_mode != SS_PAD_CONSTANT) return SS_EINVAL;
+    if (rir_cap < 1 || !obs_logmel_rows_shape_ok(out_len, n_valid, (rir_cap + ssk::kB - 1) / ssk::kB, flags)) return SS_EINVAL;
+    ssk::ConvParams p;
+    int n_cus = 1;
+    int rc = fill_conv(p, &n_cus, spec, rir, rir_len, unit_desc, rir_unit_stride, rir_chan_stride, rir_elem_stride,
+                       rir_cap, n_valid, out_len);
+    if (rc) return rc;
+    p.pad_mode = pad_mode;
+    p.out = audiogoal;
+    p.sgram = spectrogram;
+    const ssk::MelArgs m{logmel, mel_start, mel_w, n_mels, max_len, mel_eps};
+    return launch_obs_rows<false, true>(p, n_units, flags, n_cus, static_cast<hipStream_t>(stream), m);
+}
+
 // ---- 512-thread FFT core (ss_kernels32.hpp): loop-free rows only; spectra in that core's own register order ----------
 int ss_source_windows32_f32(const float* src, const int* win_desc, float* spec_out, int n_windows, void* stream) {
     if (n_windows == 0) return 0;
@@ -1022,6 +1059,28 @@ int ss_audio_obs_logmel_spec_f32(const float* spec, const float* hspec, const in
     p.sgram = spectrogram;
     const ssk::MelArgs m{logmel, mel_start, mel_w, n_mels, max_len, mel_eps};
     return launch_conv_spec_mel(p, m, n_units, flags, static_cast<hipStream_t>(stream));
+}
+
+// ss_audio_obs_logmel_rows_f32 from the spectral bank (k_obs_blocks<true, MEL> / k_obs_rows<true, .., MEL>)
+int ss_audio_obs_logmel_rows_spec_f32(const float* spec, const float* hspec, const int* rir_len, const int* unit_desc,
+                                      float* audiogoal, float* spectrogram, float* logmel, const int* mel_start,
+                                      const float* mel_w, int n_mels, int max_len, float mel_eps, int n_units, int h_blocks,
+                                      int n_valid, int out_len, int pad_mode, int flags, void* stream) {
+    if (n_units == 0) return 0;
+    if (n_units < 0 || !hspec || !mel_args_ok(logmel, mel_start, mel_w, n_mels, max_len, mel_eps)) return SS_EINVAL;
+    if (pad_mode != SS_PAD_REFLECT && pad_mode != SS_PAD_CONSTANT) return SS_EINVAL;
+    if (!obs_logmel_rows_shape_ok(out_len, n_valid, h_blocks, flags)) return SS_EINVAL;
+    ssk::ConvParams p;
+    int n_cus = 1;
+    int rc = fill_conv(p, &n_cus, spec, nullptr, rir_len, unit_desc, 0, 0, 1, 0, n_valid, out_len, false);
+    if (rc) return rc;
+    p.pad_mode = pad_mode;
+    p.hspec = reinterpret_cast<const ssk::f32x4*>(hspec);
+    p.h_blocks = h_blocks;
+    p.out = audiogoal;
+    p.sgram = spectrogram;
+    const ssk::MelArgs m{logmel, mel_start, mel_w, n_mels, max_len, mel_eps};
+    return launch_obs_rows<true, true>(p, n_units, flags, n_cus, static_cast<hipStream_t>(stream), m);
 }
 
 // ---- context API (include/ss_hip.h): planner + window-spectra cache + descriptor ring inside the library --------------
@@ -1382,11 +1441,17 @@ static int ctx_observe_on(ss_ctx* h, const ss_units* units, int n, float* audiog
     // context's own waveform scratch and runs the feature kernel over it
     const bool mel_fused = mel && c.buckets.empty() && obs_logmel_shape_ok(c.out_len, res.flags) &&
                            n >= c.mel_fused_min_units && n <= c.mel_fused_max_units;
-    if (mel && !mel_fused) {
+    // rows of 2 or 3 blocks (44.1 / 48 kHz): the log-mel form of k_obs_rows / k_obs_blocks under the same conditions, inside the
+    // range of ss_ctx_set_logmel_rows_policy (default: never - the scratch route is bit-equal to observe-then-features, the
+    // fused arithmetic only to rounding)
+    const bool mel_rows = mel && !mel_fused && c.buckets.empty() && (spectral || (c.rir && c.rir_cap > 0)) &&
+                          obs_logmel_rows_shape_ok(c.out_len, c.n_valid, nbh_bank, res.flags) &&
+                          n >= c.mel_rows_min_units && n <= c.mel_rows_max_units;
+    if (mel && !mel_fused && !mel_rows) {
         rc = get_wave_scratch(&c, lane < 0 ? 0 : lane, st, static_cast<size_t>(n) * 2 * c.out_len, &audiogoal);
         if (rc) return fail(rc);
     }
-    if (spectrogram && !audiogoal && c.out_len > ssk::kB && !wide_one_block_ok(c.out_len, c.n_valid, res.flags, spectral) &&
+    if (spectrogram && !audiogoal && !mel_rows && c.out_len > ssk::kB && !wide_one_block_ok(c.out_len, c.n_valid, res.flags, spectral) &&
         !obs_rows_ok(c.out_len, c.n_valid, nbh_bank, res.flags, spectral, true)) {  // cross-faded / very long rows hand over through memory (the context's own buffer)
         const size_t need = static_cast<size_t>(n) * 2 * c.out_len;
         if (need > c.ag_cap) {
@@ -1404,7 +1469,14 @@ static int ctx_observe_on(ss_ctx* h, const ss_units* units, int n, float* audiog
     SS_PROF_MARK(4);                                           // new windows (upload + k_source_windows), descriptor upload
     g_host_desc = no_tab ? nullptr : hd;                       // (see fill_unit_tab; cleared right after the dispatch below)
     g_launch_share = c.chip_share > 0 ? c.chip_share : c.n_lanes;
-    if (mel_fused) {
+    if (mel_rows) {
+        rc = spectral ? ss_audio_obs_logmel_rows_spec_f32(c.pool, c.hspec, c.rir_len, dd, nullptr, spectrogram, mel->logmel,
+                                                          mel->mel_start, mel->mel_w, mel->n_mels, mel->max_len, mel->mel_eps, n,
+                                                          c.h_blocks, c.n_valid, c.out_len, c.pad_mode, res.flags, stream)
+                      : ss_audio_obs_logmel_rows_f32(c.pool, c.rir, c.rir_len, dd, nullptr, spectrogram, mel->logmel, mel->mel_start,
+                                                     mel->mel_w, mel->n_mels, mel->max_len, mel->mel_eps, n, c.rir_us, c.rir_cs,
+                                                     c.rir_es, c.rir_cap, c.n_valid, c.out_len, c.pad_mode, res.flags, stream);
+    } else if (mel_fused) {
         rc = spectral ? ss_audio_obs_logmel_spec_f32(c.pool, c.hspec, c.rir_len, dd, nullptr, spectrogram, mel->logmel, mel->mel_start,
                                                      mel->mel_w, mel->n_mels, mel->max_len, mel->mel_eps, n, c.h_blocks, c.n_valid,
                                                      c.out_len, c.pad_mode, res.flags, stream)
@@ -1432,7 +1504,7 @@ static int ctx_observe_on(ss_ctx* h, const ss_units* units, int n, float* audiog
     g_host_desc = nullptr;
     g_launch_share = 1;
     SS_PROF_MARK(5);                                           // the launch entry (unit table + hipLaunchKernel)
-    if (!rc && mel && !mel_fused)                              // scratch route: the features of the waveform just rendered
+    if (!rc && mel && !mel_fused && !mel_rows)                 // scratch route: the features of the waveform just rendered
         rc = ss_audio_features_f32(audiogoal, n, c.out_len, c.pad_mode, nullptr, mel->logmel, mel->mel_start, mel->mel_w,
                                    mel->n_mels, mel->max_len, mel->mel_eps, nullptr, 1, 1.f, stream);
     if (rc) return fail(rc);
@@ -1485,6 +1557,22 @@ int ss_ctx_set_logmel_policy(ss_ctx* h, int min_units, int max_units) {
     h->c.mel_fused_min_units = min_units;
     h->c.mel_fused_max_units = max_units;
     return 0;
+}
+
+int ss_ctx_set_logmel_rows_policy(ss_ctx* h, int min_units, int max_units) {
+    if (!h || min_units < 0 || max_units < 0) return SS_EINVAL;
+    h->c.mel_rows_min_units = min_units;
+    h->c.mel_rows_max_units = max_units;
+    return 0;
+}
+
+size_t ss_ctx_wave_scratch_bytes(const ss_ctx* h) {
+    if (!h) return 0;
+    std::lock_guard<std::mutex> lk(g_mu);
+    size_t bytes = 0;
+    for (const auto& kv : g_wave_scratch)
+        if (kv.first.first == &h->c && kv.second.ptr) bytes += kv.second.floats * sizeof(float);
+    return bytes;
 }
 
 int ss_ctx_set_chip_share(ss_ctx* h, int n_sources) {

@@ -609,9 +609,13 @@ __device__ __forceinline__ float mel_log(float v) {
 //   * want_sg (wave-uniform): the pooled magnitudes from the SAME |X|^2 values, through the partial sums and the gather of
 //     stft_block (identical arithmetic) -> store(row, value).
 // Lanes >= n_mels work on a clamped band; the caller drops their mv.
-template <class STORE>
+// LEAN (the rows kernels, which enter with the other round's 32 registers live and no VGPR to spare): the split's twiddle quads
+// are read behind the Z values' barrier, pair by pair, and the band's first bin and weight row (`band`; start / wj are ignored)
+// are looked up in front of the filter bank instead of travelling through the transforms.
+template <bool LEAN = false, class STORE, class BAND = void>
 __device__ __forceinline__ void stft_block_mel(c32* sc, int lane, c32 wq, const c32* tw512, c32 (&x)[16], int start,
-                                               const f32x4* wj, int steps, float eps, bool want_sg, float (&mv)[4], STORE store) {
+                                               const f32x4* wj, int steps, float eps, bool want_sg, float (&mv)[4], STORE store,
+                                               const BAND* band = nullptr) {      // (BAND: MelArgs, declared further down)
     const int f = lane >> 4, q = lane & 15;
     c32* fr = sc + f * kFrameStride;
     c32* fn = sc + f * kNatStride;
@@ -635,7 +639,8 @@ __device__ __forceinline__ void stft_block_mel(c32* sc, int lane, c32 wq, const 
         const f32x4* zk4 = reinterpret_cast<const f32x4*>(fn + posN(4 * b));
         const f32x4* zp4 = reinterpret_cast<const f32x4*>(fn + posN(252 - 4 * b));
         const f32x4* w4 = reinterpret_cast<const f32x4*>(tw512 + posN(4 * b));
-        k01[i] = zk4[0]; k23[i] = zk4[1]; p01[i] = zp4[0]; p23[i] = zp4[1]; w01[i] = w4[0]; w23[i] = w4[1];
+        k01[i] = zk4[0]; k23[i] = zk4[1]; p01[i] = zp4[0]; p23[i] = zp4[1];
+        if constexpr (!LEAN) { w01[i] = w4[0]; w23[i] = w4[1]; }
     }
     const c32 prev0 = mk2(row_ror1(p01[0].x, lane), row_ror1(p01[0].y, lane));
     const c32 prev1 = mk2(row_ror1(p01[1].x, lane), row_ror1(p01[1].y, lane));
@@ -646,6 +651,10 @@ __device__ __forceinline__ void stft_block_mel(c32* sc, int lane, c32 wq, const 
     float dsum[2] = {0.f, 0.f}, m0[2] = {0.f, 0.f}, m123[2] = {0.f, 0.f};
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
+        if constexpr (LEAN) {
+            const f32x4* w4 = reinterpret_cast<const f32x4*>(tw512 + posN(4 * (q + 16 * i)));
+            w01[i] = w4[0]; w23[i] = w4[1];
+        }
         const c32 ptop = i == 0 ? (q == 0 ? k01[0].xy : prev0) : (q == 0 ? prev0 : prev1);
         const c32 zk[4] = {k01[i].xy, k01[i].zw, k23[i].xy, k23[i].zw};
         const c32 zp[4] = {ptop, p23[i].zw, p23[i].xy, p01[i].zw};
@@ -682,6 +691,13 @@ __device__ __forceinline__ void stft_block_mel(c32* sc, int lane, c32 wq, const 
     }
     wave_sync();
     {
+        if constexpr (LEAN) {
+            int ln = lane;
+            SSK_OPAQUE1(ln);                              // (not a register of the band's before this point)
+            const int jb = min(ln, band->n_mels - 1);
+            start = band->start[jb];
+            wj = reinterpret_cast<const f32x4*>(band->w + jb * band->max_len);
+        }
         const f32x4* pj = reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(sc) + start);
         constexpr int fs = kPowStride / 4;               // quads between two frames' spectra
         c32 acc[4] = {mk2(0.f, 0.f), mk2(0.f, 0.f), mk2(0.f, 0.f), mk2(0.f, 0.f)};
@@ -2126,11 +2142,19 @@ __device__ __forceinline__ void l2_touch(const void* ptr, int bytes, int t, int*
 // tail_in: the previous block's last samples (k_obs_rows: the workgroup's own LDS; GLOBAL_TAIL, k_obs_blocks: global memory
 // written by the workgroup that rendered block j - 1, waited for through sync.flag_in); tail_out (may be null): where the next
 // block's context goes, sync.flag_out (GLOBAL_TAIL) is released behind it.
-template <bool GLOBAL_TAIL = false>
+// MEL (log-mel form, as fused_stft_phase<.., MEL>): every pooled block also yields the log-mel values of its four frames, lane j
+// of a wave keeps band j of its two blocks in eight registers.  Once every wave of the phase is done the big buffer is dead until
+// the next output block's first pass (that block's context is already in tail_out) and collects [n_mels][4 (b1 - b0)] values
+// (kMelRowsStride floats per band: 27 KiB at 64 bands), which leave as runs of logmel[unit][band][4 b0 .. 4 b1)[ear]:
+// consecutive lanes on consecutive frames, a part only the frames of its own pooled blocks, the last phase up to n_frames.  The
+// pooled spectrogram is optional there (p.sgram may be null).
+constexpr int kMelRowsStride = kPool * kRowsMaxBlocks;      // floats per band of the collected log-mel values of one phase
+template <bool GLOBAL_TAIL = false, bool MEL = false>
 __device__ __forceinline__ void rows_stft_phase(c32* lds, const ConvParams& p, int t, int unit, int ch, int j, int b0, int b1,
                                                 bool last, const c32 (&y)[8], const float* s_win, const c32* s_tw512,
                                                 const c32* s_wq, float* s_res, const float* tail_in, float* tail_out,
-                                                int part = 0, BlockSync sync = BlockSync{nullptr, nullptr, 0}) {
+                                                int part = 0, BlockSync sync = BlockSync{nullptr, nullptr, 0},
+                                                const UnitTab<false, MEL>& mel = UnitTab<false, MEL>()) {
     float* buf = reinterpret_cast<float*>(lds);           // buf[k] = row sample 640 b0 - 256 + k
     const int base = kB * j;                              // first sample of this block
     const int ctx = j == 0 ? kNfft / 2 : base - (kHop * kPool * b0 - kNfft / 2);    // even, <= kTailFloats
@@ -2185,6 +2209,40 @@ __device__ __forceinline__ void rows_stft_phase(c32* lds, const ConvParams& p, i
     stft_load_padded(buf, 4 * kw + (lane >> 4), one ? live : 0, lane & 15, s_win, x0);      // (the window pairs in registers for
     stft_load_padded(buf, 4 * (kw + 16) + (lane >> 4), two ? live : 0, lane & 15, s_win, x1);  // both rounds spill here: 8-16 VGPRs)
     lds_barrier();
+    if constexpr (MEL) {
+        const MelArgs& m = mel;
+        const bool want_sg = p.sgram != nullptr;
+        float mv0[4], mv1[4];                               // lane = band (lanes >= n_mels: a clamped band, dropped below)
+        c32* sc = lds + wv * kWaveScratch;
+        if (one)
+            stft_block_mel<true>(sc, lane, wq, s_tw512, x0, 0, nullptr, m.max_len >> 2, m.eps, want_sg, mv0,
+                                 [&](int b, float v) { s_res[b * cnt + kw] = v; }, &m);
+        if (two) {
+            wave_sync();
+            stft_block_mel<true>(sc, lane, wq, s_tw512, x1, 0, nullptr, m.max_len >> 2, m.eps, want_sg, mv1,
+                                 [&](int b, float v) { s_res[b * cnt + kw + 16] = v; }, &m);
+        }
+        lds_barrier();                                      // every wave's scratch is dead: the buffer collects the bands
+        float* res = reinterpret_cast<float*>(lds);         // res[band][frame - 4 b0]
+        if (lane < m.n_mels) {
+            if (one) *reinterpret_cast<f32x4*>(res + lane * kMelRowsStride + 4 * kw) = f32x4{mv0[0], mv0[1], mv0[2], mv0[3]};
+            if (two) *reinterpret_cast<f32x4*>(res + lane * kMelRowsStride + 4 * (kw + 16)) = f32x4{mv1[0], mv1[1], mv1[2], mv1[3]};
+        }
+        lds_barrier();
+        const int f_lo = kPool * k_lo, f_hi = min(kPool * k_hi, live);      // this part's frames that exist, relative to 4 b0
+        float* om = m.logmel + ((size_t)unit * m.n_mels * p.n_frames + kPool * b0) * 2 + ch;
+        for (int jm = wv; jm < m.n_mels; jm += kT / 64)
+            for (int tf = f_lo + lane; tf < f_hi; tf += 64) om[2 * ((size_t)jm * p.n_frames + tf)] = res[jm * kMelRowsStride + tf];
+        if (want_sg) {                                      // (s_res: complete since the first barrier above)
+            float* o = p.sgram + ((size_t)unit * kBins4 * p.t4 + b0) * 2 + ch;
+            for (int b = t / 32; b < kBins4; b += kT / 32) {
+                const int k = t & 31;
+                if (k >= k_lo && k < k_hi) o[((size_t)b * p.t4 + k) * 2] = s_res[b * cnt + k];
+            }
+        }
+        lds_barrier();                                      // the collected values are read: the buffer goes to the next block
+        return;
+    }
     if (one) stft_block(lds + wv * kWaveScratch, lane, wq, s_tw512, x0, [&](int b, float v) { s_res[b * cnt + kw] = v; });
     if (two) {
         wave_sync();
@@ -2198,9 +2256,24 @@ __device__ __forceinline__ void rows_stft_phase(c32* lds, const ConvParams& p, i
     }
 }
 
-template <bool SPECTRAL, bool XFADE = false, bool BUCKETS = true>
-__global__ __launch_bounds__(1024) void k_obs_rows(ConvParams p, int n_rows) {
+// log-mel of frames [f0, f1) of one (unit, ear) row that are not computed (silent units, pooled blocks behind n_valid): zero
+// power in every band, log(eps)
+__device__ __forceinline__ void mel_fill_quiet(const MelArgs& m, const ConvParams& p, int t, int unit, int ch, int f0, int f1) {
+    float eps = m.eps;
+    SSK_OPAQUE1(eps);                                     // (the log is taken here: hoisted, it costs the row loop a register)
+    const float quiet = mel_log(eps);
+    float* om = m.logmel + (size_t)unit * m.n_mels * p.n_frames * 2 + ch;
+    const int nf = f1 - f0;
+    for (int jm = t >> 6; jm < m.n_mels; jm += kT / 64)
+        for (int tf = t & 63; tf < nf; tf += 64) om[2 * ((size_t)jm * p.n_frames + f0 + tf)] = quiet;
+}
+
+// MEL (log-mel form: plain rows of a single-allocation bank): the mel arguments and the log-mel output ride in the third kernel
+// argument (MelArgs, see UnitTab), the STFT phases emit the bands (rows_stft_phase<.., MEL>), p.sgram may be null.
+template <bool SPECTRAL, bool XFADE = false, bool BUCKETS = true, bool MEL = false>
+__global__ __launch_bounds__(1024) void k_obs_rows(ConvParams p, int n_rows, UnitTab<false, MEL> ut = UnitTab<false, MEL>()) {
     static_assert(!(SPECTRAL && XFADE), "cross-faded rows are rendered from the time-domain bank");
+    static_assert(!MEL || (!XFADE && !BUCKETS), "log-mel: plain rows of a single-allocation bank");
     __shared__ c32 lds[16 * kWaveScratch > kLdsComplex ? 16 * kWaveScratch : kLdsComplex];
     __shared__ float s_win[kNfft];
     __shared__ c32 s_tw512[kTw512Lds];
@@ -2262,6 +2335,10 @@ __global__ __launch_bounds__(1024) void k_obs_rows(ConvParams p, int n_rows) {
             if (p.out) {
 #pragma nounroll
                 for (int n = tz; n < p.out_len; n += kT) p.out[(size_t)row * p.out_len + n] = 0.f;
+            }
+            if constexpr (MEL) {
+                mel_fill_quiet(ut, p, tz, unit, ch, 0, p.n_frames);
+                if (!p.sgram) continue;
             }
             float* o = p.sgram + (size_t)unit * kBins4 * p.t4 * 2 + ch;
 #pragma nounroll
@@ -2332,8 +2409,10 @@ __global__ __launch_bounds__(1024) void k_obs_rows(ConvParams p, int n_rows) {
                 const f32x4* spn = p.spec + (size_t)(ndw.y + (j - n_i - ndw.z)) * blk_f4 + ti;
                 f32x4 sn[4];
                 if (has_new) {
+                    if constexpr (!(MEL && !SPECTRAL)) {
 #pragma unroll
-                    for (int hh = 0; hh < 4; ++hh) sn[hh] = spn[hh * 1024];
+                        for (int hh = 0; hh < 4; ++hh) sn[hh] = spn[hh * 1024];
+                    }
                     if (!(kRowsAbl & 8)) pass3_fwd(lds, ti);
                     lds_barrier();
                 }
@@ -2344,7 +2423,7 @@ __global__ __launch_bounds__(1024) void k_obs_rows(ConvParams p, int n_rows) {
                 for (int s = 0; s < 2; ++s) {
                     c32 v[8];
                     if (has_new) {
-                        if (s == 1) {
+                        if (s == 1 && !(MEL && !SPECTRAL)) {
 #pragma unroll
                             for (int hh = 0; hh < 4; ++hh) sn[hh] = spn[(4 + hh) * 1024];
                         }
@@ -2353,6 +2432,12 @@ __global__ __launch_bounds__(1024) void k_obs_rows(ConvParams p, int n_rows) {
                             f32x4* st = stash + (size_t)(n_term * p.stash_nbh + n_i) * blk_f4 + ti;
 #pragma unroll
                             for (int hh = 0; hh < 4; ++hh) st[(s * 4 + hh) * 1024] = mk4(v[2 * hh], v[2 * hh + 1]);
+                        }
+                        if constexpr (MEL && !SPECTRAL) {
+                            // the log-mel form of the time-domain kernel has no registers to carry the new pair's window
+                            // spectrum under pass 3 / the item loads (24 VGPRs spilled when it did): fetched where it is used
+#pragma unroll
+                            for (int hh = 0; hh < 4; ++hh) sn[hh] = spn[(s * 4 + hh) * 1024];
                         }
 #pragma unroll
                         for (int e = 0; e < 8; ++e) {
@@ -2435,12 +2520,19 @@ __global__ __launch_bounds__(1024) void k_obs_rows(ConvParams p, int n_rows) {
                 if (y[0].x == 123.456f) p.sgram[0] = y[7].y;      // keeps the convolution alive
                 lds_barrier();
             } else if (b1c > b0) {
-                rows_stft_phase(lds, p, tl, row_j >> 1, row_j & 1, j, b0, b1c, last && b1c == b1, y, s_win, s_tw512, s_wq, s_res, s_tail,
-                                s_tail, part);
+                if constexpr (MEL)
+                    rows_stft_phase<false, true>(lds, p, tl, row_j >> 1, row_j & 1, j, b0, b1c, last && b1c == b1, y, s_win, s_tw512,
+                                                 s_wq, s_res, s_tail, s_tail, part, BlockSync{nullptr, nullptr, 0}, ut);
+                else
+                    rows_stft_phase(lds, p, tl, row_j >> 1, row_j & 1, j, b0, b1c, last && b1c == b1, y, s_win, s_tw512, s_wq, s_res,
+                                    s_tail, s_tail, part);
             } else {
                 lds_barrier();                            // (the phase's entry barrier: pass-1' reads of the buffer are over)
             }
-            if (b1c < b1 && part == 0) {
+            if constexpr (MEL) {                          // pooled blocks behind n_valid: log(eps) in every band and frame
+                if (b1c < b1 && part == 0) mel_fill_quiet(ut, p, tl, row_j >> 1, row_j & 1, kPool * b1c, min(p.n_frames, kPool * b1));
+            }
+            if (b1c < b1 && part == 0 && (!MEL || p.sgram)) {
                 float* o = p.sgram + ((size_t)(row_j >> 1) * kBins4 * p.t4) * 2 + (row_j & 1);
                 const int nz = b1 - b1c;
                 for (int e = tl; e < kBins4 * nz; e += kT) {
@@ -2472,8 +2564,11 @@ __global__ __launch_bounds__(1024) void k_obs_rows(ConvParams p, int n_rows) {
 // waited for is running or about to; the wait is bounded anyway (flag_acquire).  Same arithmetic per output sample and per
 // pooled column as k_obs_rows: identical results.  Preconditions (launcher): n_valid == out_len (SoundSpaces 1.0 rows), no
 // cross-fade, 2 or 3 output blocks.
-template <bool SPECTRAL>
-__global__ __launch_bounds__(1024) void k_obs_blocks(ConvParams p, int n_rows, float* tails, int* flags, int epoch) {
+// MEL (log-mel form, as k_obs_rows<.., MEL>): a workgroup writes the log-mel frames of its own pooled blocks, the silent row's
+// early return its block's share of frames; p.sgram may be null.
+template <bool SPECTRAL, bool MEL = false>
+__global__ __launch_bounds__(1024) void k_obs_blocks(ConvParams p, int n_rows, float* tails, int* flags, int epoch,
+                                                     UnitTab<false, MEL> ut = UnitTab<false, MEL>()) {
     __shared__ c32 lds[16 * kWaveScratch > kLdsComplex ? 16 * kWaveScratch : kLdsComplex];
     __shared__ float s_win[kNfft];
     __shared__ c32 s_tw512[kTw512Lds];
@@ -2508,6 +2603,10 @@ __global__ __launch_bounds__(1024) void k_obs_blocks(ConvParams p, int n_rows, f
         if (p.out) {
             const int lo = kB * j, hi = min(p.out_len, kB * (j + 1));
             for (int n = lo + t; n < hi; n += kT) p.out[(size_t)row * p.out_len + n] = 0.f;
+        }
+        if constexpr (MEL) {
+            mel_fill_quiet(ut, p, t, unit, ch, kPool * b0, min(p.n_frames, kPool * b1));
+            if (!p.sgram) return;
         }
         float* o = p.sgram + (size_t)unit * kBins4 * p.t4 * 2 + ch;
         const int nz = b1 - b0;
@@ -2567,9 +2666,14 @@ __global__ __launch_bounds__(1024) void k_obs_blocks(ConvParams p, int n_rows, f
     if (part == 0) store_row_block(p, t, (size_t)row, j, y);
     const size_t hand = (size_t)row * (nb_rows - 1);      // the row's hand-off slots: [row][j] = block j -> block j + 1
     BlockSync sync{(!last && part == 0) ? flags + hand + j : nullptr, j > 0 ? flags + hand + (j - 1) : nullptr, epoch};
-    rows_stft_phase<true>(lds, p, t, unit, ch, j, b0, b1, last, y, s_win, s_tw512, s_wq, s_res,
-                          j > 0 ? tails + (hand + (j - 1)) * kTailFloats : nullptr,
-                          (!last && part == 0) ? tails + (hand + j) * kTailFloats : nullptr, part, sync);
+    if constexpr (MEL)
+        rows_stft_phase<true, true>(lds, p, t, unit, ch, j, b0, b1, last, y, s_win, s_tw512, s_wq, s_res,
+                                    j > 0 ? tails + (hand + (j - 1)) * kTailFloats : nullptr,
+                                    (!last && part == 0) ? tails + (hand + j) * kTailFloats : nullptr, part, sync, ut);
+    else
+        rows_stft_phase<true>(lds, p, t, unit, ch, j, b0, b1, last, y, s_win, s_tw512, s_wq, s_res,
+                              j > 0 ? tails + (hand + (j - 1)) * kTailFloats : nullptr,
+                              (!last && part == 0) ? tails + (hand + j) * kTailFloats : nullptr, part, sync);
 }
 
 // ---------------------------------------------------------------------------------------------

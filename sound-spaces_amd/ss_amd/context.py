@@ -182,6 +182,19 @@ class AudioContext:
         it (ss_ctx_set_logmel_policy).  (1, 2**31 - 1): fused whenever possible; (1, 0): never."""
         _lib.check(self.lib.ss_ctx_set_logmel_policy(self._h, int(min_units), int(max_units)), "ss_ctx_set_logmel_policy")
 
+    def set_logmel_rows_policy(self, min_units: int, max_units: int) -> None:
+        """``set_logmel_policy`` for rows of 2 or 3 partition blocks (44.1 / 48 kHz): log-mel steps without a waveform buffer of
+        ``min_units`` .. ``max_units`` units take the one-launch log-mel form of the fused row kernels (no cross-fade,
+        single-allocation bank; ss_ctx_set_logmel_rows_policy).  Default (1, 0): never - the scratch route is bit-equal to
+        observe-then-features, the fused launch only to rounding.  (1, 2**31 - 1): whenever the shape allows."""
+        _lib.check(self.lib.ss_ctx_set_logmel_rows_policy(self._h, int(min_units), int(max_units)),
+                   "ss_ctx_set_logmel_rows_policy")
+
+    def wave_scratch_bytes(self) -> int:
+        """Bytes of waveform scratch the context holds over all overlap lanes (ss_ctx_wave_scratch_bytes): 0 until a log-mel
+        step without a waveform buffer takes the scratch route, and again after ``ss_release_scratch``."""
+        return int(self.lib.ss_ctx_wave_scratch_bytes(self._h))
+
     def set_chip_share(self, n_sources: int) -> None:
         """This context is one of ``n_sources`` launch sources kept busy at once (e.g. two env groups stepped alternately, each
         with its own context and stream): its small steps split their rows over 1 / n_sources of the chip (ss_ctx_set_chip_share)."""

@@ -344,6 +344,39 @@ def audio_obs_logmel_spec_into(spec, hspec, rir_len, unit_desc, audiogoal, spect
                    "ss_audio_obs_logmel_spec_f32")
 
 
+def audio_obs_logmel_rows_into(spec, rir_bank, rir_len, unit_desc, audiogoal, spectrogram_out, logmel_out, mel_start, mel_w,
+                               n_valid: int, out_len: int, mel_eps: float = 1e-6, pad_mode="reflect", interleaved: bool = False,
+                               flags: int = 0) -> None:
+    """``audio_obs_logmel_into`` for rows of 2 or 3 partition blocks (KB < out_len <= 3 KB: 44.1 / 48 kHz;
+    ``ss_audio_obs_logmel_rows_f32``): ONE launch of the log-mel form of the fused row kernels, whichever outputs are asked for
+    next to ``logmel_out``.  No cross-fade, at most 16 RIR blocks; anything else is refused (invalid argument).  Small steps run
+    the one-workgroup-per-output-block kernel, whose launch must not be replayed from a captured graph."""
+    _chk(spec, torch.float32, "spec"); _chk(rir_bank, torch.float32, "rir_bank"); _chk(rir_len, torch.int32, "rir_len")
+    N, n_mels, max_len, ag_ptr, sg_ptr = _obs_logmel_args(unit_desc, audiogoal, spectrogram_out, logmel_out, mel_start, mel_w, out_len)
+    us, cs, es, cap = _bank_strides(rir_bank, interleaved)
+    with torch.cuda.device(spec.device):
+        _lib.check(_lib.load().ss_audio_obs_logmel_rows_f32(spec.data_ptr(), rir_bank.data_ptr(), rir_len.data_ptr(),
+                                                            unit_desc.data_ptr(), ag_ptr, sg_ptr, logmel_out.data_ptr(),
+                                                            mel_start.data_ptr(), mel_w.data_ptr(), int(n_mels), int(max_len),
+                                                            float(mel_eps), N, us, cs, es, cap, n_valid, out_len, _PAD[pad_mode],
+                                                            flags, _stream(spec)), "ss_audio_obs_logmel_rows_f32")
+
+
+def audio_obs_logmel_rows_spec_into(spec, hspec, rir_len, unit_desc, audiogoal, spectrogram_out, logmel_out, mel_start, mel_w,
+                                    n_valid: int, out_len: int, mel_eps: float = 1e-6, pad_mode="reflect", flags: int = 0) -> None:
+    """``audio_obs_logmel_rows_into`` from the spectral RIR bank (``ss_audio_obs_logmel_rows_spec_f32``)."""
+    _chk(spec, torch.float32, "spec"); _chk(hspec, torch.float32, "hspec"); _chk(rir_len, torch.int32, "rir_len")
+    assert hspec.dim() == 4
+    N, n_mels, max_len, ag_ptr, sg_ptr = _obs_logmel_args(unit_desc, audiogoal, spectrogram_out, logmel_out, mel_start, mel_w, out_len)
+    with torch.cuda.device(spec.device):
+        _lib.check(_lib.load().ss_audio_obs_logmel_rows_spec_f32(spec.data_ptr(), hspec.data_ptr(), rir_len.data_ptr(),
+                                                                 unit_desc.data_ptr(), ag_ptr, sg_ptr, logmel_out.data_ptr(),
+                                                                 mel_start.data_ptr(), mel_w.data_ptr(), int(n_mels), int(max_len),
+                                                                 float(mel_eps), N, hspec.shape[2], n_valid, out_len,
+                                                                 _PAD[pad_mode], flags, _stream(spec)),
+                   "ss_audio_obs_logmel_rows_spec_f32")
+
+
 # ---- length-bucketed RIR bank (SURVEY 8(f)2) ------------------------------------------------------------------------
 def bucket_array(banks, firsts, spectral: bool):
     """ctypes array of ss_rir_bucket for per-bucket (data [n,2,cap], spectra or None) tensors; keep it alive with the
