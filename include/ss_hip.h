@@ -177,6 +177,27 @@ int ss_audio_obs_logmel_rows_spec_f32(const float* spec, const float* hspec, con
                                       const float* mel_w, int n_mels, int max_len, float mel_eps, int n_units, int h_blocks,
                                       int n_valid, int out_len, int pad_mode, int flags, void* stream);
 
+/* SoundSpaces 2.0 steps (the reference's CONTINUOUS mode: 0.25 s of a 1-s row, cross-faded from the previous step's RIR in every
+ * step but the first of an episode; EXTENSION): the log-mel form of the fused loop kernel with the cross-fade and / or its WIDE
+ * form (only block 0 of a longer row is rendered).  Arguments and outputs as ss_audio_obs_logmel_f32, time-domain bank only (live
+ * RIRs have no spectral form); `audiogoal` and `spectrogram` may each be NULL and ANY combination of the three outputs is ONE
+ * launch, one workgroup per (unit, ear) row.  A waveform buffer and the pooled spectrogram are written exactly as
+ * ss_audio_obs_f32 writes them on the same kernel.  Served shapes:
+ *   (A) 257 <= out_len <= kB WITH SS_FLAG_CROSSFADE (term 1 of a unit = the previous RIR; units without one are not blended),
+ *       0 <= n_valid <= out_len;
+ *   (B) kB < out_len <= 3 kB, 0 <= n_valid <= kB and at most 26 live pooled blocks (44.1 / 48 kHz: n_valid = sr / 4), with or
+ *       without SS_FLAG_CROSSFADE (then int(0.05 out_len) in [1, 2414]); without the flag distractor terms are fine.  The frames
+ *       of pooled blocks behind the live ones come out as log(mel_eps), the spectrogram's columns there as zeros.
+ * Any RIR length is accepted.  Silent units and units whose RIR is empty give log(mel_eps) in every band and exact zeros in the
+ * pooled spectrogram.  Everything else - plain one-block rows (ss_audio_obs_logmel_f32), rows with more than one rendered block
+ * (ss_audio_obs_logmel_rows_f32), mel arguments outside the limits above, a bad pad_mode - is SS_EINVAL from the argument
+ * checks, before a device is touched. */
+int ss_audio_obs_logmel_ss2_f32(const float* spec, const float* rir, const int* rir_len, const int* unit_desc,
+                                float* audiogoal, float* spectrogram, float* logmel, const int* mel_start, const float* mel_w,
+                                int n_mels, int max_len, float mel_eps, int n_units, long long rir_unit_stride,
+                                int rir_chan_stride, int rir_elem_stride, int rir_cap, int n_valid, int out_len, int pad_mode,
+                                int flags, void* stream);
+
 /* ---- Length-bucketed RIR bank ------------------------------------------------------------------------
  * The reference's RIRs are variable-length wav files (soundspaces/README.md:38-42, read at simulator.py:615-618; SS2.0's
  * ray-traced RIRs run to 4 s).  One capacity for every row means one long RIR reallocates the whole bank, multiplies the
@@ -333,7 +354,11 @@ int ss_ctx_observe(ss_ctx* ctx, const ss_units* units, int n, float* audiogoal, 
  *   - ONE fused launch as well (ss_audio_obs_logmel_rows_f32 / _spec_f32) when its rows are 2 or 3 partition blocks (44.1 /
  *     48 kHz), under the same conditions, and its unit count lies inside ss_ctx_set_logmel_rows_policy's range - which is empty
  *     by default: the fused values equal the next route's to rounding (1e-4 of the largest value), not bit for bit;
- *   - otherwise (44.1 / 48 kHz rows by default, cross-faded steps, bucketed banks, unit counts outside the range) the route ss_ctx_observe
+ *   - ONE fused launch (ss_audio_obs_logmel_ss2_f32) when it is a SoundSpaces 2.0 step - a cross-faded step of one-block rows,
+ *     or a step that renders only block 0 of a 44.1 / 48 kHz row, cross-faded or not - on the time-domain rows of a
+ *     single-allocation bank (not the spectral-only binding) and its unit count lies inside ss_ctx_set_logmel_ss2_policy's
+ *     range, which is empty by default for the same reason;
+ *   - otherwise (44.1 / 48 kHz rows and cross-faded steps by default, bucketed banks, unit counts outside the range) the route ss_ctx_observe
  *     takes with an audiogoal buffer, into a waveform scratch the CONTEXT owns ([n, 2, sr] floats per overlap lane, grown on
  *     demand, freed with the context and by ss_release_scratch; a growth needed while the stream is being captured is refused
  *     with SS_EINVAL: warm the stream up first), then ss_audio_features_f32 over it: bit for bit ss_ctx_observe +
@@ -358,6 +383,12 @@ int ss_ctx_set_logmel_policy(ss_ctx* ctx, int min_units, int max_units);
 /* The same for rows of 2 or 3 partition blocks (44.1 / 48 kHz).  ss_ctx_set_logmel_policy keeps its meaning (one-block rows
  * only).  Default: never (max_units < min_units) - see above; profiles/r7/NOTES.md names the range the measurements support. */
 int ss_ctx_set_logmel_rows_policy(ss_ctx* ctx, int min_units, int max_units);
+/* The same for SoundSpaces 2.0 steps (ss_audio_obs_logmel_ss2_f32's shapes); the two setters above keep their meaning.  Default:
+ * never (max_units < min_units) - the fused values equal the scratch route's to rounding only.  Measured faster than the
+ * scratch route of the same context at every point of 1 .. 256 units (16 kHz cross-faded, 44.1 kHz cross-faded and plain; RIRs
+ * of 9000 taps: 19-58 %, of 4 s: 5-33 %; profiles/r7/kbench_obs_logmel_ss2.txt), so (1, INT_MAX) is the range a caller who
+ * accepts rounding-level differences would pass. */
+int ss_ctx_set_logmel_ss2_policy(ss_ctx* ctx, int min_units, int max_units);
 /* Bytes of waveform scratch the context currently holds over all overlap lanes (the scratch route above): 0 after creation and
  * after ss_release_scratch. */
 size_t ss_ctx_wave_scratch_bytes(const ss_ctx* ctx);

@@ -398,6 +398,20 @@ int launch_conv_mel(ssk::ConvParams p, const ssk::MelArgs& m, int n_units, int f
     return hip_err(hipGetLastError());
 }
 
+// SoundSpaces 2.0 steps (ss_audio_obs_logmel_ss2_f32): the cross-faded one-block row and the WIDE row (block 0 of a longer row,
+// with or without the cross-fade) in their log-mel forms - the loop kernel, one workgroup per (unit, ear) row
+int launch_conv_mel_ss2(ssk::ConvParams p, const ssk::MelArgs& m, int n_units, int flags, bool wide, hipStream_t st) {
+    p.nb_y = 1;
+    p.parts_log2 = 0;
+    const bool xfade = (flags & SS_FLAG_CROSSFADE) != 0;
+    if (xfade && (p.fade_len < 1 || p.fade_len > 2 * ssk::kPrevPairs - 2)) return SS_EINVAL;
+    const dim3 grid(2 * n_units), block(ssk::kT);
+    if (!wide) hipLaunchKernelGGL((ssk::k_conv<true, false, true, false, false, true>), grid, block, 0, st, p, m);
+    else if (xfade) hipLaunchKernelGGL((ssk::k_conv<true, false, true, false, true, true>), grid, block, 0, st, p, m);
+    else hipLaunchKernelGGL((ssk::k_conv<true, false, false, false, true, true>), grid, block, 0, st, p, m);
+    return hip_err(hipGetLastError());
+}
+
 int launch_conv_spec_mel(ssk::ConvParams p, const ssk::MelArgs& m, int n_units, int flags, hipStream_t st) {
     p.nb_y = 1;
     p.parts_log2 = 0;
@@ -780,6 +794,38 @@ int ss_audio_obs_logmel_f32(const float* spec, const float* rir, const int* rir_
     p.sgram = spectrogram;
     const ssk::MelArgs m{logmel, mel_start, mel_w, n_mels, max_len, mel_eps};
     return launch_conv_mel(p, m, n_units, flags, static_cast<hipStream_t>(stream));
+}
+
+// SoundSpaces 2.0 steps the log-mel form serves (time-domain bank): (A) cross-faded one-block rows - fade_len = int(0.05 out_len)
+// lies inside [1, 2 kPrevPairs - 2] for every such length - and (B) rows of 2 or 3 blocks of which only block 0 is rendered
+// (wide_one_block_ok: its own cross-fade limits).  0: neither, 1: (A), 2: (B).
+inline int obs_logmel_ss2_shape(int out_len, int n_valid, int flags) {
+    if (n_valid < 0 || n_valid > out_len) return 0;
+    if (out_len >= ssk::kNfft / 2 + 1 && out_len <= ssk::kB) return (flags & SS_FLAG_CROSSFADE) ? 1 : 0;
+    return out_len <= 3 * ssk::kB && wide_one_block_ok(out_len, n_valid, flags) ? 2 : 0;
+}
+
+// Log-mel observation of a SoundSpaces 2.0 step in ONE launch (k_conv<.., XFADE, .., WIDE, MEL>), no waveform buffer needed.
+// Every argument is checked before a device is touched.
+int ss_audio_obs_logmel_ss2_f32(const float* spec, const float* rir, const int* rir_len, const int* unit_desc, float* audiogoal,
+                                float* spectrogram, float* logmel, const int* mel_start, const float* mel_w, int n_mels,
+                                int max_len, float mel_eps, int n_units, long long rir_unit_stride, int rir_chan_stride,
+                                int rir_elem_stride, int rir_cap, int n_valid, int out_len, int pad_mode, int flags, void* stream) {
+    if (n_units == 0) return 0;
+    if (n_units < 0 || !mel_args_ok(logmel, mel_start, mel_w, n_mels, max_len, mel_eps)) return SS_EINVAL;
+    if (pad_mode != SS_PAD_REFLECT && pad_mode != SS_PAD_CONSTANT) return SS_EINVAL;
+    const int shape = obs_logmel_ss2_shape(out_len, n_valid, flags);
+    if (!shape) return SS_EINVAL;
+    ssk::ConvParams p;
+    int n_cus = 1;
+    int rc = fill_conv(p, &n_cus, spec, rir, rir_len, unit_desc, rir_unit_stride, rir_chan_stride, rir_elem_stride,
+                       rir_cap, n_valid, out_len);
+    if (rc) return rc;
+    p.pad_mode = pad_mode;
+    p.out = audiogoal;
+    p.sgram = spectrogram;
+    const ssk::MelArgs m{logmel, mel_start, mel_w, n_mels, max_len, mel_eps};
+    return launch_conv_mel_ss2(p, m, n_units, flags, shape == 2, static_cast<hipStream_t>(stream));
 }
 
 // rows the log-mel form of k_obs_rows / k_obs_blocks serves: 2 or 3 partition blocks (44.1 / 48 kHz), plain steps, at most 16
@@ -1447,7 +1493,13 @@ static int ctx_observe_on(ss_ctx* h, const ss_units* units, int n, float* audiog
     const bool mel_rows = mel && !mel_fused && c.buckets.empty() && (spectral || (c.rir && c.rir_cap > 0)) &&
                           obs_logmel_rows_shape_ok(c.out_len, c.n_valid, nbh_bank, res.flags) &&
                           n >= c.mel_rows_min_units && n <= c.mel_rows_max_units;
-    if (mel && !mel_fused && !mel_rows) {
+    // SoundSpaces 2.0 steps (cross-faded one-block rows; block 0 of a 44.1 / 48 kHz row, cross-faded or not): their own fused
+    // launch from the time-domain rows of a single-allocation bank, inside the range of ss_ctx_set_logmel_ss2_policy (default:
+    // never, for the same reason)
+    const bool mel_ss2 = mel && !mel_fused && !mel_rows && c.buckets.empty() && c.rir && !spectral &&
+                         obs_logmel_ss2_shape(c.out_len, c.n_valid, res.flags) != 0 &&
+                         n >= c.mel_ss2_min_units && n <= c.mel_ss2_max_units;
+    if (mel && !mel_fused && !mel_rows && !mel_ss2) {
         rc = get_wave_scratch(&c, lane < 0 ? 0 : lane, st, static_cast<size_t>(n) * 2 * c.out_len, &audiogoal);
         if (rc) return fail(rc);
     }
@@ -1469,7 +1521,11 @@ static int ctx_observe_on(ss_ctx* h, const ss_units* units, int n, float* audiog
     SS_PROF_MARK(4);                                           // new windows (upload + k_source_windows), descriptor upload
     g_host_desc = no_tab ? nullptr : hd;                       // (see fill_unit_tab; cleared right after the dispatch below)
     g_launch_share = c.chip_share > 0 ? c.chip_share : c.n_lanes;
-    if (mel_rows) {
+    if (mel_ss2) {
+        rc = ss_audio_obs_logmel_ss2_f32(c.pool, c.rir, c.rir_len, dd, nullptr, spectrogram, mel->logmel, mel->mel_start, mel->mel_w,
+                                         mel->n_mels, mel->max_len, mel->mel_eps, n, c.rir_us, c.rir_cs, c.rir_es, c.rir_cap,
+                                         c.n_valid, c.out_len, c.pad_mode, res.flags, stream);
+    } else if (mel_rows) {
         rc = spectral ? ss_audio_obs_logmel_rows_spec_f32(c.pool, c.hspec, c.rir_len, dd, nullptr, spectrogram, mel->logmel,
                                                           mel->mel_start, mel->mel_w, mel->n_mels, mel->max_len, mel->mel_eps, n,
                                                           c.h_blocks, c.n_valid, c.out_len, c.pad_mode, res.flags, stream)
@@ -1504,7 +1560,7 @@ static int ctx_observe_on(ss_ctx* h, const ss_units* units, int n, float* audiog
     g_host_desc = nullptr;
     g_launch_share = 1;
     SS_PROF_MARK(5);                                           // the launch entry (unit table + hipLaunchKernel)
-    if (!rc && mel && !mel_fused && !mel_rows)                 // scratch route: the features of the waveform just rendered
+    if (!rc && mel && !mel_fused && !mel_rows && !mel_ss2)     // scratch route: the features of the waveform just rendered
         rc = ss_audio_features_f32(audiogoal, n, c.out_len, c.pad_mode, nullptr, mel->logmel, mel->mel_start, mel->mel_w,
                                    mel->n_mels, mel->max_len, mel->mel_eps, nullptr, 1, 1.f, stream);
     if (rc) return fail(rc);
@@ -1563,6 +1619,13 @@ int ss_ctx_set_logmel_rows_policy(ss_ctx* h, int min_units, int max_units) {
     if (!h || min_units < 0 || max_units < 0) return SS_EINVAL;
     h->c.mel_rows_min_units = min_units;
     h->c.mel_rows_max_units = max_units;
+    return 0;
+}
+
+int ss_ctx_set_logmel_ss2_policy(ss_ctx* h, int min_units, int max_units) {
+    if (!h || min_units < 0 || max_units < 0) return SS_EINVAL;
+    h->c.mel_ss2_min_units = min_units;
+    h->c.mel_ss2_max_units = max_units;
     return 0;
 }
 

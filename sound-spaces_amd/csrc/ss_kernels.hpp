@@ -1296,17 +1296,19 @@ constexpr int kResFloats = kBins4 * 26;     // pooled spectrogram of one ear (<=
 // pooled blocks [part * per, (part + 1) * per) of a row belong to workgroup `part` of its 2^parts_log2 (ConvParams::parts_log2)
 __host__ __device__ constexpr int part_blocks(int t4, int parts_log2) { return (t4 + (1 << parts_log2) - 1) >> parts_log2; }
 
-// MEL (log-mel form; one workgroup per row, not WIDE): every pooled block also yields the log-mel values of its four frames
+// MEL (log-mel form; one workgroup per row): every pooled block also yields the log-mel values of its four frames
 // (stft_block_mel) - lane j of a wave keeps band j of its two blocks in eight registers; when every wave is done the big buffer
 // is dead and collects the ear's [n_mels][n_frames] values (26 KiB at 64 bands: s_res could not hold them), which then leave as
 // whole rows of logmel[unit][j][.][ear]: consecutive lanes, consecutive frames, every other float of a contiguous range.  The
 // pooled spectrogram is optional there (p.sgram may be null).
+// WIDE && MEL: the collection buffer holds the frames of the 26 blocks that can be live; the row's other frames (n_frames = 276 /
+// 301 at 44.1 / 48 kHz) read nothing but zeros - the right centre padding included: n_valid <= kB < out_len - 512 - and are
+// written as log(eps), as the pooled spectrogram's dead columns are written as zeros.
 constexpr int kMelResStride = 4 * 26;       // floats per band of the collected log-mel values (frames of 26 blocks)
 template <bool WIDE = false, bool MEL = false>
 __device__ __forceinline__ void fused_stft_phase(c32* lds, const ConvParams& p, int t, int unit, int ch, const c32 (&y)[8],
                                                  const float* s_win, const c32* s_tw512, c32 wq, float* s_res, int part = 0,
                                                  const UnitTab<false, MEL>& mel = UnitTab<false, MEL>()) {
-    static_assert(!(WIDE && MEL), "the log-mel form serves one-block rows");
     // The row goes to LDS with librosa's centre padding materialised around it (256 samples on each side), so that
     // every frame is an aligned, branch-free read.  (With the padding resolved per sample at load time, the three
     // waves that own the first / last frames ran a ~300-instruction edge path on top of their two blocks; two of them
@@ -1388,17 +1390,26 @@ __device__ __forceinline__ void fused_stft_phase(c32* lds, const ConvParams& p, 
         }
         lds_barrier();                                      // every wave's scratch is dead: the buffer collects the bands
         float* res = reinterpret_cast<float*>(lds);
+        const int cols = WIDE ? 26 : p.t4;                  // blocks the buffer collects (WIDE: t4 > 26, the rest is quiet)
         if (lane < m.n_mels) {
-            if (bw < p.t4) *reinterpret_cast<f32x4*>(res + lane * kMelResStride + 4 * bw) = f32x4{mv0[0], mv0[1], mv0[2], mv0[3]};
-            if (bw + 16 < p.t4)
+            if (bw < cols) *reinterpret_cast<f32x4*>(res + lane * kMelResStride + 4 * bw) = f32x4{mv0[0], mv0[1], mv0[2], mv0[3]};
+            if (bw + 16 < cols)
                 *reinterpret_cast<f32x4*>(res + lane * kMelResStride + 4 * (bw + 16)) = f32x4{mv1[0], mv1[1], mv1[2], mv1[3]};
         }
         lds_barrier();
         float* om = m.logmel + (size_t)unit * m.n_mels * p.n_frames * 2 + ch;
         for (int j = wv; j < m.n_mels; j += kT / 64)
-            for (int tf = lane; tf < p.n_frames; tf += 64) om[2 * ((size_t)j * p.n_frames + tf)] = res[j * kMelResStride + tf];
+            for (int tf = lane; tf < p.n_frames; tf += 64)
+                om[2 * ((size_t)j * p.n_frames + tf)] = !WIDE || tf < kMelResStride ? res[j * kMelResStride + tf] : quiet;
         if (!want_sg) return;
         float* o = p.sgram + (size_t)unit * kBins4 * p.t4 * 2 + ch;     // (s_res: complete since the first barrier above)
+        if (WIDE) {                                         // t4 columns per pooled row, the live ones from s_res
+            for (int idx = t; idx < kBins4 * p.t4; idx += kT) {
+                const int b = idx / p.t4, k = idx - b * p.t4;
+                o[2 * idx] = k < live ? s_res[b * rs + k] : 0.f;
+            }
+            return;
+        }
         const int k = t & 31;
         if (k < p.t4)
             for (int b = t >> 5; b < kBins4; b += kT / 32) o[2 * (b * p.t4 + k)] = k < live ? s_res[b * p.t4 + k] : 0.f;
@@ -1434,7 +1445,7 @@ __device__ __forceinline__ void fused_stft_phase(c32* lds, const ConvParams& p, 
 template <bool FUSE, bool SIMPLE, bool XFADE = false, bool TAB = false, bool WIDE = false, bool MEL = false>
 __global__ __launch_bounds__(1024) void k_conv(ConvParams p, UnitTab<TAB, MEL> ut = UnitTab<TAB, MEL>()) {
     static_assert(!(SIMPLE && XFADE), "the cross-fade needs the two-term loop kernel");
-    static_assert(!MEL || (FUSE && !XFADE && !TAB && !WIDE), "log-mel: the plain fused kernels (launched with parts_log2 = 0)");
+    static_assert(!MEL || (FUSE && !TAB), "log-mel: the fused kernels without a unit table (launched with parts_log2 = 0)");
     static_assert(!WIDE || (FUSE && !SIMPLE), "WIDE: fused loop kernel for rows of which only block 0 is rendered");
     static_assert(!TAB || SIMPLE, "the unit table serves the loop-free kernel");
     __shared__ c32 lds[FUSE && 16 * kWaveScratch > kLdsComplex ? 16 * kWaveScratch : kLdsComplex];
@@ -1601,7 +1612,7 @@ __global__ __launch_bounds__(1024) void k_conv(ConvParams p, UnitTab<TAB, MEL> u
     if (FUSE) {
         if (t < kNfft) s_win[t] = win_v;                    // visible to the STFT phase after its first barrier
         if (t < 256) s_tw512[posN(t)] = tw512_v;
-        if constexpr (MEL) fused_stft_phase<false, true>(lds, p, t, ounit, ch, y, s_win, s_tw512, wq, s_res, 0, ut);
+        if constexpr (MEL) fused_stft_phase<WIDE, true>(lds, p, t, ounit, ch, y, s_win, s_tw512, wq, s_res, 0, ut);
         else fused_stft_phase<WIDE>(lds, p, t, ounit, ch, y, s_win, s_tw512, wq, s_res, part);
     }
 }

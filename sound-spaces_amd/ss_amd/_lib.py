@@ -18,7 +18,8 @@ EXPORTS = ("ss_block_len", "ss_spec_floats", "ss_version", "ss_init", "ss_source
            "ss_source_windows32_f32", "ss_audio_obs32_f32", "ss_ctx_observe_requests", "ss_ctx_requests_units", "ss_audio_features_f32", "ss_ctx_observe_features",
            "ss_wav_read_rirs_f32", "ss_rows_gather_f32", "ss_bank_scatter_rows_f32", "ss_ctx_set_chip_share", "ss_ctx_set_spectral_policy", "ss_ctx_observe_requests_load", "ss_ctx_load_rir_files",
            "ss_bank_scatter_spectra_f32", "ss_audio_obs_logmel_f32", "ss_audio_obs_logmel_spec_f32", "ss_ctx_set_logmel_policy",
-           "ss_audio_obs_logmel_rows_f32", "ss_audio_obs_logmel_rows_spec_f32", "ss_ctx_set_logmel_rows_policy")
+           "ss_audio_obs_logmel_rows_f32", "ss_audio_obs_logmel_rows_spec_f32", "ss_ctx_set_logmel_rows_policy",
+           "ss_audio_obs_logmel_ss2_f32", "ss_ctx_set_logmel_ss2_policy")
 # entries that return a size_t, not a status (EXPORTS: every `int ss_*` of include/ss_hip.h)
 EXPORTS_SIZE = ("ss_ctx_wave_scratch_bytes",)
 
@@ -130,6 +131,8 @@ def load() -> ctypes.CDLL:
     lib.ss_audio_obs_logmel_rows_f32.argtypes = lib.ss_audio_obs_logmel_f32.argtypes
     lib.ss_audio_obs_logmel_rows_spec_f32.argtypes = lib.ss_audio_obs_logmel_spec_f32.argtypes
     lib.ss_ctx_set_logmel_rows_policy.argtypes = [vp, c_int, c_int]
+    lib.ss_audio_obs_logmel_ss2_f32.argtypes = lib.ss_audio_obs_logmel_f32.argtypes
+    lib.ss_ctx_set_logmel_ss2_policy.argtypes = [vp, c_int, c_int]
     lib.ss_ctx_wave_scratch_bytes.argtypes = [vp]
     lib.ss_source_windows32_f32.argtypes = [vp, vp, vp, c_int, vp]
     lib.ss_audio_obs32_f32.argtypes = [vp, vp, vp, vp, vp, vp, c_int, c_ll, c_int, c_int, c_int, c_int, c_int, c_int, vp]

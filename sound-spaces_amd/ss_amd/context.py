@@ -190,6 +190,15 @@ class AudioContext:
         _lib.check(self.lib.ss_ctx_set_logmel_rows_policy(self._h, int(min_units), int(max_units)),
                    "ss_ctx_set_logmel_rows_policy")
 
+    def set_logmel_ss2_policy(self, min_units: int, max_units: int) -> None:
+        """``set_logmel_policy`` for SoundSpaces 2.0 steps: log-mel steps without a waveform buffer of ``min_units`` ..
+        ``max_units`` units that are cross-faded one-block rows (16 kHz), or render only block 0 of a 44.1 / 48 kHz row
+        (cross-faded or not), take their own one-launch fused kernel (time-domain rows of a single-allocation bank;
+        ss_ctx_set_logmel_ss2_policy).  Default (1, 0): never - the scratch route is bit-equal to observe-then-features, the
+        fused launch only to rounding.  (1, 2**31 - 1): whenever the shape allows."""
+        _lib.check(self.lib.ss_ctx_set_logmel_ss2_policy(self._h, int(min_units), int(max_units)),
+                   "ss_ctx_set_logmel_ss2_policy")
+
     def wave_scratch_bytes(self) -> int:
         """Bytes of waveform scratch the context holds over all overlap lanes (ss_ctx_wave_scratch_bytes): 0 until a log-mel
         step without a waveform buffer takes the scratch route, and again after ``ss_release_scratch``."""

@@ -362,6 +362,25 @@ def audio_obs_logmel_rows_into(spec, rir_bank, rir_len, unit_desc, audiogoal, sp
                                                             flags, _stream(spec)), "ss_audio_obs_logmel_rows_f32")
 
 
+def audio_obs_logmel_ss2_into(spec, rir_bank, rir_len, unit_desc, audiogoal, spectrogram_out, logmel_out, mel_start, mel_w,
+                              n_valid: int, out_len: int, mel_eps: float = 1e-6, pad_mode="reflect", interleaved: bool = False,
+                              flags: int = 0) -> None:
+    """``audio_obs_logmel_into`` for SoundSpaces 2.0 steps (``ss_audio_obs_logmel_ss2_f32``; time-domain bank only): ONE launch,
+    whichever outputs are asked for next to ``logmel_out``.  Serves cross-faded rows of one partition block (257 <= out_len <=
+    KB with ``FLAG_CROSSFADE``) and rows of 2 or 3 blocks of which only block 0 is rendered (KB < out_len <= 3 KB, n_valid <= KB
+    and at most 26 live pooled blocks: 0.25 s of a 44.1 / 48 kHz row), cross-faded or not; anything else is refused (invalid
+    argument)."""
+    _chk(spec, torch.float32, "spec"); _chk(rir_bank, torch.float32, "rir_bank"); _chk(rir_len, torch.int32, "rir_len")
+    N, n_mels, max_len, ag_ptr, sg_ptr = _obs_logmel_args(unit_desc, audiogoal, spectrogram_out, logmel_out, mel_start, mel_w, out_len)
+    us, cs, es, cap = _bank_strides(rir_bank, interleaved)
+    with torch.cuda.device(spec.device):
+        _lib.check(_lib.load().ss_audio_obs_logmel_ss2_f32(spec.data_ptr(), rir_bank.data_ptr(), rir_len.data_ptr(),
+                                                           unit_desc.data_ptr(), ag_ptr, sg_ptr, logmel_out.data_ptr(),
+                                                           mel_start.data_ptr(), mel_w.data_ptr(), int(n_mels), int(max_len),
+                                                           float(mel_eps), N, us, cs, es, cap, n_valid, out_len, _PAD[pad_mode],
+                                                           flags, _stream(spec)), "ss_audio_obs_logmel_ss2_f32")
+
+
 def audio_obs_logmel_rows_spec_into(spec, hspec, rir_len, unit_desc, audiogoal, spectrogram_out, logmel_out, mel_start, mel_w,
                                     n_valid: int, out_len: int, mel_eps: float = 1e-6, pad_mode="reflect", flags: int = 0) -> None:
     """``audio_obs_logmel_rows_into`` from the spectral RIR bank (``ss_audio_obs_logmel_rows_spec_f32``)."""
