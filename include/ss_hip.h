@@ -155,6 +155,42 @@ int ss_audio_obs_logmel_spec_f32(const float* spec, const float* hspec, const in
                                  const float* mel_w, int n_mels, int max_len, float mel_eps, int n_units, int h_blocks,
                                  int n_valid, int out_len, int pad_mode, int flags, void* stream);
 
+/* ---- Half-precision spectral bank (EXTENSION, opt-in, LOSSY) ----------------------------------------------------------------
+ * The block spectra of the bank above stored as IEEE fp16 with one power-of-two fp32 scale per (entry r, ear c, block b): half
+ * the bytes of the fp32 spectral form, i.e. what the time-domain row costs.  For each block, v[0 .. ss_spec_floats()) being the
+ * fp32 block spectrum exactly as ss_rir_spectra_f32 / ss_bank_scatter_spectra_f32 store it (same element order; the packed
+ * (DC, Nyquist) item is a pair of components like any other):
+ *     mx = max |v[k]|;  mx == 0: every half is +0 and hscale = 1;
+ *     otherwise, 2^(e-1) <= mx < 2^e:  q[k] = fp16(v[k] * 2^(15-e)) rounded to nearest even,  hscale = 2^(e-15)
+ * (the scaled maximum lies in [2^14, 2^15]: nothing overflows, whatever the scale of the RIR file).  hspec16 is
+ * [entries][2][h_blocks][ss_spec_floats()] halves (8-byte aligned), hscale [entries][2][h_blocks] floats; float(q) * hscale is
+ * the value the kernels use, exact in fp32.  BOTH arrays of a bank must be zero-initialised: an unused or empty entry has to
+ * multiply out to exact zeros (the loop-free kernel never reads rir_len).
+ * Accuracy: against the fp32 path the waveform moves by about 2e-4 of its peak and the pooled log1p spectrogram by about 1e-4
+ * (1.5-2.2e-4 and 0.9-1.0e-4 over the RIRs tried; INTEGRATION.md "Half-precision spectral banks" says which figure was measured
+ * how) - outside the library's 1e-4 parity budget, which is why the format is never a default.
+ * Producers: ss_rir_spectra16_f32 (a planar device bank -> its half form, entry r to entry r; asynchronous on `stream`) and
+ * ss_bank_scatter_spectra16_f32 (staged rows, see ss_bank_scatter_spectra_f32).  Both quantise the bit-identical fp32 values.
+ * Consumers: the three entries below = their _spec_f32 siblings reading a half bank (k_conv_spec<.., HALF>), same results as
+ * those fed float(q) * hscale.  ss_fftconv_binaural_spec16_f32 serves every row length its sibling serves;
+ * ss_audio_obs_spec16_f32 rows of ONE partition block, 257 <= out_len <= kB (16 kHz); ss_audio_obs_logmel_spec16_f32 the shapes
+ * of ss_audio_obs_logmel_spec_f32.  No SS_FLAG_CROSSFADE, no length buckets.  Everything else (longer fused rows, NULL hscale,
+ * h_blocks < 1, a misaligned bank, the mel limits) is SS_EINVAL from the argument checks, before a device is touched.  Not
+ * provided: half forms of the 44.1 / 48 kHz fused row kernels (k_obs_rows / k_obs_blocks) and of the persistent k_conv_spec_rows
+ * (launches of more rows than CUs run one workgroup per row). */
+int ss_rir_spectra16_f32(const float* rir, void* hspec16_out, float* hscale_out, int n_entries, long long rir_unit_stride,
+                         int rir_chan_stride, int rir_cap, void* stream);
+int ss_fftconv_binaural_spec16_f32(const float* spec, const void* hspec16, const float* hscale, const int* rir_len,
+                                   const int* unit_desc, float* out, int n_units, int h_blocks, int n_valid, int out_len,
+                                   int flags, void* stream);
+int ss_audio_obs_spec16_f32(const float* spec, const void* hspec16, const float* hscale, const int* rir_len,
+                            const int* unit_desc, float* audiogoal, float* spectrogram, int n_units, int h_blocks, int n_valid,
+                            int out_len, int pad_mode, int flags, void* stream);
+int ss_audio_obs_logmel_spec16_f32(const float* spec, const void* hspec16, const float* hscale, const int* rir_len,
+                                   const int* unit_desc, float* audiogoal, float* spectrogram, float* logmel,
+                                   const int* mel_start, const float* mel_w, int n_mels, int max_len, float mel_eps, int n_units,
+                                   int h_blocks, int n_valid, int out_len, int pad_mode, int flags, void* stream);
+
 /* The same for rows of 2 or 3 partition blocks (kB < out_len <= 3 kB: 44.1 / 48 kHz, the reference's Replica rate; EXTENSION):
  * the log-mel form of the fused row kernels (k_obs_rows / k_obs_blocks), the STFT phase behind every output block emits the
  * frames it completes.  Arguments and outputs as ss_audio_obs_logmel_f32 / _spec_f32 (which keep refusing rows longer than kB);
@@ -334,6 +370,15 @@ int ss_ctx_set_rir_bank(ss_ctx* ctx, const float* rir, const int* rir_len, long 
  * before any upload or launch.  The in-call loaders (ss_miss_loader with bank = NULL, stage_desc not needed) write the
  * new rows' spectra and lengths with one k_stage_spectra launch. */
 int ss_ctx_set_rir_spectra(ss_ctx* ctx, const float* hspec, int h_blocks);
+/* The same binding for a HALF bank ("Half-precision spectral bank" above): spectral-only, so
+ *   ss_ctx_set_rir_bank(ctx, NULL, rir_len, 0, 0, 1, rir_cap);  ss_ctx_set_rir_spectra16(ctx, hspec16, hscale, ceil(rir_cap / kB));
+ * Steps then take the three *_spec16_* entries (ss_ctx_observe_features' one-launch log-mel route and the unit-count policies as
+ * they stand).  SS_EINVAL, nothing changed: a context whose rows exceed kB (sampling_rate > kB), a bank that keeps time-domain
+ * rows or length buckets, fp32 spectra already bound (and ss_ctx_set_rir_spectra while a half bank is bound): one form at a time.
+ * A cross-faded step is refused like on every spectral-only bank.  hspec16 = NULL unbinds.  The in-call loaders
+ * (ss_ctx_observe_requests_load, ss_ctx_load_rir_files) serve such a context through ss_bank_scatter_spectra16_f32; the
+ * ss_miss_loader of a spectral-only store is used as it is (bank = NULL). */
+int ss_ctx_set_rir_spectra16(ss_ctx* ctx, const void* hspec16, const float* hscale, int h_blocks);
 /* The bank as length buckets (see ss_rir_bucket; replaces the two calls above for such banks; the descriptor array is copied,
  * the device pointers are borrowed).  Call again whenever a bucket is (re)allocated. */
 int ss_ctx_set_rir_buckets(ss_ctx* ctx, const ss_rir_bucket* buckets, int n_buckets, const int* rir_len);
@@ -593,6 +638,9 @@ int ss_bank_scatter_rows_f32(const float* staged, long long staged_row_stride, c
  * Returns 0 / SS_EINVAL / -hipError_t. */
 int ss_bank_scatter_spectra_f32(const float* staged, long long staged_row_stride, int planar, const int* slots, const int* lens,
                                 int n, float* hspec, int h_blocks, int* bank_len, void* stream);
+/* ... into a HALF bank (fp16 spectra + scales, "Half-precision spectral bank"): same staging rules, same lengths table. */
+int ss_bank_scatter_spectra16_f32(const float* staged, long long staged_row_stride, int planar, const int* slots, const int* lens,
+                                  int n, void* hspec16, float* hscale, int h_blocks, int* bank_len, void* stream);
 /* n HOST arrays -> n rows of a (pinned) staging block: row i = src[i][0 .. n_floats[i]) followed by zeros up to row_floats,
  * rows row_stride floats apart, on up to n_threads plain threads.  The live RIRs of a SoundSpaces 2.0 step (one new RIR per
  * env and step from the ray tracer, soundspaces/continuous_simulator.py:419) travel to the bank this way: one block, one

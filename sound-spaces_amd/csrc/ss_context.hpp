@@ -74,6 +74,7 @@ struct Context {
     long long rir_us = 0;
     int rir_cs = 0, rir_es = 1, rir_cap = 0;
     const float* hspec = nullptr; // spectral form of the same bank (optional, borrowed)
+    const float* hscale = nullptr; // != nullptr: hspec holds a HALF bank (fp16 spectra), these are its per-block scales (borrowed)
     int h_blocks = 0;
     std::vector<ss_rir_bucket> buckets;   // length-bucketed bank (ss_ctx_set_rir_buckets); empty: the single bank above
     // window-spectra cache

@@ -422,6 +422,18 @@ int launch_conv_spec_mel(ssk::ConvParams p, const ssk::MelArgs& m, int n_units, 
     return hip_err(hipGetLastError());
 }
 
+// ... from a half bank (fp16 block spectra + one scale per block: ssk::SpecScale)
+int launch_conv_spec16_mel(ssk::ConvParams p, const ssk::MelArgs& m, const float* hscale, int n_units, int flags, hipStream_t st) {
+    p.nb_y = 1;
+    p.parts_log2 = 0;
+    const bool simple = (flags & SS_FLAG_NO_DISTRACTOR) && p.h_blocks == 1;
+    const dim3 grid(2 * n_units), block(ssk::kT);
+    const ssk::SpecScale<true> hs{hscale};
+    if (simple) hipLaunchKernelGGL((ssk::k_conv_spec<true, true, false, true, true>), grid, block, 0, st, p, m, hs);
+    else hipLaunchKernelGGL((ssk::k_conv_spec<true, false, false, true, true>), grid, block, 0, st, p, m, hs);
+    return hip_err(hipGetLastError());
+}
+
 // Waveform scratch of the contexts: ss_ctx_observe_features without an audiogoal buffer, on the shapes the log-mel form does
 // not serve, renders into [n, 2, sr] floats the library owns - one buffer per (context, overlap lane), grown on demand, freed
 // with the context (drop_wave_scratch) and by ss_release_scratch.  A growth needed while the stream is being captured is
@@ -1107,6 +1119,95 @@ int ss_audio_obs_logmel_spec_f32(const float* spec, const float* hspec, const in
     return launch_conv_spec_mel(p, m, n_units, flags, static_cast<hipStream_t>(stream));
 }
 
+}  // extern "C"
+
+// ---- half bank: fp16 block spectra + one fp32 scale per (entry, ear, block) (include/ss_hip.h "Half-precision spectral bank") ----
+// k_conv_spec<.., HALF> for every launch (one workgroup per row and output block; more rows than CUs included: the persistent
+// k_conv_spec_rows has no half form)
+template <bool FUSE>
+static int launch_conv_spec16(ssk::ConvParams p, const float* hscale, int n_units, int nb_y, int flags, hipStream_t st, int n_cus) {
+    if (nb_y < 1 || nb_y > 3 || (FUSE && nb_y != 1) || (flags & SS_FLAG_CROSSFADE)) return SS_EINVAL;
+    p.nb_y = nb_y;
+    p.parts_log2 = FUSE && n_cus > 0 ? parts_log2_for(2 * n_units, n_cus) : 0;
+    const bool simple = (flags & SS_FLAG_NO_DISTRACTOR) && nb_y == 1 && p.h_blocks == 1;
+    const dim3 grid((2 * n_units * nb_y) << p.parts_log2), block(ssk::kT);
+    const ssk::SpecScale<true> hs{hscale};
+    if (simple) {
+        ssk::UnitTab<true> ut;
+        if (fill_unit_tab(ut, g_host_desc, n_units))
+            hipLaunchKernelGGL((ssk::k_conv_spec<FUSE, true, true, false, true>), grid, block, 0, st, p, ut, hs);
+        else hipLaunchKernelGGL((ssk::k_conv_spec<FUSE, true, false, false, true>), grid, block, 0, st, p, ssk::UnitTab<false>(), hs);
+    } else hipLaunchKernelGGL((ssk::k_conv_spec<FUSE, false, false, false, true>), grid, block, 0, st, p, ssk::UnitTab<false>(), hs);
+    return hip_err(hipGetLastError());
+}
+
+// the arguments the three half entries share (checked before a device is touched): 8-byte loads of four halves
+static bool spec16_args_ok(const void* hspec16, const float* hscale, int n_units, int h_blocks, int flags) {
+    return hspec16 && hscale && n_units > 0 && h_blocks >= 1 && !(flags & SS_FLAG_CROSSFADE) &&
+           !(reinterpret_cast<size_t>(hspec16) & 7);
+}
+
+extern "C" {
+
+int ss_fftconv_binaural_spec16_f32(const float* spec, const void* hspec16, const float* hscale, const int* rir_len,
+                                   const int* unit_desc, float* out, int n_units, int h_blocks, int n_valid, int out_len, int flags,
+                                   void* stream) {
+    if (n_units == 0) return 0;
+    if (!out || !spec16_args_ok(hspec16, hscale, n_units, h_blocks, flags)) return SS_EINVAL;
+    if (out_len < 1 || n_valid < 0 || n_valid > out_len || n_valid > 3 * ssk::kB) return SS_EINVAL;
+    ssk::ConvParams p;
+    int n_cus = 1;
+    int rc = fill_conv(p, &n_cus, spec, nullptr, rir_len, unit_desc, 0, 0, 1, 0, n_valid, out_len, false);
+    if (rc) return rc;
+    p.out = out;
+    p.hspec = static_cast<const ssk::f32x4*>(hspec16);
+    p.h_blocks = h_blocks;
+    const int nb_y = n_valid == 0 ? 1 : (n_valid + ssk::kB - 1) / ssk::kB;
+    return launch_conv_spec16<false>(p, hscale, n_units, nb_y, flags, static_cast<hipStream_t>(stream), n_cus);
+}
+
+// rows of one partition block only (the 16 kHz observation): 257 <= out_len <= kB
+int ss_audio_obs_spec16_f32(const float* spec, const void* hspec16, const float* hscale, const int* rir_len, const int* unit_desc,
+                            float* audiogoal, float* spectrogram, int n_units, int h_blocks, int n_valid, int out_len, int pad_mode,
+                            int flags, void* stream) {
+    if (n_units == 0) return 0;
+    if (!spectrogram || !spec16_args_ok(hspec16, hscale, n_units, h_blocks, flags)) return SS_EINVAL;
+    if (pad_mode != SS_PAD_REFLECT && pad_mode != SS_PAD_CONSTANT) return SS_EINVAL;
+    if (out_len < ssk::kNfft / 2 + 1 || out_len > ssk::kB || t4_of(out_len) > 26 || n_valid < 0 || n_valid > out_len) return SS_EINVAL;
+    ssk::ConvParams p;
+    int n_cus = 1;
+    int rc = fill_conv(p, &n_cus, spec, nullptr, rir_len, unit_desc, 0, 0, 1, 0, n_valid, out_len, false);
+    if (rc) return rc;
+    p.pad_mode = pad_mode;
+    p.hspec = static_cast<const ssk::f32x4*>(hspec16);
+    p.h_blocks = h_blocks;
+    p.out = audiogoal;
+    p.sgram = spectrogram;
+    return launch_conv_spec16<true>(p, hscale, n_units, 1, flags, static_cast<hipStream_t>(stream), n_cus);
+}
+
+int ss_audio_obs_logmel_spec16_f32(const float* spec, const void* hspec16, const float* hscale, const int* rir_len,
+                                   const int* unit_desc, float* audiogoal, float* spectrogram, float* logmel, const int* mel_start,
+                                   const float* mel_w, int n_mels, int max_len, float mel_eps, int n_units, int h_blocks, int n_valid,
+                                   int out_len, int pad_mode, int flags, void* stream) {
+    if (n_units == 0) return 0;
+    if (!spec16_args_ok(hspec16, hscale, n_units, h_blocks, flags) || !mel_args_ok(logmel, mel_start, mel_w, n_mels, max_len, mel_eps))
+        return SS_EINVAL;
+    if (pad_mode != SS_PAD_REFLECT && pad_mode != SS_PAD_CONSTANT) return SS_EINVAL;
+    if (!obs_logmel_shape_ok(out_len, flags) || n_valid < 0 || n_valid > out_len) return SS_EINVAL;
+    ssk::ConvParams p;
+    int n_cus = 1;
+    int rc = fill_conv(p, &n_cus, spec, nullptr, rir_len, unit_desc, 0, 0, 1, 0, n_valid, out_len, false);
+    if (rc) return rc;
+    p.pad_mode = pad_mode;
+    p.hspec = static_cast<const ssk::f32x4*>(hspec16);
+    p.h_blocks = h_blocks;
+    p.out = audiogoal;
+    p.sgram = spectrogram;
+    const ssk::MelArgs m{logmel, mel_start, mel_w, n_mels, max_len, mel_eps};
+    return launch_conv_spec16_mel(p, m, hscale, n_units, flags, static_cast<hipStream_t>(stream));
+}
+
 // ss_audio_obs_logmel_rows_f32 from the spectral bank (k_obs_blocks<true, MEL> / k_obs_rows<true, .., MEL>)
 int ss_audio_obs_logmel_rows_spec_f32(const float* spec, const float* hspec, const int* rir_len, const int* unit_desc,
                                       float* audiogoal, float* spectrogram, float* logmel, const int* mel_start,
@@ -1237,6 +1338,7 @@ int ss_ctx_set_rir_bank(ss_ctx* h, const float* rir, const int* rir_len, long lo
     // the spectral form described the PREVIOUS bank (its entries, its capacity): back to the time-domain kernels until
     // ss_ctx_set_rir_spectra is called for this one (a swapped / grown bank kept rendering the old spectra)
     c.hspec = nullptr;
+    c.hscale = nullptr;
     c.h_blocks = 0;
     c.buckets.clear();
     if (nbh_new != nbh_old) {                                  // the set of partition offsets per key changes
@@ -1260,8 +1362,30 @@ int ss_ctx_set_rir_spectra(ss_ctx* h, const float* hspec, int h_blocks) {
     if (!h || (hspec && h_blocks < 1)) return SS_EINVAL;
     ssctx::Context& c = h->c;
     if (hspec && h_blocks != (c.rir_cap > 0 ? ssctx::ceil_div(c.rir_cap, c.kb) : 1)) return SS_EINVAL;
+    if (hspec && c.hscale) return SS_EINVAL;                   // a half bank is bound (ss_ctx_set_rir_spectra16): one form at a time
     c.hspec = hspec;
+    c.hscale = nullptr;
     c.h_blocks = hspec ? h_blocks : 0;
+    return 0;
+}
+
+// Half form of a SPECTRAL-ONLY bank (ss_ctx_set_rir_bank(ctx, NULL, rir_len, 0, 0, 1, rir_cap) first): fp16 block spectra and
+// their scales (include/ss_hip.h).  Steps run k_conv_spec<.., HALF>, which serves rows of one partition block: a context whose
+// rows are longer, a bank that keeps time-domain rows or buckets, and a context with fp32 spectra bound are refused.
+// hspec16 = NULL unbinds.
+int ss_ctx_set_rir_spectra16(ss_ctx* h, const void* hspec16, const float* hscale, int h_blocks) {
+    if (!h) return SS_EINVAL;
+    ssctx::Context& c = h->c;
+    if (!hspec16) {
+        if (c.hscale) { c.hspec = nullptr; c.hscale = nullptr; c.h_blocks = 0; }
+        return 0;
+    }
+    if (!hscale || h_blocks < 1 || (reinterpret_cast<size_t>(hspec16) & 7)) return SS_EINVAL;
+    if (c.out_len > c.kb || c.rir || !c.buckets.empty() || !c.rir_len || (c.hspec && !c.hscale)) return SS_EINVAL;
+    if (h_blocks != (c.rir_cap > 0 ? ssctx::ceil_div(c.rir_cap, c.kb) : 1)) return SS_EINVAL;
+    c.hspec = static_cast<const float*>(hspec16);              // (read as halves wherever hscale is set)
+    c.hscale = hscale;
+    c.h_blocks = h_blocks;
     return 0;
 }
 
@@ -1490,7 +1614,7 @@ static int ctx_observe_on(ss_ctx* h, const ss_units* units, int n, float* audiog
     // rows of 2 or 3 blocks (44.1 / 48 kHz): the log-mel form of k_obs_rows / k_obs_blocks under the same conditions, inside the
     // range of ss_ctx_set_logmel_rows_policy (default: never - the scratch route is bit-equal to observe-then-features, the
     // fused arithmetic only to rounding)
-    const bool mel_rows = mel && !mel_fused && c.buckets.empty() && (spectral || (c.rir && c.rir_cap > 0)) &&
+    const bool mel_rows = mel && !mel_fused && !c.hscale && c.buckets.empty() && (spectral || (c.rir && c.rir_cap > 0)) &&
                           obs_logmel_rows_shape_ok(c.out_len, c.n_valid, nbh_bank, res.flags) &&
                           n >= c.mel_rows_min_units && n <= c.mel_rows_max_units;
     // SoundSpaces 2.0 steps (cross-faded one-block rows; block 0 of a 44.1 / 48 kHz row, cross-faded or not): their own fused
@@ -1533,7 +1657,11 @@ static int ctx_observe_on(ss_ctx* h, const ss_units* units, int n, float* audiog
                                                      mel->mel_w, mel->n_mels, mel->max_len, mel->mel_eps, n, c.rir_us, c.rir_cs,
                                                      c.rir_es, c.rir_cap, c.n_valid, c.out_len, c.pad_mode, res.flags, stream);
     } else if (mel_fused) {
-        rc = spectral ? ss_audio_obs_logmel_spec_f32(c.pool, c.hspec, c.rir_len, dd, nullptr, spectrogram, mel->logmel, mel->mel_start,
+        rc = spectral && c.hscale
+                 ? ss_audio_obs_logmel_spec16_f32(c.pool, c.hspec, c.hscale, c.rir_len, dd, nullptr, spectrogram, mel->logmel,
+                                                  mel->mel_start, mel->mel_w, mel->n_mels, mel->max_len, mel->mel_eps, n, c.h_blocks,
+                                                  c.n_valid, c.out_len, c.pad_mode, res.flags, stream)
+             : spectral ? ss_audio_obs_logmel_spec_f32(c.pool, c.hspec, c.rir_len, dd, nullptr, spectrogram, mel->logmel, mel->mel_start,
                                                      mel->mel_w, mel->n_mels, mel->max_len, mel->mel_eps, n, c.h_blocks, c.n_valid,
                                                      c.out_len, c.pad_mode, res.flags, stream)
                       : ss_audio_obs_logmel_f32(c.pool, c.rir, c.rir_len, dd, nullptr, spectrogram, mel->logmel, mel->mel_start,
@@ -1545,7 +1673,13 @@ static int ctx_observe_on(ss_ctx* h, const ss_units* units, int n, float* audiog
                                                     c.n_valid, c.out_len, c.pad_mode, res.flags, stream)
                          : ss_fftconv_binaural_buckets_f32(c.pool, c.buckets.data(), nb, c.rir_len, dd, audiogoal, n, c.n_valid,
                                                            c.out_len, res.flags, stream);
-    } else if (spectrogram && spectral)
+    } else if (spectrogram && spectral && c.hscale)
+        rc = ss_audio_obs_spec16_f32(c.pool, c.hspec, c.hscale, c.rir_len, dd, audiogoal, spectrogram, n, c.h_blocks, c.n_valid,
+                                     c.out_len, c.pad_mode, res.flags, stream);
+    else if (spectral && c.hscale)
+        rc = ss_fftconv_binaural_spec16_f32(c.pool, c.hspec, c.hscale, c.rir_len, dd, audiogoal, n, c.h_blocks, c.n_valid, c.out_len,
+                                            res.flags, stream);
+    else if (spectrogram && spectral)
         rc = ss_audio_obs_spec_f32(c.pool, c.hspec, c.rir_len, dd, audiogoal, spectrogram, n, c.h_blocks, c.n_valid,
                                    c.out_len, c.pad_mode, res.flags, stream);
     else if (spectrogram)
@@ -1989,8 +2123,11 @@ static int loader_load_paths(ssctx::Context& c, ss_miss_loader* ld, const char* 
     ld->n_loaded = k;
     int rc = 0;
     if (spec_only) {                                           // staged rows -> block spectra + lengths, one launch
-        rc = ss_bank_scatter_spectra_f32(ld->stage, 2LL * ld->cap, 0, ld->stage_slot, ld->stage_len, k, const_cast<float*>(c.hspec),
-                                         hb, ld->dev_len, st);
+        // (a half bank, ss_ctx_set_rir_spectra16, through the half staging kernel: never fp32 spectra into its buffer)
+        rc = c.hscale ? ss_bank_scatter_spectra16_f32(ld->stage, 2LL * ld->cap, 0, ld->stage_slot, ld->stage_len, k,
+                                                      const_cast<float*>(c.hspec), const_cast<float*>(c.hscale), hb, ld->dev_len, st)
+                      : ss_bank_scatter_spectra_f32(ld->stage, 2LL * ld->cap, 0, ld->stage_slot, ld->stage_len, k,
+                                                    const_cast<float*>(c.hspec), hb, ld->dev_len, st);
         if (rc == 0 && ld->spec_stale)
             for (int i = 0; i < k; ++i) ld->spec_stale[ld->stage_slot[i]] = 0;
     } else {
@@ -2257,7 +2394,7 @@ int ss_ctx_set_rir_buckets(ss_ctx* h, const ss_rir_bucket* buckets, int n_bucket
     c.buckets.assign(buckets, buckets + n_buckets);
     c.rir = buckets[0].rir; c.rir_len = rir_len; c.rir_us = 2LL * buckets[0].cap; c.rir_cs = buckets[0].cap; c.rir_es = 1;
     c.rir_cap = hb_max * c.kb;                                 // planning depth: the longest bucket's blocks
-    c.hspec = nullptr; c.h_blocks = 0;
+    c.hspec = nullptr; c.hscale = nullptr; c.h_blocks = 0;
     if (hb_max != nbh_old) {                                   // the set of partition offsets per key changes
         const int nby = c.n_valid > 0 ? ssctx::ceil_div(c.n_valid, c.kb) : 1;
         c.stride = hb_max + nby - 1;
@@ -2339,11 +2476,64 @@ extern "C" int ss_bank_scatter_spectra_f32(const float* staged, long long staged
     p.staged = staged; p.slots = slots; p.lens = lens; p.hspec = reinterpret_cast<ssk::f32x4*>(hspec); p.bank_len = bank_len;
     p.staged_stride = staged_row_stride; p.planar = planar ? 1 : 0; p.h_blocks = h_blocks;
     p.cap = static_cast<int>(std::min(frames, hb_frames));
+    p.hscale = nullptr; p.ear_off = 0; p.slot0 = 0; p.pair_loads = 1;
     for (int lo = 0; lo < n; lo += 65535) {                    // (grid.y limit)
         const int m = n - lo < 65535 ? n - lo : 65535;
         ssk::StageSpecParams q = p;
         q.staged += static_cast<size_t>(lo) * staged_row_stride; q.slots += lo; q.lens += lo;
         hipLaunchKernelGGL(ssk::k_stage_spectra, dim3(h_blocks, m), dim3(ssk::kT), 0, static_cast<hipStream_t>(stream), q);
+    }
+    return hip_err(hipGetLastError());
+}
+
+// The same staging, into a HALF bank (k_stage_spectra16): fp16 block spectra [entries][2][h_blocks][ss_spec_floats()] and one
+// fp32 scale per (entry, ear, block), quantised from the very values the fp32 entry stores.
+extern "C" int ss_bank_scatter_spectra16_f32(const float* staged, long long staged_row_stride, int planar, const int* slots,
+                                             const int* lens, int n, void* hspec16, float* hscale, int h_blocks, int* bank_len,
+                                             void* stream) {
+    if (n == 0) return 0;
+    if (!staged || !slots || !lens || !hspec16 || !hscale || n < 0 || h_blocks < 1 || staged_row_stride < 2) return SS_EINVAL;
+    if ((reinterpret_cast<size_t>(staged) & 7) || (staged_row_stride & (planar ? 3 : 1)) || (reinterpret_cast<size_t>(hspec16) & 7))
+        return SS_EINVAL;
+    for (const void* ptr : {static_cast<const void*>(staged), static_cast<const void*>(slots), static_cast<const void*>(lens)})
+        if (!device_accessible(ptr)) return SS_EINVAL;
+    ssk::StageSpecParams p;
+    int rc = get_tables(&p.tb);
+    if (rc) return rc;
+    const long long frames = staged_row_stride / 2, hb_frames = static_cast<long long>(h_blocks) * ssk::kB;
+    p.staged = staged; p.slots = slots; p.lens = lens; p.hspec = static_cast<ssk::f32x4*>(hspec16); p.bank_len = bank_len;
+    p.staged_stride = staged_row_stride; p.planar = planar ? 1 : 0; p.h_blocks = h_blocks;
+    p.cap = static_cast<int>(std::min(frames, hb_frames));
+    p.hscale = hscale; p.ear_off = staged_row_stride >> 1; p.slot0 = 0; p.pair_loads = 1;
+    for (int lo = 0; lo < n; lo += 65535) {                    // (grid.y limit)
+        const int m = n - lo < 65535 ? n - lo : 65535;
+        ssk::StageSpecParams q = p;
+        q.staged += static_cast<size_t>(lo) * staged_row_stride; q.slots += lo; q.lens += lo;
+        hipLaunchKernelGGL(ssk::k_stage_spectra16, dim3(h_blocks, m), dim3(ssk::kT), 0, static_cast<hipStream_t>(stream), q);
+    }
+    return hip_err(hipGetLastError());
+}
+
+// A planar device bank ([n][2][rir_cap]-like rows, zero beyond each entry's length) -> its half form, entry r to entry r: the same
+// kernel with the bank as its staging block (rows of rir_cap frames, the second ear rir_chan_stride floats behind the first)
+extern "C" int ss_rir_spectra16_f32(const float* rir, void* hspec16_out, float* hscale_out, int n_entries, long long rir_unit_stride,
+                                    int rir_chan_stride, int rir_cap, void* stream) {
+    if (n_entries == 0) return 0;
+    if (!rir || !hspec16_out || !hscale_out || n_entries < 0 || rir_cap <= 0 || rir_unit_stride < 0 || rir_chan_stride < 0) return SS_EINVAL;
+    if (reinterpret_cast<size_t>(hspec16_out) & 7) return SS_EINVAL;
+    ssk::StageSpecParams p;
+    int rc = get_tables(&p.tb);
+    if (rc) return rc;
+    p.staged = rir; p.slots = nullptr; p.lens = nullptr; p.hspec = static_cast<ssk::f32x4*>(hspec16_out); p.bank_len = nullptr;
+    p.staged_stride = rir_unit_stride; p.planar = 1; p.h_blocks = (rir_cap + ssk::kB - 1) / ssk::kB;
+    p.cap = rir_cap;
+    p.hscale = hscale_out; p.ear_off = rir_chan_stride; p.slot0 = 0;
+    p.pair_loads = !(reinterpret_cast<size_t>(rir) & 7) && !(rir_unit_stride & 1) && !(rir_chan_stride & 1);
+    for (int lo = 0; lo < n_entries; lo += 65535) {            // (grid.y limit)
+        const int m = n_entries - lo < 65535 ? n_entries - lo : 65535;
+        ssk::StageSpecParams q = p;
+        q.staged += static_cast<size_t>(lo) * rir_unit_stride; q.slot0 = lo;
+        hipLaunchKernelGGL(ssk::k_stage_spectra16, dim3(p.h_blocks, m), dim3(ssk::kT), 0, static_cast<hipStream_t>(stream), q);
     }
     return hip_err(hipGetLastError());
 }

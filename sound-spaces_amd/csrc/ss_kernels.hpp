@@ -1658,8 +1658,51 @@ __device__ __forceinline__ void spec_block_product(const f32x4* spec, int t, con
         }
 }
 
-template <bool FUSE, bool SIMPLE, bool TAB = false, bool MEL = false>
-__global__ __launch_bounds__(1024) void k_conv_spec(ConvParams p, UnitTab<TAB, MEL> ut = UnitTab<TAB, MEL>()) {
+// HALF bank (rir_spectral="half"): the same block spectra stored as fp16 with ONE power-of-two scale per (entry, ear, block),
+//     q[k] = RNE_fp16(H'[k] * 2^(15-e)),  hscale = 2^(e-15),  2^(e-1) <= max_k |H'[k]| < 2^e   (k_stage_spectra16)
+// in the SAME element order: f32x4 index n of a block is h16x4 index n, so a lane loads 8 bytes where it loads 16 above, still
+// coalesced.  The halves are widened and scaled (exact in fp32) where the fp32 form uses the loaded value: the arithmetic after
+// that is the fp32 kernel's, fed float(q) * hscale.  The scale is a wave-uniform word loaded IN the row's batch of vector loads,
+// at its head (no round trip of its own in front of them; see spec_block_product16).  The scales ride in a kernel argument of
+// their own (as UnitTab does): ConvParams, and with it every fp32 instantiation, stays as it is.
+typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
+template <bool HALF>
+struct SpecScale { };
+template <>
+struct SpecScale<true> { const float* hscale; };      // [entries][2][h_blocks]
+
+__device__ __forceinline__ void spec_block_product16(const f32x4* spec, int t, const h16x4* hp, const float* scale_p, int slot,
+                                                     bool accumulate, c32 (&acc)[2][8]) {
+    const f32x4* sp = spec + (size_t)slot * (kSpecComplex / 2) + t;
+    h16x4 hv[2][4];
+    f32x4 sv[2][4];
+    // the block's scale heads the batch: the memory counter retires in order, so the first product then waits for the scale and
+    // its own two operands only, as the fp32 form waits for its two operands
+    const float sc = *scale_p;
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int hh = 0; hh < 4; ++hh) {
+            hv[s][hh] = ld_stream(hp + (s * 4 + hh) * 1024);
+            sv[s][hh] = sp[(s * 4 + hh) * 1024];
+        }
+    SSK_SCHED_BARRIER();                                  // the scale's load and all sixteen before the first multiply
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const f32x4 hf = __builtin_convertvector(hv[s][e >> 1], f32x4) * sc;
+            const c32 h = (e & 1) ? hf.zw : hf.xy;
+            const c32 w = (e & 1) ? sv[s][e >> 1].zw : sv[s][e >> 1].xy;
+            c32 pr = cmul(h, w);
+            if (s == 0 && e == 0 && t == 0) pr = mk2(h.x * w.x, h.y * w.y);      // (X[0], X[16384]) are real
+            if (accumulate) acc[s][e] += pr; else acc[s][e] = pr;
+        }
+}
+
+template <bool FUSE, bool SIMPLE, bool TAB = false, bool MEL = false, bool HALF = false>
+__global__ __launch_bounds__(1024) void k_conv_spec(ConvParams p, UnitTab<TAB, MEL> ut = UnitTab<TAB, MEL>(),
+                                                    SpecScale<HALF> hs = SpecScale<HALF>()) {
     static_assert(!TAB || SIMPLE, "the unit table serves the loop-free kernel");
     static_assert(!MEL || (FUSE && !TAB), "log-mel: the plain fused kernels (launched with parts_log2 = 0)");
     __shared__ c32 lds[FUSE && 16 * kWaveScratch > kLdsComplex ? 16 * kWaveScratch : kLdsComplex];
@@ -1718,7 +1761,10 @@ __global__ __launch_bounds__(1024) void k_conv_spec(ConvParams p, UnitTab<TAB, M
             // everything after them come out as zeros anyway.
             const f32x4* hp = hspec_base + ((size_t)ridx * 2 + ch) * row_f4 + t;
             if (dw.z <= 0 && dw.z + dw.w > 0) {
-                spec_block_product(spec_base, t, hp, dw.y - dw.z, false, acc);
+                if constexpr (HALF)
+                    spec_block_product16(spec_base, t, reinterpret_cast<const h16x4*>(hspec_base) + ((size_t)ridx * 2 + ch) * row_f4 + t,
+                                         hs.hscale + ((size_t)ridx * 2 + ch) * (size_t)p.h_blocks, dw.y - dw.z, false, acc);
+                else spec_block_product(spec_base, t, hp, dw.y - dw.z, false, acc);
                 any = true;
             }
         }
@@ -1742,7 +1788,11 @@ __global__ __launch_bounds__(1024) void k_conv_spec(ConvParams p, UnitTab<TAB, M
                 int tl = t;
                 SSK_OPAQUE1(tl);
                 const f32x4* hp = bs.hp + (size_t)i * (kSpecComplex / 2) + tl;
-                spec_block_product(spec_base, tl, hp, spec0 + (m - m_min), any, acc);
+                if constexpr (HALF) {                   // one allocation (the launcher checks): same f32x4 index, 8-byte elements
+                    const size_t blk = ((size_t)ridx * 2 + ch) * (size_t)p.h_blocks + i;
+                    spec_block_product16(spec_base, tl, reinterpret_cast<const h16x4*>(hspec_base) + blk * (kSpecComplex / 2) + tl,
+                                         hs.hscale + blk, spec0 + (m - m_min), any, acc);
+                } else spec_block_product(spec_base, tl, hp, spec0 + (m - m_min), any, acc);
                 any = true;
             }
         }
@@ -2818,6 +2868,11 @@ struct StageSpecParams {
     int planar;                // 0: [frames][2]; 1: [2][staged_stride / 2]
     int cap;                   // frames a row may hold: min(staged_stride / 2, h_blocks * kB)
     int h_blocks;
+    // k_stage_spectra16 only (the fp32 kernel reads none of these): hspec is then [entries][2][h_blocks][kSpecComplex / 2] h16x4
+    float* hscale;             // [entries][2][h_blocks]
+    long long ear_off;         // planar: floats from the first ear's row to the second's (the fp32 kernel: staged_stride / 2)
+    int slot0;                 // slots == nullptr: row i goes to entry slot0 + i; lens == nullptr: every row holds cap frames
+    int pair_loads;            // planar: rows and ear_off are 8-byte aligned (0: sample-wise loads, a bank with odd strides)
 };
 
 // pass1_fwd<false> of a block whose packed samples m = t + 1024*a, a < 8, are already in registers (an RIR block has <= kB
@@ -2852,22 +2907,69 @@ __device__ __forceinline__ void stage_block_spectrum(c32* lds, const ThreadTw& t
     }
 }
 
-__global__ __launch_bounds__(1024) void k_stage_spectra(StageSpecParams p) {
+// The HALF form of the block writer (a "half" bank, see k_conv_spec): the same instructions up to item_load_fwd, so the values
+// quantised are bit-identical to the fp32 form's; both items' 16 complex values wait in registers while the block's largest
+// |component| is found (wave butterfly, then one LDS word per wave), then four halves per 8-byte store and one scale per block.
+//   mx = 0: halves +0, scale 1;   2^(e-1) <= mx < 2^e: q = RNE_fp16(v * 2^(15-e)) (|q| <= 2^15: no overflow), scale 2^(e-15)
+__device__ __forceinline__ void stage_block_spectrum16(c32* lds, const ThreadTw& tw, int t, const c32 (&lo)[8], h16x4* o, float* scale_o,
+                                                       float* s_mx) {
+    pass1_fwd_lo(lds, tw.p1, t, lo);
+    fwd_passes(lds, tw, t);
+    c32 v[2][8];
+    float mx = 0.f;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        item_load_fwd(lds, s ? tw.i1 : tw.i0, t + 1024 * s, v[s]);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) mx = fmaxf(mx, fmaxf(fabsf(v[s][e].x), fabsf(v[s][e].y)));
+    }
+    mx = wave_reduce<0>(mx, t & 63);
+    if ((t & 63) == 0) s_mx[t >> 6] = mx;
+    lds_barrier();
+    mx = s_mx[0];
+#pragma unroll
+    for (int w = 1; w < kT / 64; ++w) mx = fmaxf(mx, s_mx[w]);
+    int ex = 15;                                         // mx = 0: scale 1, every half +0
+    if (mx > 0.f) (void)frexpf(mx, &ex);
+    if (t == 0) *scale_o = ldexpf(1.0f, ex - 15);
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int h = 0; h < 4; ++h) {
+            h16x4 q = {(_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f};
+            if (mx > 0.f) {                              // (float -> _Float16 is round-to-nearest-even)
+                q.x = (_Float16)ldexpf(v[s][2 * h].x, 15 - ex);
+                q.y = (_Float16)ldexpf(v[s][2 * h].y, 15 - ex);
+                q.z = (_Float16)ldexpf(v[s][2 * h + 1].x, 15 - ex);
+                q.w = (_Float16)ldexpf(v[s][2 * h + 1].y, 15 - ex);
+            }
+            o[(s * 4 + h) * 1024] = q;
+        }
+}
+
+template <bool HALF>
+__device__ __forceinline__ void stage_spectra_body(const StageSpecParams& p) {
     __shared__ c32 lds[kLdsComplex];
+    __shared__ float s_mx[HALF ? 2 : 1][kT / 64];
     const int t = threadIdx.x, b = blockIdx.x, i = blockIdx.y;
-    const int slot = __builtin_amdgcn_readfirstlane(p.slots[i]);
-    const int len = min(max(__builtin_amdgcn_readfirstlane(p.lens[i]), 0), p.cap);
+    int slot, len;
+    if (HALF && !p.slots) slot = p.slot0 + i;
+    else slot = __builtin_amdgcn_readfirstlane(p.slots[i]);
+    if (HALF && !p.lens) len = p.cap;
+    else len = min(max(__builtin_amdgcn_readfirstlane(p.lens[i]), 0), p.cap);
     if (b == 0 && t == 0 && p.bank_len) p.bank_len[slot] = len;
     const int nv = min(max(len - b * kB, 0), kB);        // frames of this block that hold samples
     const float* row = p.staged + (size_t)i * p.staged_stride + (p.planar ? (size_t)b * kB : 2 * (size_t)b * kB);
-    const size_t half = (size_t)(p.staged_stride >> 1);  // planar: offset of the second ear
+    const size_t half = HALF ? (size_t)p.ear_off : (size_t)(p.staged_stride >> 1);  // planar: offset of the second ear
+    const bool pairs = !HALF || p.pair_loads;
     c32 xl[8], xr[8];
 #pragma unroll
     for (int a = 0; a < 8; ++a) {
         const int j = 2 * (t + 1024 * a);                // frames j, j + 1 of the block: packed sample a of both ears
         c32 l = mk2(0.f, 0.f), r = mk2(0.f, 0.f);
         if (p.planar) {
-            if (j + 1 < nv) { l = *reinterpret_cast<const c32*>(row + j); r = *reinterpret_cast<const c32*>(row + half + j); }
+            if (j + 1 < nv && pairs) { l = *reinterpret_cast<const c32*>(row + j); r = *reinterpret_cast<const c32*>(row + half + j); }
+            else if (j + 1 < nv) { l = mk2(row[j], row[j + 1]); r = mk2(row[half + j], row[half + j + 1]); }
             else if (j < nv) { l.x = row[j]; r.x = row[half + j]; }
         } else {
             if (j < nv) {
@@ -2884,10 +2986,22 @@ __global__ __launch_bounds__(1024) void k_stage_spectra(StageSpecParams p) {
     }
     const ThreadTw tw = load_thread_tw(p.tb.twM, p.tb.twItem, t);
     const size_t ear_f4 = (size_t)p.h_blocks * (kSpecComplex / 2);
-    f32x4* o = p.hspec + (size_t)slot * 2 * ear_f4 + (size_t)b * (kSpecComplex / 2) + t;
-    stage_block_spectrum(lds, tw, t, xl, o);
-    lds_barrier();                                       // every item read of the first ear before the second one's pass 1
-    stage_block_spectrum(lds, tw, t, xr, o + ear_f4);
+    const size_t o_idx = (size_t)slot * 2 * ear_f4 + (size_t)b * (kSpecComplex / 2) + t;
+    if constexpr (HALF) {
+        h16x4* o = reinterpret_cast<h16x4*>(p.hspec) + o_idx;
+        float* so = p.hscale + (size_t)slot * 2 * p.h_blocks + b;
+        stage_block_spectrum16(lds, tw, t, xl, o, so, s_mx[0]);
+        lds_barrier();                                   // every item read of the first ear before the second one's pass 1
+        stage_block_spectrum16(lds, tw, t, xr, o + ear_f4, so + p.h_blocks, s_mx[1]);
+    } else {
+        f32x4* o = p.hspec + o_idx;
+        stage_block_spectrum(lds, tw, t, xl, o);
+        lds_barrier();                                   // every item read of the first ear before the second one's pass 1
+        stage_block_spectrum(lds, tw, t, xr, o + ear_f4);
+    }
 }
+
+__global__ __launch_bounds__(1024) void k_stage_spectra(StageSpecParams p) { stage_spectra_body<false>(p); }
+__global__ __launch_bounds__(1024) void k_stage_spectra16(StageSpecParams p) { stage_spectra_body<true>(p); }
 
 }  // namespace ssk

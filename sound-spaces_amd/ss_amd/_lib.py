@@ -19,7 +19,9 @@ EXPORTS = ("ss_block_len", "ss_spec_floats", "ss_version", "ss_init", "ss_source
            "ss_wav_read_rirs_f32", "ss_rows_gather_f32", "ss_bank_scatter_rows_f32", "ss_ctx_set_chip_share", "ss_ctx_set_spectral_policy", "ss_ctx_observe_requests_load", "ss_ctx_load_rir_files",
            "ss_bank_scatter_spectra_f32", "ss_audio_obs_logmel_f32", "ss_audio_obs_logmel_spec_f32", "ss_ctx_set_logmel_policy",
            "ss_audio_obs_logmel_rows_f32", "ss_audio_obs_logmel_rows_spec_f32", "ss_ctx_set_logmel_rows_policy",
-           "ss_audio_obs_logmel_ss2_f32", "ss_ctx_set_logmel_ss2_policy")
+           "ss_audio_obs_logmel_ss2_f32", "ss_ctx_set_logmel_ss2_policy",
+           "ss_rir_spectra16_f32", "ss_bank_scatter_spectra16_f32", "ss_fftconv_binaural_spec16_f32", "ss_audio_obs_spec16_f32",
+           "ss_audio_obs_logmel_spec16_f32", "ss_ctx_set_rir_spectra16")
 # entries that return a size_t, not a status (EXPORTS: every `int ss_*` of include/ss_hip.h)
 EXPORTS_SIZE = ("ss_ctx_wave_scratch_bytes",)
 
@@ -147,6 +149,14 @@ def load() -> ctypes.CDLL:
     lib.ss_rows_gather_f32.argtypes = [vp, vp, c_int, vp, c_ll, c_int, c_int]
     lib.ss_bank_scatter_rows_f32.argtypes = [vp, c_ll, vp, vp, c_int, vp, c_ll, c_int, c_int, vp, vp]
     lib.ss_bank_scatter_spectra_f32.argtypes = [vp, c_ll, c_int, vp, vp, c_int, vp, c_int, vp, vp]
+    # the half bank (fp16 block spectra + scales): the _spec_f32 siblings' arguments plus hscale behind the bank
+    lib.ss_rir_spectra16_f32.argtypes = [vp, vp, vp, c_int, c_ll, c_int, c_int, vp]
+    lib.ss_bank_scatter_spectra16_f32.argtypes = [vp, c_ll, c_int, vp, vp, c_int, vp, vp, c_int, vp, vp]
+    lib.ss_fftconv_binaural_spec16_f32.argtypes = [vp, vp, vp, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, vp]
+    lib.ss_audio_obs_spec16_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, vp]
+    lib.ss_audio_obs_logmel_spec16_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, c_int, c_int, ctypes.c_float, c_int, c_int,
+                                                   c_int, c_int, c_int, c_int, vp]
+    lib.ss_ctx_set_rir_spectra16.argtypes = [vp, vp, vp, c_int]
     for name in EXPORTS:
         getattr(lib, name).restype = c_int
     for name in EXPORTS_SIZE:

@@ -138,6 +138,25 @@ class AudioContext:
         _lib.check(self.lib.ss_ctx_set_rir_spectra(self._h, hspec.data_ptr(), int(hspec.shape[2])), "ss_ctx_set_rir_spectra")
         self._spectra = hspec
 
+    def set_rir_spectra16(self, hspec16, hscale, lengths, cap: int) -> None:
+        """A HALF bank (``RirStore(spectral="half")``: float16 block spectra hspec16 [R,2,ceil(cap/KB),SPEC_FLOATS], float32 scales
+        hscale [R,2,ceil(cap/KB)] and CUDA int32 lengths [R]; spectral-only, no time-domain rows):
+        ss_ctx_set_rir_bank(ctx, NULL, lengths, 0, 0, 1, cap) + ss_ctx_set_rir_spectra16.  Steps read the half spectra
+        (k_conv_spec<.., HALF>); the library refuses (SS_EINVAL) a context whose rows exceed one partition block (sampling rates
+        above KB) and cross-faded steps."""
+        import torch
+        if hspec16.dtype != torch.float16 or hscale.dtype != torch.float32 or not hspec16.is_contiguous() or not hscale.is_contiguous():
+            raise ValueError("set_rir_spectra16: contiguous float16 spectra and float32 scales expected")
+        if tuple(hscale.shape) != tuple(hspec16.shape[:3]):
+            raise ValueError("set_rir_spectra16: one scale per (entry, ear, block)")
+        _lib.check(self.lib.ss_ctx_set_rir_bank(self._h, None, lengths.data_ptr(), 0, 0, 1, int(cap)), "ss_ctx_set_rir_bank")
+        self._bank = (None, lengths)
+        self.rir_cap = int(cap)
+        self._spectra = None
+        _lib.check(self.lib.ss_ctx_set_rir_spectra16(self._h, hspec16.data_ptr(), hscale.data_ptr(), int(hspec16.shape[2])),
+                   "ss_ctx_set_rir_spectra16")
+        self._spectra = (hspec16, hscale)
+
     def set_rir_buckets(self, bank, spectral: bool = False) -> None:
         """A length-bucketed bank (``ss_amd.renderer.BucketedRirBank``; include/ss_hip.h ``ss_ctx_set_rir_buckets``):
         steps whose units all sit in bucket 0 keep the loop-free kernel, long RIRs live in buckets of their own.

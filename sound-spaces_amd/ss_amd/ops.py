@@ -222,6 +222,19 @@ def audio_obs(spec, rir_bank, rir_len, unit_desc, n_valid: int, out_len: int, pa
 
 
 # ---- spectral RIR bank ------------------------------------------------------------------------------------------
+def _chk_spectra(hspec: torch.Tensor, hscale) -> bool:
+    """the spectral bank argument of the *_spec_* ops: float32 [R,2,hb,SPEC_FLOATS], or - a HALF bank (include/ss_hip.h
+    "Half-precision spectral bank") - float16 of the same shape with its float32 scales hscale [R,2,hb].  -> half?"""
+    if hscale is None:
+        _chk(hspec, torch.float32, "hspec")
+        assert hspec.dim() == 4
+        return False
+    _chk(hspec, torch.float16, "hspec"); _chk(hscale, torch.float32, "hscale")
+    assert hspec.dim() == 4 and hspec.shape[3] == SPEC_FLOATS and tuple(hscale.shape) == tuple(hspec.shape[:3])
+    assert hscale.device == hspec.device
+    return True
+
+
 def rir_spectra_into(rir_bank: torch.Tensor, hspec: torch.Tensor, first: int = 0, count: Optional[int] = None) -> None:
     """Block spectra of bank entries [first, first+count) of a planar bank [R,2,cap] into hspec [R,2,hb,SPEC_FLOATS]
     (ss_rir_spectra_f32; one-off work at bank load, synchronous)."""
@@ -237,12 +250,13 @@ def rir_spectra_into(rir_bank: torch.Tensor, hspec: torch.Tensor, first: int = 0
 
 
 def scatter_spectra_into(staged: torch.Tensor, planar: bool, slots: torch.Tensor, lens: torch.Tensor, n: int,
-                         hspec: torch.Tensor, bank_len: torch.Tensor) -> None:
+                         hspec: torch.Tensor, bank_len: torch.Tensor, hscale: Optional[torch.Tensor] = None) -> None:
     """Rows [0, n) of a staging block -> block spectra of entries slots[i] of the spectral-only bank hspec [R,2,hb,SPEC_FLOATS]
     and lens[i] into bank_len[slots[i]] (ss_bank_scatter_spectra_f32: one launch on the current stream of hspec's device).
     staged: float32 [*, cap, 2] (wav layout) or [*, 2, cap] (planar), pinned host or device memory; slots / lens: int32, pinned
-    host or device memory.  The caller keeps all three alive and unchanged until the launch has run."""
-    _chk(hspec, torch.float32, "hspec"); _chk(bank_len, torch.int32, "bank_len")
+    host or device memory.  The caller keeps all three alive and unchanged until the launch has run.
+    hscale given: hspec is a HALF bank (float16) and hscale its scales (ss_bank_scatter_spectra16_f32)."""
+    half = _chk_spectra(hspec, hscale); _chk(bank_len, torch.int32, "bank_len")
     for t, dt, name in ((staged, torch.float32, "staged"), (slots, torch.int32, "slots"), (lens, torch.int32, "lens")):
         if not (t.is_cuda or t.is_pinned()):
             raise ValueError(f"{name}: pinned host or device memory expected (the kernel reads it in place)")
@@ -252,6 +266,12 @@ def scatter_spectra_into(staged: torch.Tensor, planar: bool, slots: torch.Tensor
     if n == 0:
         return
     with torch.cuda.device(hspec.device):
+        if half:
+            _lib.check(_lib.load().ss_bank_scatter_spectra16_f32(staged.data_ptr(), staged[0].numel(), int(bool(planar)),
+                                                                 slots.data_ptr(), lens.data_ptr(), n, hspec.data_ptr(),
+                                                                 hscale.data_ptr(), hspec.shape[2], bank_len.data_ptr(),
+                                                                 _stream(hspec)), "ss_bank_scatter_spectra16_f32")
+            return
         _lib.check(_lib.load().ss_bank_scatter_spectra_f32(staged.data_ptr(), staged[0].numel(), int(bool(planar)), slots.data_ptr(),
                                                            lens.data_ptr(), n, hspec.data_ptr(), hspec.shape[2], bank_len.data_ptr(),
                                                            _stream(hspec)), "ss_bank_scatter_spectra_f32")
@@ -264,12 +284,35 @@ def rir_spectra(rir_bank: torch.Tensor) -> torch.Tensor:
     return hspec
 
 
-def fftconv_binaural_spec_into(spec, hspec, rir_len, unit_desc, out, n_valid: int, flags: int = 0) -> None:
-    _chk(spec, torch.float32, "spec"); _chk(hspec, torch.float32, "hspec"); _chk(rir_len, torch.int32, "rir_len")
+def rir_spectra16(rir_bank: torch.Tensor):
+    """Half form of a planar bank [R,2,cap] (ss_rir_spectra16_f32, on the current stream) -> (float16 [R,2,hb,SPEC_FLOATS],
+    float32 scales [R,2,hb]): q = fp16(H' * 2^(15-e)) rounded to nearest even, scale = 2^(e-15), per block (include/ss_hip.h)."""
+    _chk(rir_bank, torch.float32, "rir_bank")
+    R, two, cap = rir_bank.shape
+    assert two == 2
+    hb = ceil_div(cap, KB)
+    hspec16 = torch.zeros((R, 2, hb, SPEC_FLOATS), dtype=torch.float16, device=rir_bank.device)
+    hscale = torch.zeros((R, 2, hb), dtype=torch.float32, device=rir_bank.device)
+    if R:
+        with torch.cuda.device(rir_bank.device):
+            _lib.check(_lib.load().ss_rir_spectra16_f32(rir_bank.data_ptr(), hspec16.data_ptr(), hscale.data_ptr(), R, 2 * cap, cap,
+                                                        cap, _stream(rir_bank)), "ss_rir_spectra16_f32")
+    return hspec16, hscale
+
+
+def fftconv_binaural_spec_into(spec, hspec, rir_len, unit_desc, out, n_valid: int, flags: int = 0, hscale=None) -> None:
+    """hscale given: hspec is a HALF bank (ss_fftconv_binaural_spec16_f32)."""
+    _chk(spec, torch.float32, "spec"); half = _chk_spectra(hspec, hscale); _chk(rir_len, torch.int32, "rir_len")
     _chk(unit_desc, torch.int32, "unit_desc"); _chk(out, torch.float32, "out")
     N, two, out_len = out.shape
     assert two == 2 and unit_desc.shape == (N, 8) and hspec.dim() == 4
     with torch.cuda.device(out.device):
+        if half:
+            _lib.check(_lib.load().ss_fftconv_binaural_spec16_f32(spec.data_ptr(), hspec.data_ptr(), hscale.data_ptr(),
+                                                                  rir_len.data_ptr(), unit_desc.data_ptr(), out.data_ptr(), N,
+                                                                  hspec.shape[2], n_valid, out_len, flags, _stream(spec)),
+                       "ss_fftconv_binaural_spec16_f32")
+            return
         _lib.check(_lib.load().ss_fftconv_binaural_spec_f32(spec.data_ptr(), hspec.data_ptr(), rir_len.data_ptr(),
                                                             unit_desc.data_ptr(), out.data_ptr(), N, hspec.shape[2],
                                                             n_valid, out_len, flags, _stream(spec)),
@@ -277,8 +320,9 @@ def fftconv_binaural_spec_into(spec, hspec, rir_len, unit_desc, out, n_valid: in
 
 
 def audio_obs_spec_into(spec, hspec, rir_len, unit_desc, audiogoal, spectrogram_out, n_valid: int, out_len: int,
-                        pad_mode="reflect", flags: int = 0) -> None:
-    _chk(spec, torch.float32, "spec"); _chk(hspec, torch.float32, "hspec"); _chk(rir_len, torch.int32, "rir_len")
+                        pad_mode="reflect", flags: int = 0, hscale=None) -> None:
+    """hscale given: hspec is a HALF bank (ss_audio_obs_spec16_f32: rows of one partition block)."""
+    _chk(spec, torch.float32, "spec"); half = _chk_spectra(hspec, hscale); _chk(rir_len, torch.int32, "rir_len")
     _chk(unit_desc, torch.int32, "unit_desc"); _chk(spectrogram_out, torch.float32, "spectrogram_out")
     N = unit_desc.shape[0]
     assert tuple(spectrogram_out.shape) == (N,) + spectrogram_shape(out_len) and hspec.dim() == 4
@@ -288,6 +332,12 @@ def audio_obs_spec_into(spec, hspec, rir_len, unit_desc, audiogoal, spectrogram_
         assert tuple(audiogoal.shape) == (N, 2, out_len)
         ag_ptr = audiogoal.data_ptr()
     with torch.cuda.device(spec.device):
+        if half:
+            _lib.check(_lib.load().ss_audio_obs_spec16_f32(spec.data_ptr(), hspec.data_ptr(), hscale.data_ptr(), rir_len.data_ptr(),
+                                                           unit_desc.data_ptr(), ag_ptr, spectrogram_out.data_ptr(), N,
+                                                           hspec.shape[2], n_valid, out_len, _PAD[pad_mode], flags, _stream(spec)),
+                       "ss_audio_obs_spec16_f32")
+            return
         _lib.check(_lib.load().ss_audio_obs_spec_f32(spec.data_ptr(), hspec.data_ptr(), rir_len.data_ptr(),
                                                      unit_desc.data_ptr(), ag_ptr, spectrogram_out.data_ptr(), N,
                                                      hspec.shape[2], n_valid, out_len, _PAD[pad_mode], flags, _stream(spec)),
@@ -331,12 +381,22 @@ def audio_obs_logmel_into(spec, rir_bank, rir_len, unit_desc, audiogoal, spectro
 
 
 def audio_obs_logmel_spec_into(spec, hspec, rir_len, unit_desc, audiogoal, spectrogram_out, logmel_out, mel_start, mel_w,
-                               n_valid: int, out_len: int, mel_eps: float = 1e-6, pad_mode="reflect", flags: int = 0) -> None:
-    """``audio_obs_logmel_into`` from the spectral RIR bank (``ss_audio_obs_logmel_spec_f32``)."""
-    _chk(spec, torch.float32, "spec"); _chk(hspec, torch.float32, "hspec"); _chk(rir_len, torch.int32, "rir_len")
+                               n_valid: int, out_len: int, mel_eps: float = 1e-6, pad_mode="reflect", flags: int = 0,
+                               hscale=None) -> None:
+    """``audio_obs_logmel_into`` from the spectral RIR bank (``ss_audio_obs_logmel_spec_f32``); hscale given: from a HALF bank
+    (``ss_audio_obs_logmel_spec16_f32``)."""
+    _chk(spec, torch.float32, "spec"); half = _chk_spectra(hspec, hscale); _chk(rir_len, torch.int32, "rir_len")
     assert hspec.dim() == 4
     N, n_mels, max_len, ag_ptr, sg_ptr = _obs_logmel_args(unit_desc, audiogoal, spectrogram_out, logmel_out, mel_start, mel_w, out_len)
     with torch.cuda.device(spec.device):
+        if half:
+            _lib.check(_lib.load().ss_audio_obs_logmel_spec16_f32(spec.data_ptr(), hspec.data_ptr(), hscale.data_ptr(),
+                                                                  rir_len.data_ptr(), unit_desc.data_ptr(), ag_ptr, sg_ptr,
+                                                                  logmel_out.data_ptr(), mel_start.data_ptr(), mel_w.data_ptr(),
+                                                                  int(n_mels), int(max_len), float(mel_eps), N, hspec.shape[2], n_valid,
+                                                                  out_len, _PAD[pad_mode], flags, _stream(spec)),
+                       "ss_audio_obs_logmel_spec16_f32")
+            return
         _lib.check(_lib.load().ss_audio_obs_logmel_spec_f32(spec.data_ptr(), hspec.data_ptr(), rir_len.data_ptr(), unit_desc.data_ptr(),
                                                             ag_ptr, sg_ptr, logmel_out.data_ptr(), mel_start.data_ptr(),
                                                             mel_w.data_ptr(), int(n_mels), int(max_len), float(mel_eps), N,

@@ -65,7 +65,11 @@ class RirBank:
 
     A SPECTRAL-ONLY bank (``RirStore(spectral="only")``) keeps no time-domain rows: ``data`` is then a zero-size
     ``[R, 2, 0]`` tensor (``len(bank)`` still counts the entries), ``cap`` is given (the rows' capacity that ``spectra``
-    ``[R, 2, ceil(cap/KB), SPEC_FLOATS]`` was built for) and ``spectral_only`` is True: only the *_spec_* kernels read it."""
+    ``[R, 2, ceil(cap/KB), SPEC_FLOATS]`` was built for) and ``spectral_only`` is True: only the *_spec_* kernels read it.
+
+    A HALF bank (``RirStore(spectral="half")``) is a spectral-only bank whose ``spectra`` are float16 with one float32 scale per
+    (entry, ear, block) in ``scales`` ``[R, 2, ceil(cap/KB)]`` (include/ss_hip.h "Half-precision spectral bank"); ``spectra16``
+    is that tensor (None on every other bank).  Lossy: about 2e-4 of peak on the waveform."""
 
     def __init__(self, data: torch.Tensor, lengths: torch.Tensor, cap: Optional[int] = None):
         assert data.dim() == 3 and data.shape[1] == 2 and data.dtype == torch.float32 and data.is_contiguous()
@@ -74,10 +78,15 @@ class RirBank:
         self.data, self.lengths = data, lengths
         self.cap = int(data.shape[2]) if cap is None else int(cap)
         self.spectra: Optional[torch.Tensor] = None      # [R, 2, ceil(cap/KB), SPEC_FLOATS]: see build_spectra()
+        self.scales: Optional[torch.Tensor] = None       # [R, 2, ceil(cap/KB)] float32: `spectra` is float16 (a half bank)
 
     @property
     def spectral_only(self) -> bool:
         return self.data.shape[2] == 0 and self.cap > 0
+
+    @property
+    def spectra16(self) -> Optional[torch.Tensor]:
+        return self.spectra if self.scales is not None else None
 
     def build_spectra(self) -> torch.Tensor:
         """Spectral form of the bank (ss_rir_spectra_f32): the forward FFT of every RIR block, done once here instead
@@ -403,7 +412,7 @@ class BatchedAudioRenderer:
                                        plan.desc, ag, sg, self.n_valid, self.out_len, self.pad_mode, flags=plan.flags)
         elif spectral:
             ops.audio_obs_spec_into(self._spec, self.rirs.spectra, self.rirs.lengths, plan.desc, ag, sg, self.n_valid,
-                                    self.out_len, self.pad_mode, flags=plan.flags)
+                                    self.out_len, self.pad_mode, flags=plan.flags, hscale=self.rirs.scales)
         else:
             ops.audio_obs_into(self._spec, self.rirs.data, self.rirs.lengths, plan.desc, ag, sg, self.n_valid,
                                self.out_len, self.pad_mode, flags=plan.flags)
@@ -429,7 +438,7 @@ class BatchedAudioRenderer:
         elif self.rirs.spectra is not None and not (plan.flags & ops.FLAG_CROSSFADE) and \
                 self._spectral_for(len(plan), not (plan.flags & ops.FLAG_NO_DISTRACTOR)):
             ops.fftconv_binaural_spec_into(self._spec, self.rirs.spectra, self.rirs.lengths, plan.desc, out, self.n_valid,
-                                           flags=plan.flags)
+                                           flags=plan.flags, hscale=self.rirs.scales)
         else:
             ops.fftconv_binaural_into(self._spec, self.rirs.data, self.rirs.lengths, plan.desc, out, self.n_valid,
                                       flags=plan.flags)
@@ -477,11 +486,15 @@ class RirStore:
         # [slots, 2, 0] tensor).  Every upload path stages the rows and transforms them on their way in (ss_bank_scatter_spectra_f32,
         # one launch): 1.49x the entries of a both-forms store per byte of HBM at 16 kHz, 1.45x at 44.1 kHz.  Only the *_spec_*
         # kernels can read such a bank: no cross-fade (SS2.0), no small-step policy, no time-domain fallback - hence no CPU store.
-        if isinstance(spectral, str) and spectral != "only":
-            raise ValueError(f"RirStore: spectral must be False, True or 'only', not {spectral!r}")
-        self.spectral_only = spectral == "only"
+        # spectral="half": a spectral-only store whose block spectra are float16 with one float32 scale per (entry, ear, block)
+        # (RirBank.spectra16 / scales; ss_bank_scatter_spectra16_f32): an entry costs what its time-domain row would, half of "only".
+        # Lossy (about 2e-4 of peak on the waveform) and served by the one-block kernels only: rows of at most KB samples (16 kHz).
+        if isinstance(spectral, str) and spectral not in ("only", "half"):
+            raise ValueError(f"RirStore: spectral must be False, True, 'only' or 'half', not {spectral!r}")
+        self.spectral_only = spectral in ("only", "half")
+        self.spectral_half = spectral == "half"
         if self.spectral_only and self.device.type != "cuda":
-            raise ValueError("RirStore(spectral='only') needs a GPU device: the spectral-only bank has no CPU fallback")
+            raise ValueError(f"RirStore(spectral={spectral!r}) needs a GPU device: the spectral-only bank has no CPU fallback")
         lengths = torch.zeros((slots,), dtype=torch.int32, device=self.device)
         if self.spectral_only:
             self.bank = RirBank(torch.zeros((slots, 2, 0), dtype=torch.float32, device=self.device), lengths, cap=cap)
@@ -522,8 +535,10 @@ class RirStore:
         self._stale = np.zeros((slots,), bool)
         self._stale_mark = not self.spectral_only               # (a spectral-only store's rows are transformed as they arrive)
         if spectral and self.device.type == "cuda":
-            self.bank.spectra = torch.zeros((slots, 2, P.ceil_div(cap, P.KB), P.SPEC_FLOATS), dtype=torch.float32,
-                                            device=self.device)
+            self.bank.spectra = torch.zeros((slots, 2, P.ceil_div(cap, P.KB), P.SPEC_FLOATS),
+                                            dtype=torch.float16 if self.spectral_half else torch.float32, device=self.device)
+            if self.spectral_half:                              # (zero-initialised, like the spectra: an unused entry is exact zeros)
+                self.bank.scales = torch.zeros((slots, 2, P.ceil_div(cap, P.KB)), dtype=torch.float32, device=self.device)
         # pinned staging ring for single-row uploads (a pageable torch copy blocks the host for the whole transfer)
         self._stage = None
         self._stage_ev: List = []
@@ -588,13 +603,16 @@ class RirStore:
         if self.spectral_only:
             # H'_i depends on block i of the row alone and rows are zero beyond their length: the old blocks stay valid, the new
             # ones are the spectra of zero blocks - exact, no row needed (and none is kept)
-            old = self.bank.spectra
-            spectra = torch.zeros((self.slots, 2, P.ceil_div(new_cap, P.KB), P.SPEC_FLOATS), dtype=torch.float32,
-                                  device=self.device)
+            # (a half store: the halves and the scales of the old blocks are copied as they are, the new blocks are zeros)
+            old, old_scales = self.bank.spectra, self.bank.scales
+            spectra = torch.zeros((self.slots, 2, P.ceil_div(new_cap, P.KB), P.SPEC_FLOATS), dtype=old.dtype, device=self.device)
             spectra[:, :, :old.shape[2]] = old
             self.bank = RirBank(torch.zeros((self.slots, 2, 0), dtype=torch.float32, device=self.device), self.bank.lengths,
                                 cap=new_cap)
             self.bank.spectra = spectra
+            if old_scales is not None:
+                self.bank.scales = torch.zeros((self.slots, 2, spectra.shape[2]), dtype=torch.float32, device=self.device)
+                self.bank.scales[:, :, :old_scales.shape[2]] = old_scales
             self.cap = new_cap
             self._stage = None
             self.grown += 1
@@ -1163,7 +1181,7 @@ class RirStore:
         pull = self.scatter_from_host and n_rows <= self.spectra_pull_rows
         src = stage if pull else stage[:n_rows].to(self.device, non_blocking=True)
         with torch.cuda.device(self.device):
-            ops.scatter_spectra_into(src, planar, pidx, plen, n_rows, self.bank.spectra, self.bank.lengths)
+            ops.scatter_spectra_into(src, planar, pidx, plen, n_rows, self.bank.spectra, self.bank.lengths, hscale=self.bank.scales)
             ev = torch.cuda.Event()
             ev.record()
         return ev
@@ -1299,8 +1317,8 @@ class BucketedRirStore:
     def __init__(self, slots: Sequence[int], caps: Sequence[int], device, truncate_to: Optional[int] = None,
                  max_cap: int = 1 << 18, on_grow=None, group: int = 1, spectral: bool = False):
         assert len(slots) == len(caps) and 1 <= len(caps) <= 4 and list(caps) == sorted(caps)
-        if spectral == "only":
-            raise ValueError("BucketedRirStore: spectral='only' (a spectral-only bank) is not supported with length buckets")
+        if isinstance(spectral, str):
+            raise ValueError(f"BucketedRirStore: spectral={spectral!r} (a spectral-only bank) is not supported with length buckets")
         self.device = torch.device(device)
         self.group, self.on_grow, self.spectral = group, on_grow, spectral
         self.first = [int(v) for v in np.cumsum([0] + list(slots[:-1]))]
@@ -1556,18 +1574,31 @@ class AudioEngine:
 
         rir_spectral="only": the block spectra WITHOUT the time-domain rows (RirStore(spectral="only")): the fast kernels of a
         static bank at ~1.5x the entries per byte of HBM (INTEGRATION.md "Spectral-only RIR banks").  Refused (ValueError) with
-        step_time / wrap (SS2.0: live RIRs and the cross-fade read rows), rir_buckets and spectral_max_units > 0."""
+        step_time / wrap (SS2.0: live RIRs and the cross-fade read rows), rir_buckets and spectral_max_units > 0.
+
+        rir_spectral="half": the spectral-only store with its block spectra as float16 plus one power-of-two float32 scale per
+        (entry, ear, block) (RirStore(spectral="half"), include/ss_hip.h "Half-precision spectral bank"): an entry costs what its
+        time-domain row would - twice the entries of "only" per byte of HBM.  LOSSY and therefore never a default: the waveform
+        moves by about 2e-4 of its peak and the pooled spectrogram by about 1e-4 against the float32 path (INTEGRATION.md says
+        which figure was measured how), outside the 1e-4 parity budget.  Same refusals as "only", and sampling rates above KB = 16384 (rows longer
+        than one partition block: the 44.1 / 48 kHz row kernels have no half form).  The eager, vector and deferred modes and the
+        C context run through it unchanged.  Time against float32 spectra: NOT MEASURED on an MI355X yet
+        (scripts/kbench_spec_half.py is the benchmark); the format's claim is capacity.  Launches of more rows than CUs run one
+        workgroup per row: the persistent k_conv_spec_rows has no half form."""
         if isinstance(rir_spectral, str):
-            if rir_spectral != "only":
-                raise ValueError(f"rir_spectral must be None, True, False or 'only', not {rir_spectral!r}")
+            if rir_spectral not in ("only", "half"):
+                raise ValueError(f"rir_spectral must be None, True, False, 'only' or 'half', not {rir_spectral!r}")
             if renderer_kwargs.get("step_time") is not None or renderer_kwargs.get("wrap"):
-                raise ValueError("rir_spectral='only' cannot serve SoundSpaces 2.0 (step_time / wrap): live RIRs and the "
+                raise ValueError(f"rir_spectral={rir_spectral!r} cannot serve SoundSpaces 2.0 (step_time / wrap): live RIRs and the "
                                  "cross-fade need time-domain rows")
             if rir_buckets:
-                raise ValueError("rir_spectral='only' does not support length-bucketed banks (rir_buckets)")
+                raise ValueError(f"rir_spectral={rir_spectral!r} does not support length-bucketed banks (rir_buckets)")
             if spectral_max_units > 0:
-                raise ValueError("rir_spectral='only' keeps no time-domain rows for the spectral_max_units policy to send "
-                                 "large steps to")
+                raise ValueError(f"rir_spectral={rir_spectral!r} keeps no time-domain rows for the spectral_max_units policy to "
+                                 "send large steps to")
+            if rir_spectral == "half" and int(sampling_rate) > P.KB:
+                raise ValueError(f"rir_spectral='half' serves rows of one partition block (sampling rates up to {P.KB}), "
+                                 f"not {sampling_rate}")
         self.renderer = BatchedAudioRenderer(sampling_rate, device=device, **renderer_kwargs)
         self._native_readers: Dict[int, tuple] = {}              # rir_file_slot: id(reader) -> (stock wav reader?, lenient?, reader)
         self._file_loader = None                                 # RirStore.miss_loader dict of rir_file_slot (ss_ctx_load_rir_files)
@@ -1580,7 +1611,8 @@ class AudioEngine:
                 self.spectral_max_units = int(spectral_max_units)
         self.renderer.spectral_max_units = self.spectral_max_units
         self.rir_spectral = bool(rir_spectral) and not full
-        self.rir_spectral_only = rir_spectral == "only"
+        self.rir_spectral_only = rir_spectral in ("only", "half")
+        self.rir_spectral_half = rir_spectral == "half"
         if rir_buckets:
             # length-bucketed bank: [(slots, cap samples), ...] ascending, e.g. [(4096, 16000), (256, 49152), (64, 65536)]
             self.store = BucketedRirStore([b[0] for b in rir_buckets], [b[1] for b in rir_buckets], self.renderer.device,
@@ -1592,7 +1624,7 @@ class AudioEngine:
         self.store = RirStore(rir_slots, rir_cap or sampling_rate, self.renderer.device,
                               truncate_to=None if full else int(sampling_rate), max_cap=rir_max_cap,
                               on_grow=self.renderer.set_rir_bank, group=rir_group,
-                              spectral="only" if self.rir_spectral_only else bool(rir_spectral) and not full)
+                              spectral=rir_spectral if self.rir_spectral_only else bool(rir_spectral) and not full)
         self.store.defer_uploads = True            # single-row uploads of a step travel as one block (flushed before every launch)
         self.renderer.set_rir_bank(self.store.bank)
 
@@ -1663,7 +1695,10 @@ class AudioEngine:
             return ctx
         if n_sync or cur is None or cur[0] is not bank.data or cur[1] is not bank.spectra:   # two data_ptr() calls per step)
             if bank.spectral_only:                               # (no rows: the context's spectral-only binding)
-                ctx.set_rir_spectra_only(bank.spectra, bank.lengths, bank.cap)
+                if bank.scales is not None:                      # (a half bank: fp16 spectra + scales)
+                    ctx.set_rir_spectra16(bank.spectra, bank.scales, bank.lengths, bank.cap)
+                else:
+                    ctx.set_rir_spectra_only(bank.spectra, bank.lengths, bank.cap)
                 self._ctx_bank = (bank.data, bank.spectra)
                 return ctx
             ctx.set_rir_bank(bank.data, bank.lengths)
