@@ -175,9 +175,9 @@ int ss_audio_obs_logmel_spec_f32(const float* spec, const float* hspec, const in
  * those fed float(q) * hscale.  ss_fftconv_binaural_spec16_f32 serves every row length its sibling serves;
  * ss_audio_obs_spec16_f32 rows of ONE partition block, 257 <= out_len <= kB (16 kHz); ss_audio_obs_logmel_spec16_f32 the shapes
  * of ss_audio_obs_logmel_spec_f32.  No SS_FLAG_CROSSFADE, no length buckets.  Everything else (longer fused rows, NULL hscale,
- * h_blocks < 1, a misaligned bank, the mel limits) is SS_EINVAL from the argument checks, before a device is touched.  Not
- * provided: half forms of the 44.1 / 48 kHz fused row kernels (k_obs_rows / k_obs_blocks) and of the persistent k_conv_spec_rows
- * (launches of more rows than CUs run one workgroup per row). */
+ * h_blocks < 1, a misaligned bank, the mel limits) is SS_EINVAL from the argument checks, before a device is touched.  Rows of
+ * 2 or 3 partition blocks (44.1 / 48 kHz) have entries of their own, below (ss_audio_obs_rows_spec16_f32).  Not provided: a half
+ * form of the persistent k_conv_spec_rows (launches of more rows than CUs run one workgroup per row). */
 int ss_rir_spectra16_f32(const float* rir, void* hspec16_out, float* hscale_out, int n_entries, long long rir_unit_stride,
                          int rir_chan_stride, int rir_cap, void* stream);
 int ss_fftconv_binaural_spec16_f32(const float* spec, const void* hspec16, const float* hscale, const int* rir_len,
@@ -190,6 +190,24 @@ int ss_audio_obs_logmel_spec16_f32(const float* spec, const void* hspec16, const
                                    const int* unit_desc, float* audiogoal, float* spectrogram, float* logmel,
                                    const int* mel_start, const float* mel_w, int n_mels, int max_len, float mel_eps, int n_units,
                                    int h_blocks, int n_valid, int out_len, int pad_mode, int flags, void* stream);
+
+/* The half bank for rows of 2 or 3 partition blocks (kB < out_len <= 3 kB: 44.1 / 48 kHz; EXTENSION, opt-in, LOSSY as above).
+ * Same format: a 44.1 kHz entry is 3 blocks x 2 ears x (65 536 + 4) + 4 = 393 244 bytes (fp32 spectral-only: 786 436; rows and
+ * spectra: 1 139 236; the bare time-domain row: 352 800).  Format loss at 44.1 kHz: INTEGRATION.md "Half-precision spectral banks".
+ * ss_audio_obs_rows_spec16_f32 = ss_audio_obs_spec_f32 on such rows reading a half bank, routed as that entry routes them:
+ * k_obs_blocks<.., HALF> while the grid fits the chip, k_obs_rows<.., HALF> beyond (one launch, `audiogoal` may be NULL); the
+ * shapes that entry renders unfused (n_valid <= kB with a waveform buffer) go to ss_fftconv_binaural_spec16_f32 + the
+ * spectrogram kernel.  ss_audio_obs_logmel_rows_spec16_f32 = ss_audio_obs_logmel_rows_spec_f32 (below) reading a half bank:
+ * `audiogoal` and `spectrogram` may each be NULL.  Same results as the siblings fed float(q) * hscale.  SS_EINVAL before a device
+ * is touched: SS_FLAG_CROSSFADE, NULL or misaligned (& 7) halves, NULL scales, h_blocks outside 1..16, out_len <= kB or > 3 kB,
+ * the mel limits.  n_units == 0 returns 0. */
+int ss_audio_obs_rows_spec16_f32(const float* spec, const void* hspec16, const float* hscale, const int* rir_len,
+                                 const int* unit_desc, float* audiogoal, float* spectrogram, int n_units, int h_blocks,
+                                 int n_valid, int out_len, int pad_mode, int flags, void* stream);
+int ss_audio_obs_logmel_rows_spec16_f32(const float* spec, const void* hspec16, const float* hscale, const int* rir_len,
+                                        const int* unit_desc, float* audiogoal, float* spectrogram, float* logmel,
+                                        const int* mel_start, const float* mel_w, int n_mels, int max_len, float mel_eps,
+                                        int n_units, int h_blocks, int n_valid, int out_len, int pad_mode, int flags, void* stream);
 
 /* The same for rows of 2 or 3 partition blocks (kB < out_len <= 3 kB: 44.1 / 48 kHz, the reference's Replica rate; EXTENSION):
  * the log-mel form of the fused row kernels (k_obs_rows / k_obs_blocks), the STFT phase behind every output block emits the
@@ -379,6 +397,14 @@ int ss_ctx_set_rir_spectra(ss_ctx* ctx, const float* hspec, int h_blocks);
  * (ss_ctx_observe_requests_load, ss_ctx_load_rir_files) serve such a context through ss_bank_scatter_spectra16_f32; the
  * ss_miss_loader of a spectral-only store is used as it is (bank = NULL). */
 int ss_ctx_set_rir_spectra16(ss_ctx* ctx, const void* hspec16, const float* hscale, int h_blocks);
+/* ... and for contexts whose rows have 2 or 3 partition blocks (kB < sampling_rate <= 3 kB: 44.1 / 48 kHz), which the call above
+ * keeps refusing: the same preconditions otherwise (spectral-only bank, no buckets, rir_len set, no fp32 spectra bound,
+ * h_blocks == ceil(rir_cap / kB) <= 16), SS_EINVAL on a context of one-block rows.  Spectrogram steps (with or without a
+ * waveform buffer) then take ss_audio_obs_rows_spec16_f32, log-mel steps inside ss_ctx_set_logmel_rows_policy's range
+ * ss_audio_obs_logmel_rows_spec16_f32 (outside it: the context's waveform scratch, as always), waveform-only steps
+ * ss_fftconv_binaural_spec16_f32.  Cross-faded steps are SS_EINVAL and leave no keys behind.  hspec16 = NULL unbinds.  The
+ * in-call loaders serve the binding through ss_bank_scatter_spectra16_f32. */
+int ss_ctx_set_rir_spectra16_rows(ss_ctx* ctx, const void* hspec16, const float* hscale, int h_blocks);
 /* The bank as length buckets (see ss_rir_bucket; replaces the two calls above for such banks; the descriptor array is copied,
  * the device pointers are borrowed).  Call again whenever a bucket is (re)allocated. */
 int ss_ctx_set_rir_buckets(ss_ctx* ctx, const ss_rir_bucket* buckets, int n_buckets, const int* rir_len);

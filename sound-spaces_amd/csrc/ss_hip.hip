@@ -297,9 +297,11 @@ inline bool obs_rows_ok(int out_len, int n_valid, int nbh_max, int flags, bool s
 // one workgroup per CU, which is also what makes the kernel's inter-workgroup hand-off safe.  Spare CUs go to parts (the STFT
 // phase of a block split 2 / 4 / 8 ways).  Returns 1 when the launch does not qualify (the caller falls through to k_obs_rows).
 // MEL: the log-mel instantiations (ss_audio_obs_logmel_rows_f32 / _spec_f32), same rule, same hand-off area.
-template <bool SPECTRAL, bool MEL = false>
+// HALF: the half-bank instantiations (ss_audio_obs_rows_spec16_f32 / ss_audio_obs_logmel_rows_spec16_f32), likewise.
+template <bool SPECTRAL, bool MEL = false, bool HALF = false>
 int launch_obs_blocks(ssk::ConvParams p, int n_units, int flags, int n_cus, hipStream_t st,
-                      const ssk::UnitTab<false, MEL>& mel = ssk::UnitTab<false, MEL>()) {
+                      const ssk::UnitTab<false, MEL>& mel = ssk::UnitTab<false, MEL>(),
+                      const ssk::SpecScale<HALF>& hs = ssk::SpecScale<HALF>()) {
     static const bool off = ab_flag("SS_HIP_NO_OBS_BLOCKS");   // (A/B builds only)
     const int n_rows = 2 * n_units, nb = (p.out_len + ssk::kB - 1) / ssk::kB;
     const int budget = n_cus / (g_launch_share > 1 ? g_launch_share : 1);
@@ -318,18 +320,24 @@ int launch_obs_blocks(ssk::ConvParams p, int n_units, int flags, int n_cus, hipS
     int rc = get_block_sync(st, &tails, &fl, &epoch);
     if (rc) return rc;
     const int grid = (n_rows * nb) << k;
+    if constexpr (HALF) {
+        hipLaunchKernelGGL((ssk::k_obs_blocks<SPECTRAL, MEL, true>), dim3(grid), dim3(ssk::kT), 0, st, p, n_rows, tails, fl, epoch, mel, hs);
+        return hip_err(hipGetLastError());
+    }
     if constexpr (MEL) hipLaunchKernelGGL((ssk::k_obs_blocks<SPECTRAL, true>), dim3(grid), dim3(ssk::kT), 0, st, p, n_rows, tails, fl, epoch, mel);
     else hipLaunchKernelGGL((ssk::k_obs_blocks<SPECTRAL>), dim3(grid), dim3(ssk::kT), 0, st, p, n_rows, tails, fl, epoch);
     return hip_err(hipGetLastError());
 }
 
-template <bool SPECTRAL, bool MEL = false>
+template <bool SPECTRAL, bool MEL = false, bool HALF = false>
 int launch_obs_rows(ssk::ConvParams p, int n_units, int flags, int n_cus, hipStream_t st,
-                    const ssk::UnitTab<false, MEL>& mel = ssk::UnitTab<false, MEL>()) {
+                    const ssk::UnitTab<false, MEL>& mel = ssk::UnitTab<false, MEL>(),
+                    const ssk::SpecScale<HALF>& hs = ssk::SpecScale<HALF>()) {
+    static_assert(!HALF || SPECTRAL, "half bank: the spectral form");
     const int n_rows = 2 * n_units;
-    if (MEL && ((flags & SS_FLAG_CROSSFADE) || p.n_buckets != 1)) return SS_EINVAL;      // (the log-mel form: plain rows, one allocation)
+    if ((MEL || HALF) && ((flags & SS_FLAG_CROSSFADE) || p.n_buckets != 1)) return SS_EINVAL;      // (the log-mel and half forms: plain rows, one allocation)
     {
-        const int rc = launch_obs_blocks<SPECTRAL, MEL>(p, n_units, flags, n_cus, st, mel);
+        const int rc = launch_obs_blocks<SPECTRAL, MEL, HALF>(p, n_units, flags, n_cus, st, mel, hs);
         if (rc != 1) return rc;
     }
     // small steps (the reference steps 5-10 envs per GPU at this rate): a row on 2 / 4 / 8 CUs, each rendering the row and
@@ -365,6 +373,10 @@ int launch_obs_rows(ssk::ConvParams p, int n_units, int flags, int n_cus, hipStr
             hipLaunchKernelGGL((ssk::k_obs_rows<false, true>), dim3(grid), dim3(ssk::kT), 0, st, p, n_rows);
             return hip_err(hipGetLastError());
         }
+    }
+    if constexpr (HALF) {
+        hipLaunchKernelGGL((ssk::k_obs_rows<true, false, false, MEL, true>), dim3(grid), dim3(ssk::kT), 0, st, p, n_rows, mel, hs);
+        return hip_err(hipGetLastError());
     }
     if constexpr (MEL) {
         hipLaunchKernelGGL((ssk::k_obs_rows<SPECTRAL, false, false, true>), dim3(grid), dim3(ssk::kT), 0, st, p, n_rows, mel);
@@ -1230,6 +1242,67 @@ int ss_audio_obs_logmel_rows_spec_f32(const float* spec, const float* hspec, con
     return launch_obs_rows<true, true>(p, n_units, flags, n_cus, static_cast<hipStream_t>(stream), m);
 }
 
+// ---- half bank, rows of 2 or 3 partition blocks (44.1 / 48 kHz): k_obs_blocks<true, MEL, HALF> / k_obs_rows<true, .., MEL, HALF> ----
+// what the two entries refuse before a device is touched
+static bool spec16_rows_args_ok(const float* spec, const void* hspec16, const float* hscale, const int* rir_len, const int* unit_desc,
+                                int n_units, int h_blocks, int n_valid, int out_len, int pad_mode, int flags) {
+    return spec && rir_len && unit_desc && spec16_args_ok(hspec16, hscale, n_units, h_blocks, flags) && h_blocks <= 16 &&
+           out_len > ssk::kB && out_len <= 3 * ssk::kB && n_valid >= 0 && n_valid <= out_len &&
+           (pad_mode == SS_PAD_REFLECT || pad_mode == SS_PAD_CONSTANT);
+}
+
+// ss_audio_obs_spec_f32 for rows of 2 or 3 partition blocks, from a half bank: the same routing (k_obs_blocks while the grid fits
+// the chip, k_obs_rows beyond; shapes the fp32 entry hands to the unfused convolution + k_spectrogram go to the half convolution)
+int ss_audio_obs_rows_spec16_f32(const float* spec, const void* hspec16, const float* hscale, const int* rir_len, const int* unit_desc,
+                                 float* audiogoal, float* spectrogram, int n_units, int h_blocks, int n_valid, int out_len,
+                                 int pad_mode, int flags, void* stream) {
+    if (n_units == 0) return 0;
+    if (!spectrogram || !spec16_rows_args_ok(spec, hspec16, hscale, rir_len, unit_desc, n_units, h_blocks, n_valid, out_len, pad_mode, flags))
+        return SS_EINVAL;
+    const bool fused = obs_rows_ok(out_len, n_valid, h_blocks, flags, true, audiogoal != nullptr);
+    if (!fused && !audiogoal) return SS_EINVAL;
+    if (!fused) {
+        const int rc = ss_fftconv_binaural_spec16_f32(spec, hspec16, hscale, rir_len, unit_desc, audiogoal, n_units, h_blocks, n_valid,
+                                                      out_len, flags, stream);
+        if (rc) return rc;
+        return spectrogram_of_rows(audiogoal, spectrogram, n_units, out_len, n_valid, pad_mode, stream);
+    }
+    ssk::ConvParams p;
+    int n_cus = 1;
+    int rc = fill_conv(p, &n_cus, spec, nullptr, rir_len, unit_desc, 0, 0, 1, 0, n_valid, out_len, false);
+    if (rc) return rc;
+    p.pad_mode = pad_mode;
+    p.hspec = static_cast<const ssk::f32x4*>(hspec16);
+    p.h_blocks = h_blocks;
+    p.out = audiogoal;
+    p.sgram = spectrogram;
+    return launch_obs_rows<true, false, true>(p, n_units, flags, n_cus, static_cast<hipStream_t>(stream), ssk::UnitTab<false>(),
+                                              ssk::SpecScale<true>{hscale});
+}
+
+// ss_audio_obs_logmel_rows_spec_f32 from a half bank
+int ss_audio_obs_logmel_rows_spec16_f32(const float* spec, const void* hspec16, const float* hscale, const int* rir_len,
+                                        const int* unit_desc, float* audiogoal, float* spectrogram, float* logmel,
+                                        const int* mel_start, const float* mel_w, int n_mels, int max_len, float mel_eps, int n_units,
+                                        int h_blocks, int n_valid, int out_len, int pad_mode, int flags, void* stream) {
+    if (n_units == 0) return 0;
+    if (!spec16_rows_args_ok(spec, hspec16, hscale, rir_len, unit_desc, n_units, h_blocks, n_valid, out_len, pad_mode, flags) ||
+        !mel_args_ok(logmel, mel_start, mel_w, n_mels, max_len, mel_eps))
+        return SS_EINVAL;
+    if (!obs_logmel_rows_shape_ok(out_len, n_valid, h_blocks, flags)) return SS_EINVAL;
+    ssk::ConvParams p;
+    int n_cus = 1;
+    int rc = fill_conv(p, &n_cus, spec, nullptr, rir_len, unit_desc, 0, 0, 1, 0, n_valid, out_len, false);
+    if (rc) return rc;
+    p.pad_mode = pad_mode;
+    p.hspec = static_cast<const ssk::f32x4*>(hspec16);
+    p.h_blocks = h_blocks;
+    p.out = audiogoal;
+    p.sgram = spectrogram;
+    const ssk::MelArgs m{logmel, mel_start, mel_w, n_mels, max_len, mel_eps};
+    return launch_obs_rows<true, true, true>(p, n_units, flags, n_cus, static_cast<hipStream_t>(stream), m, ssk::SpecScale<true>{hscale});
+}
+
 // ---- context API (include/ss_hip.h): planner + window-spectra cache + descriptor ring inside the library --------------
 struct ss_ctx { ssctx::Context c; };
 
@@ -1382,6 +1455,26 @@ int ss_ctx_set_rir_spectra16(ss_ctx* h, const void* hspec16, const float* hscale
     }
     if (!hscale || h_blocks < 1 || (reinterpret_cast<size_t>(hspec16) & 7)) return SS_EINVAL;
     if (c.out_len > c.kb || c.rir || !c.buckets.empty() || !c.rir_len || (c.hspec && !c.hscale)) return SS_EINVAL;
+    if (h_blocks != (c.rir_cap > 0 ? ssctx::ceil_div(c.rir_cap, c.kb) : 1)) return SS_EINVAL;
+    c.hspec = static_cast<const float*>(hspec16);              // (read as halves wherever hscale is set)
+    c.hscale = hscale;
+    c.h_blocks = h_blocks;
+    return 0;
+}
+
+// The same binding for contexts whose rows have 2 or 3 partition blocks (44.1 / 48 kHz): steps then go to
+// ss_audio_obs_rows_spec16_f32 / ss_audio_obs_logmel_rows_spec16_f32 (k_obs_blocks / k_obs_rows <.., HALF>), waveform-only steps
+// to ss_fftconv_binaural_spec16_f32.  Same preconditions otherwise; hspec16 = NULL unbinds.
+int ss_ctx_set_rir_spectra16_rows(ss_ctx* h, const void* hspec16, const float* hscale, int h_blocks) {
+    if (!h) return SS_EINVAL;
+    ssctx::Context& c = h->c;
+    if (!hspec16) {
+        if (c.hscale) { c.hspec = nullptr; c.hscale = nullptr; c.h_blocks = 0; }
+        return 0;
+    }
+    if (!hscale || h_blocks < 1 || h_blocks > 16 || (reinterpret_cast<size_t>(hspec16) & 7)) return SS_EINVAL;
+    if (c.out_len <= c.kb || c.out_len > 3 * c.kb) return SS_EINVAL;
+    if (c.rir || !c.buckets.empty() || !c.rir_len || (c.hspec && !c.hscale)) return SS_EINVAL;
     if (h_blocks != (c.rir_cap > 0 ? ssctx::ceil_div(c.rir_cap, c.kb) : 1)) return SS_EINVAL;
     c.hspec = static_cast<const float*>(hspec16);              // (read as halves wherever hscale is set)
     c.hscale = hscale;
@@ -1614,7 +1707,8 @@ static int ctx_observe_on(ss_ctx* h, const ss_units* units, int n, float* audiog
     // rows of 2 or 3 blocks (44.1 / 48 kHz): the log-mel form of k_obs_rows / k_obs_blocks under the same conditions, inside the
     // range of ss_ctx_set_logmel_rows_policy (default: never - the scratch route is bit-equal to observe-then-features, the
     // fused arithmetic only to rounding)
-    const bool mel_rows = mel && !mel_fused && !c.hscale && c.buckets.empty() && (spectral || (c.rir && c.rir_cap > 0)) &&
+    // (a half bank: only the one bound by ss_ctx_set_rir_spectra16_rows has rows this long)
+    const bool mel_rows = mel && !mel_fused && (!c.hscale || c.out_len > c.kb) && c.buckets.empty() && (spectral || (c.rir && c.rir_cap > 0)) &&
                           obs_logmel_rows_shape_ok(c.out_len, c.n_valid, nbh_bank, res.flags) &&
                           n >= c.mel_rows_min_units && n <= c.mel_rows_max_units;
     // SoundSpaces 2.0 steps (cross-faded one-block rows; block 0 of a 44.1 / 48 kHz row, cross-faded or not): their own fused
@@ -1650,7 +1744,11 @@ static int ctx_observe_on(ss_ctx* h, const ss_units* units, int n, float* audiog
                                          mel->n_mels, mel->max_len, mel->mel_eps, n, c.rir_us, c.rir_cs, c.rir_es, c.rir_cap,
                                          c.n_valid, c.out_len, c.pad_mode, res.flags, stream);
     } else if (mel_rows) {
-        rc = spectral ? ss_audio_obs_logmel_rows_spec_f32(c.pool, c.hspec, c.rir_len, dd, nullptr, spectrogram, mel->logmel,
+        rc = spectral && c.hscale
+                 ? ss_audio_obs_logmel_rows_spec16_f32(c.pool, c.hspec, c.hscale, c.rir_len, dd, nullptr, spectrogram, mel->logmel,
+                                                       mel->mel_start, mel->mel_w, mel->n_mels, mel->max_len, mel->mel_eps, n,
+                                                       c.h_blocks, c.n_valid, c.out_len, c.pad_mode, res.flags, stream)
+             : spectral ? ss_audio_obs_logmel_rows_spec_f32(c.pool, c.hspec, c.rir_len, dd, nullptr, spectrogram, mel->logmel,
                                                           mel->mel_start, mel->mel_w, mel->n_mels, mel->max_len, mel->mel_eps, n,
                                                           c.h_blocks, c.n_valid, c.out_len, c.pad_mode, res.flags, stream)
                       : ss_audio_obs_logmel_rows_f32(c.pool, c.rir, c.rir_len, dd, nullptr, spectrogram, mel->logmel, mel->mel_start,
@@ -1673,7 +1771,10 @@ static int ctx_observe_on(ss_ctx* h, const ss_units* units, int n, float* audiog
                                                     c.n_valid, c.out_len, c.pad_mode, res.flags, stream)
                          : ss_fftconv_binaural_buckets_f32(c.pool, c.buckets.data(), nb, c.rir_len, dd, audiogoal, n, c.n_valid,
                                                            c.out_len, res.flags, stream);
-    } else if (spectrogram && spectral && c.hscale)
+    } else if (spectrogram && spectral && c.hscale && c.out_len > c.kb)      // (bound by ss_ctx_set_rir_spectra16_rows)
+        rc = ss_audio_obs_rows_spec16_f32(c.pool, c.hspec, c.hscale, c.rir_len, dd, audiogoal, spectrogram, n, c.h_blocks, c.n_valid,
+                                          c.out_len, c.pad_mode, res.flags, stream);
+    else if (spectrogram && spectral && c.hscale)
         rc = ss_audio_obs_spec16_f32(c.pool, c.hspec, c.hscale, c.rir_len, dd, audiogoal, spectrogram, n, c.h_blocks, c.n_valid,
                                      c.out_len, c.pad_mode, res.flags, stream);
     else if (spectral && c.hscale)

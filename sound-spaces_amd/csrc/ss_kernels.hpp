@@ -2148,6 +2148,29 @@ __device__ __forceinline__ void rows_product(const f32x4* hp, const f32x4* sp, i
     }
 }
 
+// ... for a pair of a HALF bank (see spec_block_product16): hp points at the thread's h16x4 of the block, scale_p at the block's
+// scale - a wave-uniform word at the head of the batch; the arithmetic behind the widening is rows_product's
+__device__ __forceinline__ void rows_product16(const h16x4* hp, const float* scale_p, const f32x4* sp, int t, int s, c32 (&v)[8]) {
+    h16x4 hv[4];
+    f32x4 sv[4];
+    const float sc = *scale_p;
+#pragma unroll
+    for (int hh = 0; hh < 4; ++hh) { hv[hh] = ld_stream(hp + (s * 4 + hh) * 1024); sv[hh] = sp[(s * 4 + hh) * 1024]; }
+    if (kRowsAbl & 4) {
+#pragma unroll
+        for (int hh = 0; hh < 4; ++hh) sv[hh] = f32x4{1.f, 0.f, 1.f, 0.f};
+    }
+    SSK_SCHED_BARRIER();                                  // the scale's load and all eight before the first multiply
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const f32x4 hf = __builtin_convertvector(hv[e >> 1], f32x4) * sc;
+        const c32 h = (e & 1) ? hf.zw : hf.xy, w = (e & 1) ? sv[e >> 1].zw : sv[e >> 1].xy;
+        c32 pr = cmul(h, w);
+        if (s == 0 && e == 0 && t == 0) pr = mk2(h.x * w.x, h.y * w.y);      // (X[0], X[16384]) are real
+        v[e] += pr;
+    }
+}
+
 // Hand-off between WORKGROUPS of one launch (k_obs_blocks: the samples an output block leaves for the STFT frames that straddle
 // into the next block travel through global memory): agent-scope release / acquire on a flag word, the data itself read with
 // agent-scope loads (the XCDs' L2s are not coherent with each other for plain accesses).  The wait is BOUNDED: a consumer
@@ -2331,9 +2354,13 @@ __device__ __forceinline__ void mel_fill_quiet(const MelArgs& m, const ConvParam
 
 // MEL (log-mel form: plain rows of a single-allocation bank): the mel arguments and the log-mel output ride in the third kernel
 // argument (MelArgs, see UnitTab), the STFT phases emit the bands (rows_stft_phase<.., MEL>), p.sgram may be null.
-template <bool SPECTRAL, bool XFADE = false, bool BUCKETS = true, bool MEL = false>
-__global__ __launch_bounds__(1024) void k_obs_rows(ConvParams p, int n_rows, UnitTab<false, MEL> ut = UnitTab<false, MEL>()) {
+// HALF (a half bank, see k_conv_spec<.., HALF>): the pairs in memory are fp16 block spectra with one scale per block
+// (rows_product16); the scales ride in a kernel argument of their own.
+template <bool SPECTRAL, bool XFADE = false, bool BUCKETS = true, bool MEL = false, bool HALF = false>
+__global__ __launch_bounds__(1024) void k_obs_rows(ConvParams p, int n_rows, UnitTab<false, MEL> ut = UnitTab<false, MEL>(),
+                                                   SpecScale<HALF> hs = SpecScale<HALF>()) {
     static_assert(!(SPECTRAL && XFADE), "cross-faded rows are rendered from the time-domain bank");
+    static_assert(!HALF || (SPECTRAL && !XFADE && !BUCKETS), "half bank: plain rows of a single-allocation spectral bank");
     static_assert(!MEL || (!XFADE && !BUCKETS), "log-mel: plain rows of a single-allocation bank");
     __shared__ c32 lds[16 * kWaveScratch > kLdsComplex ? 16 * kWaveScratch : kLdsComplex];
     __shared__ float s_win[kNfft];
@@ -2520,7 +2547,10 @@ __global__ __launch_bounds__(1024) void k_obs_rows(ConvParams p, int n_rows, Uni
                         const f32x4* hp = SPECTRAL ? bank_spec<BUCKETS>(p, dw.x, ch).hp + (size_t)i * blk_f4
                                                    : stash + (size_t)(term * p.stash_nbh + i) * blk_f4;
                         const f32x4* sp = p.spec + (size_t)(dw.y + (j - i - dw.z)) * blk_f4;
-                        rows_product(hp + ti, sp + ti, ti, s, v);
+                        if constexpr (HALF) {             // one allocation: same f32x4 index, 8-byte elements (see k_conv_spec)
+                            const size_t blk = ((size_t)dw.x * 2 + ch) * (size_t)p.h_blocks + i;
+                            rows_product16(reinterpret_cast<const h16x4*>(p.hspec) + blk * blk_f4 + ti, hs.hscale + blk, sp + ti, ti, s, v);
+                        } else rows_product(hp + ti, sp + ti, ti, s, v);
                     }
                     item_store_inv(lds, s ? tw.i1 : tw.i0, ti + 1024 * s, v);
                 }
@@ -2627,9 +2657,12 @@ __global__ __launch_bounds__(1024) void k_obs_rows(ConvParams p, int n_rows, Uni
 // cross-fade, 2 or 3 output blocks.
 // MEL (log-mel form, as k_obs_rows<.., MEL>): a workgroup writes the log-mel frames of its own pooled blocks, the silent row's
 // early return its block's share of frames; p.sgram may be null.
-template <bool SPECTRAL, bool MEL = false>
+// HALF (a half bank, see k_conv_spec<.., HALF>): the spectral branch reads fp16 block spectra and their scales.
+template <bool SPECTRAL, bool MEL = false, bool HALF = false>
 __global__ __launch_bounds__(1024) void k_obs_blocks(ConvParams p, int n_rows, float* tails, int* flags, int epoch,
-                                                     UnitTab<false, MEL> ut = UnitTab<false, MEL>()) {
+                                                     UnitTab<false, MEL> ut = UnitTab<false, MEL>(),
+                                                     SpecScale<HALF> hs = SpecScale<HALF>()) {
+    static_assert(!HALF || SPECTRAL, "half bank: the spectral form");
     __shared__ c32 lds[16 * kWaveScratch > kLdsComplex ? 16 * kWaveScratch : kLdsComplex];
     __shared__ float s_win[kNfft];
     __shared__ c32 s_tw512[kTw512Lds];
@@ -2696,7 +2729,11 @@ __global__ __launch_bounds__(1024) void k_obs_blocks(ConvParams p, int n_rows, f
                 if (m < m_min || m >= m_min + m_cnt) continue;
                 int tl = t;
                 SSK_OPAQUE1(tl);
-                spec_block_product(p.spec, tl, bs.hp + (size_t)i * (kSpecComplex / 2) + tl, spec0 + (m - m_min), any, acc);
+                if constexpr (HALF) {                     // one allocation (the launcher checks): see k_conv_spec
+                    const size_t blk = ((size_t)ridx * 2 + ch) * (size_t)p.h_blocks + i;
+                    spec_block_product16(p.spec, tl, reinterpret_cast<const h16x4*>(p.hspec) + blk * (kSpecComplex / 2) + tl,
+                                         hs.hscale + blk, spec0 + (m - m_min), any, acc);
+                } else spec_block_product(p.spec, tl, bs.hp + (size_t)i * (kSpecComplex / 2) + tl, spec0 + (m - m_min), any, acc);
                 any = true;
             }
         } else {

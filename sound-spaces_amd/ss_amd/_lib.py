@@ -21,7 +21,8 @@ EXPORTS = ("ss_block_len", "ss_spec_floats", "ss_version", "ss_init", "ss_source
            "ss_audio_obs_logmel_rows_f32", "ss_audio_obs_logmel_rows_spec_f32", "ss_ctx_set_logmel_rows_policy",
            "ss_audio_obs_logmel_ss2_f32", "ss_ctx_set_logmel_ss2_policy",
            "ss_rir_spectra16_f32", "ss_bank_scatter_spectra16_f32", "ss_fftconv_binaural_spec16_f32", "ss_audio_obs_spec16_f32",
-           "ss_audio_obs_logmel_spec16_f32", "ss_ctx_set_rir_spectra16")
+           "ss_audio_obs_logmel_spec16_f32", "ss_ctx_set_rir_spectra16",
+           "ss_audio_obs_rows_spec16_f32", "ss_audio_obs_logmel_rows_spec16_f32", "ss_ctx_set_rir_spectra16_rows")
 # entries that return a size_t, not a status (EXPORTS: every `int ss_*` of include/ss_hip.h)
 EXPORTS_SIZE = ("ss_ctx_wave_scratch_bytes",)
 
@@ -157,6 +158,10 @@ def load() -> ctypes.CDLL:
     lib.ss_audio_obs_logmel_spec16_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, c_int, c_int, ctypes.c_float, c_int, c_int,
                                                    c_int, c_int, c_int, c_int, vp]
     lib.ss_ctx_set_rir_spectra16.argtypes = [vp, vp, vp, c_int]
+    # ... for rows of 2 or 3 partition blocks (44.1 / 48 kHz)
+    lib.ss_audio_obs_rows_spec16_f32.argtypes = lib.ss_audio_obs_spec16_f32.argtypes
+    lib.ss_audio_obs_logmel_rows_spec16_f32.argtypes = lib.ss_audio_obs_logmel_spec16_f32.argtypes
+    lib.ss_ctx_set_rir_spectra16_rows.argtypes = [vp, vp, vp, c_int]
     for name in EXPORTS:
         getattr(lib, name).restype = c_int
     for name in EXPORTS_SIZE:

@@ -138,12 +138,14 @@ class AudioContext:
         _lib.check(self.lib.ss_ctx_set_rir_spectra(self._h, hspec.data_ptr(), int(hspec.shape[2])), "ss_ctx_set_rir_spectra")
         self._spectra = hspec
 
-    def set_rir_spectra16(self, hspec16, hscale, lengths, cap: int) -> None:
+    def set_rir_spectra16(self, hspec16, hscale, lengths, cap: int, rows: bool = False) -> None:
         """A HALF bank (``RirStore(spectral="half")``: float16 block spectra hspec16 [R,2,ceil(cap/KB),SPEC_FLOATS], float32 scales
         hscale [R,2,ceil(cap/KB)] and CUDA int32 lengths [R]; spectral-only, no time-domain rows):
         ss_ctx_set_rir_bank(ctx, NULL, lengths, 0, 0, 1, cap) + ss_ctx_set_rir_spectra16.  Steps read the half spectra
         (k_conv_spec<.., HALF>); the library refuses (SS_EINVAL) a context whose rows exceed one partition block (sampling rates
-        above KB) and cross-faded steps."""
+        above KB) and cross-faded steps.
+        rows=True: the binding for contexts whose rows have 2 or 3 partition blocks (44.1 / 48 kHz; ss_ctx_set_rir_spectra16_rows):
+        steps read the half spectra through k_obs_blocks / k_obs_rows <.., HALF>; refused on a context of one-block rows."""
         import torch
         if hspec16.dtype != torch.float16 or hscale.dtype != torch.float32 or not hspec16.is_contiguous() or not hscale.is_contiguous():
             raise ValueError("set_rir_spectra16: contiguous float16 spectra and float32 scales expected")
@@ -153,8 +155,8 @@ class AudioContext:
         self._bank = (None, lengths)
         self.rir_cap = int(cap)
         self._spectra = None
-        _lib.check(self.lib.ss_ctx_set_rir_spectra16(self._h, hspec16.data_ptr(), hscale.data_ptr(), int(hspec16.shape[2])),
-                   "ss_ctx_set_rir_spectra16")
+        name = "ss_ctx_set_rir_spectra16_rows" if rows else "ss_ctx_set_rir_spectra16"
+        _lib.check(getattr(self.lib, name)(self._h, hspec16.data_ptr(), hscale.data_ptr(), int(hspec16.shape[2])), name)
         self._spectra = (hspec16, hscale)
 
     def set_rir_buckets(self, bank, spectral: bool = False) -> None:

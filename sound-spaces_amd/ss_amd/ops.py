@@ -321,7 +321,8 @@ def fftconv_binaural_spec_into(spec, hspec, rir_len, unit_desc, out, n_valid: in
 
 def audio_obs_spec_into(spec, hspec, rir_len, unit_desc, audiogoal, spectrogram_out, n_valid: int, out_len: int,
                         pad_mode="reflect", flags: int = 0, hscale=None) -> None:
-    """hscale given: hspec is a HALF bank (ss_audio_obs_spec16_f32: rows of one partition block)."""
+    """hscale given: hspec is a HALF bank (ss_audio_obs_spec16_f32: rows of one partition block; ss_audio_obs_rows_spec16_f32:
+    rows of 2 or 3, KB < out_len <= 3 KB)."""
     _chk(spec, torch.float32, "spec"); half = _chk_spectra(hspec, hscale); _chk(rir_len, torch.int32, "rir_len")
     _chk(unit_desc, torch.int32, "unit_desc"); _chk(spectrogram_out, torch.float32, "spectrogram_out")
     N = unit_desc.shape[0]
@@ -333,10 +334,10 @@ def audio_obs_spec_into(spec, hspec, rir_len, unit_desc, audiogoal, spectrogram_
         ag_ptr = audiogoal.data_ptr()
     with torch.cuda.device(spec.device):
         if half:
-            _lib.check(_lib.load().ss_audio_obs_spec16_f32(spec.data_ptr(), hspec.data_ptr(), hscale.data_ptr(), rir_len.data_ptr(),
-                                                           unit_desc.data_ptr(), ag_ptr, spectrogram_out.data_ptr(), N,
-                                                           hspec.shape[2], n_valid, out_len, _PAD[pad_mode], flags, _stream(spec)),
-                       "ss_audio_obs_spec16_f32")
+            name = "ss_audio_obs_rows_spec16_f32" if out_len > KB else "ss_audio_obs_spec16_f32"
+            _lib.check(getattr(_lib.load(), name)(spec.data_ptr(), hspec.data_ptr(), hscale.data_ptr(), rir_len.data_ptr(),
+                                                  unit_desc.data_ptr(), ag_ptr, spectrogram_out.data_ptr(), N, hspec.shape[2],
+                                                  n_valid, out_len, _PAD[pad_mode], flags, _stream(spec)), name)
             return
         _lib.check(_lib.load().ss_audio_obs_spec_f32(spec.data_ptr(), hspec.data_ptr(), rir_len.data_ptr(),
                                                      unit_desc.data_ptr(), ag_ptr, spectrogram_out.data_ptr(), N,
@@ -442,12 +443,22 @@ def audio_obs_logmel_ss2_into(spec, rir_bank, rir_len, unit_desc, audiogoal, spe
 
 
 def audio_obs_logmel_rows_spec_into(spec, hspec, rir_len, unit_desc, audiogoal, spectrogram_out, logmel_out, mel_start, mel_w,
-                                    n_valid: int, out_len: int, mel_eps: float = 1e-6, pad_mode="reflect", flags: int = 0) -> None:
-    """``audio_obs_logmel_rows_into`` from the spectral RIR bank (``ss_audio_obs_logmel_rows_spec_f32``)."""
-    _chk(spec, torch.float32, "spec"); _chk(hspec, torch.float32, "hspec"); _chk(rir_len, torch.int32, "rir_len")
+                                    n_valid: int, out_len: int, mel_eps: float = 1e-6, pad_mode="reflect", flags: int = 0,
+                                    hscale=None) -> None:
+    """``audio_obs_logmel_rows_into`` from the spectral RIR bank (``ss_audio_obs_logmel_rows_spec_f32``); hscale given: from a
+    HALF bank (``ss_audio_obs_logmel_rows_spec16_f32``)."""
+    _chk(spec, torch.float32, "spec"); half = _chk_spectra(hspec, hscale); _chk(rir_len, torch.int32, "rir_len")
     assert hspec.dim() == 4
     N, n_mels, max_len, ag_ptr, sg_ptr = _obs_logmel_args(unit_desc, audiogoal, spectrogram_out, logmel_out, mel_start, mel_w, out_len)
     with torch.cuda.device(spec.device):
+        if half:
+            _lib.check(_lib.load().ss_audio_obs_logmel_rows_spec16_f32(spec.data_ptr(), hspec.data_ptr(), hscale.data_ptr(),
+                                                                       rir_len.data_ptr(), unit_desc.data_ptr(), ag_ptr, sg_ptr,
+                                                                       logmel_out.data_ptr(), mel_start.data_ptr(), mel_w.data_ptr(),
+                                                                       int(n_mels), int(max_len), float(mel_eps), N, hspec.shape[2],
+                                                                       n_valid, out_len, _PAD[pad_mode], flags, _stream(spec)),
+                       "ss_audio_obs_logmel_rows_spec16_f32")
+            return
         _lib.check(_lib.load().ss_audio_obs_logmel_rows_spec_f32(spec.data_ptr(), hspec.data_ptr(), rir_len.data_ptr(),
                                                                  unit_desc.data_ptr(), ag_ptr, sg_ptr, logmel_out.data_ptr(),
                                                                  mel_start.data_ptr(), mel_w.data_ptr(), int(n_mels), int(max_len),

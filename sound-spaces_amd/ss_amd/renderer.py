@@ -1557,7 +1557,7 @@ class AudioEngine:
     def __init__(self, sampling_rate: int, device="cuda", rir_slots: int = 4096, rir_cap: Optional[int] = None,
                  rir_max_cap: int = 1 << 18, rir_group: int = 1, rir_spectral: Union[None, bool, str] = None,
                  rir_buckets: Optional[Sequence[Tuple[int, int]]] = None, spectral_hbm_fraction: float = 0.5,
-                 spectral_max_units: int = 0, **renderer_kwargs):
+                 spectral_max_units: int = 0, rir_half_rows: bool = False, **renderer_kwargs):
         """rir_spectral: keep the RIR rows' block spectra in HBM as well (2x the bytes per row) and run k_conv_spec /
         k_obs_rows<SPECTRAL> (no forward FFT per step): for STATIC banks (SoundSpaces 1.0 RIR files); live SS2.0 RIRs change
         every step and stay on the time-domain kernels.  None (default) = decided here: ON for file-backed stores at rates
@@ -1581,10 +1581,17 @@ class AudioEngine:
         time-domain row would - twice the entries of "only" per byte of HBM.  LOSSY and therefore never a default: the waveform
         moves by about 2e-4 of its peak and the pooled spectrogram by about 1e-4 against the float32 path (INTEGRATION.md says
         which figure was measured how), outside the 1e-4 parity budget.  Same refusals as "only", and sampling rates above KB = 16384 (rows longer
-        than one partition block: the 44.1 / 48 kHz row kernels have no half form).  The eager, vector and deferred modes and the
+        than one partition block) unless rir_half_rows is set.  The eager, vector and deferred modes and the
         C context run through it unchanged.  Time against float32 spectra: NOT MEASURED on an MI355X yet
         (scripts/kbench_spec_half.py is the benchmark); the format's claim is capacity.  Launches of more rows than CUs run one
-        workgroup per row: the persistent k_conv_spec_rows has no half form."""
+        workgroup per row: the persistent k_conv_spec_rows has no half form.
+
+        rir_half_rows=True (with rir_spectral="half" only): the half store for rows of 2 or 3 partition blocks (sampling rates in
+        (KB, 3 KB]: 44.1 / 48 kHz) - the fused row kernels' half forms (k_obs_blocks / k_obs_rows <.., HALF>,
+        ss_audio_obs_rows_spec16_f32 and its log-mel sibling) and the context binding ss_ctx_set_rir_spectra16_rows.  A 44.1 kHz
+        entry costs 393 244 bytes against 786 436 of "only".  Same loss, same refusals; rates above 3 KB are not served."""
+        if rir_half_rows and rir_spectral != "half":
+            raise ValueError("rir_half_rows goes with rir_spectral='half'")
         if isinstance(rir_spectral, str):
             if rir_spectral not in ("only", "half"):
                 raise ValueError(f"rir_spectral must be None, True, False, 'only' or 'half', not {rir_spectral!r}")
@@ -1596,9 +1603,12 @@ class AudioEngine:
             if spectral_max_units > 0:
                 raise ValueError(f"rir_spectral={rir_spectral!r} keeps no time-domain rows for the spectral_max_units policy to "
                                  "send large steps to")
-            if rir_spectral == "half" and int(sampling_rate) > P.KB:
+            if rir_spectral == "half" and int(sampling_rate) > P.KB and not rir_half_rows:
                 raise ValueError(f"rir_spectral='half' serves rows of one partition block (sampling rates up to {P.KB}), "
-                                 f"not {sampling_rate}")
+                                 f"not {sampling_rate}; rir_half_rows=True opts in to the half forms of the 44.1 / 48 kHz row kernels")
+            if rir_spectral == "half" and int(sampling_rate) > 3 * P.KB:
+                raise ValueError(f"rir_spectral='half' with rir_half_rows serves rows of up to three partition blocks (sampling "
+                                 f"rates up to {3 * P.KB}), not {sampling_rate}")
         self.renderer = BatchedAudioRenderer(sampling_rate, device=device, **renderer_kwargs)
         self._native_readers: Dict[int, tuple] = {}              # rir_file_slot: id(reader) -> (stock wav reader?, lenient?, reader)
         self._file_loader = None                                 # RirStore.miss_loader dict of rir_file_slot (ss_ctx_load_rir_files)
@@ -1696,7 +1706,7 @@ class AudioEngine:
         if n_sync or cur is None or cur[0] is not bank.data or cur[1] is not bank.spectra:   # two data_ptr() calls per step)
             if bank.spectral_only:                               # (no rows: the context's spectral-only binding)
                 if bank.scales is not None:                      # (a half bank: fp16 spectra + scales)
-                    ctx.set_rir_spectra16(bank.spectra, bank.scales, bank.lengths, bank.cap)
+                    ctx.set_rir_spectra16(bank.spectra, bank.scales, bank.lengths, bank.cap, rows=self.renderer.out_len > P.KB)
                 else:
                     ctx.set_rir_spectra_only(bank.spectra, bank.lengths, bank.cap)
                 self._ctx_bank = (bank.data, bank.spectra)
