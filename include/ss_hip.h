@@ -174,7 +174,8 @@ int ss_audio_obs_logmel_spec_f32(const float* spec, const float* hspec, const in
  * Consumers: the three entries below = their _spec_f32 siblings reading a half bank (k_conv_spec<.., HALF>), same results as
  * those fed float(q) * hscale.  ss_fftconv_binaural_spec16_f32 serves every row length its sibling serves;
  * ss_audio_obs_spec16_f32 rows of ONE partition block, 257 <= out_len <= kB (16 kHz); ss_audio_obs_logmel_spec16_f32 the shapes
- * of ss_audio_obs_logmel_spec_f32.  No SS_FLAG_CROSSFADE, no length buckets.  Everything else (longer fused rows, NULL hscale,
+ * of ss_audio_obs_logmel_spec_f32.  No SS_FLAG_CROSSFADE; one allocation (a half bank in length buckets has entries of its own:
+ * "Spectral length buckets" below, ss_spec_bucket).  Everything else (longer fused rows, NULL hscale,
  * h_blocks < 1, a misaligned bank, the mel limits) is SS_EINVAL from the argument checks, before a device is touched.  Rows of
  * 2 or 3 partition blocks (44.1 / 48 kHz) have entries of their own, below (ss_audio_obs_rows_spec16_f32).  Not provided: a half
  * form of the persistent k_conv_spec_rows (launches of more rows than CUs run one workgroup per row). */
@@ -277,6 +278,44 @@ int ss_fftconv_binaural_buckets_f32(const float* spec, const ss_rir_bucket* buck
 int ss_audio_obs_buckets_f32(const float* spec, const ss_rir_bucket* buckets, int n_buckets, const int* rir_len,
                              const int* unit_desc, float* audiogoal, float* spectrogram, int n_units, int n_valid,
                              int out_len, int pad_mode, int flags, void* stream);
+
+/* ---- Spectral length buckets: a bucketed bank WITHOUT time-domain rows ------------------------------------------------------
+ * The two dense forms of a bank - fp32 block spectra alone ("Spectral-only" binding of ss_ctx_set_rir_spectra) and the half form
+ * ("Half-precision spectral bank") - for the length-bucketed store.  Bucket b holds bank indices [first, first + n_entries) in an
+ * allocation of its own, in the per-bucket layout of the single-allocation forms:
+ *   hspec   fp32: [n_entries, 2, ceil(cap/kB), ss_spec_floats()] floats, 16-byte aligned (ss_rir_spectra_f32 /
+ *                 ss_bank_scatter_spectra_f32 of that bucket);
+ *           half: the same count of fp16, 8-byte aligned (ss_rir_spectra16_f32 / ss_bank_scatter_spectra16_f32 of that bucket);
+ *   hscale  half: [n_entries, 2, ceil(cap/kB)] floats, zero-initialised like the single-allocation bank's; fp32: NULL.
+ * hscale NULL in every bucket = fp32, non-NULL in every bucket = half; a mixture is SS_EINVAL.  Block i of (entry r, ear ch) of
+ * bucket b is block ((r - first_b) * 2 + ch) * ceil(cap_b/kB) + i of both arrays.  Ordering, count (<= 4), rir_len and the unit
+ * descriptors as for ss_rir_bucket; a bucket has at most 16 blocks.  A half entry of bucket b costs 2 * h_blocks_b * (65 536 + 4)
+ * + 4 bytes, an fp32 one 2 * h_blocks_b * 131 072 + 4 (ss_rir_bucket with both forms: three times the row bytes more).
+ * Kernels: fp32 - the spectral kernels ss_*_buckets_f32 runs when every bucket carries hspec (they never read rows), results bit
+ * for bit; half - k_conv_spec<.., HALF, HBK>, which resolves halves, scales and depth of a term's bucket from the wave-uniform
+ * bank index.  Launches that promise SS_FLAG_FIRST_BUCKET (or have one bucket) are single-allocation launches on bucket 0 and
+ * keep the loop-free kernels.
+ *   ss_fftconv_binaural_spec_buckets_f32   every row length ss_fftconv_binaural_spec_f32 / _spec16_f32 serve (n_valid <= 3 kB);
+ *   ss_audio_obs_spec_buckets_f32          fp32: the shapes ss_audio_obs_buckets_f32 serves from spectra; half: rows of one
+ *                                          partition block, 257 <= out_len <= kB (the fused 44.1 / 48 kHz row kernels do not read
+ *                                          half bucketed banks; neither do the log-mel launches).
+ * SS_EINVAL from the argument checks, before a device is touched: a NULL or misaligned hspec, mixed forms, more than 4 buckets,
+ * `first` not ascending / overlapping / != 0 for bucket 0, an odd cap or cap < 2, a bucket of more than 16 blocks,
+ * SS_FLAG_CROSSFADE, half with out_len > kB in the fused entry.  n_units == 0 returns 0. */
+typedef struct ss_spec_bucket {
+    const void*  hspec;   /* device; see above */
+    const float* hscale;  /* device, or NULL (fp32) */
+    int first;            /* global bank index of entry 0 of the bucket */
+    int n_entries;
+    int cap;              /* samples per (entry, ear) row the spectra cover, even */
+    int reserved;
+} ss_spec_bucket;
+int ss_fftconv_binaural_spec_buckets_f32(const float* spec, const ss_spec_bucket* buckets, int n_buckets, const int* rir_len,
+                                         const int* unit_desc, float* out, int n_units, int n_valid, int out_len, int flags,
+                                         void* stream);
+int ss_audio_obs_spec_buckets_f32(const float* spec, const ss_spec_bucket* buckets, int n_buckets, const int* rir_len,
+                                  const int* unit_desc, float* audiogoal, float* spectrogram, int n_units, int n_valid,
+                                  int out_len, int pad_mode, int flags, void* stream);
 
 /* EXTENSION, one pass for every STFT-derived feature (BASELINE.json configs[4] "GCC-PHAT + log-mel fused sensor"): each
  * (unit, ear, frame) of x [n_units, 2, len] is framed, windowed and transformed ONCE (both ears in one wave), and from that
@@ -408,6 +447,17 @@ int ss_ctx_set_rir_spectra16_rows(ss_ctx* ctx, const void* hspec16, const float*
 /* The bank as length buckets (see ss_rir_bucket; replaces the two calls above for such banks; the descriptor array is copied,
  * the device pointers are borrowed).  Call again whenever a bucket is (re)allocated. */
 int ss_ctx_set_rir_buckets(ss_ctx* ctx, const ss_rir_bucket* buckets, int n_buckets, const int* rir_len);
+/* The bank as spectral length buckets (see ss_spec_bucket), either form.  Replaces ANY earlier binding - rows, spectra of either
+ * form, ss_rir_bucket buckets - and is replaced by ss_ctx_set_rir_bank / ss_ctx_set_rir_buckets; while it is bound,
+ * ss_ctx_set_rir_spectra / _spectra16 / _spectra16_rows with a bank are SS_EINVAL: one form at a time.  Planning depth is the
+ * longest bucket's blocks, as for ss_ctx_set_rir_buckets; steps whose units all sit in bucket 0 keep the loop-free kernels.
+ * SS_EINVAL, nothing changed: the refusals of ss_spec_bucket, rir_len == NULL, half buckets on a context whose rows exceed kB.
+ * A cross-faded step is SS_EINVAL and leaves no keys behind, as on every spectral-only bank; log-mel steps render into the
+ * context's waveform scratch and run the feature kernel over it, as on ss_ctx_set_rir_buckets contexts.  The in-call loaders are
+ * not extended and load nothing on such a context: ss_ctx_load_rir_files returns 1 ("not served", nothing changed);
+ * ss_ctx_observe_requests_load returns 0 with the unresolved requests reported in miss_out / n_miss and no launch made, as
+ * ss_ctx_observe_requests reports them (a step without misses is rendered).  Call again whenever a bucket is (re)allocated. */
+int ss_ctx_set_rir_spec_buckets(ss_ctx* ctx, const ss_spec_bucket* buckets, int n_buckets, const int* rir_len);
 /* One step.  audiogoal [n,2,sr] and spectrogram [n,65,T4,2] are device buffers; either may be NULL (not both).
  * Asynchronous on `stream`; the host arrays of `units` may be reused as soon as the call returns. */
 int ss_ctx_observe(ss_ctx* ctx, const ss_units* units, int n, float* audiogoal, float* spectrogram, void* stream);

@@ -77,6 +77,7 @@ struct Context {
     const float* hscale = nullptr; // != nullptr: hspec holds a HALF bank (fp16 spectra), these are its per-block scales (borrowed)
     int h_blocks = 0;
     std::vector<ss_rir_bucket> buckets;   // length-bucketed bank (ss_ctx_set_rir_buckets); empty: the single bank above
+    std::vector<ss_spec_bucket> spec_buckets;   // ... without time-domain rows (ss_ctx_set_rir_spec_buckets): rir / hspec are NULL then
     // window-spectra cache
     int stride = 1;               // pool slots per entry = nbh_max + nby - 1
     int n_entries = 0;            // host bookkeeping (may run ahead of the device pool, see cache_grow)
@@ -313,6 +314,7 @@ inline int plan_units(Context& c, const ss_units* u, int n, int* desc, PlanResul
     if (any_fade && any_dis) return SS_EINVAL;                    // a launch is either cross-faded or has distractors
     res->flags = any_fade ? SS_FLAG_CROSSFADE : (any_dis ? 0 : SS_FLAG_NO_DISTRACTOR);
     if (c.buckets.size() > 1 && max_rir < c.buckets[1].first) res->flags |= SS_FLAG_FIRST_BUCKET;
+    if (c.spec_buckets.size() > 1 && max_rir < c.spec_buckets[1].first) res->flags |= SS_FLAG_FIRST_BUCKET;
     res->n_new_windows = static_cast<int>(c.new_win.size() / 5);
     return 0;
 }

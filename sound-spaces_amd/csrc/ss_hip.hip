@@ -1414,6 +1414,7 @@ int ss_ctx_set_rir_bank(ss_ctx* h, const float* rir, const int* rir_len, long lo
     c.hscale = nullptr;
     c.h_blocks = 0;
     c.buckets.clear();
+    c.spec_buckets.clear();
     if (nbh_new != nbh_old) {                                  // the set of partition offsets per key changes
         const int nby = c.n_valid > 0 ? ssctx::ceil_div(c.n_valid, c.kb) : 1;
         c.stride = nbh_new + nby - 1;
@@ -1435,7 +1436,7 @@ int ss_ctx_set_rir_spectra(ss_ctx* h, const float* hspec, int h_blocks) {
     if (!h || (hspec && h_blocks < 1)) return SS_EINVAL;
     ssctx::Context& c = h->c;
     if (hspec && h_blocks != (c.rir_cap > 0 ? ssctx::ceil_div(c.rir_cap, c.kb) : 1)) return SS_EINVAL;
-    if (hspec && c.hscale) return SS_EINVAL;                   // a half bank is bound (ss_ctx_set_rir_spectra16): one form at a time
+    if (hspec && (c.hscale || !c.spec_buckets.empty())) return SS_EINVAL;     // a half bank (ss_ctx_set_rir_spectra16) or spectral buckets are bound: one form at a time
     c.hspec = hspec;
     c.hscale = nullptr;
     c.h_blocks = hspec ? h_blocks : 0;
@@ -1454,7 +1455,7 @@ int ss_ctx_set_rir_spectra16(ss_ctx* h, const void* hspec16, const float* hscale
         return 0;
     }
     if (!hscale || h_blocks < 1 || (reinterpret_cast<size_t>(hspec16) & 7)) return SS_EINVAL;
-    if (c.out_len > c.kb || c.rir || !c.buckets.empty() || !c.rir_len || (c.hspec && !c.hscale)) return SS_EINVAL;
+    if (c.out_len > c.kb || c.rir || !c.buckets.empty() || !c.spec_buckets.empty() || !c.rir_len || (c.hspec && !c.hscale)) return SS_EINVAL;
     if (h_blocks != (c.rir_cap > 0 ? ssctx::ceil_div(c.rir_cap, c.kb) : 1)) return SS_EINVAL;
     c.hspec = static_cast<const float*>(hspec16);              // (read as halves wherever hscale is set)
     c.hscale = hscale;
@@ -1474,7 +1475,7 @@ int ss_ctx_set_rir_spectra16_rows(ss_ctx* h, const void* hspec16, const float* h
     }
     if (!hscale || h_blocks < 1 || h_blocks > 16 || (reinterpret_cast<size_t>(hspec16) & 7)) return SS_EINVAL;
     if (c.out_len <= c.kb || c.out_len > 3 * c.kb) return SS_EINVAL;
-    if (c.rir || !c.buckets.empty() || !c.rir_len || (c.hspec && !c.hscale)) return SS_EINVAL;
+    if (c.rir || !c.buckets.empty() || !c.spec_buckets.empty() || !c.rir_len || (c.hspec && !c.hscale)) return SS_EINVAL;
     if (h_blocks != (c.rir_cap > 0 ? ssctx::ceil_div(c.rir_cap, c.kb) : 1)) return SS_EINVAL;
     c.hspec = static_cast<const float*>(hspec16);              // (read as halves wherever hscale is set)
     c.hscale = hscale;
@@ -1645,7 +1646,9 @@ static int ctx_observe_on(ss_ctx* h, const ss_units* units, int n, float* audiog
     if (rc) return rc;                                         // (refused before the cache or the ring was touched)
     // a spectral-only bank (spectra bound, no rows: ss_ctx_set_rir_bank(ctx, NULL, ...) + ss_ctx_set_rir_spectra) cannot serve a
     // step whose route reads the time-domain rows (a cross-fade): refused before any upload or launch, the plan's keys given back
-    if (!c.rir && c.buckets.empty() && (!c.hspec || (res.flags & SS_FLAG_CROSSFADE))) {
+    // (spectral length buckets, ss_ctx_set_rir_spec_buckets, are such a bank)
+    const bool spec_bk = !c.spec_buckets.empty();
+    if (!c.rir && c.buckets.empty() && ((!c.hspec && !spec_bk) || (res.flags & SS_FLAG_CROSSFADE))) {
         ssctx::cache_rollback(c);
         return SS_EINVAL;
     }
@@ -1695,20 +1698,20 @@ static int ctx_observe_on(ss_ctx* h, const ss_units* units, int n, float* audiog
     // so (ss_ctx_set_spectral_policy): there the forward FFT hides under the row's load and the spectral rows are twice the bytes
     // (... unless its units carry a second term - a distractor, simulator.py:649-664: two forward transforms per row do not hide
     // under one row's load; savi's 256-env step: 87.9 against 96.3 us)
-    const bool spectral = c.hspec && !(res.flags & SS_FLAG_CROSSFADE) &&
+    const bool spectral = (c.hspec || spec_bk) && !(res.flags & SS_FLAG_CROSSFADE) &&
                           !(c.spectral_max_units > 0 && c.rir && c.out_len <= ssk::kB && n > c.spectral_max_units &&
                             (res.flags & SS_FLAG_NO_DISTRACTOR));
-    const int nbh_bank = spectral ? c.h_blocks : (c.rir_cap > 0 ? ssctx::ceil_div(c.rir_cap, c.kb) : 1);
+    const int nbh_bank = spectral && !spec_bk ? c.h_blocks : (c.rir_cap > 0 ? ssctx::ceil_div(c.rir_cap, c.kb) : 1);
     // log-mel without a waveform buffer: one fused launch for one-block rows of a single-allocation bank in a step without a
     // cross-fade, inside the units range the measured policy gives (ss_ctx_set_logmel_policy); everything else renders into the
     // context's own waveform scratch and runs the feature kernel over it
-    const bool mel_fused = mel && c.buckets.empty() && obs_logmel_shape_ok(c.out_len, res.flags) &&
+    const bool mel_fused = mel && c.buckets.empty() && !spec_bk && obs_logmel_shape_ok(c.out_len, res.flags) &&
                            n >= c.mel_fused_min_units && n <= c.mel_fused_max_units;
     // rows of 2 or 3 blocks (44.1 / 48 kHz): the log-mel form of k_obs_rows / k_obs_blocks under the same conditions, inside the
     // range of ss_ctx_set_logmel_rows_policy (default: never - the scratch route is bit-equal to observe-then-features, the
     // fused arithmetic only to rounding)
     // (a half bank: only the one bound by ss_ctx_set_rir_spectra16_rows has rows this long)
-    const bool mel_rows = mel && !mel_fused && (!c.hscale || c.out_len > c.kb) && c.buckets.empty() && (spectral || (c.rir && c.rir_cap > 0)) &&
+    const bool mel_rows = mel && !mel_fused && (!c.hscale || c.out_len > c.kb) && c.buckets.empty() && !spec_bk && (spectral || (c.rir && c.rir_cap > 0)) &&
                           obs_logmel_rows_shape_ok(c.out_len, c.n_valid, nbh_bank, res.flags) &&
                           n >= c.mel_rows_min_units && n <= c.mel_rows_max_units;
     // SoundSpaces 2.0 steps (cross-faded one-block rows; block 0 of a 44.1 / 48 kHz row, cross-faded or not): their own fused
@@ -1765,6 +1768,12 @@ static int ctx_observe_on(ss_ctx* h, const ss_units* units, int n, float* audiog
                       : ss_audio_obs_logmel_f32(c.pool, c.rir, c.rir_len, dd, nullptr, spectrogram, mel->logmel, mel->mel_start,
                                                 mel->mel_w, mel->n_mels, mel->max_len, mel->mel_eps, n, c.rir_us, c.rir_cs, c.rir_es,
                                                 c.rir_cap, c.n_valid, c.out_len, c.pad_mode, res.flags, stream);
+    } else if (spec_bk) {
+        const int nb = static_cast<int>(c.spec_buckets.size());
+        rc = spectrogram ? ss_audio_obs_spec_buckets_f32(c.pool, c.spec_buckets.data(), nb, c.rir_len, dd, audiogoal, spectrogram, n,
+                                                         c.n_valid, c.out_len, c.pad_mode, res.flags, stream)
+                         : ss_fftconv_binaural_spec_buckets_f32(c.pool, c.spec_buckets.data(), nb, c.rir_len, dd, audiogoal, n,
+                                                                c.n_valid, c.out_len, res.flags, stream);
     } else if (!c.buckets.empty()) {
         const int nb = static_cast<int>(c.buckets.size());
         rc = spectrogram ? ss_audio_obs_buckets_f32(c.pool, c.buckets.data(), nb, c.rir_len, dd, audiogoal, spectrogram, n,
@@ -1942,7 +1951,7 @@ static int ctx_observe_any(ss_ctx* h, const ss_units* units, int n, float* audio
         return SS_EINVAL;
     if (n == 0) return 0;
     ssctx::Context& c = h->c;
-    if ((!c.rir && !c.hspec && c.buckets.empty()) || !c.rir_len || !c.src_dev) return SS_EINVAL;
+    if ((!c.rir && !c.hspec && c.buckets.empty() && c.spec_buckets.empty()) || !c.rir_len || !c.src_dev) return SS_EINVAL;
     const bool sg_late = features_take_spectrogram(f, audiogoal, spectrogram);
     if (c.n_lanes <= 1) {
         if (mel_only) return ctx_observe_on(h, units, n, nullptr, spectrogram, stream, -1, f);
@@ -2493,7 +2502,164 @@ int ss_ctx_set_rir_buckets(ss_ctx* h, const ss_rir_bucket* buckets, int n_bucket
     ssctx::Context& c = h->c;
     const int nbh_old = c.rir_cap > 0 ? ssctx::ceil_div(c.rir_cap, c.kb) : 1;
     c.buckets.assign(buckets, buckets + n_buckets);
+    c.spec_buckets.clear();
     c.rir = buckets[0].rir; c.rir_len = rir_len; c.rir_us = 2LL * buckets[0].cap; c.rir_cs = buckets[0].cap; c.rir_es = 1;
+    c.rir_cap = hb_max * c.kb;                                 // planning depth: the longest bucket's blocks
+    c.hspec = nullptr; c.hscale = nullptr; c.h_blocks = 0;
+    if (hb_max != nbh_old) {                                   // the set of partition offsets per key changes
+        const int nby = c.n_valid > 0 ? ssctx::ceil_div(c.n_valid, c.kb) : 1;
+        c.stride = hb_max + nby - 1;
+        ssctx::cache_reset(c);
+        if (c.pool) {
+            hipError_t e = hipDeviceSynchronize();
+            if (e != hipSuccess) return hip_err(e);
+            (void)hipFree(c.pool);
+            c.pool = nullptr;
+            c.pool_entries = 0;
+        }
+    }
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- length-bucketed bank without time-domain rows: fp32 spectra ("only") or fp16 spectra + scales ("half") --------------
+// (include/ss_hip.h "Spectral length buckets").  Everything here is checked on the host before a device is touched.
+// *half = the form (every bucket carries scales / none does), *hb_max = the longest bucket's blocks.
+static int spec_buckets_check(const ss_spec_bucket* bk, int n_buckets, bool* half, int* hb_max) {
+    if (!bk || n_buckets < 1 || n_buckets > ssk::kMaxBuckets) return SS_EINVAL;
+    const bool h = bk[0].hscale != nullptr;
+    int hb = 1;
+    for (int b = 0; b < n_buckets; ++b) {
+        if (!bk[b].hspec || (bk[b].hscale != nullptr) != h) return SS_EINVAL;                   // one form in every bucket
+        if (reinterpret_cast<size_t>(bk[b].hspec) & (h ? 7 : 15)) return SS_EINVAL;             // h16x4 / f32x4 loads
+        if (bk[b].cap < 2 || (bk[b].cap & 1) || bk[b].n_entries < 0 || bk[b].first < 0) return SS_EINVAL;
+        if (b && bk[b].first < bk[b - 1].first + bk[b - 1].n_entries) return SS_EINVAL;         // ascending, disjoint ranges
+        const int blocks = (bk[b].cap + ssk::kB - 1) / ssk::kB;
+        if (blocks > 16) return SS_EINVAL;
+        hb = std::max(hb, blocks);
+    }
+    if (bk[0].first != 0) return SS_EINVAL;
+    *half = h;
+    *hb_max = hb;
+    return 0;
+}
+
+// the arguments fill_conv refuses, before it reaches for the device's tables
+static bool spec_buckets_launch_args_ok(const float* spec, const int* rir_len, const int* unit_desc, int n_units, int n_valid, int out_len,
+                                        int flags) {
+    return spec && rir_len && unit_desc && n_units > 0 && !(flags & SS_FLAG_CROSSFADE) && out_len >= 1 && n_valid >= 0 &&
+           n_valid <= out_len && n_valid <= 3 * ssk::kB;
+}
+
+// bucket 0 into the single-bank fields, the others into p.bk[] (no rows anywhere); the half form's scales into hs
+static void fill_spec_buckets(ssk::ConvParams& p, ssk::SpecScale<true, true>& hs, const ss_spec_bucket* bk, int n_buckets) {
+    p.hspec = static_cast<const ssk::f32x4*>(bk[0].hspec);
+    p.h_blocks = (bk[0].cap + ssk::kB - 1) / ssk::kB;
+    p.n_buckets = n_buckets;
+    hs.hscale = bk[0].hscale;
+    for (auto& s : hs.bk) s = nullptr;
+    for (int b = 1; b < n_buckets; ++b) {
+        p.bk[b - 1] = ssk::BankBucket{nullptr, static_cast<const ssk::f32x4*>(bk[b].hspec), bk[b].first, bk[b].cap,
+                                      (bk[b].cap + ssk::kB - 1) / ssk::kB, 0};
+        hs.bk[b - 1] = bk[b].hscale;
+    }
+}
+
+// Half buckets.  Launches that only touch bucket 0 (one bucket, or SS_FLAG_FIRST_BUCKET) are single-allocation launches on
+// bucket 0's arrays: the existing HALF kernels, the loop-free ones included.  Everything else: k_conv_spec<.., HALF, HBK>.
+template <bool FUSE>
+static int launch_conv_spec16_buckets(ssk::ConvParams p, const ssk::SpecScale<true, true>& hs, int n_units, int nb_y, int flags,
+                                      hipStream_t st, int n_cus) {
+    if (p.n_buckets == 1 || (flags & SS_FLAG_FIRST_BUCKET)) return launch_conv_spec16<FUSE>(p, hs.hscale, n_units, nb_y, flags, st, n_cus);
+    if (nb_y < 1 || nb_y > 3 || (FUSE && nb_y != 1) || (flags & SS_FLAG_CROSSFADE)) return SS_EINVAL;
+    p.nb_y = nb_y;
+    p.parts_log2 = FUSE && n_cus > 0 ? parts_log2_for(2 * n_units, n_cus) : 0;
+    const dim3 grid((2 * n_units * nb_y) << p.parts_log2), block(ssk::kT);
+    hipLaunchKernelGGL((ssk::k_conv_spec<FUSE, false, false, false, true, true>), grid, block, 0, st, p, ssk::UnitTab<false>(), hs);
+    return hip_err(hipGetLastError());
+}
+
+extern "C" {
+
+int ss_fftconv_binaural_spec_buckets_f32(const float* spec, const ss_spec_bucket* buckets, int n_buckets, const int* rir_len,
+                                         const int* unit_desc, float* out, int n_units, int n_valid, int out_len, int flags,
+                                         void* stream) {
+    if (n_units == 0) return 0;
+    bool half = false;
+    int hb_max = 1;
+    if (!out || spec_buckets_check(buckets, n_buckets, &half, &hb_max) ||
+        !spec_buckets_launch_args_ok(spec, rir_len, unit_desc, n_units, n_valid, out_len, flags))
+        return SS_EINVAL;
+    ssk::ConvParams p;
+    int n_cus = 1;
+    int rc = fill_conv(p, &n_cus, spec, nullptr, rir_len, unit_desc, 0, 0, 1, 0, n_valid, out_len, false);
+    if (rc) return rc;
+    ssk::SpecScale<true, true> hs;
+    fill_spec_buckets(p, hs, buckets, n_buckets);
+    p.out = out;
+    const int nb_y = n_valid == 0 ? 1 : (n_valid + ssk::kB - 1) / ssk::kB;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    return half ? launch_conv_spec16_buckets<false>(p, hs, n_units, nb_y, flags, st, n_cus)
+                : launch_conv_spec<false>(p, n_units, nb_y, flags, st, n_cus);
+}
+
+int ss_audio_obs_spec_buckets_f32(const float* spec, const ss_spec_bucket* buckets, int n_buckets, const int* rir_len,
+                                  const int* unit_desc, float* audiogoal, float* spectrogram, int n_units, int n_valid, int out_len,
+                                  int pad_mode, int flags, void* stream) {
+    if (n_units == 0) return 0;
+    bool half = false;
+    int hb_max = 1;
+    if (!spectrogram || spec_buckets_check(buckets, n_buckets, &half, &hb_max) ||
+        !spec_buckets_launch_args_ok(spec, rir_len, unit_desc, n_units, n_valid, out_len, flags))
+        return SS_EINVAL;
+    if (pad_mode != SS_PAD_REFLECT && pad_mode != SS_PAD_CONSTANT) return SS_EINVAL;
+    if (out_len < ssk::kNfft / 2 + 1) return SS_EINVAL;
+    // half: rows of one partition block (the fused row kernels do not read half bucketed banks)
+    if (half && (out_len > ssk::kB || t4_of(out_len) > 26)) return SS_EINVAL;
+    ssk::ConvParams p;
+    int n_cus = 1;
+    int rc = fill_conv(p, &n_cus, spec, nullptr, rir_len, unit_desc, 0, 0, 1, 0, n_valid, out_len, false);
+    if (rc) return rc;
+    ssk::SpecScale<true, true> hs;
+    fill_spec_buckets(p, hs, buckets, n_buckets);
+    p.pad_mode = pad_mode;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (half) {
+        p.out = audiogoal;
+        p.sgram = spectrogram;
+        return launch_conv_spec16_buckets<true>(p, hs, n_units, 1, flags, st, n_cus);
+    }
+    // fp32: the routes ss_audio_obs_buckets_f32 takes when every bucket carries its spectra
+    if (out_len <= ssk::kB && p.t4 <= 26) {
+        p.out = audiogoal;
+        p.sgram = spectrogram;
+        return launch_conv_spec<true>(p, n_units, 1, flags, st, n_cus);
+    }
+    if (obs_rows_ok(out_len, n_valid, hb_max, flags, true, audiogoal != nullptr)) {
+        p.out = audiogoal;
+        p.sgram = spectrogram;
+        return launch_obs_rows<true>(p, n_units, flags, n_cus, st);
+    }
+    if (!audiogoal) return SS_EINVAL;
+    rc = ss_fftconv_binaural_spec_buckets_f32(spec, buckets, n_buckets, rir_len, unit_desc, audiogoal, n_units, n_valid, out_len,
+                                              flags, stream);
+    if (rc) return rc;
+    return spectrogram_of_rows(audiogoal, spectrogram, n_units, out_len, n_valid, pad_mode, stream);
+}
+
+// The context's bank as spectral length buckets: replaces any earlier binding (rows, spectra of either form, ss_rir_bucket
+// buckets); the descriptor array is copied, the device pointers are borrowed.  Planning depth as ss_ctx_set_rir_buckets.
+int ss_ctx_set_rir_spec_buckets(ss_ctx* h, const ss_spec_bucket* buckets, int n_buckets, const int* rir_len) {
+    bool half = false;
+    int hb_max = 1;
+    if (!h || !rir_len || spec_buckets_check(buckets, n_buckets, &half, &hb_max)) return SS_EINVAL;
+    ssctx::Context& c = h->c;
+    if (half && c.out_len > c.kb) return SS_EINVAL;            // (ss_audio_obs_spec_buckets_f32: half serves one-block rows)
+    const int nbh_old = c.rir_cap > 0 ? ssctx::ceil_div(c.rir_cap, c.kb) : 1;
+    c.spec_buckets.assign(buckets, buckets + n_buckets);
+    c.buckets.clear();
+    c.rir = nullptr; c.rir_len = rir_len; c.rir_us = 0; c.rir_cs = 0; c.rir_es = 1;
     c.rir_cap = hb_max * c.kb;                                 // planning depth: the longest bucket's blocks
     c.hspec = nullptr; c.hscale = nullptr; c.h_blocks = 0;
     if (hb_max != nbh_old) {                                   // the set of partition offsets per key changes

@@ -1666,10 +1666,36 @@ __device__ __forceinline__ void spec_block_product(const f32x4* spec, int t, con
 // at its head (no round trip of its own in front of them; see spec_block_product16).  The scales ride in a kernel argument of
 // their own (as UnitTab does): ConvParams, and with it every fp32 instantiation, stays as it is.
 typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
-template <bool HALF>
+// HBK (a half bank in length buckets, ss_spec_bucket): bucket b >= 1 keeps its halves behind ConvParams::bk[b - 1].hspec (read as
+// h16x4) and its scales behind bk[b - 1] HERE - three more pointers in this argument, none in ConvParams.
+template <bool HALF, bool HBK = false>
 struct SpecScale { };
 template <>
-struct SpecScale<true> { const float* hscale; };      // [entries][2][h_blocks]
+struct SpecScale<true, false> { const float* hscale; };      // [entries][2][h_blocks]
+template <>
+struct SpecScale<true, true> {
+    const float* hscale;                                     // bucket 0: [n_0][2][h_blocks_0]
+    const float* bk[kMaxBuckets - 1];                        // bucket b + 1: [n][2][h_blocks of that bucket]
+};
+// Half row of bank entry ridx, ear ch in a bucketed half bank: the fp16 block spectra and the scales of its FIRST block, and the
+// blocks its bucket stores per row - block i of the row is hp + i * (kSpecComplex / 2) and sp + i.  Resolved as bank_spec
+// resolves the fp32 row: scalar compares on the wave-uniform index, no memory access.
+struct BankSpec16 { const h16x4* hp; const float* sp; int h_blocks; };
+__device__ __forceinline__ BankSpec16 bank_spec16(const ConvParams& p, const SpecScale<true, true>& hs, int ridx, int ch) {
+    const h16x4* base = reinterpret_cast<const h16x4*>(p.hspec);
+    const float* sbase = hs.hscale;
+    int first = 0, hb = p.h_blocks;
+#pragma unroll
+    for (int b = 0; b < kMaxBuckets - 1; ++b)
+        if (b + 1 < p.n_buckets && ridx >= p.bk[b].first) {
+            base = reinterpret_cast<const h16x4*>(p.bk[b].hspec);
+            sbase = hs.bk[b];
+            first = p.bk[b].first;
+            hb = p.bk[b].h_blocks;
+        }
+    const size_t blk = ((size_t)(ridx - first) * 2 + ch) * (size_t)hb;
+    return BankSpec16{base + blk * (kSpecComplex / 2), sbase + blk, hb};
+}
 
 __device__ __forceinline__ void spec_block_product16(const f32x4* spec, int t, const h16x4* hp, const float* scale_p, int slot,
                                                      bool accumulate, c32 (&acc)[2][8]) {
@@ -1700,10 +1726,11 @@ __device__ __forceinline__ void spec_block_product16(const f32x4* spec, int t, c
         }
 }
 
-template <bool FUSE, bool SIMPLE, bool TAB = false, bool MEL = false, bool HALF = false>
+template <bool FUSE, bool SIMPLE, bool TAB = false, bool MEL = false, bool HALF = false, bool HBK = false>
 __global__ __launch_bounds__(1024) void k_conv_spec(ConvParams p, UnitTab<TAB, MEL> ut = UnitTab<TAB, MEL>(),
-                                                    SpecScale<HALF> hs = SpecScale<HALF>()) {
+                                                    SpecScale<HALF, HBK> hs = SpecScale<HALF, HBK>()) {
     static_assert(!TAB || SIMPLE, "the unit table serves the loop-free kernel");
+    static_assert(!HBK || (HALF && !SIMPLE && !MEL), "bucketed half bank: the loop kernel (bucket-0 launches take the loop-free HALF ones)");
     static_assert(!MEL || (FUSE && !TAB), "log-mel: the plain fused kernels (launched with parts_log2 = 0)");
     __shared__ c32 lds[FUSE && 16 * kWaveScratch > kLdsComplex ? 16 * kWaveScratch : kLdsComplex];
     const int t = threadIdx.x;
@@ -1779,20 +1806,26 @@ __global__ __launch_bounds__(1024) void k_conv_spec(ConvParams p, UnitTab<TAB, M
             const int ridx = dw.x;
             if (ridx < 0) continue;
             const int spec0 = dw.y, m_min = dw.z, m_cnt = dw.w;
-            const BankSpec bs = bank_spec(p, ridx, ch);
-            int nbh = bs.h_blocks;
+            // a half bank in length buckets (HBK): the entry's bucket gives the fp16 base, the scale base and the depth
+            BankSpec bs{nullptr, 0};
+            BankSpec16 b16{nullptr, nullptr, 0};
+            if constexpr (HBK) b16 = bank_spec16(p, hs, ridx, ch);
+            else bs = bank_spec(p, ridx, ch);
+            int nbh = HBK ? b16.h_blocks : bs.h_blocks;
             if (nbh > 1) nbh = min(nbh, (uniform_load(p.rir_len + ridx) + kB - 1) / kB);
             for (int i = 0; i < nbh; ++i) {
                 const int m = j - i;
                 if (m < m_min || m >= m_min + m_cnt) continue;
                 int tl = t;
                 SSK_OPAQUE1(tl);
-                const f32x4* hp = bs.hp + (size_t)i * (kSpecComplex / 2) + tl;
-                if constexpr (HALF) {                   // one allocation (the launcher checks): same f32x4 index, 8-byte elements
+                if constexpr (HBK) {
+                    spec_block_product16(spec_base, tl, b16.hp + (size_t)i * (kSpecComplex / 2) + tl, b16.sp + i, spec0 + (m - m_min),
+                                         any, acc);
+                } else if constexpr (HALF) {            // one allocation (the launcher checks): same f32x4 index, 8-byte elements
                     const size_t blk = ((size_t)ridx * 2 + ch) * (size_t)p.h_blocks + i;
                     spec_block_product16(spec_base, tl, reinterpret_cast<const h16x4*>(hspec_base) + blk * (kSpecComplex / 2) + tl,
                                          hs.hscale + blk, spec0 + (m - m_min), any, acc);
-                } else spec_block_product(spec_base, tl, hp, spec0 + (m - m_min), any, acc);
+                } else spec_block_product(spec_base, tl, bs.hp + (size_t)i * (kSpecComplex / 2) + tl, spec0 + (m - m_min), any, acc);
                 any = true;
             }
         }

@@ -22,7 +22,8 @@ EXPORTS = ("ss_block_len", "ss_spec_floats", "ss_version", "ss_init", "ss_source
            "ss_audio_obs_logmel_ss2_f32", "ss_ctx_set_logmel_ss2_policy",
            "ss_rir_spectra16_f32", "ss_bank_scatter_spectra16_f32", "ss_fftconv_binaural_spec16_f32", "ss_audio_obs_spec16_f32",
            "ss_audio_obs_logmel_spec16_f32", "ss_ctx_set_rir_spectra16",
-           "ss_audio_obs_rows_spec16_f32", "ss_audio_obs_logmel_rows_spec16_f32", "ss_ctx_set_rir_spectra16_rows")
+           "ss_audio_obs_rows_spec16_f32", "ss_audio_obs_logmel_rows_spec16_f32", "ss_ctx_set_rir_spectra16_rows",
+           "ss_fftconv_binaural_spec_buckets_f32", "ss_audio_obs_spec_buckets_f32", "ss_ctx_set_rir_spec_buckets")
 # entries that return a size_t, not a status (EXPORTS: every `int ss_*` of include/ss_hip.h)
 EXPORTS_SIZE = ("ss_ctx_wave_scratch_bytes",)
 
@@ -30,6 +31,12 @@ EXPORTS_SIZE = ("ss_ctx_wave_scratch_bytes",)
 class SsRirBucket(ctypes.Structure):
     """struct ss_rir_bucket of include/ss_hip.h."""
     _fields_ = [("rir", ctypes.c_void_p), ("hspec", ctypes.c_void_p), ("first", ctypes.c_int), ("n_entries", ctypes.c_int),
+                ("cap", ctypes.c_int), ("reserved", ctypes.c_int)]
+
+
+class SsSpecBucket(ctypes.Structure):
+    """struct ss_spec_bucket of include/ss_hip.h."""
+    _fields_ = [("hspec", ctypes.c_void_p), ("hscale", ctypes.c_void_p), ("first", ctypes.c_int), ("n_entries", ctypes.c_int),
                 ("cap", ctypes.c_int), ("reserved", ctypes.c_int)]
 
 
@@ -162,6 +169,10 @@ def load() -> ctypes.CDLL:
     lib.ss_audio_obs_rows_spec16_f32.argtypes = lib.ss_audio_obs_spec16_f32.argtypes
     lib.ss_audio_obs_logmel_rows_spec16_f32.argtypes = lib.ss_audio_obs_logmel_spec16_f32.argtypes
     lib.ss_ctx_set_rir_spectra16_rows.argtypes = [vp, vp, vp, c_int]
+    # spectral length buckets (ss_spec_bucket): the ss_*_buckets_f32 arguments
+    lib.ss_fftconv_binaural_spec_buckets_f32.argtypes = lib.ss_fftconv_binaural_buckets_f32.argtypes
+    lib.ss_audio_obs_spec_buckets_f32.argtypes = lib.ss_audio_obs_buckets_f32.argtypes
+    lib.ss_ctx_set_rir_spec_buckets.argtypes = [vp, vp, c_int, vp]
     for name in EXPORTS:
         getattr(lib, name).restype = c_int
     for name in EXPORTS_SIZE:

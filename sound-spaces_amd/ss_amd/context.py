@@ -170,6 +170,17 @@ class AudioContext:
         self.rir_cap = int(bank.cap)
         self._spectra = None
 
+    def set_rir_spec_buckets(self, bank) -> None:
+        """A SPECTRAL-ONLY length-bucketed bank (``BucketedRirBank`` whose buckets keep block spectra - float32, or float16 with
+        scales - and no rows; include/ss_hip.h ``ss_ctx_set_rir_spec_buckets``).  Replaces any earlier binding.  The library
+        refuses (SS_EINVAL) half buckets on a context whose rows exceed one partition block, and cross-faded steps."""
+        arr = bank.spec_c_array()
+        _lib.check(self.lib.ss_ctx_set_rir_spec_buckets(self._h, ctypes.cast(arr, ctypes.c_void_p), len(bank.banks),
+                                                        bank.lengths.data_ptr()), "ss_ctx_set_rir_spec_buckets")
+        self._bank = (bank, arr)
+        self.rir_cap = int(bank.cap)
+        self._spectra = None
+
     def set_rir_spectra(self, hspec) -> None:
         """Spectral form of the bank set by set_rir_bank() (ops.rir_spectra / RirBank.build_spectra): steps without a
         cross-fade then run k_conv_spec.  None switches back to the time-domain kernels."""

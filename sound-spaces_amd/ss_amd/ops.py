@@ -504,6 +504,63 @@ def audio_obs_buckets_into(spec, buckets, n_buckets: int, rir_len, unit_desc, au
                                                         _PAD[pad_mode], flags, _stream(spec)), "ss_audio_obs_buckets_f32")
 
 
+# ---- spectral length buckets: a bucketed bank without time-domain rows (include/ss_hip.h "Spectral length buckets") --------
+def spec_bucket_array(spectra, scales, firsts, caps):
+    """ctypes array of ss_spec_bucket: per bucket its block spectra [n,2,hb,SPEC_FLOATS] (float32, or float16 of a HALF bank),
+    its scales [n,2,hb] (half) or None (fp32), the global index of its entry 0 and its row capacity in samples.  One form in
+    every bucket.  Keep the array alive with the tensors it points to."""
+    scales = [None] * len(spectra) if scales is None else list(scales)
+    assert len(spectra) == len(scales) == len(firsts) == len(caps)
+    half = bool(scales) and scales[0] is not None
+    arr = (_lib.SsSpecBucket * len(spectra))()
+    for b, (hs, sc, first, cap) in enumerate(zip(spectra, scales, firsts, caps)):
+        if (sc is not None) != half:
+            raise ValueError("spec_bucket_array: every bucket carries scales (half) or none does (fp32)")
+        _chk_spectra(hs, sc)
+        assert hs.shape[1] == 2 and hs.shape[2] == ceil_div(int(cap), KB) and hs.shape[3] == SPEC_FLOATS
+        arr[b].hspec = hs.data_ptr()
+        arr[b].hscale = sc.data_ptr() if half else None
+        arr[b].first, arr[b].n_entries, arr[b].cap, arr[b].reserved = int(first), int(hs.shape[0]), int(cap), 0
+    return arr
+
+
+def fftconv_binaural_spec_buckets_into(spec, buckets, n_buckets: int, rir_len, unit_desc, out, n_valid: int, flags: int = 0) -> None:
+    """``fftconv_binaural_spec_into`` on spectral length buckets: ``buckets`` = ``spec_bucket_array(...)``
+    (ss_fftconv_binaural_spec_buckets_f32)."""
+    _chk(spec, torch.float32, "spec"); _chk(rir_len, torch.int32, "rir_len"); _chk(unit_desc, torch.int32, "unit_desc")
+    _chk(out, torch.float32, "out")
+    N, two, out_len = out.shape
+    assert two == 2 and unit_desc.shape == (N, 8)
+    with torch.cuda.device(out.device):
+        _lib.check(_lib.load().ss_fftconv_binaural_spec_buckets_f32(spec.data_ptr(), ctypes_ref(buckets), n_buckets,
+                                                                    rir_len.data_ptr(), unit_desc.data_ptr(), out.data_ptr(), N,
+                                                                    n_valid, out_len, flags, _stream(spec)),
+                   "ss_fftconv_binaural_spec_buckets_f32")
+
+
+def audio_obs_spec_buckets_into(spec, buckets, n_buckets: int, rir_len, unit_desc, audiogoal, spectrogram_out, n_valid: int,
+                                out_len: int, pad_mode="reflect", flags: int = 0) -> None:
+    """``audio_obs_spec_into`` on spectral length buckets (ss_audio_obs_spec_buckets_f32; spectrogram_out None: the waveform
+    alone, ss_fftconv_binaural_spec_buckets_f32).  A half bank serves rows of one partition block here."""
+    if spectrogram_out is None:
+        fftconv_binaural_spec_buckets_into(spec, buckets, n_buckets, rir_len, unit_desc, audiogoal, n_valid, flags)
+        return
+    _chk(spec, torch.float32, "spec"); _chk(rir_len, torch.int32, "rir_len"); _chk(unit_desc, torch.int32, "unit_desc")
+    _chk(spectrogram_out, torch.float32, "spectrogram_out")
+    N = unit_desc.shape[0]
+    assert tuple(spectrogram_out.shape) == (N,) + spectrogram_shape(out_len)
+    ag_ptr = None
+    if audiogoal is not None:
+        _chk(audiogoal, torch.float32, "audiogoal")
+        assert tuple(audiogoal.shape) == (N, 2, out_len)
+        ag_ptr = audiogoal.data_ptr()
+    with torch.cuda.device(spec.device):
+        _lib.check(_lib.load().ss_audio_obs_spec_buckets_f32(spec.data_ptr(), ctypes_ref(buckets), n_buckets, rir_len.data_ptr(),
+                                                             unit_desc.data_ptr(), ag_ptr, spectrogram_out.data_ptr(), N, n_valid,
+                                                             out_len, _PAD[pad_mode], flags, _stream(spec)),
+                   "ss_audio_obs_spec_buckets_f32")
+
+
 def ctypes_ref(arr):
     import ctypes
     return ctypes.cast(arr, ctypes.c_void_p)

@@ -128,10 +128,17 @@ class BucketedRirBank:
     own (rows of ``cap_b`` samples) holding the global bank indices ``[first_b, first_b + len(bucket b))``; ``lengths`` is
     ONE int32 tensor over all indices (the buckets' own ``lengths`` are views of it).  A 3-s RIR lands in a long bucket
     without lengthening - or reallocating - the rows of the short ones, and launches whose units all sit in bucket 0 keep
-    the loop-free kernel."""
+    the loop-free kernel.
+
+    Buckets that are all spectral-only banks (``RirStore(spectral="only" | "half")``: no rows) make a SPECTRAL-ONLY bucketed
+    bank (``spectral_only``; include/ss_hip.h ``ss_spec_bucket``): ``spec_c_array()`` describes it, a half one with every
+    bucket's ``scales``."""
 
     def __init__(self, banks: Sequence[RirBank], lengths: torch.Tensor, firsts: Optional[Sequence[int]] = None):
         assert 1 <= len(banks) <= 4
+        only = [b.spectral_only for b in banks]
+        assert all(only) or not any(only), "every bucket keeps rows or none does"
+        assert len({b.scales is not None for b in banks}) == 1 or not all(only), "one spectral form in every bucket"
         self.banks = list(banks)
         self.first = list(firsts) if firsts is not None else list(np.cumsum([0] + [len(b) for b in banks[:-1]]))
         assert self.first[0] == 0 and all(self.first[b + 1] >= self.first[b] + len(banks[b]) for b in range(len(banks) - 1))
@@ -154,7 +161,26 @@ class BucketedRirBank:
     def refresh(self) -> None:
         self._carr = None
 
+    @property
+    def spectral_only(self) -> bool:            # no bucket keeps time-domain rows
+        return all(b.spectral_only for b in self.banks)
+
+    @property
+    def half(self) -> bool:                     # a half bank: every bucket's spectra are float16 with scales of their own
+        return all(b.scales is not None for b in self.banks)
+
+    def spec_c_array(self):
+        """ss_spec_bucket array of a spectral-only bucketed bank (cached on the buckets' tensors, like c_array)."""
+        assert self.spectral_only and self.spectra
+        now = [b.spectra.data_ptr() for b in self.banks] + [b.scales.data_ptr() for b in self.banks if b.scales is not None]
+        if self._carr is None or self._carr[1] != "spec" or self._carr[2] != now:
+            arr = ops.spec_bucket_array([b.spectra for b in self.banks], [b.scales for b in self.banks], self.first,
+                                        [b.cap for b in self.banks])
+            self._carr = (arr, "spec", now)
+        return self._carr[0]
+
     def c_array(self, spectral: bool):
+        assert not self.spectral_only, "a spectral-only bucketed bank is described by spec_c_array()"
         if self._carr is None or self._carr[1] != spectral or self._carr[2] != [b.data.data_ptr() for b in self.banks]:
             self._carr = (ops.bucket_array(self.banks, self.first, spectral), spectral, [b.data.data_ptr() for b in self.banks])
         return self._carr[0]
@@ -407,7 +433,10 @@ class BatchedAudioRenderer:
         sg = spectrogram_out
         if sg is None:
             sg = torch.empty((N,) + self.spectrogram_shape, dtype=torch.float32, device=self.device)
-        if isinstance(self.rirs, BucketedRirBank):
+        if isinstance(self.rirs, BucketedRirBank) and self.rirs.spectral_only:
+            ops.audio_obs_spec_buckets_into(self._spec, self.rirs.spec_c_array(), len(self.rirs.banks), self.rirs.lengths,
+                                            plan.desc, ag, sg, self.n_valid, self.out_len, self.pad_mode, flags=plan.flags)
+        elif isinstance(self.rirs, BucketedRirBank):
             ops.audio_obs_buckets_into(self._spec, self.rirs.c_array(spectral), len(self.rirs.banks), self.rirs.lengths,
                                        plan.desc, ag, sg, self.n_valid, self.out_len, self.pad_mode, flags=plan.flags)
         elif spectral:
@@ -433,6 +462,11 @@ class BatchedAudioRenderer:
         if isinstance(self.rirs, BucketedRirBank):
             spectral = bool(self.rirs.spectra) and not (plan.flags & ops.FLAG_CROSSFADE) and \
                 self._spectral_for(len(plan), not (plan.flags & ops.FLAG_NO_DISTRACTOR))
+            self._check_rows(spectral)
+            if self.rirs.spectral_only:
+                ops.fftconv_binaural_spec_buckets_into(self._spec, self.rirs.spec_c_array(), len(self.rirs.banks), self.rirs.lengths,
+                                                       plan.desc, out, self.n_valid, flags=plan.flags)
+                return out
             ops.audio_obs_buckets_into(self._spec, self.rirs.c_array(spectral), len(self.rirs.banks), self.rirs.lengths,
                                        plan.desc, out, None, self.n_valid, self.out_len, self.pad_mode, flags=plan.flags)
         elif self.rirs.spectra is not None and not (plan.flags & ops.FLAG_CROSSFADE) and \
@@ -1315,10 +1349,25 @@ class BucketedRirStore:
     ``caps`` ascending (samples; bucket 0 <= one partition block keeps the loop-free kernel), ``slots[b]`` entries each."""
 
     def __init__(self, slots: Sequence[int], caps: Sequence[int], device, truncate_to: Optional[int] = None,
-                 max_cap: int = 1 << 18, on_grow=None, group: int = 1, spectral: bool = False):
+                 max_cap: int = 1 << 18, on_grow=None, group: int = 1, spectral: Union[bool, str] = False,
+                 spectral_buckets: bool = False):
+        """spectral="only" | "half" with spectral_buckets=True (opt-in): every bucket is a spectral-only sub-store of that form
+        (``RirStore(spectral=...)``: block spectra staged as the rows arrive, no time-domain rows, a GPU device) and the bank is
+        served through ``ss_spec_bucket`` - a half entry of bucket b costs 2 * h_blocks_b * (65 536 + 4) + 4 bytes, an "only"
+        one 2 * h_blocks_b * 131 072 + 4.  Routing by length, re-bucketing, eviction and growth of the last bucket are the
+        sub-stores' own.  A bucket has at most 16 partition blocks."""
         assert len(slots) == len(caps) and 1 <= len(caps) <= 4 and list(caps) == sorted(caps)
-        if isinstance(spectral, str):
+        if isinstance(spectral, str) and not spectral_buckets:
             raise ValueError(f"BucketedRirStore: spectral={spectral!r} (a spectral-only bank) is not supported with length buckets")
+        if spectral_buckets:
+            if spectral not in ("only", "half"):
+                raise ValueError("BucketedRirStore: spectral_buckets goes with spectral='only' or 'half'")
+            if torch.device(device).type != "cuda":
+                raise ValueError(f"BucketedRirStore(spectral={spectral!r}) needs a GPU device: the spectral-only bank has no CPU "
+                                 "fallback")
+            if P.ceil_div(max(max_cap, caps[-1]), P.KB) > 16:
+                raise ValueError("BucketedRirStore: a spectral bucket holds at most 16 partition blocks per row "
+                                 f"(max_cap <= {16 * P.KB})")
         self.device = torch.device(device)
         self.group, self.on_grow, self.spectral = group, on_grow, spectral
         self.first = [int(v) for v in np.cumsum([0] + list(slots[:-1]))]
@@ -1362,6 +1411,11 @@ class BucketedRirStore:
     @property
     def grown(self) -> int:
         return sum(st.grown for st in self.stores)
+
+    def resident(self, key) -> bool:
+        """`key` holds an entry of some bucket right now"""
+        b = self._where.get(key)
+        return b is not None and key in self.stores[b]._slot_of
 
     def _sub_grown(self, _bank) -> None:                          # (only the last bucket can: its rows alone moved)
         self.bank = BucketedRirBank([st.bank for st in self.stores], self.bank.lengths, self.first)
@@ -1557,7 +1611,8 @@ class AudioEngine:
     def __init__(self, sampling_rate: int, device="cuda", rir_slots: int = 4096, rir_cap: Optional[int] = None,
                  rir_max_cap: int = 1 << 18, rir_group: int = 1, rir_spectral: Union[None, bool, str] = None,
                  rir_buckets: Optional[Sequence[Tuple[int, int]]] = None, spectral_hbm_fraction: float = 0.5,
-                 spectral_max_units: int = 0, rir_half_rows: bool = False, **renderer_kwargs):
+                 spectral_max_units: int = 0, rir_half_rows: bool = False, rir_spectral_buckets: bool = False,
+                 **renderer_kwargs):
         """rir_spectral: keep the RIR rows' block spectra in HBM as well (2x the bytes per row) and run k_conv_spec /
         k_obs_rows<SPECTRAL> (no forward FFT per step): for STATIC banks (SoundSpaces 1.0 RIR files); live SS2.0 RIRs change
         every step and stay on the time-domain kernels.  None (default) = decided here: ON for file-backed stores at rates
@@ -1589,7 +1644,17 @@ class AudioEngine:
         rir_half_rows=True (with rir_spectral="half" only): the half store for rows of 2 or 3 partition blocks (sampling rates in
         (KB, 3 KB]: 44.1 / 48 kHz) - the fused row kernels' half forms (k_obs_blocks / k_obs_rows <.., HALF>,
         ss_audio_obs_rows_spec16_f32 and its log-mel sibling) and the context binding ss_ctx_set_rir_spectra16_rows.  A 44.1 kHz
-        entry costs 393 244 bytes against 786 436 of "only".  Same loss, same refusals; rates above 3 KB are not served."""
+        entry costs 393 244 bytes against 786 436 of "only".  Same loss, same refusals; rates above 3 KB are not served.
+
+        rir_spectral_buckets=True (with rir_buckets and rir_spectral="only" | "half"; opt-in): the length-bucketed store in a
+        dense form (BucketedRirStore(spectral_buckets=True), include/ss_hip.h "Spectral length buckets") - without the keyword
+        the combination stays refused.  "only" works at every rate a bucketed both-forms bank serves from its spectra; "half"
+        serves sampling rates up to KB (the fused 44.1 / 48 kHz row kernels do not read half bucketed banks yet).  A GPU device;
+        step_time / wrap and spectral_max_units > 0 stay refused.  The last bucket grows up to min(rir_max_cap, 16 KB): a bucket
+        holds at most 16 partition blocks per row, so a larger rir_max_cap is clamped here (a bucket capacity above 16 KB is the
+        store's ValueError)."""
+        if rir_spectral_buckets and not (rir_buckets and rir_spectral in ("only", "half")):
+            raise ValueError("rir_spectral_buckets goes with rir_buckets and rir_spectral='only' or 'half'")
         if rir_half_rows and rir_spectral != "half":
             raise ValueError("rir_half_rows goes with rir_spectral='half'")
         if isinstance(rir_spectral, str):
@@ -1598,11 +1663,16 @@ class AudioEngine:
             if renderer_kwargs.get("step_time") is not None or renderer_kwargs.get("wrap"):
                 raise ValueError(f"rir_spectral={rir_spectral!r} cannot serve SoundSpaces 2.0 (step_time / wrap): live RIRs and the "
                                  "cross-fade need time-domain rows")
-            if rir_buckets:
+            if rir_buckets and not rir_spectral_buckets:
                 raise ValueError(f"rir_spectral={rir_spectral!r} does not support length-bucketed banks (rir_buckets)")
             if spectral_max_units > 0:
                 raise ValueError(f"rir_spectral={rir_spectral!r} keeps no time-domain rows for the spectral_max_units policy to "
                                  "send large steps to")
+            if rir_spectral_buckets and rir_spectral == "half" and int(sampling_rate) > P.KB:
+                raise ValueError(f"rir_spectral='half' on length buckets serves sampling rates up to {P.KB}, not {sampling_rate}: "
+                                 "the fused row kernels do not read half bucketed banks yet")
+            if rir_spectral_buckets and torch.device(device).type != "cuda":
+                raise ValueError(f"rir_spectral={rir_spectral!r} needs a GPU device: the spectral-only bank has no CPU fallback")
             if rir_spectral == "half" and int(sampling_rate) > P.KB and not rir_half_rows:
                 raise ValueError(f"rir_spectral='half' serves rows of one partition block (sampling rates up to {P.KB}), "
                                  f"not {sampling_rate}; rir_half_rows=True opts in to the half forms of the 44.1 / 48 kHz row kernels")
@@ -1623,12 +1693,15 @@ class AudioEngine:
         self.rir_spectral = bool(rir_spectral) and not full
         self.rir_spectral_only = rir_spectral in ("only", "half")
         self.rir_spectral_half = rir_spectral == "half"
+        if rir_buckets and rir_spectral_buckets:
+            rir_max_cap = min(int(rir_max_cap), 16 * P.KB)         # (ss_spec_bucket: at most 16 blocks per row)
         if rir_buckets:
             # length-bucketed bank: [(slots, cap samples), ...] ascending, e.g. [(4096, 16000), (256, 49152), (64, 65536)]
             self.store = BucketedRirStore([b[0] for b in rir_buckets], [b[1] for b in rir_buckets], self.renderer.device,
                                           truncate_to=None if full else int(sampling_rate), max_cap=rir_max_cap,
                                           on_grow=self.renderer.set_rir_bank, group=rir_group,
-                                          spectral=rir_spectral and not full)
+                                          spectral=False if full else rir_spectral,
+                                          **(dict(spectral_buckets=True) if rir_spectral_buckets else {}))
             self.renderer.set_rir_bank(self.store.bank)
             return
         self.store = RirStore(rir_slots, rir_cap or sampling_rate, self.renderer.device,
@@ -1700,7 +1773,10 @@ class AudioEngine:
         if isinstance(bank, BucketedRirBank):                    # length buckets: ss_ctx_set_rir_buckets (every bucket's rows, and
             now = tuple(b.data for b in bank.banks) + tuple(b.spectra for b in bank.banks)      # its block spectra when kept)
             if n_sync or cur is None or len(cur) != len(now) or any(a is not b for a, b in zip(cur, now)):
-                ctx.set_rir_buckets(bank, spectral=bool(self.store.spectral and bank.spectra))
+                if bank.spectral_only:                           # (no rows: ss_ctx_set_rir_spec_buckets, either form)
+                    ctx.set_rir_spec_buckets(bank)
+                else:
+                    ctx.set_rir_buckets(bank, spectral=bool(self.store.spectral and bank.spectra))
                 self._ctx_bank = now
             return ctx
         if n_sync or cur is None or cur[0] is not bank.data or cur[1] is not bank.spectra:   # two data_ptr() calls per step)
@@ -1759,7 +1835,9 @@ class AudioEngine:
         reference's ValueError -> zero-RIR fallback, simulator.py:617-624) instead of scipy + a host transpose + a row upload: what
         an eager call pays on EVERY step of an agent that moves (simulator.py:615-618 reads the file on every cache-missing step)."""
         store = self.store
-        if path in store._slot_of or getattr(store, "group", 1) != 1 or not hasattr(store, "load_files"):
+        # (a length-bucketed store keeps its keys per bucket: it answers through resident())
+        resident = store.resident(path) if isinstance(store, BucketedRirStore) else path in store._slot_of
+        if resident or getattr(store, "group", 1) != 1 or not hasattr(store, "load_files"):
             return store.slot(path, lambda: reader(path))
         native = self._native_readers.get(id(reader))
         if native is None:
