@@ -677,6 +677,13 @@ int ss_ctx_plan(ss_ctx* ctx, const ss_units* units, int n, int* unit_desc_out, i
                 int* new_windows_out, int new_windows_cap);
 /* out8 = {cache hits, misses, evictions, grows, capacity (keys), keys resident, pool slots per key, steps planned} */
 int ss_ctx_stats(ss_ctx* ctx, long long* out8);
+/* The descriptor ring's release bookkeeping, four counters that only grow: out4 = {ring events recorded, host waits for a ring
+ * event, pace events recorded, host waits for a pace event}.  A ring group records an event only when the device was given one of
+ * its slots to read (descriptors read in place or uploaded, a window upload): steps whose launch carries its units in the kernel
+ * arguments and that upload no window add to neither of the first two.  Such steps are paced instead: one event per 16 of them,
+ * waited for 16 steps later, so a caller that never synchronises stays at most two ring lengths ahead of the device.
+ * (A getter of its own: ss_ctx_stats keeps its eight words.) */
+int ss_ctx_ring_stats(ss_ctx* ctx, long long* out4);
 
 /* ---- RIR files -> staging rows (the step BEFORE the path: SURVEY 8(f)2) ---------------------------------------------
  * Replaces the reference's per-miss `scipy.io.wavfile.read(binaural_rir_file)` (soundspaces/simulator.py:615-618, float32

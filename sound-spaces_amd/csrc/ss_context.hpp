@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../include/ss_hip.h"
+#include "ss_ring.hpp"
 
 namespace ssctx {
 
@@ -96,10 +97,11 @@ struct Context {
     int win_cap = 0;
     int* h_win = nullptr;                         // pinned [kRing][win_cap][5]: {src_offset, src_len, start, wrap, pool slot}
     int* d_win = nullptr;
-    hipEvent_t ev_done[kRing / kGroup] = {};      // group g's launches have finished
-    bool group_open = false;                      // a group has been started and its event not yet recorded
-    int open_group = 0;
-    hipStream_t group_stream = nullptr;           // ... on this stream
+    hipEvent_t ev_done[kRing / kGroup] = {};      // group g's launches have finished (recorded only when they read its slots)
+    ssring::Release<kRing, kGroup> ring;          // which groups record / are waited for (single-stream mode; ss_ring.hpp)
+    hipStream_t group_stream = nullptr;           // stream of the open group
+    ssring::Pace<kRing> pace;                     // host run-ahead bound for steps that record no ring event (ss_ring.hpp)
+    hipEvent_t ev_pace = nullptr;
     bool ev_made = false;
     float* ag_scratch = nullptr;                  // hand-over buffer for rows longer than one block (44.1 kHz) when the
     size_t ag_cap = 0;                            // caller does not want the audiogoal itself

@@ -102,6 +102,11 @@ inline int t4_of(int len) { return (n_frames_of(len) + ssk::kPool - 1) / ssk::kP
 // launch call it leaves them here, and loop-free launches of <= kTabUnits units then carry {index, slot} per unit in the
 // kernel arguments (ConvParams::tab).  Callers of the stateless entry points hand over device pointers only: nullptr.
 thread_local const int* g_host_desc = nullptr;
+// ... and reads back whether the launch took that route: a launch with a unit table never dereferences its descriptor pointer,
+// so the ring slot the descriptors lie in holds nothing the device reads (ss_ring.hpp).  Set by fill_unit_tab only; every
+// launcher that does not go through it leaves the flag alone and counts as "slot read".  (Every entry point issues ONE launch
+// that consumes descriptors, so one flag per call is enough.)
+thread_local bool g_tab_taken = false;
 // ... and, in its overlap mode, the number of launches it keeps in flight (its lanes): a launch that spreads its rows over
 // idle CUs (parts_log2_for) then leaves the other lanes' launches their share of the chip.  1 for everybody else.
 thread_local int g_launch_share = 1;
@@ -133,6 +138,7 @@ inline bool fill_unit_tab(ssk::UnitTab<true>& ut, const int* host_desc, int n_un
         ut.tab[ssk::kTabWords * k + 1] = ok ? d[1] - d[2] : 0;
         ut.tab[ssk::kTabWords * k + 2] = i;
     }
+    g_tab_taken = true;
     return true;
 }
 
@@ -1334,6 +1340,7 @@ static void ctx_free_device(ssctx::Context& c) {
     drop_wave_scratch(&c);
     if (c.ev_made)
         for (int k = 0; k < ssctx::kRing / ssctx::kGroup; ++k) (void)hipEventDestroy(c.ev_done[k]);
+    if (c.ev_pace) { (void)hipEventDestroy(c.ev_pace); c.ev_pace = nullptr; }
     if (c.ev_xstream) (void)hipEventDestroy(c.ev_xstream);
     if (c.miss_ev) { (void)hipEventDestroy(static_cast<hipEvent_t>(c.miss_ev)); c.miss_ev = nullptr; }
     c.ev_xstream = nullptr; c.have_last_stream = false;
@@ -1500,6 +1507,13 @@ int ss_ctx_plan(ss_ctx* h, const ss_units* units, int n, int* unit_desc_out, int
     return 0;
 }
 
+int ss_ctx_ring_stats(ss_ctx* h, long long* out4) {
+    if (!h || !out4) return SS_EINVAL;
+    out4[0] = h->c.ring.n_records; out4[1] = h->c.ring.n_waits;
+    out4[2] = h->c.pace.n_records; out4[3] = h->c.pace.n_waits;
+    return 0;
+}
+
 int ss_ctx_stats(ss_ctx* h, long long* out8) {
     if (!h || !out8) return SS_EINVAL;
     const ssctx::Context& c = h->c;
@@ -1515,6 +1529,8 @@ static int ctx_ensure_ring(ssctx::Context& c, int n, int n_win, hipStream_t st) 
             e = hipEventCreateWithFlags(&c.ev_done[k], hipEventDisableTiming);
             if (e != hipSuccess) return hip_err(e);
         }
+        e = hipEventCreateWithFlags(&c.ev_pace, hipEventDisableTiming);
+        if (e != hipSuccess) return hip_err(e);
         c.ev_made = true;
     }
     if (n > c.ring_cap) {
@@ -1615,22 +1631,33 @@ static int ctx_observe_on(ss_ctx* h, const ss_units* units, int n, float* audiog
     if (rc) return rc;
     // Ring slots are released in GROUPS: one completion event per kGroup consecutive steps (recorded after the group's
     // last launch, waited for - on the host - before the group's first slot is written again, a full ring later).  An
-    // event record per step puts a marker packet between every two launches (measured: ~2 us of a 26-us step).  A caller
-    // that changes streams inside a group closes it on the old stream and starts the next group.
-    if (lane < 0 && c.group_open && (st != c.group_stream || c.ring_k / ssctx::kGroup != c.open_group)) {
-        e = hipEventRecord(c.ev_done[c.open_group], c.group_stream);     // (also a group a failed step left open)
-        if (e != hipSuccess) return hip_err(e);
-        c.group_open = false;
-        c.ring_k = (c.open_group + 1) * ssctx::kGroup % ssctx::kRing;
+    // event record per step puts a marker packet between every two launches (measured: 2.6-3 us of a 27-us step).
+    // An event exists only for groups whose slots the device read: descriptors read in place by a kernel without a unit
+    // table, a descriptor upload, a window upload.  A group of unit-table steps that upload nothing records no event and
+    // its next round waits for none (c.ring, ss_ring.hpp: the flag per group says whether its event holds a record of the
+    // group's last round - a never-recorded or stale event is not consulted).  A caller that changes streams inside a
+    // group closes it on the old stream and starts the next group.
+    // Overlap mode (lane >= 0) stays as it was: every lane records its share of every group and every group is waited for.
+    if (lane < 0 && c.ring.must_close_before(c.ring_k, st == c.group_stream)) {
+        const int og = c.ring.open_group;
+        if (c.ring.close_early()) {                            // (also a group a failed step left open)
+            e = hipEventRecord(c.ev_done[og], c.group_stream);
+            if (e != hipSuccess) return hip_err(e);
+        }
+        c.ring_k = c.ring.next_slot();
     }
     const int k = c.ring_k, g = k / ssctx::kGroup;
-    if (k % ssctx::kGroup == 0) {
-        e = hipEventSynchronize(c.ev_done[g]);                 // every launch that read the group's slots has finished
-        for (int l = 1; lane >= 0 && l < c.n_lanes && e == hipSuccess; ++l) e = hipEventSynchronize(c.ev_done_l[l][g]);   // ... on every lane
+    if (lane < 0) {
+        if (c.ring.begin(k)) {
+            e = hipEventSynchronize(c.ev_done[g]);             // every launch that read the group's slots has finished
+            if (e != hipSuccess) return hip_err(e);
+        }
+        if (k % ssctx::kGroup == 0) c.group_stream = st;
+    } else if (k % ssctx::kGroup == 0) {
+        e = hipEventSynchronize(c.ev_done[g]);
+        for (int l = 1; l < c.n_lanes && e == hipSuccess; ++l) e = hipEventSynchronize(c.ev_done_l[l][g]);   // ... on every lane
         if (e != hipSuccess) return hip_err(e);
-        c.group_open = lane < 0;
-        c.group_stream = st;
-        c.open_group = g;
+        ++c.ring.n_waits;
     }
     // Small steps: the kernels read the unit descriptors straight from the pinned ring slot (one 32-byte scalar load per
     // workgroup over the host link) - an upload between two launches on the stream costs a blit kernel plus a barrier on
@@ -1657,13 +1684,25 @@ static int ctx_observe_on(ss_ctx* h, const ss_units* units, int n, float* audiog
     // The slot's group is released by an event recorded behind the group's last launch (overlap mode: behind each lane's
     // last launch of the group); a step that fails after this point must still record it, or the group's next round
     // would be checked against a stale event.
+    bool slot_read = true;                                     // until the launch has reported the unit-table route
     auto close_slot = [&]() -> int {
         hipError_t ee = hipSuccess;
         if (lane >= 0) {
-            if (k % ssctx::kGroup >= ssctx::kGroup - c.n_lanes) ee = hipEventRecord(lane == 0 ? c.ev_done[g] : c.ev_done_l[lane][g], st);
-        } else if (k % ssctx::kGroup == ssctx::kGroup - 1) {
+            if (k % ssctx::kGroup >= ssctx::kGroup - c.n_lanes) {
+                ee = hipEventRecord(lane == 0 ? c.ev_done[g] : c.ev_done_l[lane][g], st);
+                ++c.ring.n_records;
+            }
+        } else if (c.ring.end(k, slot_read)) {
             ee = hipEventRecord(c.ev_done[g], st);
-            c.group_open = false;
+            c.pace.ring_event();
+        } else {
+            // no ring event behind this step: the host's run-ahead is bounded by the pace event instead (ss_ring.hpp), one record
+            // per kRing such steps, waited for one period later
+            bool wait_first = false;
+            if (c.pace.step(&wait_first)) {
+                if (wait_first) ee = hipEventSynchronize(c.ev_pace);
+                if (ee == hipSuccess) ee = hipEventRecord(c.ev_pace, st);
+            }
         }
         return hip_err(ee);
     };
@@ -1741,6 +1780,7 @@ static int ctx_observe_on(ss_ctx* h, const ss_units* units, int n, float* audiog
     static const bool no_tab = ab_flag("SS_HIP_NO_UNIT_TAB");
     SS_PROF_MARK(4);                                           // new windows (upload + k_source_windows), descriptor upload
     g_host_desc = no_tab ? nullptr : hd;                       // (see fill_unit_tab; cleared right after the dispatch below)
+    g_tab_taken = false;
     g_launch_share = c.chip_share > 0 ? c.chip_share : c.n_lanes;
     if (mel_ss2) {
         rc = ss_audio_obs_logmel_ss2_f32(c.pool, c.rir, c.rir_len, dd, nullptr, spectrogram, mel->logmel, mel->mel_start, mel->mel_w,
@@ -1803,6 +1843,9 @@ static int ctx_observe_on(ss_ctx* h, const ss_units* units, int n, float* audiog
                                      c.n_valid, c.out_len, res.flags, stream);
     g_host_desc = nullptr;
     g_launch_share = 1;
+    // what the device may read from this step's ring slot after the call: descriptors in place (no unit table), the source of
+    // their upload, the source of the window upload
+    slot_read = !direct || res.n_new_windows > 0 || !g_tab_taken;
     SS_PROF_MARK(5);                                           // the launch entry (unit table + hipLaunchKernel)
     if (!rc && mel && !mel_fused && !mel_rows && !mel_ss2)     // scratch route: the features of the waveform just rendered
         rc = ss_audio_features_f32(audiogoal, n, c.out_len, c.pad_mode, nullptr, mel->logmel, mel->mel_start, mel->mel_w,
@@ -1840,7 +1883,8 @@ int ss_ctx_set_overlap(ss_ctx* h, int n_streams) {
     c.n_lanes = n_streams;
     c.lane_next = 0;
     c.ring_k = 0;                                              // groups start afresh (everything has completed)
-    c.group_open = false;
+    c.ring.reset();
+    c.pace.reset();
     c.have_last_stream = false;
     for (int l = 0; l < ssctx::kLanes; ++l) { c.lane_dirty[l] = false; c.lane_joined[l] = false; c.lane_join_valid[l] = false; for (int o = 0; o < ssctx::kLanes; ++o) c.win_seen[l][o] = c.win_seq[o]; }
     return 0;

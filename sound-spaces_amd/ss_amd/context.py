@@ -463,4 +463,6 @@ class AudioContext:
         out = np.zeros(8, np.int64)
         _lib.check(self.lib.ss_ctx_stats(self._h, out.ctypes.data), "ss_ctx_stats")
         keys = ("hits", "misses", "evictions", "grows", "capacity", "resident", "slots_per_key", "steps")
-        return dict(zip(keys, (int(v) for v in out)))
+        ring = np.zeros(4, np.int64)                 # descriptor ring: completion events / host waits; run-ahead pace: the same
+        _lib.check(self.lib.ss_ctx_ring_stats(self._h, ring.ctypes.data), "ss_ctx_ring_stats")
+        return dict(zip(keys + ("ring_events", "ring_waits", "pace_events", "pace_waits"), (int(v) for v in (*out, *ring))))
