@@ -278,6 +278,21 @@ int ss_fftconv_binaural_buckets_f32(const float* spec, const ss_rir_bucket* buck
 int ss_audio_obs_buckets_f32(const float* spec, const ss_rir_bucket* buckets, int n_buckets, const int* rir_len,
                              const int* unit_desc, float* audiogoal, float* spectrogram, int n_units, int n_valid,
                              int out_len, int pad_mode, int flags, void* stream);
+/* Log-mel observation from a length-bucketed bank in ONE launch, no waveform buffer needed: outputs and mel arguments exactly
+ * those of ss_audio_obs_logmel_f32 / ss_audio_obs_logmel_rows_f32 (logmel required; audiogoal and spectrogram may each be
+ * NULL; any combination is one launch; a waveform buffer is written as ss_audio_obs_buckets_f32 writes it on the same kernel;
+ * silent units and empty RIRs give log(mel_eps) in every band and exact zeros in the spectrogram).  Served: rows of one
+ * partition block (257 <= out_len <= kB: k_conv / k_conv_spec <loop, MEL>) and rows of 2 or 3 blocks (kB < out_len <= 3 kB,
+ * the deepest bucket at most 16 blocks: k_obs_blocks<.., MEL> while the grid fits the chip, k_obs_rows<.., BUCKETS, MEL>
+ * beyond); spectral kernels when every bucket carries hspec, as above.  Launches that promise SS_FLAG_FIRST_BUCKET (or have one
+ * bucket) are single-allocation launches on bucket 0 and equal ss_audio_obs_logmel_f32 / _spec_f32 / _rows_f32 / _rows_spec_f32
+ * on its arrays bit for bit.  SS_EINVAL from the argument checks, before a device is touched: SS_FLAG_CROSSFADE, a bucket array
+ * ss_audio_obs_buckets_f32 refuses, the mel limits of ss_audio_features_f32, a bad pad_mode, out_len < 257 or > 3 kB, n_valid
+ * outside [0, out_len].  n_units == 0 returns 0. */
+int ss_audio_obs_logmel_buckets_f32(const float* spec, const ss_rir_bucket* buckets, int n_buckets, const int* rir_len,
+                                    const int* unit_desc, float* audiogoal, float* spectrogram, float* logmel,
+                                    const int* mel_start, const float* mel_w, int n_mels, int max_len, float mel_eps, int n_units,
+                                    int n_valid, int out_len, int pad_mode, int flags, void* stream);
 
 /* ---- Spectral length buckets: a bucketed bank WITHOUT time-domain rows ------------------------------------------------------
  * The two dense forms of a bank - fp32 block spectra alone ("Spectral-only" binding of ss_ctx_set_rir_spectra) and the half form
@@ -298,10 +313,14 @@ int ss_audio_obs_buckets_f32(const float* spec, const ss_rir_bucket* buckets, in
  *   ss_fftconv_binaural_spec_buckets_f32   every row length ss_fftconv_binaural_spec_f32 / _spec16_f32 serve (n_valid <= 3 kB);
  *   ss_audio_obs_spec_buckets_f32          fp32: the shapes ss_audio_obs_buckets_f32 serves from spectra; half: rows of one
  *                                          partition block, 257 <= out_len <= kB (the fused 44.1 / 48 kHz row kernels do not read
- *                                          half bucketed banks; neither do the log-mel launches).
+ *                                          half bucketed banks);
+ *   ss_audio_obs_logmel_spec_buckets_f32   ss_audio_obs_logmel_buckets_f32 on these buckets, same outputs, shapes and refusals:
+ *                                          fp32 - one-block rows (k_conv_spec<loop, MEL>) and rows of 2 or 3 blocks (k_obs_blocks /
+ *                                          k_obs_rows <true, .., BUCKETS, MEL>); half - one-block rows only
+ *                                          (k_conv_spec<.., MEL, HALF, HBK>), out_len > kB is SS_EINVAL.
  * SS_EINVAL from the argument checks, before a device is touched: a NULL or misaligned hspec, mixed forms, more than 4 buckets,
  * `first` not ascending / overlapping / != 0 for bucket 0, an odd cap or cap < 2, a bucket of more than 16 blocks,
- * SS_FLAG_CROSSFADE, half with out_len > kB in the fused entry.  n_units == 0 returns 0. */
+ * SS_FLAG_CROSSFADE, half with out_len > kB in the fused entries.  n_units == 0 returns 0. */
 typedef struct ss_spec_bucket {
     const void*  hspec;   /* device; see above */
     const float* hscale;  /* device, or NULL (fp32) */
@@ -316,6 +335,10 @@ int ss_fftconv_binaural_spec_buckets_f32(const float* spec, const ss_spec_bucket
 int ss_audio_obs_spec_buckets_f32(const float* spec, const ss_spec_bucket* buckets, int n_buckets, const int* rir_len,
                                   const int* unit_desc, float* audiogoal, float* spectrogram, int n_units, int n_valid,
                                   int out_len, int pad_mode, int flags, void* stream);
+int ss_audio_obs_logmel_spec_buckets_f32(const float* spec, const ss_spec_bucket* buckets, int n_buckets, const int* rir_len,
+                                         const int* unit_desc, float* audiogoal, float* spectrogram, float* logmel,
+                                         const int* mel_start, const float* mel_w, int n_mels, int max_len, float mel_eps,
+                                         int n_units, int n_valid, int out_len, int pad_mode, int flags, void* stream);
 
 /* EXTENSION, one pass for every STFT-derived feature (BASELINE.json configs[4] "GCC-PHAT + log-mel fused sensor"): each
  * (unit, ear, frame) of x [n_units, 2, len] is framed, windowed and transformed ONCE (both ears in one wave), and from that
@@ -453,7 +476,8 @@ int ss_ctx_set_rir_buckets(ss_ctx* ctx, const ss_rir_bucket* buckets, int n_buck
  * longest bucket's blocks, as for ss_ctx_set_rir_buckets; steps whose units all sit in bucket 0 keep the loop-free kernels.
  * SS_EINVAL, nothing changed: the refusals of ss_spec_bucket, rir_len == NULL, half buckets on a context whose rows exceed kB.
  * A cross-faded step is SS_EINVAL and leaves no keys behind, as on every spectral-only bank; log-mel steps render into the
- * context's waveform scratch and run the feature kernel over it, as on ss_ctx_set_rir_buckets contexts.  The in-call loaders are
+ * context's waveform scratch and run the feature kernel over it, as on ss_ctx_set_rir_buckets contexts, unless
+ * ss_ctx_set_logmel_buckets_policy admits them to the one-launch route.  The in-call loaders are
  * not extended and load nothing on such a context: ss_ctx_load_rir_files returns 1 ("not served", nothing changed);
  * ss_ctx_observe_requests_load returns 0 with the unresolved requests reported in miss_out / n_miss and no launch made, as
  * ss_ctx_observe_requests reports them (a step without misses is rendered).  Call again whenever a bucket is (re)allocated. */
@@ -479,7 +503,11 @@ int ss_ctx_observe(ss_ctx* ctx, const ss_units* units, int n, float* audiogoal, 
  *     or a step that renders only block 0 of a 44.1 / 48 kHz row, cross-faded or not - on the time-domain rows of a
  *     single-allocation bank (not the spectral-only binding) and its unit count lies inside ss_ctx_set_logmel_ss2_policy's
  *     range, which is empty by default for the same reason;
- *   - otherwise (44.1 / 48 kHz rows and cross-faded steps by default, bucketed banks, unit counts outside the range) the route ss_ctx_observe
+ *   - ONE fused launch (ss_audio_obs_logmel_buckets_f32 / _spec_buckets_f32) on a context bound by ss_ctx_set_rir_buckets or
+ *     ss_ctx_set_rir_spec_buckets, when the step has no cross-fade, its rows are one partition block (every bank form) or 2 or
+ *     3 blocks (the fp32 forms) and its unit count lies inside ss_ctx_set_logmel_buckets_policy's range, which is empty by
+ *     default for the same reason; the three ranges above never apply to such a context;
+ *   - otherwise (44.1 / 48 kHz rows, cross-faded steps and bucketed banks by default, unit counts outside the range) the route ss_ctx_observe
  *     takes with an audiogoal buffer, into a waveform scratch the CONTEXT owns ([n, 2, sr] floats per overlap lane, grown on
  *     demand, freed with the context and by ss_release_scratch; a growth needed while the stream is being captured is refused
  *     with SS_EINVAL: warm the stream up first), then ss_audio_features_f32 over it: bit for bit ss_ctx_observe +
@@ -510,6 +538,15 @@ int ss_ctx_set_logmel_rows_policy(ss_ctx* ctx, int min_units, int max_units);
  * of 9000 taps: 19-58 %, of 4 s: 5-33 %; profiles/r7/kbench_obs_logmel_ss2.txt), so (1, INT_MAX) is the range a caller who
  * accepts rounding-level differences would pass. */
 int ss_ctx_set_logmel_ss2_policy(ss_ctx* ctx, int min_units, int max_units);
+/* The same for contexts bound by ss_ctx_set_rir_buckets / ss_ctx_set_rir_spec_buckets (ss_audio_obs_logmel_buckets_f32 /
+ * _spec_buckets_f32 and their shapes); the three setters above keep their meaning and never apply to such a context.  The pool,
+ * the planner's SS_FLAG_FIRST_BUCKET and the step's flags pass through unchanged; cross-faded steps keep the scratch route.
+ * Default: never (max_units < min_units) - the fused values equal the scratch route's to rounding only.  Measured against the
+ * scratch route of the same context on a mixed-bucket step (profiles/r7/kbench_obs_logmel_buckets.txt): 16 kHz, every bank form,
+ * 1 .. 128 units: 9-41 % faster, so (1, INT_MAX) is the range a caller would pass there; 44.1 kHz: faster up to 42 units and
+ * whenever the spectrogram is asked for as well (8-29 %), but log-mel alone at 43 units costs 1.7 x the scratch route (the row
+ * kernel takes over from the one-workgroup-per-block kernel) and 128 units are a tie: (1, 42) there. */
+int ss_ctx_set_logmel_buckets_policy(ss_ctx* ctx, int min_units, int max_units);
 /* Bytes of waveform scratch the context currently holds over all overlap lanes (the scratch route above): 0 after creation and
  * after ss_release_scratch. */
 size_t ss_ctx_wave_scratch_bytes(const ss_ctx* ctx);

@@ -122,6 +122,7 @@ struct Context {
     // ss_ctx_set_logmel_rows_policy: the same for rows of 2 or 3 blocks (44.1 / 48 kHz); default: never
     int mel_rows_min_units = 1, mel_rows_max_units = 0;
     int mel_ss2_min_units = 1, mel_ss2_max_units = 0;          // ss_ctx_set_logmel_ss2_policy: never, by default
+    int mel_bk_min_units = 1, mel_bk_max_units = 0;            // ss_ctx_set_logmel_buckets_policy (length-bucketed banks): never, by default
     int chip_share = 0;                 // ss_ctx_set_chip_share: launch sources the chip is shared with (0: the lane count)
     hipStream_t lane_stream[kLanes] = {};
     bool lane_dirty[kLanes] = {};                 // work issued on the lane since ev_lane was last recorded

@@ -341,7 +341,8 @@ int launch_obs_rows(ssk::ConvParams p, int n_units, int flags, int n_cus, hipStr
                     const ssk::SpecScale<HALF>& hs = ssk::SpecScale<HALF>()) {
     static_assert(!HALF || SPECTRAL, "half bank: the spectral form");
     const int n_rows = 2 * n_units;
-    if ((MEL || HALF) && ((flags & SS_FLAG_CROSSFADE) || p.n_buckets != 1)) return SS_EINVAL;      // (the log-mel and half forms: plain rows, one allocation)
+    if ((MEL || HALF) && (flags & SS_FLAG_CROSSFADE)) return SS_EINVAL;                            // (the log-mel and half forms: plain rows)
+    if (HALF && p.n_buckets != 1) return SS_EINVAL;                                                 // (half: one allocation)
     {
         const int rc = launch_obs_blocks<SPECTRAL, MEL, HALF>(p, n_units, flags, n_cus, st, mel, hs);
         if (rc != 1) return rc;
@@ -384,8 +385,9 @@ int launch_obs_rows(ssk::ConvParams p, int n_units, int flags, int n_cus, hipStr
         hipLaunchKernelGGL((ssk::k_obs_rows<true, false, false, MEL, true>), dim3(grid), dim3(ssk::kT), 0, st, p, n_rows, mel, hs);
         return hip_err(hipGetLastError());
     }
-    if constexpr (MEL) {
-        hipLaunchKernelGGL((ssk::k_obs_rows<SPECTRAL, false, false, true>), dim3(grid), dim3(ssk::kT), 0, st, p, n_rows, mel);
+    if constexpr (MEL) {                                        // (length buckets: the instantiation that resolves them)
+        if (p.n_buckets == 1) hipLaunchKernelGGL((ssk::k_obs_rows<SPECTRAL, false, false, true>), dim3(grid), dim3(ssk::kT), 0, st, p, n_rows, mel);
+        else hipLaunchKernelGGL((ssk::k_obs_rows<SPECTRAL, false, true, true>), dim3(grid), dim3(ssk::kT), 0, st, p, n_rows, mel);
         return hip_err(hipGetLastError());
     }
     // one bank allocation (every launch but those of a length-bucketed store): the instantiation without the bucket descriptors
@@ -862,6 +864,14 @@ int ss_audio_obs_logmel_ss2_f32(const float* spec, const float* rir, const int* 
 // RIR blocks (obs_rows_ok without a cross-fade; a waveform buffer changes nothing here: the caller chose the entry)
 inline bool obs_logmel_rows_shape_ok(int out_len, int n_valid, int nbh_max, int flags) {
     return !(flags & SS_FLAG_CROSSFADE) && n_valid >= 0 && obs_rows_ok(out_len, n_valid, nbh_max, flags);
+}
+
+// rows the log-mel entries of the length-bucketed banks serve (ss_audio_obs_logmel_buckets_f32 / _spec_buckets_f32): one partition
+// block on every bank form; 2 or 3 blocks on the fp32 forms, with the deepest bucket's blocks inside the row kernels' limit
+inline bool obs_logmel_buckets_shape_ok(int out_len, int n_valid, int nbh_max, int flags, bool half) {
+    if (n_valid < 0 || n_valid > out_len) return false;
+    if (obs_logmel_shape_ok(out_len, flags)) return true;
+    return !half && obs_logmel_rows_shape_ok(out_len, n_valid, nbh_max, flags);
 }
 
 // Log-mel observation of rows of 2 or 3 partition blocks in ONE launch (k_obs_blocks<.., MEL> for small steps, else
@@ -1759,11 +1769,19 @@ static int ctx_observe_on(ss_ctx* h, const ss_units* units, int n, float* audiog
     const bool mel_ss2 = mel && !mel_fused && !mel_rows && c.buckets.empty() && c.rir && !spectral &&
                          obs_logmel_ss2_shape(c.out_len, c.n_valid, res.flags) != 0 &&
                          n >= c.mel_ss2_min_units && n <= c.mel_ss2_max_units;
-    if (mel && !mel_fused && !mel_rows && !mel_ss2) {
+    // length-bucketed banks (ss_ctx_set_rir_buckets / ss_ctx_set_rir_spec_buckets): their own fused launch, one-block rows on every
+    // bank form and rows of 2 or 3 blocks on the fp32 forms, inside the range of ss_ctx_set_logmel_buckets_policy (default: never,
+    // for the same reason); the three policies above never apply to these contexts
+    const bool mel_bk = mel && (spec_bk || !c.buckets.empty()) &&
+                        obs_logmel_buckets_shape_ok(c.out_len, c.n_valid, c.rir_cap > 0 ? ssctx::ceil_div(c.rir_cap, c.kb) : 1, res.flags,
+                                                    spec_bk && c.spec_buckets[0].hscale != nullptr) &&
+                        n >= c.mel_bk_min_units && n <= c.mel_bk_max_units;
+    const bool mel_one_launch = mel_fused || mel_rows || mel_ss2 || mel_bk;
+    if (mel && !mel_one_launch) {
         rc = get_wave_scratch(&c, lane < 0 ? 0 : lane, st, static_cast<size_t>(n) * 2 * c.out_len, &audiogoal);
         if (rc) return fail(rc);
     }
-    if (spectrogram && !audiogoal && !mel_rows && c.out_len > ssk::kB && !wide_one_block_ok(c.out_len, c.n_valid, res.flags, spectral) &&
+    if (spectrogram && !audiogoal && !mel_rows && !mel_bk && c.out_len > ssk::kB && !wide_one_block_ok(c.out_len, c.n_valid, res.flags, spectral) &&
         !obs_rows_ok(c.out_len, c.n_valid, nbh_bank, res.flags, spectral, true)) {  // cross-faded / very long rows hand over through memory (the context's own buffer)
         const size_t need = static_cast<size_t>(n) * 2 * c.out_len;
         if (need > c.ag_cap) {
@@ -1808,6 +1826,14 @@ static int ctx_observe_on(ss_ctx* h, const ss_units* units, int n, float* audiog
                       : ss_audio_obs_logmel_f32(c.pool, c.rir, c.rir_len, dd, nullptr, spectrogram, mel->logmel, mel->mel_start,
                                                 mel->mel_w, mel->n_mels, mel->max_len, mel->mel_eps, n, c.rir_us, c.rir_cs, c.rir_es,
                                                 c.rir_cap, c.n_valid, c.out_len, c.pad_mode, res.flags, stream);
+    } else if (mel_bk) {
+        rc = spec_bk ? ss_audio_obs_logmel_spec_buckets_f32(c.pool, c.spec_buckets.data(), static_cast<int>(c.spec_buckets.size()),
+                                                            c.rir_len, dd, nullptr, spectrogram, mel->logmel, mel->mel_start, mel->mel_w,
+                                                            mel->n_mels, mel->max_len, mel->mel_eps, n, c.n_valid, c.out_len, c.pad_mode,
+                                                            res.flags, stream)
+                     : ss_audio_obs_logmel_buckets_f32(c.pool, c.buckets.data(), static_cast<int>(c.buckets.size()), c.rir_len, dd,
+                                                       nullptr, spectrogram, mel->logmel, mel->mel_start, mel->mel_w, mel->n_mels,
+                                                       mel->max_len, mel->mel_eps, n, c.n_valid, c.out_len, c.pad_mode, res.flags, stream);
     } else if (spec_bk) {
         const int nb = static_cast<int>(c.spec_buckets.size());
         rc = spectrogram ? ss_audio_obs_spec_buckets_f32(c.pool, c.spec_buckets.data(), nb, c.rir_len, dd, audiogoal, spectrogram, n,
@@ -1847,7 +1873,7 @@ static int ctx_observe_on(ss_ctx* h, const ss_units* units, int n, float* audiog
     // their upload, the source of the window upload
     slot_read = !direct || res.n_new_windows > 0 || !g_tab_taken;
     SS_PROF_MARK(5);                                           // the launch entry (unit table + hipLaunchKernel)
-    if (!rc && mel && !mel_fused && !mel_rows && !mel_ss2)     // scratch route: the features of the waveform just rendered
+    if (!rc && mel && !mel_one_launch)                         // scratch route: the features of the waveform just rendered
         rc = ss_audio_features_f32(audiogoal, n, c.out_len, c.pad_mode, nullptr, mel->logmel, mel->mel_start, mel->mel_w,
                                    mel->n_mels, mel->max_len, mel->mel_eps, nullptr, 1, 1.f, stream);
     if (rc) return fail(rc);
@@ -1914,6 +1940,13 @@ int ss_ctx_set_logmel_ss2_policy(ss_ctx* h, int min_units, int max_units) {
     if (!h || min_units < 0 || max_units < 0) return SS_EINVAL;
     h->c.mel_ss2_min_units = min_units;
     h->c.mel_ss2_max_units = max_units;
+    return 0;
+}
+
+int ss_ctx_set_logmel_buckets_policy(ss_ctx* h, int min_units, int max_units) {
+    if (!h || min_units < 0 || max_units < 0) return SS_EINVAL;
+    h->c.mel_bk_min_units = min_units;
+    h->c.mel_bk_max_units = max_units;
     return 0;
 }
 
@@ -2534,6 +2567,42 @@ int ss_audio_obs_buckets_f32(const float* spec, const ss_rir_bucket* buckets, in
     return spectrogram_of_rows(audiogoal, spectrogram, n_units, out_len, n_valid, pad_mode, stream);
 }
 
+// Log-mel observation from a length-bucketed bank in ONE launch, no waveform buffer needed: the log-mel forms of the kernels
+// ss_audio_obs_buckets_f32 launches for the same shape (k_conv / k_conv_spec <loop, MEL> for one-block rows, k_obs_blocks /
+// k_obs_rows <.., BUCKETS, MEL> for rows of 2 or 3 blocks).  Launches that only touch bucket 0 (one bucket, or
+// SS_FLAG_FIRST_BUCKET) are single-allocation launches on bucket 0's arrays: the existing log-mel launchers, loop-free kernels
+// included.  Every argument is checked before a device is touched.
+int ss_audio_obs_logmel_buckets_f32(const float* spec, const ss_rir_bucket* buckets, int n_buckets, const int* rir_len,
+                                    const int* unit_desc, float* audiogoal, float* spectrogram, float* logmel, const int* mel_start,
+                                    const float* mel_w, int n_mels, int max_len, float mel_eps, int n_units, int n_valid, int out_len,
+                                    int pad_mode, int flags, void* stream) {
+    if (n_units == 0) return 0;
+    if (n_units < 0 || !spec || !rir_len || !unit_desc || !mel_args_ok(logmel, mel_start, mel_w, n_mels, max_len, mel_eps)) return SS_EINVAL;
+    if (pad_mode != SS_PAD_REFLECT && pad_mode != SS_PAD_CONSTANT) return SS_EINVAL;
+    const bool spectral = buckets_spectral(buckets, n_buckets, flags);
+    int nbh_max = 1;
+    {
+        ssk::ConvParams probe;                              // (the bucket array's own refusals, without the device's tables)
+        const int rc = fill_buckets(probe, buckets, n_buckets, spectral, &nbh_max);
+        if (rc) return rc;
+    }
+    if (!obs_logmel_buckets_shape_ok(out_len, n_valid, nbh_max, flags, false)) return SS_EINVAL;
+    ssk::ConvParams p;
+    int n_cus = 1;
+    int rc = fill_conv(p, &n_cus, spec, buckets[0].rir, rir_len, unit_desc, 2LL * buckets[0].cap, buckets[0].cap, 1,
+                       buckets[0].cap, n_valid, out_len);
+    if (rc == 0) rc = fill_buckets(p, buckets, n_buckets, spectral, &nbh_max);
+    if (rc) return rc;
+    if (flags & SS_FLAG_FIRST_BUCKET) p.n_buckets = 1;
+    p.pad_mode = pad_mode;
+    p.out = audiogoal;
+    p.sgram = spectrogram;
+    const ssk::MelArgs m{logmel, mel_start, mel_w, n_mels, max_len, mel_eps};
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (out_len <= ssk::kB) return spectral ? launch_conv_spec_mel(p, m, n_units, flags, st) : launch_conv_mel(p, m, n_units, flags, st);
+    return spectral ? launch_obs_rows<true, true>(p, n_units, flags, n_cus, st, m) : launch_obs_rows<false, true>(p, n_units, flags, n_cus, st, m);
+}
+
 // The context's bank as length buckets (replaces ss_ctx_set_rir_bank + ss_ctx_set_rir_spectra for such banks; borrowed
 // device pointers, the array itself is copied).  Steps whose units all sit in bucket 0 keep the loop-free kernels.
 int ss_ctx_set_rir_buckets(ss_ctx* h, const ss_rir_bucket* buckets, int n_buckets, const int* rir_len) {
@@ -2690,6 +2759,45 @@ int ss_audio_obs_spec_buckets_f32(const float* spec, const ss_spec_bucket* bucke
                                               flags, stream);
     if (rc) return rc;
     return spectrogram_of_rows(audiogoal, spectrogram, n_units, out_len, n_valid, pad_mode, stream);
+}
+
+// ss_audio_obs_logmel_buckets_f32 on spectral length buckets.  fp32: the log-mel forms of the kernels
+// ss_audio_obs_spec_buckets_f32 launches (k_conv_spec<loop, MEL>; k_obs_blocks / k_obs_rows <true, .., BUCKETS, MEL>).  Half:
+// one-block rows, k_conv_spec<.., MEL, HALF, HBK>.  Bucket-0 launches: the single-allocation log-mel launchers, as above.
+int ss_audio_obs_logmel_spec_buckets_f32(const float* spec, const ss_spec_bucket* buckets, int n_buckets, const int* rir_len,
+                                         const int* unit_desc, float* audiogoal, float* spectrogram, float* logmel,
+                                         const int* mel_start, const float* mel_w, int n_mels, int max_len, float mel_eps, int n_units,
+                                         int n_valid, int out_len, int pad_mode, int flags, void* stream) {
+    if (n_units == 0) return 0;
+    bool half = false;
+    int hb_max = 1;
+    if (spec_buckets_check(buckets, n_buckets, &half, &hb_max) ||
+        !spec_buckets_launch_args_ok(spec, rir_len, unit_desc, n_units, n_valid, out_len, flags) ||
+        !mel_args_ok(logmel, mel_start, mel_w, n_mels, max_len, mel_eps))
+        return SS_EINVAL;
+    if (pad_mode != SS_PAD_REFLECT && pad_mode != SS_PAD_CONSTANT) return SS_EINVAL;
+    if (!obs_logmel_buckets_shape_ok(out_len, n_valid, hb_max, flags, half)) return SS_EINVAL;
+    ssk::ConvParams p;
+    int n_cus = 1;
+    int rc = fill_conv(p, &n_cus, spec, nullptr, rir_len, unit_desc, 0, 0, 1, 0, n_valid, out_len, false);
+    if (rc) return rc;
+    ssk::SpecScale<true, true> hs;
+    fill_spec_buckets(p, hs, buckets, n_buckets);
+    if (flags & SS_FLAG_FIRST_BUCKET) p.n_buckets = 1;
+    p.pad_mode = pad_mode;
+    p.out = audiogoal;
+    p.sgram = spectrogram;
+    const ssk::MelArgs m{logmel, mel_start, mel_w, n_mels, max_len, mel_eps};
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (half) {
+        if (p.n_buckets == 1) return launch_conv_spec16_mel(p, m, hs.hscale, n_units, flags, st);
+        p.nb_y = 1;
+        p.parts_log2 = 0;
+        hipLaunchKernelGGL((ssk::k_conv_spec<true, false, false, true, true, true>), dim3(2 * n_units), dim3(ssk::kT), 0, st, p, m, hs);
+        return hip_err(hipGetLastError());
+    }
+    if (out_len <= ssk::kB) return launch_conv_spec_mel(p, m, n_units, flags, st);
+    return launch_obs_rows<true, true>(p, n_units, flags, n_cus, st, m);
 }
 
 // The context's bank as spectral length buckets: replaces any earlier binding (rows, spectra of either form, ss_rir_bucket

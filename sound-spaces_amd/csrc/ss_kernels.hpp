@@ -1730,7 +1730,7 @@ template <bool FUSE, bool SIMPLE, bool TAB = false, bool MEL = false, bool HALF 
 __global__ __launch_bounds__(1024) void k_conv_spec(ConvParams p, UnitTab<TAB, MEL> ut = UnitTab<TAB, MEL>(),
                                                     SpecScale<HALF, HBK> hs = SpecScale<HALF, HBK>()) {
     static_assert(!TAB || SIMPLE, "the unit table serves the loop-free kernel");
-    static_assert(!HBK || (HALF && !SIMPLE && !MEL), "bucketed half bank: the loop kernel (bucket-0 launches take the loop-free HALF ones)");
+    static_assert(!HBK || (HALF && !SIMPLE), "bucketed half bank: the loop kernel (bucket-0 launches take the loop-free HALF ones)");
     static_assert(!MEL || (FUSE && !TAB), "log-mel: the plain fused kernels (launched with parts_log2 = 0)");
     __shared__ c32 lds[FUSE && 16 * kWaveScratch > kLdsComplex ? 16 * kWaveScratch : kLdsComplex];
     const int t = threadIdx.x;
@@ -2385,8 +2385,10 @@ __device__ __forceinline__ void mel_fill_quiet(const MelArgs& m, const ConvParam
         for (int tf = t & 63; tf < nf; tf += 64) om[2 * ((size_t)jm * p.n_frames + f0 + tf)] = quiet;
 }
 
-// MEL (log-mel form: plain rows of a single-allocation bank): the mel arguments and the log-mel output ride in the third kernel
-// argument (MelArgs, see UnitTab), the STFT phases emit the bands (rows_stft_phase<.., MEL>), p.sgram may be null.
+// MEL (log-mel form: plain rows): the mel arguments and the log-mel output ride in the third kernel argument (MelArgs, see
+// UnitTab), the STFT phases emit the bands (rows_stft_phase<.., MEL>), p.sgram may be null.  With BUCKETS (a length-bucketed fp32
+// bank, ss_audio_obs_logmel_buckets_f32 / _spec_buckets_f32) the bucket of a term is resolved where the plain BUCKETS form
+// resolves it: 124 / 122 VGPRs, no VGPR spills, no scratch (profiles/r7/NOTES.md).
 // HALF (a half bank, see k_conv_spec<.., HALF>): the pairs in memory are fp16 block spectra with one scale per block
 // (rows_product16); the scales ride in a kernel argument of their own.
 template <bool SPECTRAL, bool XFADE = false, bool BUCKETS = true, bool MEL = false, bool HALF = false>
@@ -2394,7 +2396,7 @@ __global__ __launch_bounds__(1024) void k_obs_rows(ConvParams p, int n_rows, Uni
                                                    SpecScale<HALF> hs = SpecScale<HALF>()) {
     static_assert(!(SPECTRAL && XFADE), "cross-faded rows are rendered from the time-domain bank");
     static_assert(!HALF || (SPECTRAL && !XFADE && !BUCKETS), "half bank: plain rows of a single-allocation spectral bank");
-    static_assert(!MEL || (!XFADE && !BUCKETS), "log-mel: plain rows of a single-allocation bank");
+    static_assert(!MEL || !XFADE, "log-mel: plain rows (of one allocation, or of a length-bucketed fp32 bank)");
     __shared__ c32 lds[16 * kWaveScratch > kLdsComplex ? 16 * kWaveScratch : kLdsComplex];
     __shared__ float s_win[kNfft];
     __shared__ c32 s_tw512[kTw512Lds];

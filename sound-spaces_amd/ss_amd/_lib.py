@@ -23,7 +23,8 @@ EXPORTS = ("ss_block_len", "ss_spec_floats", "ss_version", "ss_init", "ss_source
            "ss_rir_spectra16_f32", "ss_bank_scatter_spectra16_f32", "ss_fftconv_binaural_spec16_f32", "ss_audio_obs_spec16_f32",
            "ss_audio_obs_logmel_spec16_f32", "ss_ctx_set_rir_spectra16",
            "ss_audio_obs_rows_spec16_f32", "ss_audio_obs_logmel_rows_spec16_f32", "ss_ctx_set_rir_spectra16_rows",
-           "ss_fftconv_binaural_spec_buckets_f32", "ss_audio_obs_spec_buckets_f32", "ss_ctx_set_rir_spec_buckets")
+           "ss_fftconv_binaural_spec_buckets_f32", "ss_audio_obs_spec_buckets_f32", "ss_ctx_set_rir_spec_buckets",
+           "ss_audio_obs_logmel_buckets_f32", "ss_audio_obs_logmel_spec_buckets_f32", "ss_ctx_set_logmel_buckets_policy")
 # entries that return a size_t, not a status (EXPORTS: every `int ss_*` of include/ss_hip.h)
 EXPORTS_SIZE = ("ss_ctx_wave_scratch_bytes",)
 
@@ -174,6 +175,11 @@ def load() -> ctypes.CDLL:
     lib.ss_fftconv_binaural_spec_buckets_f32.argtypes = lib.ss_fftconv_binaural_buckets_f32.argtypes
     lib.ss_audio_obs_spec_buckets_f32.argtypes = lib.ss_audio_obs_buckets_f32.argtypes
     lib.ss_ctx_set_rir_spec_buckets.argtypes = [vp, vp, c_int, vp]
+    # log-mel from length buckets of either kind: the bucket array, the outputs and mel arguments of ss_audio_obs_logmel_f32
+    lib.ss_audio_obs_logmel_buckets_f32.argtypes = [vp, vp, c_int, vp, vp, vp, vp, vp, vp, vp, c_int, c_int, ctypes.c_float, c_int,
+                                                    c_int, c_int, c_int, c_int, vp]
+    lib.ss_audio_obs_logmel_spec_buckets_f32.argtypes = lib.ss_audio_obs_logmel_buckets_f32.argtypes
+    lib.ss_ctx_set_logmel_buckets_policy.argtypes = [vp, c_int, c_int]
     for name in EXPORTS:
         getattr(lib, name).restype = c_int
     for name in EXPORTS_SIZE:

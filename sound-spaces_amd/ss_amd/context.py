@@ -231,6 +231,17 @@ class AudioContext:
         _lib.check(self.lib.ss_ctx_set_logmel_ss2_policy(self._h, int(min_units), int(max_units)),
                    "ss_ctx_set_logmel_ss2_policy")
 
+    def set_logmel_buckets_policy(self, min_units: int, max_units: int) -> None:
+        """``set_logmel_policy`` for contexts bound by ``set_rir_buckets`` / ``set_rir_spec_buckets``: log-mel steps without a
+        waveform buffer of ``min_units`` .. ``max_units`` units, without a cross-fade, take the one-launch fused kernels of the
+        length-bucketed banks (one-block rows on every bank form, 44.1 / 48 kHz rows on the fp32 forms;
+        ss_ctx_set_logmel_buckets_policy).  The three setters above never apply to such a context.  Default (1, 0): never -
+        the scratch route is bit-equal to observe-then-features, the fused launch only to rounding.  (1, 2**31 - 1): whenever
+        the shape allows - the range the measurements support at 16 kHz; at 44.1 kHz they support (1, 42) for log-mel alone
+        (profiles/r7/NOTES.md)."""
+        _lib.check(self.lib.ss_ctx_set_logmel_buckets_policy(self._h, int(min_units), int(max_units)),
+                   "ss_ctx_set_logmel_buckets_policy")
+
     def wave_scratch_bytes(self) -> int:
         """Bytes of waveform scratch the context holds over all overlap lanes (ss_ctx_wave_scratch_bytes): 0 until a log-mel
         step without a waveform buffer takes the scratch route, and again after ``ss_release_scratch``."""

@@ -561,6 +561,36 @@ def audio_obs_spec_buckets_into(spec, buckets, n_buckets: int, rir_len, unit_des
                    "ss_audio_obs_spec_buckets_f32")
 
 
+def _obs_logmel_buckets(entry: str, spec, buckets, n_buckets, rir_len, unit_desc, audiogoal, spectrogram_out, logmel_out, mel_start,
+                        mel_w, n_valid, out_len, mel_eps, pad_mode, flags) -> None:
+    _chk(spec, torch.float32, "spec"); _chk(rir_len, torch.int32, "rir_len")
+    N, n_mels, max_len, ag_ptr, sg_ptr = _obs_logmel_args(unit_desc, audiogoal, spectrogram_out, logmel_out, mel_start, mel_w, out_len)
+    with torch.cuda.device(spec.device):
+        _lib.check(getattr(_lib.load(), entry)(spec.data_ptr(), ctypes_ref(buckets), n_buckets, rir_len.data_ptr(),
+                                               unit_desc.data_ptr(), ag_ptr, sg_ptr, logmel_out.data_ptr(), mel_start.data_ptr(),
+                                               mel_w.data_ptr(), int(n_mels), int(max_len), float(mel_eps), N, n_valid, out_len,
+                                               _PAD[pad_mode], flags, _stream(spec)), entry)
+
+
+def audio_obs_logmel_buckets_into(spec, buckets, n_buckets: int, rir_len, unit_desc, audiogoal, spectrogram_out, logmel_out,
+                                  mel_start, mel_w, n_valid: int, out_len: int, mel_eps: float = 1e-6, pad_mode="reflect",
+                                  flags: int = 0) -> None:
+    """``audio_obs_logmel_into`` / ``audio_obs_logmel_rows_into`` on a length-bucketed bank (``ss_audio_obs_logmel_buckets_f32``;
+    ``buckets`` = ``bucket_array(...)``): ONE launch, whichever outputs are asked for next to ``logmel_out``.  Rows of one
+    partition block, and of 2 or 3 blocks with at most 16 RIR blocks in the deepest bucket; no cross-fade."""
+    _obs_logmel_buckets("ss_audio_obs_logmel_buckets_f32", spec, buckets, n_buckets, rir_len, unit_desc, audiogoal, spectrogram_out,
+                        logmel_out, mel_start, mel_w, n_valid, out_len, mel_eps, pad_mode, flags)
+
+
+def audio_obs_logmel_spec_buckets_into(spec, buckets, n_buckets: int, rir_len, unit_desc, audiogoal, spectrogram_out, logmel_out,
+                                       mel_start, mel_w, n_valid: int, out_len: int, mel_eps: float = 1e-6, pad_mode="reflect",
+                                       flags: int = 0) -> None:
+    """``audio_obs_logmel_buckets_into`` on spectral length buckets (``ss_audio_obs_logmel_spec_buckets_f32``; ``buckets`` =
+    ``spec_bucket_array(...)``).  A half bank serves rows of one partition block here."""
+    _obs_logmel_buckets("ss_audio_obs_logmel_spec_buckets_f32", spec, buckets, n_buckets, rir_len, unit_desc, audiogoal,
+                        spectrogram_out, logmel_out, mel_start, mel_w, n_valid, out_len, mel_eps, pad_mode, flags)
+
+
 def ctypes_ref(arr):
     import ctypes
     return ctypes.cast(arr, ctypes.c_void_p)
