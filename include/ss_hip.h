@@ -722,6 +722,66 @@ int ss_ctx_stats(ss_ctx* ctx, long long* out8);
  * (A getter of its own: ss_ctx_stats keeps its eight words.) */
 int ss_ctx_ring_stats(ss_ctx* ctx, long long* out4);
 
+/* ---- Pose memo on the column path ----------------------------------------------------------------------------------
+ * The reference memoises observations per pose (soundspaces/simulator.py:678-701): the key is (source, receiver, azimuth)
+ * and ignores _audio_index; _audio_index advances inside a miss only (:634-635); the caches are dropped on a scene or sound
+ * change (:395-397).  For multi-second sounds this changes what the agent hears: an agent that stands still or comes back
+ * to a pose gets the observation FIRST rendered there again.  The entries below reproduce it inside the step's call.
+ *
+ * ss_memo_rows_f32 (k_memo_rows, stateless): one launch moves rows between up to 4 (output, pool) array pairs.  moves =
+ * {row, slot} per move: the first n_store moves STORE row `row` of every io[a].out into row `slot` of io[a].pool, the
+ * following n_fetch moves FETCH pool row `slot` into output row `row`.  Rows are contiguous, row i at base + i * row_floats.
+ * `moves` may be device memory or pinned host memory (the kernel reads it in place; pageable host memory is refused).
+ * PRECONDITION: rows are distinct and slots are distinct over the WHOLE list - one launch then needs no ordering between
+ * its moves (a list that breaks it has an unspecified result in the rows named twice).  Access width per pair from what
+ * both bases and row_floats allow: 16 bytes, else 8, else 4.  Rows and slots that are not named, and bytes behind a row's
+ * end, are never touched.  n_store + n_fetch == 0 returns 0 without a launch.  SS_EINVAL before a device is touched: n_io
+ * outside 1..4, negative counts, and with moves pending a NULL io / out / pool / moves, row_floats < 1, a base that is not
+ * 4-byte aligned.  Asynchronous on `stream`. */
+typedef struct ss_memo_io { float* out; float* pool; int row_floats; int reserved; } ss_memo_io;
+int ss_memo_rows_f32(const ss_memo_io* io, int n_io, const int* moves, int n_store, int n_fetch, void* stream);
+/* The memo of a context (host state; csrc/ss_memo.hpp): per env a tag (scene, sound) and a map pose key -> pool row, one
+ * free list over the caller's pool rows.  n_envs >= 1 switches it on for steps of exactly n_envs envs (again: reset with a
+ * new size); 0 switches it off and frees the state.  _reset forgets every pose and the counters (the pools' contents become
+ * meaningless); _stats: out4 = {hits, misses, pool rows in use, maps dropped by a scene / sound change}.  _reset and _stats
+ * are SS_EINVAL while the memo is off. */
+int ss_ctx_memo_enable(ss_ctx* ctx, int n_envs);
+int ss_ctx_memo_reset(ss_ctx* ctx);
+int ss_ctx_memo_stats(ss_ctx* ctx, long long* out4);
+/* The device-side pools, owned by the caller: `rows` rows each, a row the size of one env's output row ([65,T4,2] /
+ * [2,sr] floats).  An array is given exactly when its output is.  The caller may replace them by LARGER ones (contents
+ * kept, ordered against the step streams by the caller: in overlap mode ss_ctx_join first); rows never shrinks below the
+ * value rows were last handed out of (SS_EINVAL; ss_ctx_memo_reset starts over). */
+typedef struct ss_memo_pool { float* spectrogram; float* audiogoal; int rows; int reserved; } ss_memo_pool;
+/* ss_ctx_observe_sims with the memo inside: plan, render, move - in that order.
+ *   plan:   an env whose (scene, sound) changed drops its map first (its rows are free again and may serve this very step);
+ *           an env whose pose key (src << 40 | recv << 20 | azimuth) is present is a HIT and is HELD: a silent unit, no RIR
+ *           looked up (never an RIR miss), audio_index not advanced; every other env is a MISS: rendered as
+ *           ss_ctx_observe_sims renders it and given a free pool row - silent envs too (the reference caches its zeros
+ *           under the pose as well);
+ *   render: as ss_ctx_observe, held envs as silent units;
+ *   move:   k_memo_rows on the same stream right behind the step's launches (overlap mode: on the step's lane, behind the
+ *           other lanes' latest moves by stream waits - no join is needed for it and none is issued; results are visible to
+ *           a stream after ss_ctx_join as for every step).  The move list travels in the kernel arguments: no copy, no host
+ *           wait, nothing of the descriptor ring is read.
+ * TRANSACTIONAL: a non-resident pair of an env that is neither held nor silent (*n_miss > 0, indices in miss_out, capacity n)
+ * or too few free pool rows (*need_rows = rows the pools need in total, > pool->rows) launches nothing and commits nothing -
+ * no audio_index change, no memo entry, no move - and returns 0; both may be reported by one call.  Otherwise
+ * *need_rows = 0.  A step that fails with an error commits nothing either.
+ * SS_EINVAL: the memo is off; n != n_envs; cols->dis_sound / dis_src != NULL (the reference bypasses its caches with a
+ * distractor, :679-681 - use ss_ctx_observe_sims there); pool == NULL or pool->rows < 0 or below the rows already handed
+ * out; an output without its pool array or a pool array without its output; a set of outputs other than the one the memo's
+ * rows were first stored with; everything ss_ctx_observe_sims refuses.
+ * Pool row numbering is the library's own. */
+int ss_ctx_observe_sims_memo(ss_ctx* ctx, const ss_sim_columns* cols, int n, float* audiogoal, float* spectrogram,
+                             const ss_memo_pool* pool, int* miss_out, int* n_miss, int* need_rows, void* stream);
+/* The host half alone (needs no GPU; commits exactly as the full call would, the set of outputs apart): units_out int32
+ * [5, n] as ss_ctx_sims_units (held envs silent), hold_out [n] 1 = held, moves_out int32 [n][2] = {env, pool row}: the
+ * step's *n_store misses first, then its *n_fetch hits (both 0 when the step was not committed). */
+int ss_ctx_sims_memo_plan(ss_ctx* ctx, const ss_sim_columns* cols, int n, int pool_rows, int* units_out,
+                          unsigned char* hold_out, int* moves_out, int* n_store, int* n_fetch, int* miss_out, int* n_miss,
+                          int* need_rows);
+
 /* ---- RIR files -> staging rows (the step BEFORE the path: SURVEY 8(f)2) ---------------------------------------------
  * Replaces the reference's per-miss `scipy.io.wavfile.read(binaural_rir_file)` (soundspaces/simulator.py:615-618, float32
  * stereo files under <binaural_rir_dir>/<azimuth>/<recv>_<src>.wav) for bulk loads and the per-step pose misses of the

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../include/ss_hip.h"
+#include "ss_memo.hpp"
 #include "ss_ring.hpp"
 
 namespace ssctx {
@@ -137,6 +138,17 @@ struct Context {
     hipEvent_t ev_done_l[kLanes][kRing / kGroup] = {};   // ring release, lane l's share of a group (l >= 1; lane 0 / single
                                                          // stream: ev_done)
     bool lanes_made = false;
+    // pose memo of the column path (ss_ctx_memo_enable / ss_ctx_observe_sims_memo; ss_memo.hpp)
+    bool memo_on = false;
+    ssmemo::Memo memo;
+    int memo_outputs = 0;                         // bit 0 audiogoal, bit 1 spectrogram: what the memo's rows were first stored with (0: nothing yet)
+    std::vector<int> memo_moves;                  // [n][2] of the step
+    // overlap mode: the pools are shared by the lanes (a row stored on one lane is fetched, or stored again, on another) - each
+    // lane's k_memo_rows goes behind the other lanes' latest one
+    hipEvent_t ev_memo[kLanes] = {};
+    bool memo_ev_made = false;
+    long long memo_seq[kLanes] = {};
+    long long memo_seen[kLanes][kLanes] = {};
 };
 
 inline uint64_t make_key(int sound, long long t0, bool wrap) {

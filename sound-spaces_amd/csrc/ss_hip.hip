@@ -1319,6 +1319,54 @@ int ss_audio_obs_logmel_rows_spec16_f32(const float* spec, const void* hspec16, 
     return launch_obs_rows<true, true, true>(p, n_units, flags, n_cus, static_cast<hipStream_t>(stream), m, ssk::SpecScale<true>{hscale});
 }
 
+// ---- pose memo: the row copies (k_memo_rows) ---------------------------------------------------------------------------
+static bool memo_io_ok(const ss_memo_io* io, int n_io) {
+    if (!io || n_io < 1 || n_io > ssk::kMemoArrays) return false;
+    for (int a = 0; a < n_io; ++a)
+        if (!io[a].out || !io[a].pool || io[a].row_floats < 1 || ((reinterpret_cast<size_t>(io[a].out) | reinterpret_cast<size_t>(io[a].pool)) & 3))
+            return false;
+    return true;
+}
+
+// host_moves: `moves` is a HOST list the launch carries in its kernel arguments, kMemoTabMoves moves at a time (the moves are
+// independent of each other: several launches are as good as one); else device-accessible memory the kernel reads in place
+static int launch_memo_rows(const ss_memo_io* io, int n_io, const int* moves, bool host_moves, int n_store, int n_fetch, hipStream_t st) {
+    ssk::MemoRowsParams p;
+    int longest = 1;
+    for (int a = 0; a < ssk::kMemoArrays; ++a) {
+        const ss_memo_io& x = io[a < n_io ? a : 0];
+        p.out[a] = x.out; p.pool[a] = x.pool; p.row_floats[a] = x.row_floats;
+        if (x.row_floats > longest) longest = x.row_floats;
+    }
+    const unsigned gx = static_cast<unsigned>((static_cast<long long>(longest) + ssk::kMemoChunk - 1) / ssk::kMemoChunk);
+    const int n = n_store + n_fetch, per = host_moves ? ssk::kMemoTabMoves : 65535;      // (65535: grid.y limit)
+    for (int lo = 0; lo < n; lo += per) {
+        const int m = n - lo < per ? n - lo : per;
+        p.n_store = n_store - lo < 0 ? 0 : (n_store - lo < m ? n_store - lo : m);
+        if (host_moves) {
+            ssk::MoveTab<true> mt;
+            std::memcpy(mt.mv, moves + 2 * static_cast<size_t>(lo), sizeof(int) * 2 * static_cast<size_t>(m));
+            p.moves = nullptr;
+            hipLaunchKernelGGL(ssk::k_memo_rows<true>, dim3(gx, m, n_io), dim3(256), 0, st, p, mt);
+        } else {
+            p.moves = moves + 2 * static_cast<size_t>(lo);
+            hipLaunchKernelGGL(ssk::k_memo_rows<false>, dim3(gx, m, n_io), dim3(256), 0, st, p, ssk::MoveTab<false>());
+        }
+    }
+    return hip_err(hipGetLastError());
+}
+
+int ss_memo_rows_f32(const ss_memo_io* io, int n_io, const int* moves, int n_store, int n_fetch, void* stream) {
+    if (n_io < 1 || n_io > ssk::kMemoArrays || n_store < 0 || n_fetch < 0 || n_store > 0x7fffffff - n_fetch) return SS_EINVAL;
+    if (n_store + n_fetch == 0) return 0;
+    if (!moves || !memo_io_ok(io, n_io)) return SS_EINVAL;
+    // the kernel dereferences `moves`: pageable host memory would be a GPU memory fault, not an error code
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, moves) != hipSuccess) { (void)hipGetLastError(); return SS_EINVAL; }
+    if (attr.type != hipMemoryTypeHost && attr.type != hipMemoryTypeDevice && attr.type != hipMemoryTypeManaged) return SS_EINVAL;
+    return launch_memo_rows(io, n_io, moves, false, n_store, n_fetch, static_cast<hipStream_t>(stream));
+}
+
 // ---- context API (include/ss_hip.h): planner + window-spectra cache + descriptor ring inside the library --------------
 struct ss_ctx { ssctx::Context c; };
 
@@ -1354,6 +1402,10 @@ static void ctx_free_device(ssctx::Context& c) {
     if (c.ev_xstream) (void)hipEventDestroy(c.ev_xstream);
     if (c.miss_ev) { (void)hipEventDestroy(static_cast<hipEvent_t>(c.miss_ev)); c.miss_ev = nullptr; }
     c.ev_xstream = nullptr; c.have_last_stream = false;
+    if (c.memo_ev_made) {
+        for (int l = 0; l < ssctx::kLanes; ++l) (void)hipEventDestroy(c.ev_memo[l]);
+        c.memo_ev_made = false;
+    }
     if (c.lanes_made) {
         for (int l = 0; l < ssctx::kLanes; ++l) {
             (void)hipStreamSynchronize(c.lane_stream[l]);
@@ -2091,7 +2143,11 @@ int ss_ctx_observe_features(ss_ctx* h, const ss_units* units, int n, float* audi
 
 
 }  // extern "C"
-static int sims_to_units(ss_ctx* h, const ss_sim_columns* sc, int n, int* w, int* miss_out, int* n_miss);
+// hold (pose memo): envs served from the memo this step - silent units, no RIR looked up, never a miss; advance = false: leave
+// audio_index alone (sims_advance does pass 2 once the step is certain to go ahead)
+static int sims_to_units(ss_ctx* h, const ss_sim_columns* sc, int n, int* w, int* miss_out, int* n_miss,
+                         const unsigned char* hold = nullptr, bool advance = true);
+static void sims_advance(ss_ctx* h, const ss_sim_columns* sc, int n, const int* w);
 extern "C" {
 
 // One step from the simulators' state columns (see include/ss_hip.h): the per-step numpy of ss_amd/vector.py in C++.
@@ -2114,9 +2170,133 @@ int ss_ctx_observe_sims(ss_ctx* h, const ss_sim_columns* sc, int n, float* audio
     return ss_ctx_observe(h, &u, n, audiogoal, spectrogram, stream);
 }
 
+// ---- pose memo on the column path (ss_memo.hpp) ---------------------------------------------------------------------
+int ss_ctx_memo_enable(ss_ctx* h, int n_envs) {
+    if (!h || n_envs < 0) return SS_EINVAL;
+    ssctx::Context& c = h->c;
+    c.memo.reset(n_envs);
+    c.memo_on = n_envs > 0;
+    c.memo_outputs = 0;
+    if (!c.memo_on) { c.memo = ssmemo::Memo(); std::vector<int>().swap(c.memo_moves); }
+    return 0;
+}
+
+int ss_ctx_memo_reset(ss_ctx* h) {
+    if (!h || !h->c.memo_on) return SS_EINVAL;
+    h->c.memo.clear();
+    h->c.memo_outputs = 0;
+    return 0;
+}
+
+int ss_ctx_memo_stats(ss_ctx* h, long long* out4) {
+    if (!h || !out4 || !h->c.memo_on) return SS_EINVAL;
+    const ssmemo::Memo& m = h->c.memo;
+    out4[0] = m.hits; out4[1] = m.misses; out4[2] = m.in_use; out4[3] = m.dropped;
+    return 0;
+}
+
 }  // extern "C"
 
-static int sims_to_units(ss_ctx* h, const ss_sim_columns* sc, int n, int* w, int* miss_out, int* n_miss) {
+// The host half of a memo step up to the point of no return: memo plan (who is held), unit columns with the hold mask, RIR
+// misses.  Changes nothing.  *need_rows / *n_miss say whether the step may go ahead.
+static int memo_plan_step(ss_ctx* h, const ss_sim_columns* sc, int n, int pool_rows, int* w, int* miss_out, int* n_miss,
+                          int* need_rows) {
+    if (!h || !sc || !n_miss || !need_rows || !h->c.memo_on || n != h->c.memo.n_envs() || pool_rows < 0 || sc->dis_sound ||
+        sc->dis_src)
+        return SS_EINVAL;
+    ssmemo::Memo& m = h->c.memo;
+    *n_miss = 0; *need_rows = 0;
+    const int need = m.plan(sc->scene, sc->sound, sc->src, sc->recv, sc->rot, n, pool_rows);
+    if (need < 0) return SS_EINVAL;
+    const int rc = sims_to_units(h, sc, n, w, miss_out, n_miss, m.hold.data(), false);
+    if (rc) return rc;
+    *need_rows = need;
+    return 0;
+}
+
+// ... and past it: audio_index advances for the envs that were rendered, the memo takes the step's entries.  -> moves
+static void memo_commit_step(ss_ctx* h, const ss_sim_columns* sc, int n, const int* w, int* moves, int* n_store, int* n_fetch) {
+    sims_advance(h, sc, n, w);
+    h->c.memo.commit(sc->scene, sc->sound, moves, n_store, n_fetch);
+}
+
+extern "C" {
+
+int ss_ctx_sims_memo_plan(ss_ctx* h, const ss_sim_columns* sc, int n, int pool_rows, int* units_out, unsigned char* hold_out,
+                          int* moves_out, int* n_store, int* n_fetch, int* miss_out, int* n_miss, int* need_rows) {
+    if (!units_out || !hold_out || !moves_out || !n_store || !n_fetch) return SS_EINVAL;
+    const int rc = memo_plan_step(h, sc, n, pool_rows, units_out, miss_out, n_miss, need_rows);
+    if (rc) return rc;
+    *n_store = *n_fetch = 0;
+    std::memcpy(hold_out, h->c.memo.hold.data(), static_cast<size_t>(n));
+    if (*n_miss || *need_rows) return 0;
+    memo_commit_step(h, sc, n, units_out, moves_out, n_store, n_fetch);
+    return 0;
+}
+
+int ss_ctx_observe_sims_memo(ss_ctx* h, const ss_sim_columns* sc, int n, float* audiogoal, float* spectrogram,
+                             const ss_memo_pool* pool, int* miss_out, int* n_miss, int* need_rows, void* stream) {
+    if (!h || !pool || pool->rows < 0 || (!audiogoal && !spectrogram) || !audiogoal != !pool->audiogoal ||
+        !spectrogram != !pool->spectrogram)
+        return SS_EINVAL;
+    ssctx::Context& c = h->c;
+    const int outputs = (audiogoal ? 1 : 0) | (spectrogram ? 2 : 0);
+    if (c.memo_on && c.memo_outputs && outputs != c.memo_outputs) return SS_EINVAL;
+    ss_memo_io io[2];
+    int n_io = 0;
+    const int t4 = t4_of(c.out_len);
+    if (spectrogram) io[n_io++] = ss_memo_io{spectrogram, pool->spectrogram, ssk::kBins4 * t4 * 2, 0};
+    if (audiogoal) io[n_io++] = ss_memo_io{audiogoal, pool->audiogoal, 2 * c.out_len, 0};
+    if (!memo_io_ok(io, n_io)) return SS_EINVAL;
+    std::vector<int>& w = c.sim_scratch;
+    w.resize(static_cast<size_t>(n < 0 ? 0 : n) * 5 + 1);
+    int rc = memo_plan_step(h, sc, n, pool->rows, w.data(), miss_out, n_miss, need_rows);
+    if (rc != 0 || *n_miss || *need_rows) return rc;                      // refused or reported: nothing launched, nothing committed
+    ss_units u;
+    std::memset(&u, 0, sizeof u);
+    u.sound = w.data(); u.t0 = u.sound + n; u.rir = u.t0 + n;
+    rc = ss_ctx_observe(h, &u, n, audiogoal, spectrogram, stream);       // held envs are silent units
+    if (rc) return rc;                                                    // (a step that failed commits nothing either)
+    c.memo_moves.resize(static_cast<size_t>(n) * 2);
+    int n_store = 0, n_fetch = 0;
+    memo_commit_step(h, sc, n, w.data(), c.memo_moves.data(), &n_store, &n_fetch);
+    c.memo_outputs = outputs;
+    // the row copies go right behind the step's launches, on the stream that carries them: the caller's, or in overlap mode the
+    // lane the step was given - there behind the other lanes' latest copies as well (the pools are shared by the lanes; the
+    // renders stay unordered), which takes stream waits, no join and no host wait.  The moves travel in the kernel arguments:
+    // nothing of the step's ring slot is read.
+    hipStream_t st = c.n_lanes > 1 ? c.last_stream : static_cast<hipStream_t>(stream);
+    int lane = -1;
+    for (int l = 0; l < c.n_lanes && c.n_lanes > 1; ++l)
+        if (c.lane_stream[l] == st) lane = l;
+    hipError_t e = hipSuccess;
+    if (lane >= 0) {
+        if (!c.memo_ev_made) {
+            for (int l = 0; l < ssctx::kLanes && e == hipSuccess; ++l) e = hipEventCreateWithFlags(&c.ev_memo[l], hipEventDisableTiming);
+            if (e != hipSuccess) return hip_err(e);
+            c.memo_ev_made = true;
+        }
+        for (int o = 0; o < ssctx::kLanes; ++o) {
+            if (o == lane || c.memo_seen[lane][o] >= c.memo_seq[o]) continue;
+            e = hipStreamWaitEvent(st, c.ev_memo[o], 0);
+            if (e != hipSuccess) return hip_err(e);
+            c.memo_seen[lane][o] = c.memo_seq[o];
+        }
+    }
+    rc = launch_memo_rows(io, n_io, c.memo_moves.data(), true, n_store, n_fetch, st);
+    if (rc) return rc;
+    if (lane >= 0) {
+        e = hipEventRecord(c.ev_memo[lane], st);
+        if (e != hipSuccess) return hip_err(e);
+        ++c.memo_seq[lane];
+    }
+    return 0;
+}
+
+}  // extern "C"
+
+static int sims_to_units(ss_ctx* h, const ss_sim_columns* sc, int n, int* w, int* miss_out, int* n_miss,
+                         const unsigned char* hold, bool advance) {
     if (!h || !sc || n < 0 || !n_miss || !sc->sound || !sc->audio_index || !sc->step_count || !sc->duration || !sc->recv ||
         !sc->src || !sc->rot || !sc->scene || !sc->index_flat || !sc->index_off || !sc->index_dim || sc->azimuths < 1 ||
         360 % sc->azimuths || (!sc->dis_sound != !sc->dis_src))
@@ -2141,7 +2321,7 @@ static int sims_to_units(ss_ctx* h, const ss_sim_columns* sc, int n, int* w, int
     int misses = 0;
     for (int i = 0; i < n; ++i) {                              // pass 1: everything except the audio_index advance
         const long long s = sc->sound[i];
-        const bool silent = s < 0 || s >= n_src || sc->step_count[i] > sc->duration[i];
+        const bool silent = s < 0 || s >= n_src || sc->step_count[i] > sc->duration[i] || (hold && hold[i]);
         sound[i] = silent ? 0 : static_cast<int>(s);
         dsound[i] = 0; drir[i] = -1;
         if (silent) { rir[i] = -1; t0[i] = 0; continue; }
@@ -2161,12 +2341,18 @@ static int sims_to_units(ss_ctx* h, const ss_sim_columns* sc, int n, int* w, int
         misses += miss;
     }
     if (misses) { *n_miss = misses; return 0; }
+    if (advance) sims_advance(h, sc, n, w);
+    return 0;
+}
+
+static void sims_advance(ss_ctx* h, const ss_sim_columns* sc, int n, const int* w) {
+    const ssctx::Context& c = h->c;
+    const int* sound = w; const int* rir = w + 2 * static_cast<size_t>(n);
     for (int i = 0; i < n; ++i) {                              // pass 2: simulator.py:634-635
         if (rir[i] < 0) continue;
         const int len = c.src_len[sound[i]];
         if (len != c.sr && len >= c.sr) sc->audio_index[i] = (sc->audio_index[i] + 1) % (len / c.sr);
     }
-    return 0;
 }
 
 // ---- request records of a multi-process vector env (ss_amd/deferred.py) -> unit columns ------------------------------

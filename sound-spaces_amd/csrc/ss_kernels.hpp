@@ -2919,6 +2919,70 @@ __global__ __launch_bounds__(256) void k_scatter_rows(ScatterRowsParams p) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// k_memo_rows: the row copies of the pose memo (ss_memo.hpp; reference: the per-pose caches of soundspaces/simulator.py:678-701).
+// One launch moves observation rows between a step's output arrays and device-side pools, for up to kMemoArrays (output, pool)
+// pairs at once: move m < n_store STORES row `row` of every output into row `slot` of its pool (this step's misses), the
+// others FETCH pool row `slot` into output row `row` (this step's hits).  moves = {row, slot} per move, read in place from
+// device or pinned host memory (TAB = false), or carried in the kernel arguments when the host knows them (TAB = true: <=
+// kMemoTabMoves moves, no pointer is dereferenced for them).  Rows are distinct and slots are distinct over the whole list, so
+// no move depends on another and workgroups never communicate.  Grid (chunks of kMemoChunk floats, move, array), 256 threads;
+// a chunk is read whole before it is written (four 16-byte loads in flight per thread).  Access width per array from what
+// both bases and the row size allow: 16 bytes, else 8 (the 44.1 kHz spectrogram row: 65 x 69 x 2 = 8970 floats), else 4.
+// Rows and slots not named, and bytes behind a row's end, are never touched.
+constexpr int kMemoArrays = 4;
+constexpr int kMemoTabMoves = 256;
+constexpr int kMemoChunk = 4096;
+struct MemoRowsParams {
+    float* out[kMemoArrays];       // row i of array a at out[a] + i * row_floats[a]
+    float* pool[kMemoArrays];
+    int row_floats[kMemoArrays];
+    const int* moves;              // [n][2] (TAB = false)
+    int n_store;                   // moves [0, n_store) store, the others fetch
+};
+template <bool TAB>
+struct MoveTab { };
+template <>
+struct MoveTab<true> { int mv[2 * kMemoTabMoves]; };
+static_assert(sizeof(MemoRowsParams) + sizeof(MoveTab<true>) + 64 <= 4096, "kernel arguments of k_memo_rows<true>");
+
+template <bool TAB>
+__global__ __launch_bounds__(256) void k_memo_rows(MemoRowsParams p, MoveTab<TAB> mt = MoveTab<TAB>()) {
+    const int a = blockIdx.z, m = blockIdx.y, t = threadIdx.x;
+    const int rf = p.row_floats[a];
+    const long long e0 = (long long)blockIdx.x * kMemoChunk;
+    if (e0 >= rf) return;                                  // (the grid's x extent is the longest array's)
+    int row, slot;
+    if constexpr (TAB) { row = mt.mv[2 * m]; slot = mt.mv[2 * m + 1]; }
+    else { row = p.moves[2 * m]; slot = p.moves[2 * m + 1]; }
+    float* o = p.out[a] + (size_t)row * rf;
+    float* q = p.pool[a] + (size_t)slot * rf;
+    const bool store = m < p.n_store;
+    const float* src = (store ? o : q) + e0;
+    float* dst = (store ? q : o) + e0;
+    const int left = (int)(rf - e0 < kMemoChunk ? rf - e0 : kMemoChunk);
+    const unsigned al = (unsigned)(reinterpret_cast<size_t>(p.out[a]) | reinterpret_cast<size_t>(p.pool[a])) | ((unsigned)rf << 2);
+    if ((al & 15u) == 0) {                                 // every row of both arrays starts on 16 bytes and ends on 16
+        f32x4 v[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { const int e = k * 1024 + 4 * t; if (e < left) v[k] = *reinterpret_cast<const f32x4*>(src + e); }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { const int e = k * 1024 + 4 * t; if (e < left) *reinterpret_cast<f32x4*>(dst + e) = v[k]; }
+    } else if ((al & 7u) == 0) {
+        c32 v[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) { const int e = k * 512 + 2 * t; if (e < left) v[k] = *reinterpret_cast<const c32*>(src + e); }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) { const int e = k * 512 + 2 * t; if (e < left) *reinterpret_cast<c32*>(dst + e) = v[k]; }
+    } else {
+        float v[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) { const int e = k * 256 + t; if (e < left) v[k] = src[e]; }
+#pragma unroll
+        for (int k = 0; k < 16; ++k) { const int e = k * 256 + t; if (e < left) dst[e] = v[k]; }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // k_stage_spectra: the miss path of a SPECTRAL-ONLY bank (no time-domain rows).  n staged rows -> the block spectra
 // H'_b = 2*rFFT_{2kB}(row[b*kB : (b+1)*kB]) of both ears, straight into entry slots[i] of the spectral bank, and the rows'
 // lengths into its length table: one launch where a bank that keeps rows takes two (k_scatter_rows, then k_source_windows

@@ -24,7 +24,9 @@ EXPORTS = ("ss_block_len", "ss_spec_floats", "ss_version", "ss_init", "ss_source
            "ss_audio_obs_logmel_spec16_f32", "ss_ctx_set_rir_spectra16",
            "ss_audio_obs_rows_spec16_f32", "ss_audio_obs_logmel_rows_spec16_f32", "ss_ctx_set_rir_spectra16_rows",
            "ss_fftconv_binaural_spec_buckets_f32", "ss_audio_obs_spec_buckets_f32", "ss_ctx_set_rir_spec_buckets",
-           "ss_audio_obs_logmel_buckets_f32", "ss_audio_obs_logmel_spec_buckets_f32", "ss_ctx_set_logmel_buckets_policy")
+           "ss_audio_obs_logmel_buckets_f32", "ss_audio_obs_logmel_spec_buckets_f32", "ss_ctx_set_logmel_buckets_policy",
+           "ss_memo_rows_f32", "ss_ctx_memo_enable", "ss_ctx_memo_reset", "ss_ctx_memo_stats", "ss_ctx_observe_sims_memo",
+           "ss_ctx_sims_memo_plan")
 # entries that return a size_t, not a status (EXPORTS: every `int ss_*` of include/ss_hip.h)
 EXPORTS_SIZE = ("ss_ctx_wave_scratch_bytes",)
 
@@ -55,6 +57,16 @@ class SsMissLoader(ctypes.Structure):
                 ("n_evicted", ctypes.c_int), ("evict_cap", ctypes.c_int),
                 ("loaded_key", ctypes.c_void_p), ("loaded_slot", ctypes.c_void_p), ("loaded_frames", ctypes.c_void_p),
                 ("n_loaded", ctypes.c_int), ("loaded_cap", ctypes.c_int)]
+
+
+class SsMemoIo(ctypes.Structure):
+    """struct ss_memo_io of include/ss_hip.h."""
+    _fields_ = [("out", ctypes.c_void_p), ("pool", ctypes.c_void_p), ("row_floats", ctypes.c_int), ("reserved", ctypes.c_int)]
+
+
+class SsMemoPool(ctypes.Structure):
+    """struct ss_memo_pool of include/ss_hip.h."""
+    _fields_ = [("spectrogram", ctypes.c_void_p), ("audiogoal", ctypes.c_void_p), ("rows", ctypes.c_int), ("reserved", ctypes.c_int)]
 
 
 class SsSimColumns(ctypes.Structure):
@@ -180,6 +192,13 @@ def load() -> ctypes.CDLL:
                                                     c_int, c_int, c_int, c_int, vp]
     lib.ss_audio_obs_logmel_spec_buckets_f32.argtypes = lib.ss_audio_obs_logmel_buckets_f32.argtypes
     lib.ss_ctx_set_logmel_buckets_policy.argtypes = [vp, c_int, c_int]
+    # pose memo of the column path
+    lib.ss_memo_rows_f32.argtypes = [vp, c_int, vp, c_int, c_int, vp]
+    lib.ss_ctx_memo_enable.argtypes = [vp, c_int]
+    lib.ss_ctx_memo_reset.argtypes = [vp]
+    lib.ss_ctx_memo_stats.argtypes = [vp, vp]
+    lib.ss_ctx_observe_sims_memo.argtypes = [vp, ctypes.POINTER(SsSimColumns), c_int, vp, vp, vp, vp, vp, vp, vp]
+    lib.ss_ctx_sims_memo_plan.argtypes = [vp, ctypes.POINTER(SsSimColumns), c_int, c_int, vp, vp, vp, vp, vp, vp, vp, vp]
     for name in EXPORTS:
         getattr(lib, name).restype = c_int
     for name in EXPORTS_SIZE:

@@ -410,6 +410,91 @@ class AudioContext:
         k = bound["n_miss"].value
         return bound["miss"][:min(k, bound["n"])] if k else _NO_MISS
 
+    # ---- pose memo of the column path (include/ss_hip.h "Pose memo on the column path") ---------------------------------
+    def memo_enable(self, n_envs: int) -> None:
+        """Switch the library's per-pose memo on for steps of ``n_envs`` envs (again: reset with a new size; 0: off)."""
+        _lib.check(self.lib.ss_ctx_memo_enable(self._h, int(n_envs)), "ss_ctx_memo_enable")
+
+    def memo_reset(self) -> None:
+        """Forget every pose and the counters (the pools' contents become meaningless)."""
+        _lib.check(self.lib.ss_ctx_memo_reset(self._h), "ss_ctx_memo_reset")
+
+    def memo_stats(self) -> Dict[str, int]:
+        out = np.zeros(4, np.int64)
+        _lib.check(self.lib.ss_ctx_memo_stats(self._h, out.ctypes.data), "ss_ctx_memo_stats")
+        return dict(zip(("hits", "misses", "rows", "dropped"), (int(v) for v in out)))
+
+    @staticmethod
+    def memo_pool(spectrogram=None, audiogoal=None):
+        """The caller's device-side pools ([rows,65,T4,2] / [rows,2,sr] float32 CUDA tensors, one per output the steps are
+        asked for) as the C struct ``ss_memo_pool`` (borrowed; build it again when a pool is replaced by a larger one)."""
+        import torch
+        rows = None
+        for t in (spectrogram, audiogoal):
+            if t is not None:
+                assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and (rows is None or t.shape[0] == rows)
+                rows = int(t.shape[0])
+        p = _lib.SsMemoPool(None if spectrogram is None else spectrogram.data_ptr(),
+                            None if audiogoal is None else audiogoal.data_ptr(), rows or 0, 0)
+        need = ctypes.c_int(0)
+        return dict(s=p, ref=ctypes.byref(p), rows=rows or 0, need=need, need_ptr=ctypes.addressof(need),
+                    keep=(spectrogram, audiogoal))
+
+    def observe_sims_memo(self, bound, pool, spectrogram_out=None, audiogoal_out=None, stream: Optional[int] = None):
+        """``observe_sims`` with the library's pose memo inside (ss_ctx_observe_sims_memo: plan, render, row copies, one C
+        call).  ``pool``: ``memo_pool(...)`` with an array per output given.  -> (env indices whose RIR pair is not resident,
+        pool rows needed in total or 0): with either set nothing was launched, advanced or memoised - serve it, call again."""
+        import torch
+        sg = ag = None
+        dev = None
+        if spectrogram_out is not None:
+            sg, dev = spectrogram_out.data_ptr(), spectrogram_out.device
+        if audiogoal_out is not None:
+            ag, dev = audiogoal_out.data_ptr(), audiogoal_out.device
+        if dev is None:
+            raise ValueError("observe_sims_memo: pass spectrogram_out and / or audiogoal_out")
+        if bound.get("dev") != dev:                    # shapes / dtypes checked once per (bound, device)
+            n = bound["n"]
+            for t, shape in ((spectrogram_out, (n,) + self.spectrogram_shape), (audiogoal_out, (n, 2, self.sr))):
+                if t is not None:
+                    assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape
+            bound["dev"] = dev
+        if pool.get("dev") != dev:                     # ... and once per pool
+            for t, shape in ((pool["keep"][0], self.spectrogram_shape), (pool["keep"][1], (2, self.sr))):
+                assert t is None or (tuple(t.shape[1:]) == shape and t.device == dev)
+            pool["dev"] = dev
+        if stream is None:
+            stream = torch._C._cuda_getCurrentRawStream(dev.index if dev.index is not None else torch.cuda.current_device())
+        if torch.cuda.current_device() == dev.index:
+            rc = self.lib.ss_ctx_observe_sims_memo(self._h, *bound["c_args"], ag, sg, pool["ref"], *bound["c_miss"],
+                                                   pool["need_ptr"], stream)
+        else:
+            with torch.cuda.device(dev):
+                rc = self.lib.ss_ctx_observe_sims_memo(self._h, *bound["c_args"], ag, sg, pool["ref"], *bound["c_miss"],
+                                                       pool["need_ptr"], stream)
+        if rc != 0:
+            _lib.check(rc, "ss_ctx_observe_sims_memo")
+        k = bound["n_miss"].value
+        return (bound["miss"][:min(k, bound["n"])] if k else _NO_MISS), pool["need"].value
+
+    def sims_memo_plan(self, bound, pool_rows: int):
+        """Host only (ss_ctx_sims_memo_plan): the memo's plan of the step ``observe_sims_memo`` would run against pools of
+        ``pool_rows`` rows, committed the same way -> dict(cols: int32 unit columns (held envs silent), hold: bool [n],
+        stores / fetches: int32 [k,2] = (env, pool row), missing: env indices, need_rows)."""
+        n = bound["n"]
+        out = np.zeros((5, max(n, 1)), np.int32)
+        hold = np.zeros((max(n, 1),), np.uint8)
+        moves = np.zeros((max(n, 1), 2), np.int32)
+        ns, nf, need = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+        _lib.check(self.lib.ss_ctx_sims_memo_plan(self._h, ctypes.byref(bound["cols"]), n, int(pool_rows), out.ctypes.data,
+                                                  hold.ctypes.data, moves.ctypes.data, ctypes.addressof(ns), ctypes.addressof(nf),
+                                                  bound["miss"].ctypes.data, ctypes.addressof(bound["n_miss"]),
+                                                  ctypes.addressof(need)), "ss_ctx_sims_memo_plan")
+        cols = dict(zip(("sound", "t0", "rir", "dis_sound", "dis_rir"), out[:, :n]))
+        return dict(cols=cols, hold=hold[:n].astype(bool), stores=moves[:ns.value].copy(),
+                    fetches=moves[ns.value:ns.value + nf.value].copy(),
+                    missing=bound["miss"][:min(bound["n_miss"].value, n)].copy(), need_rows=need.value)
+
     # ---- request records of a multi-process vector env (ss_amd/deferred.py) ------------------------------------------
     @staticmethod
     def request_tables(sound_keys, sound_ids, table_keys, table_ids, pair_keys, pair_slots, stale=None, last_used=None):

@@ -257,8 +257,11 @@ class DeferredResolver:
     PREFETCH_MAX_POSES = 4                      # new poses per step up to which their sibling azimuths are loaded along
 
     def __init__(self, engine, rir_reader: Optional[Callable[[str], Optional[np.ndarray]]] = None,
-                 fast: Optional[bool] = None, prefetch_azimuths: bool = True):
-        """fast: None = use the column path when the engine has one and every request of the step carries `rec`;
+                 fast: Optional[bool] = None, prefetch_azimuths: bool = True, native_pose_cache: bool = False):
+        """native_pose_cache (opt-in; pose_cache workers only): the pool copies of a step - misses stored, hits fetched - are ONE
+        ``ops.memo_rows_`` launch (k_memo_rows) over a pinned move list instead of index tensors built from lists and two torch
+        index dispatches per output and direction.  The workers still decide hit or miss; results are the same bit for bit.
+        fast: None = use the column path when the engine has one and every request of the step carries `rec`;
         False = always walk the requests (per-unit Python planner); True = require the column path.
         prefetch_azimuths (column path): a pose that is not resident is loaded together with the OTHER azimuths of its
         (receiver, source) pair - `<binaural_rir_dir>/{0,90,180,270}/<recv>_<src>.wav`, simulator.py:615-616 - in the same
@@ -312,6 +315,9 @@ class DeferredResolver:
         self._pose_pool: Dict[str, object] = {}
         self._pose_free: List[int] = []
         self._pose_cap = 0
+        self.native_pose_cache = bool(native_pose_cache)
+        self._pose_moves: List[list] = []                   # ring of [pinned int32 [cap, 2], event behind its last launch]
+        self._pose_moves_k = 0
         self.native_steps = self.miss_steps = 0
         if self.columns_ok:                       # every resolver over this store hears about evictions (their pair tables
             if hasattr(store, "add_evict_hook"):  # name store slots); held weakly: a dropped resolver drops out
@@ -859,6 +865,19 @@ class DeferredResolver:
         the pool itself only grows - size it by (poses visited per episode) x (envs)."""
         return int(sum(t.numel() * t.element_size() for t in self._pose_pool.values()))
 
+    def _pose_move_list(self, n: int) -> list:
+        """A pinned move list the launch reads in place: the next of a small ring, free once the launch that read it last has run."""
+        import torch
+        if len(self._pose_moves) < 8:
+            self._pose_moves.append([torch.empty((max(256, n), 2), dtype=torch.int32).pin_memory(), torch.cuda.Event()])
+            return self._pose_moves[-1]
+        mv = self._pose_moves[self._pose_moves_k]
+        self._pose_moves_k = (self._pose_moves_k + 1) % len(self._pose_moves)
+        mv[1].synchronize()
+        if mv[0].shape[0] < n:
+            mv[0] = torch.empty((2 * n, 2), dtype=torch.int32).pin_memory()
+        return mv
+
     def _resolve_with_pose_cache(self, requests, want_audiogoal, want_spectrogram, spectrogram_out, audiogoal_out):
         """pose_cache workers: misses are rendered and their rows kept in a device-side pool under (env, pose); hits are
         row copies out of it (the reference returns the array it cached at that pose, simulator.py:683-686)."""
@@ -901,6 +920,20 @@ class DeferredResolver:
                 j = self._pose_free.pop()
                 maps[requests[i].env][1][requests[i].cache_key] = j
                 miss_slots.append(j)
+        if self.native_pose_cache and dev.type == "cuda":
+            # one k_memo_rows launch for every copy of the step: request rows are distinct, and so are the pool rows written
+            slots = [maps[requests[i].env][1][requests[i].cache_key] for i in hits]
+            if hits and set(out) - set(self._pose_pool):
+                raise KeyError(f"pose_cache: {sorted(set(out) - set(self._pose_pool))} was not among the outputs when this pose was first rendered")
+            n_mv = len(miss_rows) + len(hits)
+            if n_mv:
+                from . import ops
+                mv = self._pose_move_list(n_mv)
+                mv[0][:n_mv] = torch.tensor([miss_rows + hits, miss_slots + slots], dtype=torch.int32).t()
+                ops.memo_rows_([(t, self._pose_pool[name]) for name, t in out.items()], mv[0], len(miss_rows), len(hits))
+                mv[1].record()
+            return out
+        if miss_rows:
             mi, sj = (torch.as_tensor(v, dtype=torch.long, device=dev) for v in (miss_rows, miss_slots))
             for name, t in out.items():
                 self._pose_pool[name].index_copy_(0, sj, t.index_select(0, mi))

@@ -591,6 +591,42 @@ def audio_obs_logmel_spec_buckets_into(spec, buckets, n_buckets: int, rir_len, u
                         spectrogram_out, logmel_out, mel_start, mel_w, n_valid, out_len, mel_eps, pad_mode, flags)
 
 
+def memo_rows_(pairs, moves: torch.Tensor, n_store: int, n_fetch: int) -> None:
+    """The row copies of a pose memo in ONE launch (ss_memo_rows_f32, k_memo_rows) on the current stream: ``pairs`` = up to 4
+    (out, pool) pairs of contiguous float32 CUDA tensors with equal row shapes; ``moves`` int32 [n_store + n_fetch, 2] =
+    (row, slot), device or pinned host memory, read in place (keep it alive and unchanged until the launch has run).  The first
+    n_store moves store out[row] into pool[slot], the following n_fetch fetch pool[slot] into out[row]; rows are distinct and
+    slots are distinct over the whole list.  In place; nothing is returned (like the ``*_into`` entry points, not a registered op)."""
+    pairs = list(pairs)
+    if not 1 <= len(pairs) <= 4:
+        raise ValueError("memo_rows_: 1 to 4 (out, pool) pairs")
+    io = (_lib.SsMemoIo * len(pairs))()
+    dev = None
+    for k, (out, pool) in enumerate(pairs):
+        _chk(out, torch.float32, "out"); _chk(pool, torch.float32, "pool")
+        if tuple(out.shape[1:]) != tuple(pool.shape[1:]) or out.dim() < 2 or out.device != pool.device:
+            raise ValueError("memo_rows_: out and pool must be [rows, ...] tensors with equal row shapes on one device")
+        if dev is not None and out.device != dev:
+            raise ValueError("memo_rows_: all arrays must live on one device")
+        dev = out.device
+        io[k] = _lib.SsMemoIo(out.data_ptr(), pool.data_ptr(), out[0].numel(), 0)
+    if not (moves.is_cuda or moves.is_pinned()):
+        raise ValueError("moves: pinned host or device memory expected (the kernel reads it in place)")
+    if moves.dtype != torch.int32 or not moves.is_contiguous() or moves.dim() != 2 or moves.shape[1] != 2 or \
+            moves.shape[0] < n_store + n_fetch:
+        raise ValueError("moves: contiguous int32 [n_store + n_fetch, 2] expected")
+    if n_store + n_fetch > 0:                              # (rows / slots inside the arrays: a wrong index is a memory fault)
+        m = moves[:n_store + n_fetch]
+        lim_r, lim_s = min(o.shape[0] for o, _ in pairs), min(p.shape[0] for _, p in pairs)
+        if not moves.is_cuda and (int(m[:, 0].min()) < 0 or int(m[:, 0].max()) >= lim_r or int(m[:, 1].min()) < 0 or
+                                  int(m[:, 1].max()) >= lim_s):
+            raise ValueError("moves: a row or slot outside the arrays")
+    import ctypes
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().ss_memo_rows_f32(ctypes.cast(io, ctypes.c_void_p), len(pairs), moves.data_ptr(), int(n_store),
+                                                int(n_fetch), _stream(pairs[0][0])), "ss_memo_rows_f32")
+
+
 def ctypes_ref(arr):
     import ctypes
     return ctypes.cast(arr, ctypes.c_void_p)

@@ -262,7 +262,8 @@ class FastVectorAudioObserver:
     """One launch per vector step, state read from columns (module docstring)."""
 
     def __init__(self, ctx, state: VectorSimState, index: RirIndex, sampling_rate: int, has_distractor: bool = False,
-                 miss: Optional[Callable[[int, int, int, int], int]] = None, native: bool = True, pose_cache: bool = False):
+                 miss: Optional[Callable[[int, int, int, int], int]] = None, native: bool = True, pose_cache: bool = False,
+                 native_pose_cache: bool = False, pose_pool_rows: int = 256):
         """ctx: ss_amd.context.AudioContext with its RIR bank set; miss(env, recv, src, azimuth) -> slot is called for
         envs whose pair is not in the index (loads it AND enters it into the index; default: raise).
         pose_cache: the REFERENCE-EXACT mode for multi-second sounds.  The reference memoises observations per (source,
@@ -272,7 +273,14 @@ class FastVectorAudioObserver:
         column observer does the same: a per-env map pose -> row of a device-side pool; hits are device-to-device row
         copies, misses are rendered and stored; an env's map is dropped when its scene or sound changes (:395-397).
         Ignored with a distractor (the reference bypasses its caches then, :679-681).  Default False: every step renders
-        the cache-miss path (identical for 1-s sounds, whose window never changes)."""
+        the cache-miss path (identical for 1-s sounds, whose window never changes).
+        native_pose_cache (opt-in, with pose_cache=True): the same memo INSIDE the step's C call
+        (``ss_ctx_observe_sims_memo``: per-env maps and the free list in libss_hip.so, the row copies one ``k_memo_rows``
+        launch right behind the render on the same stream or overlap lane - no Python walk over the envs, no index tensors, no
+        join).  Same observations bit for bit, same ``_audio_index``, same hit / miss counts; pool row numbers are the
+        library's own.  ``obs.native_memo`` says whether this path is active (it needs a context with the entry and no
+        distractor); ``obs.native`` stays False under pose_cache either way.  pose_pool_rows: rows the device-side pools start
+        with on this path (they double when a step needs more, contents kept)."""
         self.ctx, self.state, self.index, self.sr = ctx, state, index, int(sampling_rate)
         self.has_distractor = has_distractor
         self.miss = miss
@@ -284,9 +292,31 @@ class FastVectorAudioObserver:
         self._pool_cap = 0
         self.pose_hits = self.pose_misses = 0
         self.native = native and hasattr(ctx, "observe_sims") and not self.pose_cache
+        self.native_memo = bool(native_pose_cache) and self.pose_cache and hasattr(ctx, "observe_sims_memo")
+        self._memo_pool, self._memo_rows0 = None, max(1, int(pose_pool_rows))
+        if self.native_memo:
+            ctx.memo_enable(state.n)
         self._bound, self._bound_version = None, -1
         self._rollouts, self._names = None, []
         self._clip_len = np.zeros((0,), np.int64)
+
+    # hits / misses of the pose cache: the observer's own counts, or on the native path the library's (read when asked for: the
+    # step itself pays nothing for them)
+    @property
+    def pose_hits(self) -> int:
+        return self.ctx.memo_stats()["hits"] if self.native_memo else self._pose_hits
+
+    @pose_hits.setter
+    def pose_hits(self, v: int) -> None:
+        self._pose_hits = v
+
+    @property
+    def pose_misses(self) -> int:
+        return self.ctx.memo_stats()["misses"] if self.native_memo else self._pose_misses
+
+    @pose_misses.setter
+    def pose_misses(self, v: int) -> None:
+        self._pose_misses = v
 
     def _lengths(self) -> np.ndarray:
         if self._clip_len.shape[0] != len(self.ctx.lengths):
@@ -338,6 +368,8 @@ class FastVectorAudioObserver:
     def observe(self, spectrogram_out=None, audiogoal_out=None) -> None:
         """Native path (default): the per-step host work runs inside libss_hip.so (``ss_ctx_observe_sims``) on pointers
         to the state columns; ``native=False`` keeps the numpy formulation of ``columns()`` (same results, tested)."""
+        if self.native_memo:
+            return self._observe_with_native_memo(spectrogram_out, audiogoal_out)
         if self.pose_cache:
             return self._observe_with_pose_cache(spectrogram_out, audiogoal_out)
         if not self.native:
@@ -423,6 +455,56 @@ class FastVectorAudioObserver:
             hj = torch.as_tensor(hit_pool, dtype=torch.long, device=dev)
             for name, t in outs.items():
                 t.index_copy_(0, hi, self._pool[name].index_select(0, hj))
+
+    # ---- the same memo inside the step's C call (native_pose_cache=True) -------------------------------------------------
+    def _grow_memo_pool(self, outs, need: int) -> None:
+        """Device-side pools of at least `need` rows (contents kept), and their C struct."""
+        import torch
+        old = self._memo_pool
+        rows = old["rows"] if old else 0
+        new_rows = max(self._memo_rows0, rows)
+        while new_rows < need:
+            new_rows *= 2
+        if old is not None and hasattr(self.ctx, "join"):
+            self.ctx.join()                                   # (overlap lanes: steps in flight still store into the old pools)
+        grown = {}
+        for name, t in outs.items():
+            g = torch.empty((new_rows,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
+            if old is not None:
+                g[:rows] = old["keep"][0 if name == "spectrogram" else 1]
+            grown[name] = g
+        self._memo_pool = self.ctx.memo_pool(grown.get("spectrogram"), grown.get("audiogoal"))
+
+    def _observe_with_native_memo(self, spectrogram_out, audiogoal_out) -> None:
+        st = self.state
+        if st.dirty.any():
+            st.resolve_sounds(self.ctx.add_source)
+        if self._memo_pool is None or (spectrogram_out is None) != (self._memo_pool["keep"][0] is None) or \
+                (audiogoal_out is None) != (self._memo_pool["keep"][1] is None):
+            if self._memo_pool is not None:
+                raise ValueError("pose_cache: the observer must be asked for the same outputs every step")
+            outs = {k: v for k, v in (("spectrogram", spectrogram_out), ("audiogoal", audiogoal_out)) if v is not None}
+            self._grow_memo_pool(outs, 0)
+        for _ in range(3):
+            self.index.tables()                                                                      # rebuild if stale
+            if self._bound is None or self._bound_version != self.index.version:
+                self._bound = self.ctx.bind_sims(st, self.index, False)
+                self._bound_version = self.index.version
+            missing, need = self.ctx.observe_sims_memo(self._bound, self._memo_pool, spectrogram_out=spectrogram_out,
+                                                       audiogoal_out=audiogoal_out)
+            if missing.shape[0] == 0 and need == 0:
+                return
+            if need:
+                outs = {k: v for k, v in (("spectrogram", spectrogram_out), ("audiogoal", audiogoal_out)) if v is not None}
+                self._grow_memo_pool(outs, need)
+            if missing.shape[0]:
+                if self.miss is None:
+                    raise KeyError(f"RIR pairs of envs {missing.tolist()} are not resident and no miss loader was given")
+                az = (-st.rot) % 360
+                for i in missing:                               # load the pairs (the loader puts them into the index)
+                    i = int(i)
+                    self.miss(i, int(st.recv[i]), int(st.src[i]), int(az[i]))
+        raise KeyError("RIR pairs still missing after the miss loader ran (it must enter them into the RirIndex)")
 
     def observe_into(self, rollouts):
         """Render this vector step straight into the rollout rows the next ``rollouts.insert()`` fills
