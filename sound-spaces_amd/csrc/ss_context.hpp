@@ -21,6 +21,7 @@
 #include "../../include/ss_hip.h"
 #include "ss_memo.hpp"
 #include "ss_ring.hpp"
+#include "ss_route.hpp"
 
 namespace ssctx {
 
@@ -117,13 +118,7 @@ struct Context {
     // overlap mode (ss_ctx_set_overlap): consecutive steps alternate between internal streams ("lanes")
     int n_lanes = 1, lane_next = 0;
     void* miss_ev = nullptr;            // hipEvent_t behind the last scatter of ss_ctx_observe_requests_load (its staging block is reused)
-    int spectral_max_units = 0;         // ss_ctx_set_spectral_policy: one-block rows take the spectral bank only for steps of <= this many units (0: always)
-    // ss_ctx_set_logmel_policy: log-mel steps without a waveform buffer take the fused launch for min <= units <= max
-    int mel_fused_min_units = 1, mel_fused_max_units = 0x7fffffff;
-    // ss_ctx_set_logmel_rows_policy: the same for rows of 2 or 3 blocks (44.1 / 48 kHz); default: never
-    int mel_rows_min_units = 1, mel_rows_max_units = 0;
-    int mel_ss2_min_units = 1, mel_ss2_max_units = 0;          // ss_ctx_set_logmel_ss2_policy: never, by default
-    int mel_bk_min_units = 1, mel_bk_max_units = 0;            // ss_ctx_set_logmel_buckets_policy (length-bucketed banks): never, by default
+    ssroute::Policies policy;           // ss_ctx_set_spectral_policy and the ss_ctx_set_logmel_*_policy ranges (ss_route.hpp)
     int chip_share = 0;                 // ss_ctx_set_chip_share: launch sources the chip is shared with (0: the lane count)
     hipStream_t lane_stream[kLanes] = {};
     bool lane_dirty[kLanes] = {};                 // work issued on the lane since ev_lane was last recorded

@@ -23,6 +23,8 @@
 // the index algebra is checked on CPU; the product always runs the gfx950 build.
 #pragma once
 
+#include "ss_consts.hpp"             // kB, the partition block
+
 // Stops the compiler from common-subexpression-ing the (cheap) twiddle power chains of a forward pass
 // with those of the matching inverse pass: keeping ~30 values alive across the whole kernel costs
 // scratch spills at the 128-VGPR budget of a 1024-thread workgroup.  (No-op in the host-side test build.)
@@ -125,7 +127,6 @@ __device__ __forceinline__ void lds_st(c32* p, c32 v) {
 }
 
 constexpr int kM = 16384;            // complex points of one block FFT
-constexpr int kB = 16384;            // real samples of one partition block (FFT covers 2*kB)
 constexpr int kT = 1024;             // threads per workgroup
 constexpr int kLdsComplex = 4 * 4352;  // 17408 complex = 139264 B (layout B; layout A needs 16640)
 constexpr int kSpecComplex = 16384;  // complex values of one stored block spectrum (kernel order)

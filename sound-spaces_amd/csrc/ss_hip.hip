@@ -16,6 +16,7 @@
 #include "ss_context.hpp"
 #include "ss_kernels.hpp"
 #include "ss_kernels32.hpp"
+#include "ss_route.hpp"
 #include "ss_features.hpp"
 #include "ss_tables.hpp"
 #include "ss_wavio.hpp"
@@ -95,23 +96,33 @@ int get_tables(ssk::Tables* out, int* n_cus = nullptr) {
     return 0;
 }
 
-inline int n_frames_of(int len) { return 1 + len / ssk::kHop; }
-inline int t4_of(int len) { return (n_frames_of(len) + ssk::kPool - 1) / ssk::kPool; }
+using ssroute::n_frames_of;
+using ssroute::t4_of;
 
-// The context API knows the unit descriptors of a step on the HOST (it has just planned them): for the duration of its
-// launch call it leaves them here, and loop-free launches of <= kTabUnits units then carry {index, slot} per unit in the
-// kernel arguments (ConvParams::tab).  Callers of the stateless entry points hand over device pointers only: nullptr.
-thread_local const int* g_host_desc = nullptr;
-// ... and reads back whether the launch took that route: a launch with a unit table never dereferences its descriptor pointer,
-// so the ring slot the descriptors lie in holds nothing the device reads (ss_ring.hpp).  Set by fill_unit_tab only; every
-// launcher that does not go through it leaves the flag alone and counts as "slot read".  (Every entry point issues ONE launch
-// that consumes descriptors, so one flag per call is enough.)
-thread_local bool g_tab_taken = false;
-// ... and, in its overlap mode, the number of launches it keeps in flight (its lanes): a launch that spreads its rows over
-// idle CUs (parts_log2_for) then leaves the other lanes' launches their share of the chip.  1 for everybody else.
-thread_local int g_launch_share = 1;
+// the A/B switches the shape rules of ss_route.hpp take as plain values
+inline const ssroute::Switches& route_switches() {
+    static const ssroute::Switches sw{ab_flag("SS_HIP_NO_WIDE")};      // (A/B builds only: -DSS_AB)
+    return sw;
+}
 
-inline bool fill_unit_tab(ssk::UnitTab<true>& ut, const int* host_desc, int n_units) {
+// What a launch is given besides its parameters.
+struct LaunchEnv {
+    hipStream_t st = nullptr;
+    // The context API knows the unit descriptors of a step on the HOST (it has just planned them): loop-free launches of
+    // <= kTabUnits units then carry {index, slot} per unit in the kernel arguments (ConvParams::tab).  Callers of the stateless
+    // entry points hand over device pointers only: nullptr.
+    const int* host_desc = nullptr;
+    // ... and, in its overlap mode, the number of launches it keeps in flight (its lanes): a launch that spreads its rows over
+    // idle CUs (parts_log2_for) then leaves the other lanes' launches their share of the chip.  1 for everybody else.
+    int share = 1;
+    // ... and reads back whether the launch took the unit-table route: such a launch never dereferences its descriptor pointer,
+    // so the ring slot the descriptors lie in holds nothing the device reads (ss_ring.hpp).  Set by fill_unit_tab only.  (Every
+    // entry point issues ONE launch that consumes descriptors, so one flag per call is enough.)
+    bool* tab_taken = nullptr;
+};
+
+inline bool fill_unit_tab(ssk::UnitTab<true>& ut, const LaunchEnv& env, int n_units) {
+    const int* host_desc = env.host_desc;
     if (!host_desc || n_units > ssk::kTabUnits) return false;
     // Units are dealt to the launch slots SORTED by their window spectrum (stable; silent units last): row_slot() gives every
     // XCD a contiguous range of slots, so the rows that read one 128-KiB spectrum - 128 envs draw from 102 sounds, ~73 distinct
@@ -138,38 +149,28 @@ inline bool fill_unit_tab(ssk::UnitTab<true>& ut, const int* host_desc, int n_un
         ut.tab[ssk::kTabWords * k + 1] = ok ? d[1] - d[2] : 0;
         ut.tab[ssk::kTabWords * k + 2] = i;
     }
-    g_tab_taken = true;
+    if (env.tab_taken) *env.tab_taken = true;
     return true;
-}
-
-// Rows longer than one block of which only block 0 is rendered (SS2.0 steps at 44.1 kHz: 0.25 s of a 1-s row) and whose live
-// pooled blocks all lie inside that block: the fused LOOP kernel serves them in one launch (k_conv<..., WIDE>: block spectra
-// accumulated in registers, the spectrogram's dead columns written as zeros) - with or without a waveform buffer.
-inline bool wide_one_block_ok(int out_len, int n_valid, int flags, bool spectral = false) {
-    static const bool off = ab_flag("SS_HIP_NO_WIDE");        // (A/B builds only: -DSS_AB)
-    if (off || spectral || out_len <= ssk::kB || n_valid < 0 || n_valid > ssk::kB) return false;
-    if ((flags & SS_FLAG_CROSSFADE) &&
-        (static_cast<int>(0.05 * out_len) < 1 || static_cast<int>(0.05 * out_len) > 2 * ssk::kPrevPairs - 2)) return false;
-    return ssk::live_blocks(n_valid, out_len, t4_of(out_len)) <= 26;
 }
 
 // Small steps (fewer rows than CUs): a fused one-block row is rendered by 2^k workgroups on as many CUs, each running the
 // row's convolution and its share of the pooled STFT blocks (ConvParams::parts_log2) - as long as the grid still fits the
 // chip in one round of one workgroup per CU.  26 pooled blocks: k <= 3 (shares of 13 / 7 / 4 blocks).
-inline int parts_log2_for(int n_rows, int n_cus) {
+inline int parts_log2_for(int n_rows, int n_cus, int share) {
     static const int forced = ab_int("SS_HIP_PARTS_LOG2", -1);        // (A/B builds only: -DSS_AB)
     if (forced >= 0) return forced < 3 ? forced : 3;
-    const int cus = n_cus / (g_launch_share > 1 ? g_launch_share : 1);       // overlap mode: the lanes share the chip
+    const int cus = n_cus / (share > 1 ? share : 1);       // overlap mode: the lanes share the chip
     int k = 0;
     while (k < 3 && (n_rows << (k + 1)) <= cus) ++k;
     return k;
 }
 
 template <bool FUSE>
-int launch_conv(ssk::ConvParams p, int n_units, int nb_y, int flags, int n_cus, hipStream_t st, bool wide = false) {
+int launch_conv(ssk::ConvParams p, int n_units, int nb_y, int flags, int n_cus, const LaunchEnv& env, bool wide = false) {
+    const hipStream_t st = env.st;
     if (nb_y < 1 || nb_y > 3 || (FUSE && nb_y != 1)) return SS_EINVAL;
     p.nb_y = nb_y;
-    p.parts_log2 = FUSE && !wide ? parts_log2_for(2 * n_units, n_cus) : 0;
+    p.parts_log2 = FUSE && !wide ? parts_log2_for(2 * n_units, n_cus, env.share) : 0;
     if constexpr (FUSE) {
         if (wide) {
             if ((flags & SS_FLAG_CROSSFADE) && (p.fade_len < 1 || p.fade_len > 2 * ssk::kPrevPairs - 2)) return SS_EINVAL;
@@ -201,7 +202,7 @@ int launch_conv(ssk::ConvParams p, int n_units, int nb_y, int flags, int n_cus, 
     if (flags & SS_FLAG_CROSSFADE) hipLaunchKernelGGL((ssk::k_conv<FUSE, false, true>), grid, block, 0, st, p, ssk::UnitTab<false>());
     else if (simple) {
         ssk::UnitTab<true> ut;
-        if (fill_unit_tab(ut, g_host_desc, n_units)) hipLaunchKernelGGL((ssk::k_conv<FUSE, true, false, true>), grid, block, 0, st, p, ut);
+        if (fill_unit_tab(ut, env, n_units)) hipLaunchKernelGGL((ssk::k_conv<FUSE, true, false, true>), grid, block, 0, st, p, ut);
         else hipLaunchKernelGGL((ssk::k_conv<FUSE, true>), grid, block, 0, st, p, ssk::UnitTab<false>());
     }
     else hipLaunchKernelGGL((ssk::k_conv<FUSE, false>), grid, block, 0, st, p, ssk::UnitTab<false>());
@@ -286,18 +287,6 @@ void drop_stash(hipStream_t st) {
     g_stash.erase(it);
 }
 
-// should k_obs_rows serve this shape?  (rows of 2 or 3 blocks, stash mask of 32 bits.)  Rows with ONE rendered block
-// (n_valid <= kB: SS2.0 steps at 44.1 kHz) and cross-faded rows: only when the caller has no waveform buffer.  With one,
-// the loop kernel (block spectra accumulated in registers: every one is used once, the rows kernel's stash is pure overhead
-// there) + k_spectrogram (told where the zeros of a short step begin) is faster - per 128 units at 44.1 kHz: plain steps
-// 61.6 vs 72.5 us (66.3 without the waveform written), cross-faded 92.7 vs 117.8 us (profiles/r3/NOTES.md section 8)
-inline bool obs_rows_ok(int out_len, int n_valid, int nbh_max, int flags, bool spectral = false, bool have_waveform_buffer = false) {
-    if (have_waveform_buffer && ((flags & SS_FLAG_CROSSFADE) || n_valid <= ssk::kB)) return false;
-    if ((flags & SS_FLAG_CROSSFADE) &&
-        (spectral || static_cast<int>(0.05 * out_len) < 1 || static_cast<int>(0.05 * out_len) > 2 * ssk::kPrevPairs - 2)) return false;
-    return out_len > ssk::kB && out_len <= 3 * ssk::kB && n_valid <= out_len && nbh_max >= 1 && nbh_max <= 16;
-}
-
 // Small steps of rows longer than one block (the reference's Replica arrangement: 5 envs per GPU at 44.1 kHz): one workgroup
 // per OUTPUT BLOCK of a row instead of one per row (k_obs_blocks) - while the whole grid fits the launch's share of the chip at
 // one workgroup per CU, which is also what makes the kernel's inter-workgroup hand-off safe.  Spare CUs go to parts (the STFT
@@ -305,12 +294,13 @@ inline bool obs_rows_ok(int out_len, int n_valid, int nbh_max, int flags, bool s
 // MEL: the log-mel instantiations (ss_audio_obs_logmel_rows_f32 / _spec_f32), same rule, same hand-off area.
 // HALF: the half-bank instantiations (ss_audio_obs_rows_spec16_f32 / ss_audio_obs_logmel_rows_spec16_f32), likewise.
 template <bool SPECTRAL, bool MEL = false, bool HALF = false>
-int launch_obs_blocks(ssk::ConvParams p, int n_units, int flags, int n_cus, hipStream_t st,
+int launch_obs_blocks(ssk::ConvParams p, int n_units, int flags, int n_cus, const LaunchEnv& env,
                       const ssk::UnitTab<false, MEL>& mel = ssk::UnitTab<false, MEL>(),
                       const ssk::SpecScale<HALF>& hs = ssk::SpecScale<HALF>()) {
+    const hipStream_t st = env.st;
     static const bool off = ab_flag("SS_HIP_NO_OBS_BLOCKS");   // (A/B builds only)
     const int n_rows = 2 * n_units, nb = (p.out_len + ssk::kB - 1) / ssk::kB;
-    const int budget = n_cus / (g_launch_share > 1 ? g_launch_share : 1);
+    const int budget = n_cus / (env.share > 1 ? env.share : 1);
     if (off || (flags & SS_FLAG_CROSSFADE) || p.n_valid != p.out_len || nb < 2 || nb > 3 || n_rows * nb > budget ||
         n_rows > kSyncRows || st == hipStreamPerThread)
         return 1;
@@ -336,15 +326,16 @@ int launch_obs_blocks(ssk::ConvParams p, int n_units, int flags, int n_cus, hipS
 }
 
 template <bool SPECTRAL, bool MEL = false, bool HALF = false>
-int launch_obs_rows(ssk::ConvParams p, int n_units, int flags, int n_cus, hipStream_t st,
+int launch_obs_rows(ssk::ConvParams p, int n_units, int flags, int n_cus, const LaunchEnv& env,
                     const ssk::UnitTab<false, MEL>& mel = ssk::UnitTab<false, MEL>(),
                     const ssk::SpecScale<HALF>& hs = ssk::SpecScale<HALF>()) {
+    const hipStream_t st = env.st;
     static_assert(!HALF || SPECTRAL, "half bank: the spectral form");
     const int n_rows = 2 * n_units;
     if ((MEL || HALF) && (flags & SS_FLAG_CROSSFADE)) return SS_EINVAL;                            // (the log-mel and half forms: plain rows)
     if (HALF && p.n_buckets != 1) return SS_EINVAL;                                                 // (half: one allocation)
     {
-        const int rc = launch_obs_blocks<SPECTRAL, MEL, HALF>(p, n_units, flags, n_cus, st, mel, hs);
+        const int rc = launch_obs_blocks<SPECTRAL, MEL, HALF>(p, n_units, flags, n_cus, env, mel, hs);
         if (rc != 1) return rc;
     }
     // small steps (the reference steps 5-10 envs per GPU at this rate): a row on 2 / 4 / 8 CUs, each rendering the row and
@@ -353,7 +344,7 @@ int launch_obs_rows(ssk::ConvParams p, int n_units, int flags, int n_cus, hipStr
     // memory-bound long before the CUs run out - same box, alternating, us per launch at 1 / 5 / 10 / 16 units with up to 8
     // parts per row: 58.7 / 62.2 / 69.5 / 75.4 against 70.8 / 71.1 / 72.1 / 72.6 with one (profiles/r5/kbench_parts_44k.txt) -
     // so the split stops at 96 workgroups there.  The spectral bank has no stash: -20 % up to 32 units (256 workgroups).
-    p.parts_log2 = parts_log2_for(n_rows, SPECTRAL ? n_cus : std::min(n_cus, 96));
+    p.parts_log2 = parts_log2_for(n_rows, SPECTRAL ? n_cus : std::min(n_cus, 96), env.share);
     const int grid = (n_rows << p.parts_log2) < n_cus ? (n_rows << p.parts_log2) : n_cus;
     p.nb_y = p.n_valid == 0 ? 0 : (p.n_valid + ssk::kB - 1) / ssk::kB;
     p.stash = nullptr;
@@ -403,11 +394,6 @@ inline bool mel_args_ok(const float* logmel, const int* mel_start, const float* 
            max_len <= ssk::kFeatMaxLen && !(max_len & 3) && n_mels * max_len <= ssk::kFeatMelTable && eps > 0.f &&
            !(reinterpret_cast<size_t>(mel_w) & 15);
 }
-// rows the log-mel form serves: one partition block, long enough for the reflect padding, no cross-fade
-inline bool obs_logmel_shape_ok(int out_len, int flags) {
-    return out_len >= ssk::kNfft / 2 + 1 && out_len <= ssk::kB && !(flags & SS_FLAG_CROSSFADE);
-}
-
 int launch_conv_mel(ssk::ConvParams p, const ssk::MelArgs& m, int n_units, int flags, hipStream_t st) {
     p.nb_y = 1;
     p.parts_log2 = 0;
@@ -495,13 +481,381 @@ void drop_wave_scratch(const void* owner) {
 }
 
 template <bool FUSE>
-int launch_conv32(ssk::ConvParams& p, int n_units, hipStream_t st) {
+int launch_conv32(ssk::ConvParams& p, int n_units, const LaunchEnv& env) {
+    const hipStream_t st = env.st;
     const dim3 grid(2 * n_units), block(ssk::kT32);
     ssk::UnitTab<true> ut;
-    if (fill_unit_tab(ut, g_host_desc, n_units)) hipLaunchKernelGGL((ssk::k_conv32<FUSE, true>), grid, block, 0, st, p, ut);
+    if (fill_unit_tab(ut, env, n_units)) hipLaunchKernelGGL((ssk::k_conv32<FUSE, true>), grid, block, 0, st, p, ut);
     else hipLaunchKernelGGL((ssk::k_conv32<FUSE, false>), grid, block, 0, st, p, ssk::UnitTab<false>());
     return hip_err(hipGetLastError());
 }
+
+int fill_conv(ssk::ConvParams& p, int* n_cus, const float* spec, const float* rir, const int* rir_len,
+                     const int* unit_desc, long long us, int cs, int es, int cap, int n_valid, int out_len,
+                     bool need_rir = true) {
+    if (!spec || (need_rir && !rir) || !rir_len || !unit_desc) return SS_EINVAL;
+    if (n_valid < 0 || out_len <= 0 || n_valid > out_len || n_valid > 3 * ssk::kB) return SS_EINVAL;
+    if (es < 1 || cs < 0 || us < 0 || cap < 0) return SS_EINVAL;
+    int rc = get_tables(&p.tb, n_cus);
+    if (rc) return rc;
+    p.spec = reinterpret_cast<const ssk::f32x4*>(spec);
+    p.rir = rir;
+    p.rir_len = rir_len;
+    p.desc = unit_desc;
+    p.out = nullptr;
+    p.sgram = nullptr;
+    p.rir_unit_stride = us;
+    p.rir_chan_stride = cs;
+    p.rir_elem_stride = es;
+    p.rir_cap = cap;
+    p.n_valid = n_valid;
+    p.out_len = out_len;
+    p.n_frames = n_frames_of(out_len);
+    p.t4 = t4_of(out_len);
+    p.pad_mode = 0;
+    p.fade_len = static_cast<int>(0.05 * out_len);     // crossfade_samples = int(0.05 * sr), rows are 1 s (out_len == sr)
+    p.hspec = nullptr;
+    p.h_blocks = 0;
+    // default on: the two ears of a unit (same window spectrum) share an XCD's L2; SS_HIP_XCD_MAP=0 is the A/B switch
+    static const int xcd_map = ab_int("SS_HIP_XCD_MAP", 1);
+    p.xcd_map = xcd_map;
+    p.stash = nullptr;
+    p.stash_nbh = 0;
+    p.stash_terms = 0;
+    p.n_terms = 2;
+    p.parts_log2 = 0;
+    p.n_buckets = 1;
+    for (auto& b : p.bk) b = ssk::BankBucket{nullptr, nullptr, 0x7fffffff, 0, 0, 0};
+#if defined(SS_LADDER)                                     // profiling builds only (scripts/gpu_ladder.sh compiles with -DSS_LADDER)
+    static const int dbg = getenv("SS_HIP_DBG") ? atoi(getenv("SS_HIP_DBG")) : 0;
+    p.dbg = dbg;
+#endif
+    return 0;
+}
+
+
+// n_valid: samples from n_valid on are KNOWN to be zero (rows this library rendered itself); len: nothing known
+int spectrogram_of_rows(const float* x, float* out, int n_units, int len, int n_valid, int pad_mode, void* stream) {
+    if (n_units == 0) return 0;
+    if (!x || !out || n_units < 0 || len < 1) return SS_EINVAL;   // any length: the centre padding folds as np.pad does
+    if (pad_mode != SS_PAD_REFLECT && pad_mode != SS_PAD_CONSTANT) return SS_EINVAL;
+    ssk::SpecParams p;
+    int rc = get_tables(&p.tb);
+    if (rc) return rc;
+    p.x = x;
+    p.out = out;
+    p.len = len;
+    p.n_frames = n_frames_of(len);
+    p.t4 = t4_of(len);
+    p.pad_mode = pad_mode;
+    p.live = ssk::live_blocks(n_valid, len, p.t4);
+    const int groups = (p.t4 + 3) / 4;                      // 4 pooled time blocks x 2 ears per round of a workgroup
+    // large batches: one workgroup walks several groups (tables staged once, next segment prefetched under the math);
+    // small batches keep one group per workgroup so that the launch still fills 256 CUs x 2 workgroups
+    long long gpw = (long long)n_units * groups / 2048;
+    p.gpw = gpw < 1 ? 1 : gpw > groups ? groups : (int)gpw;
+    const int chunks = (groups + p.gpw - 1) / p.gpw;
+    hipLaunchKernelGGL(ssk::k_spectrogram, dim3(n_units * chunks), dim3(512), 0,
+                       static_cast<hipStream_t>(stream), p);
+    return hip_err(hipGetLastError());
+}
+
+
+template <bool FUSE>
+int launch_conv_spec(ssk::ConvParams p, int n_units, int nb_y, int flags, const LaunchEnv& env, int n_cus = 0) {
+    const hipStream_t st = env.st;
+    if (nb_y < 1 || nb_y > 3 || (FUSE && nb_y != 1) || (flags & SS_FLAG_CROSSFADE)) return SS_EINVAL;
+    p.nb_y = nb_y;
+    p.parts_log2 = FUSE && n_cus > 0 ? parts_log2_for(2 * n_units, n_cus, env.share) : 0;
+    const bool simple = (flags & SS_FLAG_NO_DISTRACTOR) && nb_y == 1 && p.h_blocks == 1 &&
+                        (p.n_buckets == 1 || (flags & SS_FLAG_FIRST_BUCKET));
+    static const bool no_rows = ab_flag("SS_HIP_NO_ROW_KERNEL");
+    if constexpr (!FUSE) {              // more rows than CUs: persistent workgroups prefetching the next row's H'
+        if (simple && !no_rows && n_cus > 0 && n_units > n_cus && !(reinterpret_cast<size_t>(p.hspec) & 15)) {
+            hipLaunchKernelGGL(ssk::k_conv_spec_rows, dim3(n_cus), dim3(ssk::kT), 0, st, p, 2 * n_units);
+            return hip_err(hipGetLastError());
+        }
+    }
+    const dim3 grid((2 * n_units * nb_y) << p.parts_log2), block(ssk::kT);
+    if (simple) {
+        ssk::UnitTab<true> ut;
+        if (fill_unit_tab(ut, env, n_units)) hipLaunchKernelGGL((ssk::k_conv_spec<FUSE, true, true>), grid, block, 0, st, p, ut);
+        else hipLaunchKernelGGL((ssk::k_conv_spec<FUSE, true>), grid, block, 0, st, p, ssk::UnitTab<false>());
+    } else hipLaunchKernelGGL((ssk::k_conv_spec<FUSE, false>), grid, block, 0, st, p, ssk::UnitTab<false>());
+    return hip_err(hipGetLastError());
+}
+
+
+// ---- half bank: fp16 block spectra + one fp32 scale per (entry, ear, block) (include/ss_hip.h "Half-precision spectral bank") ----
+// k_conv_spec<.., HALF> for every launch (one workgroup per row and output block; more rows than CUs included: the persistent
+// k_conv_spec_rows has no half form)
+template <bool FUSE>
+int launch_conv_spec16(ssk::ConvParams p, const float* hscale, int n_units, int nb_y, int flags, const LaunchEnv& env, int n_cus) {
+    const hipStream_t st = env.st;
+    if (nb_y < 1 || nb_y > 3 || (FUSE && nb_y != 1) || (flags & SS_FLAG_CROSSFADE)) return SS_EINVAL;
+    p.nb_y = nb_y;
+    p.parts_log2 = FUSE && n_cus > 0 ? parts_log2_for(2 * n_units, n_cus, env.share) : 0;
+    const bool simple = (flags & SS_FLAG_NO_DISTRACTOR) && nb_y == 1 && p.h_blocks == 1;
+    const dim3 grid((2 * n_units * nb_y) << p.parts_log2), block(ssk::kT);
+    const ssk::SpecScale<true> hs{hscale};
+    if (simple) {
+        ssk::UnitTab<true> ut;
+        if (fill_unit_tab(ut, env, n_units))
+            hipLaunchKernelGGL((ssk::k_conv_spec<FUSE, true, true, false, true>), grid, block, 0, st, p, ut, hs);
+        else hipLaunchKernelGGL((ssk::k_conv_spec<FUSE, true, false, false, true>), grid, block, 0, st, p, ssk::UnitTab<false>(), hs);
+    } else hipLaunchKernelGGL((ssk::k_conv_spec<FUSE, false, false, false, true>), grid, block, 0, st, p, ssk::UnitTab<false>(), hs);
+    return hip_err(hipGetLastError());
+}
+
+
+// ---- length-bucketed RIR bank (SURVEY 8(f)2) ---------------------------------------------------------------------------
+// buckets[0..n): HOST array; bucket b holds bank entries [first_b, first_b + n_entries_b) as planar rows of cap_b samples
+// in an allocation of its own.  Bucket 0 fills the legacy fields of ConvParams, the others p.bk[].
+int fill_buckets(ssk::ConvParams& p, const ss_rir_bucket* bk, int n_buckets, bool spectral, int* nbh_max) {
+    if (!bk || n_buckets < 1 || n_buckets > ssk::kMaxBuckets) return SS_EINVAL;
+    int hb_max = 1;
+    for (int b = 0; b < n_buckets; ++b) {
+        if (!bk[b].rir || bk[b].cap < 2 || (bk[b].cap & 1) || bk[b].n_entries < 0 || bk[b].first < 0) return SS_EINVAL;
+        if (b && bk[b].first < bk[b - 1].first + bk[b - 1].n_entries) return SS_EINVAL;     // ascending, disjoint ranges
+        if (spectral && !bk[b].hspec) return SS_EINVAL;
+        hb_max = std::max(hb_max, (bk[b].cap + ssk::kB - 1) / ssk::kB);
+    }
+    if (bk[0].first != 0) return SS_EINVAL;
+    p.rir = bk[0].rir;
+    p.rir_unit_stride = 2LL * bk[0].cap;
+    p.rir_chan_stride = bk[0].cap;
+    p.rir_elem_stride = 1;
+    p.rir_cap = bk[0].cap;
+    p.hspec = spectral ? reinterpret_cast<const ssk::f32x4*>(bk[0].hspec) : nullptr;
+    p.h_blocks = spectral ? (bk[0].cap + ssk::kB - 1) / ssk::kB : 0;
+    p.n_buckets = n_buckets;
+    for (int b = 1; b < n_buckets; ++b)
+        p.bk[b - 1] = ssk::BankBucket{bk[b].rir, reinterpret_cast<const ssk::f32x4*>(bk[b].hspec), bk[b].first, bk[b].cap,
+                                      (bk[b].cap + ssk::kB - 1) / ssk::kB, 0};
+    *nbh_max = hb_max;
+    return 0;
+}
+
+bool buckets_spectral(const ss_rir_bucket* bk, int n_buckets, int flags) {
+    if (!bk || (flags & SS_FLAG_CROSSFADE)) return false;
+    for (int b = 0; b < n_buckets; ++b) if (!bk[b].hspec) return false;
+    return n_buckets > 0;
+}
+
+
+// ---- length-bucketed bank without time-domain rows: fp32 spectra ("only") or fp16 spectra + scales ("half") --------------
+// (include/ss_hip.h "Spectral length buckets").  Everything here is checked on the host before a device is touched.
+// *half = the form (every bucket carries scales / none does), *hb_max = the longest bucket's blocks.
+int spec_buckets_check(const ss_spec_bucket* bk, int n_buckets, bool* half, int* hb_max) {
+    if (!bk || n_buckets < 1 || n_buckets > ssk::kMaxBuckets) return SS_EINVAL;
+    const bool h = bk[0].hscale != nullptr;
+    int hb = 1;
+    for (int b = 0; b < n_buckets; ++b) {
+        if (!bk[b].hspec || (bk[b].hscale != nullptr) != h) return SS_EINVAL;                   // one form in every bucket
+        if (reinterpret_cast<size_t>(bk[b].hspec) & (h ? 7 : 15)) return SS_EINVAL;             // h16x4 / f32x4 loads
+        if (bk[b].cap < 2 || (bk[b].cap & 1) || bk[b].n_entries < 0 || bk[b].first < 0) return SS_EINVAL;
+        if (b && bk[b].first < bk[b - 1].first + bk[b - 1].n_entries) return SS_EINVAL;         // ascending, disjoint ranges
+        const int blocks = (bk[b].cap + ssk::kB - 1) / ssk::kB;
+        if (blocks > 16) return SS_EINVAL;
+        hb = std::max(hb, blocks);
+    }
+    if (bk[0].first != 0) return SS_EINVAL;
+    *half = h;
+    *hb_max = hb;
+    return 0;
+}
+
+// bucket 0 into the single-bank fields, the others into p.bk[] (no rows anywhere); the half form's scales into hs
+void fill_spec_buckets(ssk::ConvParams& p, ssk::SpecScale<true, true>& hs, const ss_spec_bucket* bk, int n_buckets) {
+    p.hspec = static_cast<const ssk::f32x4*>(bk[0].hspec);
+    p.h_blocks = (bk[0].cap + ssk::kB - 1) / ssk::kB;
+    p.n_buckets = n_buckets;
+    hs.hscale = bk[0].hscale;
+    for (auto& s : hs.bk) s = nullptr;
+    for (int b = 1; b < n_buckets; ++b) {
+        p.bk[b - 1] = ssk::BankBucket{nullptr, static_cast<const ssk::f32x4*>(bk[b].hspec), bk[b].first, bk[b].cap,
+                                      (bk[b].cap + ssk::kB - 1) / ssk::kB, 0};
+        hs.bk[b - 1] = bk[b].hscale;
+    }
+}
+
+// Half buckets.  Launches that only touch bucket 0 (one bucket, or SS_FLAG_FIRST_BUCKET) are single-allocation launches on
+// bucket 0's arrays: the existing HALF kernels, the loop-free ones included.  Everything else: k_conv_spec<.., HALF, HBK>.
+template <bool FUSE>
+int launch_conv_spec16_buckets(ssk::ConvParams p, const ssk::SpecScale<true, true>& hs, int n_units, int nb_y, int flags,
+                               const LaunchEnv& env, int n_cus) {
+    if (p.n_buckets == 1 || (flags & SS_FLAG_FIRST_BUCKET)) return launch_conv_spec16<FUSE>(p, hs.hscale, n_units, nb_y, flags, env, n_cus);
+    const hipStream_t st = env.st;
+    if (nb_y < 1 || nb_y > 3 || (FUSE && nb_y != 1) || (flags & SS_FLAG_CROSSFADE)) return SS_EINVAL;
+    p.nb_y = nb_y;
+    p.parts_log2 = FUSE && n_cus > 0 ? parts_log2_for(2 * n_units, n_cus, env.share) : 0;
+    const dim3 grid((2 * n_units * nb_y) << p.parts_log2), block(ssk::kT);
+    hipLaunchKernelGGL((ssk::k_conv_spec<FUSE, false, false, false, true, true>), grid, block, 0, st, p, ssk::UnitTab<false>(), hs);
+    return hip_err(hipGetLastError());
+}
+
+
+// ---- one launch body behind the observation entries -------------------------------------------------------------------
+// A RIR bank in whichever form its holder keeps it: built from the arguments of a C entry, or from a Context (bank_of).
+struct Bank {
+    const float* rir = nullptr;             // time-domain rows (length buckets that keep rows: bucket 0's)
+    long long us = 0;
+    int cs = 0, es = 1, cap = 0;
+    const void* hspec = nullptr;            // block spectra of the same entries: fp32, or - with hscale - fp16 + a scale per block
+    const float* hscale = nullptr;
+    int h_blocks = 0;
+    const ss_rir_bucket* bk = nullptr;      // length buckets that keep rows (every bucket may carry its fp32 spectra as well) ...
+    const ss_spec_bucket* sbk = nullptr;    // ... or hold spectra only, fp32 or half
+    int n_buckets = 0;
+};
+inline Bank rows_bank(const float* rir, long long us, int cs, int es, int cap) {
+    Bank b;
+    b.rir = rir; b.us = us; b.cs = cs; b.es = es; b.cap = cap;
+    return b;
+}
+inline Bank spec_bank(const void* hspec, int h_blocks, const float* hscale = nullptr) {
+    Bank b;
+    b.hspec = hspec; b.h_blocks = h_blocks; b.hscale = hscale;
+    return b;
+}
+inline Bank buckets_bank(const ss_rir_bucket* bk, int n_buckets) {
+    Bank b = bk && n_buckets >= 1 ? rows_bank(bk[0].rir, 2LL * bk[0].cap, bk[0].cap, 1, bk[0].cap) : Bank();
+    b.bk = bk; b.n_buckets = n_buckets;
+    return b;
+}
+inline Bank spec_buckets_bank(const ss_spec_bucket* sbk, int n_buckets) {
+    Bank b;
+    b.sbk = sbk; b.n_buckets = n_buckets;
+    return b;
+}
+
+// the convolution of whichever form the launch reads: k_conv (time-domain rows), k_conv_spec (fp32 spectra) or its half forms
+template <bool FUSE>
+int launch_conv_any(const ssk::ConvParams& p, const ssk::SpecScale<true, true>& hs, bool spectral, int n_units, int nb_y, int flags,
+                    int n_cus, const LaunchEnv& env) {
+    if (!spectral) return launch_conv<FUSE>(p, n_units, nb_y, flags, n_cus, env);
+    if (hs.hscale) return launch_conv_spec16_buckets<FUSE>(p, hs, n_units, nb_y, flags, env, n_cus);
+    return launch_conv_spec<FUSE>(p, n_units, nb_y, flags, env, n_cus);
+}
+
+// ... and k_obs_blocks / k_obs_rows likewise (launch_obs_rows' own choice, hand-off area and stash)
+template <bool MEL>
+int launch_rows_any(const ssk::ConvParams& p, const ssk::SpecScale<true, true>& hs, bool spectral, int n_units, int flags, int n_cus,
+                    const LaunchEnv& env, const ssk::UnitTab<false, MEL>& mel = ssk::UnitTab<false, MEL>()) {
+    if (!spectral) return launch_obs_rows<false, MEL>(p, n_units, flags, n_cus, env, mel);
+    if (hs.hscale) return launch_obs_rows<true, MEL, true>(p, n_units, flags, n_cus, env, mel, ssk::SpecScale<true>{hs.hscale});
+    return launch_obs_rows<true, MEL>(p, n_units, flags, n_cus, env, mel);
+}
+
+// One step from bank `b`: the body of every ss_fftconv_binaural_* (want = kConv: the waveform alone), ss_audio_obs_* (kObs: the
+// chain of ss_route.hpp - fused one-block, wide, rows, else the convolution into `audiogoal` and k_spectrogram over it) and
+// ss_audio_obs_logmel_* entry (the kMel forms: one launch, `mel` set, audiogoal / spectrogram optional), and of the context's step.
+// spectral: read the block spectra of a single-allocation bank, not its rows (length buckets decide for themselves: those that
+// keep rows when every bucket carries spectra and the step has no cross-fade, spectral buckets always).
+// Everything that is refused is refused before a device is touched - this level owns no scratch to fall back on.
+int render(const Bank& b, bool spectral, ssroute::Launch want, const float* spec, const int* rir_len, const int* unit_desc,
+           float* audiogoal, float* spectrogram, const ssk::MelArgs* mel, int n_units, int n_valid, int out_len, int pad_mode,
+           int flags, const LaunchEnv& env) {
+    using ssroute::Chain;
+    using ssroute::Launch;
+    const bool bucketed = b.bk || b.sbk;
+    bool half = b.hscale != nullptr;
+    int nbh_max = 1;
+    if (n_units < 0) return SS_EINVAL;
+    if (b.sbk) {                                            // (no rows anywhere: a cross-fade has nothing to read)
+        if (spec_buckets_check(b.sbk, b.n_buckets, &half, &nbh_max) || (flags & SS_FLAG_CROSSFADE)) return SS_EINVAL;
+        spectral = true;
+    } else if (b.bk) {
+        ssk::ConvParams probe;                              // (the bucket array's own refusals, without the device's tables)
+        spectral = buckets_spectral(b.bk, b.n_buckets, flags);
+        if (fill_buckets(probe, b.bk, b.n_buckets, spectral, &nbh_max)) return SS_EINVAL;
+    } else if (spectral) {
+        if (!b.hspec || b.h_blocks < 1) return SS_EINVAL;
+        nbh_max = b.h_blocks;
+    } else {
+        nbh_max = (b.cap + ssk::kB - 1) / ssk::kB;
+    }
+    if (want != Launch::kConv) {
+        if (pad_mode != SS_PAD_REFLECT && pad_mode != SS_PAD_CONSTANT) return SS_EINVAL;
+        if (out_len < ssk::kNfft / 2 + 1) return SS_EINVAL;
+    }
+    Chain chain = Chain::kFused;
+    int ss2_shape = 0;
+    switch (want) {
+        case Launch::kConv:
+            if (!audiogoal) return SS_EINVAL;
+            break;
+        case Launch::kObs:
+            if (!spectrogram) return SS_EINVAL;
+            // half spectral buckets: rows of one partition block (the fused row kernels do not read half bucketed banks)
+            if (b.sbk && half && (out_len > ssk::kB || t4_of(out_len) > 26)) return SS_EINVAL;
+            chain = ssroute::obs_chain(out_len, n_valid, nbh_max, flags, spectral, audiogoal != nullptr, route_switches());
+            if (chain == Chain::kTwo && !audiogoal) return SS_EINVAL;      // cross-faded long rows hand over through HBM/L2
+            break;
+        case Launch::kMelOneBlock:
+            if (!mel || !ssroute::obs_logmel_shape_ok(out_len, flags)) return SS_EINVAL;
+            break;
+        case Launch::kMelSs2:
+            ss2_shape = ssroute::obs_logmel_ss2_shape(out_len, n_valid, flags, route_switches());
+            if (!mel || spectral || bucketed || !ss2_shape) return SS_EINVAL;
+            break;
+        case Launch::kMelRows:
+            if (!mel || (half && bucketed) || (!spectral && !bucketed && b.cap < 1) ||
+                !ssroute::obs_logmel_rows_shape_ok(out_len, n_valid, nbh_max, flags))
+                return SS_EINVAL;
+            break;
+        default:
+            return SS_EINVAL;
+    }
+    ssk::ConvParams p;
+    int n_cus = 1;
+    const bool rows = !spectral || b.bk;                    // (length buckets that keep rows always describe them)
+    int rc = rows ? fill_conv(p, &n_cus, spec, b.rir, rir_len, unit_desc, b.us, b.cs, b.es, b.cap, n_valid, out_len)
+                  : fill_conv(p, &n_cus, spec, nullptr, rir_len, unit_desc, 0, 0, 1, 0, n_valid, out_len, false);
+    if (rc) return rc;
+    ssk::SpecScale<true, true> hs;
+    hs.hscale = b.hscale;
+    for (auto& sc : hs.bk) sc = nullptr;
+    if (b.sbk) fill_spec_buckets(p, hs, b.sbk, b.n_buckets);
+    else if (b.bk) rc = fill_buckets(p, b.bk, b.n_buckets, spectral, &nbh_max);
+    else if (spectral) { p.hspec = static_cast<const ssk::f32x4*>(b.hspec); p.h_blocks = b.h_blocks; }
+    if (rc) return rc;
+    p.out = audiogoal;
+    const int nb_y = n_valid == 0 ? 1 : (n_valid + ssk::kB - 1) / ssk::kB;
+    if (want == Launch::kConv) return launch_conv_any<false>(p, hs, spectral, n_units, nb_y, flags, n_cus, env);
+    if (want == Launch::kObs && chain == Chain::kTwo) {     // (pad_mode, sgram: as the convolution alone leaves them)
+        rc = launch_conv_any<false>(p, hs, spectral, n_units, nb_y, flags, n_cus, env);
+        if (rc) return rc;
+        return spectrogram_of_rows(audiogoal, spectrogram, n_units, out_len, n_valid, pad_mode, env.st);
+    }
+    p.pad_mode = pad_mode;
+    p.sgram = spectrogram;
+    if (want == Launch::kObs) {
+        if (chain == Chain::kFused) return launch_conv_any<true>(p, hs, spectral, n_units, 1, flags, n_cus, env);
+        if (chain == Chain::kWide) return launch_conv<true>(p, n_units, 1, flags, n_cus, env, true);
+        return launch_rows_any<false>(p, hs, spectral, n_units, flags, n_cus, env);
+    }
+    // the log-mel forms.  Launches that only touch bucket 0 (one bucket, or SS_FLAG_FIRST_BUCKET) are single-allocation launches
+    // on bucket 0's arrays: the single-bank log-mel launchers, loop-free kernels included.
+    if (flags & SS_FLAG_FIRST_BUCKET) p.n_buckets = 1;
+    if (want == Launch::kMelSs2) return launch_conv_mel_ss2(p, *mel, n_units, flags, ss2_shape == 2, env.st);
+    if (want == Launch::kMelRows) return launch_rows_any<true>(p, hs, spectral, n_units, flags, n_cus, env, *mel);
+    if (!spectral) return launch_conv_mel(p, *mel, n_units, flags, env.st);
+    if (!half) return launch_conv_spec_mel(p, *mel, n_units, flags, env.st);
+    if (p.n_buckets == 1) return launch_conv_spec16_mel(p, *mel, hs.hscale, n_units, flags, env.st);
+    p.nb_y = 1;
+    p.parts_log2 = 0;
+    hipLaunchKernelGGL((ssk::k_conv_spec<true, false, false, true, true, true>), dim3(2 * n_units), dim3(ssk::kT), 0, env.st, p, *mel, hs);
+    return hip_err(hipGetLastError());
+}
+
+// the stateless entries: device pointers only, the whole chip
+inline LaunchEnv stateless(void* stream) {
+    LaunchEnv env;
+    env.st = static_cast<hipStream_t>(stream);
+    return env;
+}
+using ssroute::Launch;
 
 }  // namespace
 
@@ -586,94 +940,16 @@ static int launch_windows_scatter(const float* src, const int* win_desc5, float*
     return hip_err(hipGetLastError());
 }
 
-static int fill_conv(ssk::ConvParams& p, int* n_cus, const float* spec, const float* rir, const int* rir_len,
-                     const int* unit_desc, long long us, int cs, int es, int cap, int n_valid, int out_len,
-                     bool need_rir = true) {
-    if (!spec || (need_rir && !rir) || !rir_len || !unit_desc) return SS_EINVAL;
-    if (n_valid < 0 || out_len <= 0 || n_valid > out_len || n_valid > 3 * ssk::kB) return SS_EINVAL;
-    if (es < 1 || cs < 0 || us < 0 || cap < 0) return SS_EINVAL;
-    int rc = get_tables(&p.tb, n_cus);
-    if (rc) return rc;
-    p.spec = reinterpret_cast<const ssk::f32x4*>(spec);
-    p.rir = rir;
-    p.rir_len = rir_len;
-    p.desc = unit_desc;
-    p.out = nullptr;
-    p.sgram = nullptr;
-    p.rir_unit_stride = us;
-    p.rir_chan_stride = cs;
-    p.rir_elem_stride = es;
-    p.rir_cap = cap;
-    p.n_valid = n_valid;
-    p.out_len = out_len;
-    p.n_frames = n_frames_of(out_len);
-    p.t4 = t4_of(out_len);
-    p.pad_mode = 0;
-    p.fade_len = static_cast<int>(0.05 * out_len);     // crossfade_samples = int(0.05 * sr), rows are 1 s (out_len == sr)
-    p.hspec = nullptr;
-    p.h_blocks = 0;
-    // default on: the two ears of a unit (same window spectrum) share an XCD's L2; SS_HIP_XCD_MAP=0 is the A/B switch
-    static const int xcd_map = ab_int("SS_HIP_XCD_MAP", 1);
-    p.xcd_map = xcd_map;
-    p.stash = nullptr;
-    p.stash_nbh = 0;
-    p.stash_terms = 0;
-    p.n_terms = 2;
-    p.parts_log2 = 0;
-    p.n_buckets = 1;
-    for (auto& b : p.bk) b = ssk::BankBucket{nullptr, nullptr, 0x7fffffff, 0, 0, 0};
-#if defined(SS_LADDER)                                     // profiling builds only (scripts/gpu_ladder.sh compiles with -DSS_LADDER)
-    static const int dbg = getenv("SS_HIP_DBG") ? atoi(getenv("SS_HIP_DBG")) : 0;
-    p.dbg = dbg;
-#endif
-    return 0;
-}
-
 int ss_fftconv_binaural_f32(const float* spec, const float* rir, const int* rir_len, const int* unit_desc,
                             float* out, int n_units, long long rir_unit_stride, int rir_chan_stride,
                             int rir_elem_stride, int rir_cap, int n_valid, int out_len, int flags, void* stream) {
     if (n_units == 0) return 0;
-    if (!out || n_units < 0) return SS_EINVAL;
-    ssk::ConvParams p;
-    int n_cus = 1;
-    int rc = fill_conv(p, &n_cus, spec, rir, rir_len, unit_desc, rir_unit_stride, rir_chan_stride, rir_elem_stride,
-                       rir_cap, n_valid, out_len);
-    if (rc) return rc;
-    p.out = out;
-    const int nb_y = n_valid == 0 ? 1 : (n_valid + ssk::kB - 1) / ssk::kB;
-    return launch_conv<false>(p, n_units, nb_y, flags, n_cus, static_cast<hipStream_t>(stream));
+    return render(rows_bank(rir, rir_unit_stride, rir_chan_stride, rir_elem_stride, rir_cap), false, Launch::kConv, spec, rir_len,
+                  unit_desc, out, nullptr, nullptr, n_units, n_valid, out_len, SS_PAD_REFLECT, flags, stateless(stream));
 }
-
-// n_valid: samples from n_valid on are KNOWN to be zero (rows this library rendered itself); len: nothing known
-static int spectrogram_of_rows(const float* x, float* out, int n_units, int len, int n_valid, int pad_mode, void* stream);
 
 int ss_spectrogram_f32(const float* x, float* out, int n_units, int len, int pad_mode, void* stream) {
     return spectrogram_of_rows(x, out, n_units, len, len, pad_mode, stream);
-}
-
-static int spectrogram_of_rows(const float* x, float* out, int n_units, int len, int n_valid, int pad_mode, void* stream) {
-    if (n_units == 0) return 0;
-    if (!x || !out || n_units < 0 || len < 1) return SS_EINVAL;   // any length: the centre padding folds as np.pad does
-    if (pad_mode != SS_PAD_REFLECT && pad_mode != SS_PAD_CONSTANT) return SS_EINVAL;
-    ssk::SpecParams p;
-    int rc = get_tables(&p.tb);
-    if (rc) return rc;
-    p.x = x;
-    p.out = out;
-    p.len = len;
-    p.n_frames = n_frames_of(len);
-    p.t4 = t4_of(len);
-    p.pad_mode = pad_mode;
-    p.live = ssk::live_blocks(n_valid, len, p.t4);
-    const int groups = (p.t4 + 3) / 4;                      // 4 pooled time blocks x 2 ears per round of a workgroup
-    // large batches: one workgroup walks several groups (tables staged once, next segment prefetched under the math);
-    // small batches keep one group per workgroup so that the launch still fills 256 CUs x 2 workgroups
-    long long gpw = (long long)n_units * groups / 2048;
-    p.gpw = gpw < 1 ? 1 : gpw > groups ? groups : (int)gpw;
-    const int chunks = (groups + p.gpw - 1) / p.gpw;
-    hipLaunchKernelGGL(ssk::k_spectrogram, dim3(n_units * chunks), dim3(512), 0,
-                       static_cast<hipStream_t>(stream), p);
-    return hip_err(hipGetLastError());
 }
 
 int ss_logmel_f32(const float* x, float* out, int n_units, int len, int pad_mode, const int* mel_start,
@@ -775,35 +1051,8 @@ int ss_audio_obs_f32(const float* spec, const float* rir, const int* rir_len, co
                      int rir_chan_stride, int rir_elem_stride, int rir_cap, int n_valid, int out_len,
                      int pad_mode, int flags, void* stream) {
     if (n_units == 0) return 0;
-    if (!spectrogram || n_units < 0) return SS_EINVAL;
-    if (pad_mode != SS_PAD_REFLECT && pad_mode != SS_PAD_CONSTANT) return SS_EINVAL;
-    if (out_len < ssk::kNfft / 2 + 1) return SS_EINVAL;
-    ssk::ConvParams p;
-    int n_cus = 1;
-    int rc = fill_conv(p, &n_cus, spec, rir, rir_len, unit_desc, rir_unit_stride, rir_chan_stride, rir_elem_stride,
-                       rir_cap, n_valid, out_len);
-    if (rc) return rc;
-    p.pad_mode = pad_mode;
-    if (out_len <= ssk::kB && p.t4 <= 26) {             // fused: waveform stays in LDS
-        p.out = audiogoal;
-        p.sgram = spectrogram;
-        return launch_conv<true>(p, n_units, 1, flags, n_cus, static_cast<hipStream_t>(stream));
-    }
-    if (wide_one_block_ok(out_len, n_valid, flags)) {    // one rendered block of a longer row: fused loop kernel, one launch
-        p.out = audiogoal;
-        p.sgram = spectrogram;
-        return launch_conv<true>(p, n_units, 1, flags, n_cus, static_cast<hipStream_t>(stream), true);
-    }
-    if (obs_rows_ok(out_len, n_valid, (rir_cap + ssk::kB - 1) / ssk::kB, flags, false, audiogoal != nullptr)) {   // rows of 2-3 blocks: fused as well
-        p.out = audiogoal;
-        p.sgram = spectrogram;
-        return launch_obs_rows<false>(p, n_units, flags, n_cus, static_cast<hipStream_t>(stream));
-    }
-    if (!audiogoal) return SS_EINVAL;                   // cross-faded long rows hand over through HBM/L2
-    rc = ss_fftconv_binaural_f32(spec, rir, rir_len, unit_desc, audiogoal, n_units, rir_unit_stride,
-                                 rir_chan_stride, rir_elem_stride, rir_cap, n_valid, out_len, flags, stream);
-    if (rc) return rc;
-    return spectrogram_of_rows(audiogoal, spectrogram, n_units, out_len, n_valid, pad_mode, stream);
+    return render(rows_bank(rir, rir_unit_stride, rir_chan_stride, rir_elem_stride, rir_cap), false, Launch::kObs, spec, rir_len,
+                  unit_desc, audiogoal, spectrogram, nullptr, n_units, n_valid, out_len, pad_mode, flags, stateless(stream));
 }
 
 // Log-mel observation in ONE launch, no waveform buffer needed (k_conv<.., MEL>): rows of one partition block only.  Every
@@ -813,28 +1062,10 @@ int ss_audio_obs_logmel_f32(const float* spec, const float* rir, const int* rir_
                             float mel_eps, int n_units, long long rir_unit_stride, int rir_chan_stride, int rir_elem_stride,
                             int rir_cap, int n_valid, int out_len, int pad_mode, int flags, void* stream) {
     if (n_units == 0) return 0;
-    if (n_units < 0 || !mel_args_ok(logmel, mel_start, mel_w, n_mels, max_len, mel_eps)) return SS_EINVAL;
-    if (pad_mode != SS_PAD_REFLECT && pad_mode != SS_PAD_CONSTANT) return SS_EINVAL;
-    if (!obs_logmel_shape_ok(out_len, flags)) return SS_EINVAL;
-    ssk::ConvParams p;
-    int n_cus = 1;
-    int rc = fill_conv(p, &n_cus, spec, rir, rir_len, unit_desc, rir_unit_stride, rir_chan_stride, rir_elem_stride,
-                       rir_cap, n_valid, out_len);
-    if (rc) return rc;
-    p.pad_mode = pad_mode;
-    p.out = audiogoal;
-    p.sgram = spectrogram;
+    if (!mel_args_ok(logmel, mel_start, mel_w, n_mels, max_len, mel_eps)) return SS_EINVAL;
     const ssk::MelArgs m{logmel, mel_start, mel_w, n_mels, max_len, mel_eps};
-    return launch_conv_mel(p, m, n_units, flags, static_cast<hipStream_t>(stream));
-}
-
-// SoundSpaces 2.0 steps the log-mel form serves (time-domain bank): (A) cross-faded one-block rows - fade_len = int(0.05 out_len)
-// lies inside [1, 2 kPrevPairs - 2] for every such length - and (B) rows of 2 or 3 blocks of which only block 0 is rendered
-// (wide_one_block_ok: its own cross-fade limits).  0: neither, 1: (A), 2: (B).
-inline int obs_logmel_ss2_shape(int out_len, int n_valid, int flags) {
-    if (n_valid < 0 || n_valid > out_len) return 0;
-    if (out_len >= ssk::kNfft / 2 + 1 && out_len <= ssk::kB) return (flags & SS_FLAG_CROSSFADE) ? 1 : 0;
-    return out_len <= 3 * ssk::kB && wide_one_block_ok(out_len, n_valid, flags) ? 2 : 0;
+    return render(rows_bank(rir, rir_unit_stride, rir_chan_stride, rir_elem_stride, rir_cap), false, Launch::kMelOneBlock, spec, rir_len,
+                  unit_desc, audiogoal, spectrogram, &m, n_units, n_valid, out_len, pad_mode, flags, stateless(stream));
 }
 
 // Log-mel observation of a SoundSpaces 2.0 step in ONE launch (k_conv<.., XFADE, .., WIDE, MEL>), no waveform buffer needed.
@@ -844,34 +1075,10 @@ int ss_audio_obs_logmel_ss2_f32(const float* spec, const float* rir, const int* 
                                 int max_len, float mel_eps, int n_units, long long rir_unit_stride, int rir_chan_stride,
                                 int rir_elem_stride, int rir_cap, int n_valid, int out_len, int pad_mode, int flags, void* stream) {
     if (n_units == 0) return 0;
-    if (n_units < 0 || !mel_args_ok(logmel, mel_start, mel_w, n_mels, max_len, mel_eps)) return SS_EINVAL;
-    if (pad_mode != SS_PAD_REFLECT && pad_mode != SS_PAD_CONSTANT) return SS_EINVAL;
-    const int shape = obs_logmel_ss2_shape(out_len, n_valid, flags);
-    if (!shape) return SS_EINVAL;
-    ssk::ConvParams p;
-    int n_cus = 1;
-    int rc = fill_conv(p, &n_cus, spec, rir, rir_len, unit_desc, rir_unit_stride, rir_chan_stride, rir_elem_stride,
-                       rir_cap, n_valid, out_len);
-    if (rc) return rc;
-    p.pad_mode = pad_mode;
-    p.out = audiogoal;
-    p.sgram = spectrogram;
+    if (!mel_args_ok(logmel, mel_start, mel_w, n_mels, max_len, mel_eps)) return SS_EINVAL;
     const ssk::MelArgs m{logmel, mel_start, mel_w, n_mels, max_len, mel_eps};
-    return launch_conv_mel_ss2(p, m, n_units, flags, shape == 2, static_cast<hipStream_t>(stream));
-}
-
-// rows the log-mel form of k_obs_rows / k_obs_blocks serves: 2 or 3 partition blocks (44.1 / 48 kHz), plain steps, at most 16
-// RIR blocks (obs_rows_ok without a cross-fade; a waveform buffer changes nothing here: the caller chose the entry)
-inline bool obs_logmel_rows_shape_ok(int out_len, int n_valid, int nbh_max, int flags) {
-    return !(flags & SS_FLAG_CROSSFADE) && n_valid >= 0 && obs_rows_ok(out_len, n_valid, nbh_max, flags);
-}
-
-// rows the log-mel entries of the length-bucketed banks serve (ss_audio_obs_logmel_buckets_f32 / _spec_buckets_f32): one partition
-// block on every bank form; 2 or 3 blocks on the fp32 forms, with the deepest bucket's blocks inside the row kernels' limit
-inline bool obs_logmel_buckets_shape_ok(int out_len, int n_valid, int nbh_max, int flags, bool half) {
-    if (n_valid < 0 || n_valid > out_len) return false;
-    if (obs_logmel_shape_ok(out_len, flags)) return true;
-    return !half && obs_logmel_rows_shape_ok(out_len, n_valid, nbh_max, flags);
+    return render(rows_bank(rir, rir_unit_stride, rir_chan_stride, rir_elem_stride, rir_cap), false, Launch::kMelSs2, spec, rir_len,
+                  unit_desc, audiogoal, spectrogram, &m, n_units, n_valid, out_len, pad_mode, flags, stateless(stream));
 }
 
 // Log-mel observation of rows of 2 or 3 partition blocks in ONE launch (k_obs_blocks<.., MEL> for small steps, else
@@ -881,19 +1088,10 @@ int ss_audio_obs_logmel_rows_f32(const float* spec, const float* rir, const int*
                                  int max_len, float mel_eps, int n_units, long long rir_unit_stride, int rir_chan_stride,
                                  int rir_elem_stride, int rir_cap, int n_valid, int out_len, int pad_mode, int flags, void* stream) {
     if (n_units == 0) return 0;
-    if (n_units < 0 || !mel_args_ok(logmel, mel_start, mel_w, n_mels, max_len, mel_eps)) return SS_EINVAL;
-    if (pad_mode != SS_PAD_REFLECT && pad_mode != SS_PAD_CONSTANT) return SS_EINVAL;
-    if (rir_cap < 1 || !obs_logmel_rows_shape_ok(out_len, n_valid, (rir_cap + ssk::kB - 1) / ssk::kB, flags)) return SS_EINVAL;
-    ssk::ConvParams p;
-    int n_cus = 1;
-    int rc = fill_conv(p, &n_cus, spec, rir, rir_len, unit_desc, rir_unit_stride, rir_chan_stride, rir_elem_stride,
-                       rir_cap, n_valid, out_len);
-    if (rc) return rc;
-    p.pad_mode = pad_mode;
-    p.out = audiogoal;
-    p.sgram = spectrogram;
+    if (!mel_args_ok(logmel, mel_start, mel_w, n_mels, max_len, mel_eps)) return SS_EINVAL;
     const ssk::MelArgs m{logmel, mel_start, mel_w, n_mels, max_len, mel_eps};
-    return launch_obs_rows<false, true>(p, n_units, flags, n_cus, static_cast<hipStream_t>(stream), m);
+    return render(rows_bank(rir, rir_unit_stride, rir_chan_stride, rir_elem_stride, rir_cap), false, Launch::kMelRows, spec, rir_len,
+                  unit_desc, audiogoal, spectrogram, &m, n_units, n_valid, out_len, pad_mode, flags, stateless(stream));
 }
 
 // ---- 512-thread FFT core (ss_kernels32.hpp): loop-free rows only; spectra in that core's own register order ----------
@@ -932,9 +1130,9 @@ int ss_audio_obs32_f32(const float* spec32, const float* rir, const int* rir_len
     p.sgram = spectrogram;
     if (spectrogram) {
         if (out_len > ssk::kB || p.t4 > 26) return SS_EINVAL;
-        return launch_conv32<true>(p, n_units, static_cast<hipStream_t>(stream));
+        return launch_conv32<true>(p, n_units, stateless(stream));
     }
-    return launch_conv32<false>(p, n_units, static_cast<hipStream_t>(stream));
+    return launch_conv32<false>(p, n_units, stateless(stream));
 }
 
 int ss_intensity_f32(const float* audiogoal, float* out, int n_units, int len, int num_frame, void* stream) {
@@ -1053,76 +1251,22 @@ int ss_rir_spectra_f32(const float* rir, float* hspec_out, int n_entries, long l
 
 }  // extern "C"
 
-template <bool FUSE>
-static int launch_conv_spec(ssk::ConvParams p, int n_units, int nb_y, int flags, hipStream_t st, int n_cus = 0) {
-    if (nb_y < 1 || nb_y > 3 || (FUSE && nb_y != 1) || (flags & SS_FLAG_CROSSFADE)) return SS_EINVAL;
-    p.nb_y = nb_y;
-    p.parts_log2 = FUSE && n_cus > 0 ? parts_log2_for(2 * n_units, n_cus) : 0;
-    const bool simple = (flags & SS_FLAG_NO_DISTRACTOR) && nb_y == 1 && p.h_blocks == 1 &&
-                        (p.n_buckets == 1 || (flags & SS_FLAG_FIRST_BUCKET));
-    static const bool no_rows = ab_flag("SS_HIP_NO_ROW_KERNEL");
-    if constexpr (!FUSE) {              // more rows than CUs: persistent workgroups prefetching the next row's H'
-        if (simple && !no_rows && n_cus > 0 && n_units > n_cus && !(reinterpret_cast<size_t>(p.hspec) & 15)) {
-            hipLaunchKernelGGL(ssk::k_conv_spec_rows, dim3(n_cus), dim3(ssk::kT), 0, st, p, 2 * n_units);
-            return hip_err(hipGetLastError());
-        }
-    }
-    const dim3 grid((2 * n_units * nb_y) << p.parts_log2), block(ssk::kT);
-    if (simple) {
-        ssk::UnitTab<true> ut;
-        if (fill_unit_tab(ut, g_host_desc, n_units)) hipLaunchKernelGGL((ssk::k_conv_spec<FUSE, true, true>), grid, block, 0, st, p, ut);
-        else hipLaunchKernelGGL((ssk::k_conv_spec<FUSE, true>), grid, block, 0, st, p, ssk::UnitTab<false>());
-    } else hipLaunchKernelGGL((ssk::k_conv_spec<FUSE, false>), grid, block, 0, st, p, ssk::UnitTab<false>());
-    return hip_err(hipGetLastError());
-}
-
 extern "C" {
 
 int ss_fftconv_binaural_spec_f32(const float* spec, const float* hspec, const int* rir_len, const int* unit_desc,
                                  float* out, int n_units, int h_blocks, int n_valid, int out_len, int flags,
                                  void* stream) {
     if (n_units == 0) return 0;
-    if (!out || !hspec || n_units < 0 || h_blocks < 1) return SS_EINVAL;
-    ssk::ConvParams p;
-    int n_cus = 1;
-    int rc = fill_conv(p, &n_cus, spec, nullptr, rir_len, unit_desc, 0, 0, 1, 0, n_valid, out_len, false);
-    if (rc) return rc;
-    p.out = out;
-    p.hspec = reinterpret_cast<const ssk::f32x4*>(hspec);
-    p.h_blocks = h_blocks;
-    const int nb_y = n_valid == 0 ? 1 : (n_valid + ssk::kB - 1) / ssk::kB;
-    return launch_conv_spec<false>(p, n_units, nb_y, flags, static_cast<hipStream_t>(stream), n_cus);
+    return render(spec_bank(hspec, h_blocks), true, Launch::kConv, spec, rir_len, unit_desc, out, nullptr, nullptr, n_units, n_valid,
+                  out_len, SS_PAD_REFLECT, flags, stateless(stream));
 }
 
 int ss_audio_obs_spec_f32(const float* spec, const float* hspec, const int* rir_len, const int* unit_desc,
                           float* audiogoal, float* spectrogram, int n_units, int h_blocks, int n_valid, int out_len,
                           int pad_mode, int flags, void* stream) {
     if (n_units == 0) return 0;
-    if (!spectrogram || !hspec || n_units < 0 || h_blocks < 1) return SS_EINVAL;
-    if (pad_mode != SS_PAD_REFLECT && pad_mode != SS_PAD_CONSTANT) return SS_EINVAL;
-    if (out_len < ssk::kNfft / 2 + 1) return SS_EINVAL;
-    ssk::ConvParams p;
-    int n_cus = 1;
-    int rc = fill_conv(p, &n_cus, spec, nullptr, rir_len, unit_desc, 0, 0, 1, 0, n_valid, out_len, false);
-    if (rc) return rc;
-    p.pad_mode = pad_mode;
-    p.hspec = reinterpret_cast<const ssk::f32x4*>(hspec);
-    p.h_blocks = h_blocks;
-    if (out_len <= ssk::kB && p.t4 <= 26) {
-        p.out = audiogoal;
-        p.sgram = spectrogram;
-        return launch_conv_spec<true>(p, n_units, 1, flags, static_cast<hipStream_t>(stream), n_cus);
-    }
-    if (obs_rows_ok(out_len, n_valid, h_blocks, flags, true, audiogoal != nullptr)) {
-        p.out = audiogoal;
-        p.sgram = spectrogram;
-        return launch_obs_rows<true>(p, n_units, flags, n_cus, static_cast<hipStream_t>(stream));
-    }
-    if (!audiogoal) return SS_EINVAL;
-    rc = ss_fftconv_binaural_spec_f32(spec, hspec, rir_len, unit_desc, audiogoal, n_units, h_blocks, n_valid, out_len,
-                                      flags, stream);
-    if (rc) return rc;
-    return spectrogram_of_rows(audiogoal, spectrogram, n_units, out_len, n_valid, pad_mode, stream);
+    return render(spec_bank(hspec, h_blocks), true, Launch::kObs, spec, rir_len, unit_desc, audiogoal, spectrogram, nullptr, n_units,
+                  n_valid, out_len, pad_mode, flags, stateless(stream));
 }
 
 // ss_audio_obs_logmel_f32 from the spectral bank (k_conv_spec<.., MEL>)
@@ -1131,43 +1275,13 @@ int ss_audio_obs_logmel_spec_f32(const float* spec, const float* hspec, const in
                                  int max_len, float mel_eps, int n_units, int h_blocks, int n_valid, int out_len, int pad_mode,
                                  int flags, void* stream) {
     if (n_units == 0) return 0;
-    if (n_units < 0 || !hspec || h_blocks < 1 || !mel_args_ok(logmel, mel_start, mel_w, n_mels, max_len, mel_eps)) return SS_EINVAL;
-    if (pad_mode != SS_PAD_REFLECT && pad_mode != SS_PAD_CONSTANT) return SS_EINVAL;
-    if (!obs_logmel_shape_ok(out_len, flags)) return SS_EINVAL;
-    ssk::ConvParams p;
-    int n_cus = 1;
-    int rc = fill_conv(p, &n_cus, spec, nullptr, rir_len, unit_desc, 0, 0, 1, 0, n_valid, out_len, false);
-    if (rc) return rc;
-    p.pad_mode = pad_mode;
-    p.hspec = reinterpret_cast<const ssk::f32x4*>(hspec);
-    p.h_blocks = h_blocks;
-    p.out = audiogoal;
-    p.sgram = spectrogram;
+    if (!mel_args_ok(logmel, mel_start, mel_w, n_mels, max_len, mel_eps)) return SS_EINVAL;
     const ssk::MelArgs m{logmel, mel_start, mel_w, n_mels, max_len, mel_eps};
-    return launch_conv_spec_mel(p, m, n_units, flags, static_cast<hipStream_t>(stream));
+    return render(spec_bank(hspec, h_blocks), true, Launch::kMelOneBlock, spec, rir_len, unit_desc, audiogoal, spectrogram, &m,
+                  n_units, n_valid, out_len, pad_mode, flags, stateless(stream));
 }
 
 }  // extern "C"
-
-// ---- half bank: fp16 block spectra + one fp32 scale per (entry, ear, block) (include/ss_hip.h "Half-precision spectral bank") ----
-// k_conv_spec<.., HALF> for every launch (one workgroup per row and output block; more rows than CUs included: the persistent
-// k_conv_spec_rows has no half form)
-template <bool FUSE>
-static int launch_conv_spec16(ssk::ConvParams p, const float* hscale, int n_units, int nb_y, int flags, hipStream_t st, int n_cus) {
-    if (nb_y < 1 || nb_y > 3 || (FUSE && nb_y != 1) || (flags & SS_FLAG_CROSSFADE)) return SS_EINVAL;
-    p.nb_y = nb_y;
-    p.parts_log2 = FUSE && n_cus > 0 ? parts_log2_for(2 * n_units, n_cus) : 0;
-    const bool simple = (flags & SS_FLAG_NO_DISTRACTOR) && nb_y == 1 && p.h_blocks == 1;
-    const dim3 grid((2 * n_units * nb_y) << p.parts_log2), block(ssk::kT);
-    const ssk::SpecScale<true> hs{hscale};
-    if (simple) {
-        ssk::UnitTab<true> ut;
-        if (fill_unit_tab(ut, g_host_desc, n_units))
-            hipLaunchKernelGGL((ssk::k_conv_spec<FUSE, true, true, false, true>), grid, block, 0, st, p, ut, hs);
-        else hipLaunchKernelGGL((ssk::k_conv_spec<FUSE, true, false, false, true>), grid, block, 0, st, p, ssk::UnitTab<false>(), hs);
-    } else hipLaunchKernelGGL((ssk::k_conv_spec<FUSE, false, false, false, true>), grid, block, 0, st, p, ssk::UnitTab<false>(), hs);
-    return hip_err(hipGetLastError());
-}
 
 // the arguments the three half entries share (checked before a device is touched): 8-byte loads of four halves
 static bool spec16_args_ok(const void* hspec16, const float* hscale, int n_units, int h_blocks, int flags) {
@@ -1181,17 +1295,9 @@ int ss_fftconv_binaural_spec16_f32(const float* spec, const void* hspec16, const
                                    const int* unit_desc, float* out, int n_units, int h_blocks, int n_valid, int out_len, int flags,
                                    void* stream) {
     if (n_units == 0) return 0;
-    if (!out || !spec16_args_ok(hspec16, hscale, n_units, h_blocks, flags)) return SS_EINVAL;
-    if (out_len < 1 || n_valid < 0 || n_valid > out_len || n_valid > 3 * ssk::kB) return SS_EINVAL;
-    ssk::ConvParams p;
-    int n_cus = 1;
-    int rc = fill_conv(p, &n_cus, spec, nullptr, rir_len, unit_desc, 0, 0, 1, 0, n_valid, out_len, false);
-    if (rc) return rc;
-    p.out = out;
-    p.hspec = static_cast<const ssk::f32x4*>(hspec16);
-    p.h_blocks = h_blocks;
-    const int nb_y = n_valid == 0 ? 1 : (n_valid + ssk::kB - 1) / ssk::kB;
-    return launch_conv_spec16<false>(p, hscale, n_units, nb_y, flags, static_cast<hipStream_t>(stream), n_cus);
+    if (!spec16_args_ok(hspec16, hscale, n_units, h_blocks, flags)) return SS_EINVAL;
+    return render(spec_bank(hspec16, h_blocks, hscale), true, Launch::kConv, spec, rir_len, unit_desc, out, nullptr, nullptr, n_units,
+                  n_valid, out_len, SS_PAD_REFLECT, flags, stateless(stream));
 }
 
 // rows of one partition block only (the 16 kHz observation): 257 <= out_len <= kB
@@ -1199,19 +1305,10 @@ int ss_audio_obs_spec16_f32(const float* spec, const void* hspec16, const float*
                             float* audiogoal, float* spectrogram, int n_units, int h_blocks, int n_valid, int out_len, int pad_mode,
                             int flags, void* stream) {
     if (n_units == 0) return 0;
-    if (!spectrogram || !spec16_args_ok(hspec16, hscale, n_units, h_blocks, flags)) return SS_EINVAL;
-    if (pad_mode != SS_PAD_REFLECT && pad_mode != SS_PAD_CONSTANT) return SS_EINVAL;
-    if (out_len < ssk::kNfft / 2 + 1 || out_len > ssk::kB || t4_of(out_len) > 26 || n_valid < 0 || n_valid > out_len) return SS_EINVAL;
-    ssk::ConvParams p;
-    int n_cus = 1;
-    int rc = fill_conv(p, &n_cus, spec, nullptr, rir_len, unit_desc, 0, 0, 1, 0, n_valid, out_len, false);
-    if (rc) return rc;
-    p.pad_mode = pad_mode;
-    p.hspec = static_cast<const ssk::f32x4*>(hspec16);
-    p.h_blocks = h_blocks;
-    p.out = audiogoal;
-    p.sgram = spectrogram;
-    return launch_conv_spec16<true>(p, hscale, n_units, 1, flags, static_cast<hipStream_t>(stream), n_cus);
+    if (!spec16_args_ok(hspec16, hscale, n_units, h_blocks, flags)) return SS_EINVAL;
+    if (out_len > ssk::kB || t4_of(out_len) > 26) return SS_EINVAL;
+    return render(spec_bank(hspec16, h_blocks, hscale), true, Launch::kObs, spec, rir_len, unit_desc, audiogoal, spectrogram, nullptr,
+                  n_units, n_valid, out_len, pad_mode, flags, stateless(stream));
 }
 
 int ss_audio_obs_logmel_spec16_f32(const float* spec, const void* hspec16, const float* hscale, const int* rir_len,
@@ -1219,21 +1316,11 @@ int ss_audio_obs_logmel_spec16_f32(const float* spec, const void* hspec16, const
                                    const float* mel_w, int n_mels, int max_len, float mel_eps, int n_units, int h_blocks, int n_valid,
                                    int out_len, int pad_mode, int flags, void* stream) {
     if (n_units == 0) return 0;
-    if (!spec16_args_ok(hspec16, hscale, n_units, h_blocks, flags) || !mel_args_ok(logmel, mel_start, mel_w, n_mels, max_len, mel_eps))
-        return SS_EINVAL;
-    if (pad_mode != SS_PAD_REFLECT && pad_mode != SS_PAD_CONSTANT) return SS_EINVAL;
-    if (!obs_logmel_shape_ok(out_len, flags) || n_valid < 0 || n_valid > out_len) return SS_EINVAL;
-    ssk::ConvParams p;
-    int n_cus = 1;
-    int rc = fill_conv(p, &n_cus, spec, nullptr, rir_len, unit_desc, 0, 0, 1, 0, n_valid, out_len, false);
-    if (rc) return rc;
-    p.pad_mode = pad_mode;
-    p.hspec = static_cast<const ssk::f32x4*>(hspec16);
-    p.h_blocks = h_blocks;
-    p.out = audiogoal;
-    p.sgram = spectrogram;
+    if (!spec16_args_ok(hspec16, hscale, n_units, h_blocks, flags)) return SS_EINVAL;
+    if (!mel_args_ok(logmel, mel_start, mel_w, n_mels, max_len, mel_eps)) return SS_EINVAL;
     const ssk::MelArgs m{logmel, mel_start, mel_w, n_mels, max_len, mel_eps};
-    return launch_conv_spec16_mel(p, m, hscale, n_units, flags, static_cast<hipStream_t>(stream));
+    return render(spec_bank(hspec16, h_blocks, hscale), true, Launch::kMelOneBlock, spec, rir_len, unit_desc, audiogoal, spectrogram,
+                  &m, n_units, n_valid, out_len, pad_mode, flags, stateless(stream));
 }
 
 // ss_audio_obs_logmel_rows_f32 from the spectral bank (k_obs_blocks<true, MEL> / k_obs_rows<true, .., MEL>)
@@ -1242,29 +1329,16 @@ int ss_audio_obs_logmel_rows_spec_f32(const float* spec, const float* hspec, con
                                       const float* mel_w, int n_mels, int max_len, float mel_eps, int n_units, int h_blocks,
                                       int n_valid, int out_len, int pad_mode, int flags, void* stream) {
     if (n_units == 0) return 0;
-    if (n_units < 0 || !hspec || !mel_args_ok(logmel, mel_start, mel_w, n_mels, max_len, mel_eps)) return SS_EINVAL;
-    if (pad_mode != SS_PAD_REFLECT && pad_mode != SS_PAD_CONSTANT) return SS_EINVAL;
-    if (!obs_logmel_rows_shape_ok(out_len, n_valid, h_blocks, flags)) return SS_EINVAL;
-    ssk::ConvParams p;
-    int n_cus = 1;
-    int rc = fill_conv(p, &n_cus, spec, nullptr, rir_len, unit_desc, 0, 0, 1, 0, n_valid, out_len, false);
-    if (rc) return rc;
-    p.pad_mode = pad_mode;
-    p.hspec = reinterpret_cast<const ssk::f32x4*>(hspec);
-    p.h_blocks = h_blocks;
-    p.out = audiogoal;
-    p.sgram = spectrogram;
+    if (!mel_args_ok(logmel, mel_start, mel_w, n_mels, max_len, mel_eps)) return SS_EINVAL;
     const ssk::MelArgs m{logmel, mel_start, mel_w, n_mels, max_len, mel_eps};
-    return launch_obs_rows<true, true>(p, n_units, flags, n_cus, static_cast<hipStream_t>(stream), m);
+    return render(spec_bank(hspec, h_blocks), true, Launch::kMelRows, spec, rir_len, unit_desc, audiogoal, spectrogram, &m, n_units,
+                  n_valid, out_len, pad_mode, flags, stateless(stream));
 }
 
 // ---- half bank, rows of 2 or 3 partition blocks (44.1 / 48 kHz): k_obs_blocks<true, MEL, HALF> / k_obs_rows<true, .., MEL, HALF> ----
-// what the two entries refuse before a device is touched
-static bool spec16_rows_args_ok(const float* spec, const void* hspec16, const float* hscale, const int* rir_len, const int* unit_desc,
-                                int n_units, int h_blocks, int n_valid, int out_len, int pad_mode, int flags) {
-    return spec && rir_len && unit_desc && spec16_args_ok(hspec16, hscale, n_units, h_blocks, flags) && h_blocks <= 16 &&
-           out_len > ssk::kB && out_len <= 3 * ssk::kB && n_valid >= 0 && n_valid <= out_len &&
-           (pad_mode == SS_PAD_REFLECT || pad_mode == SS_PAD_CONSTANT);
+// what the two entries refuse on top (the fused row kernels' limits: obs_rows_ok)
+static bool spec16_rows_args_ok(const void* hspec16, const float* hscale, int n_units, int h_blocks, int out_len, int flags) {
+    return spec16_args_ok(hspec16, hscale, n_units, h_blocks, flags) && h_blocks <= 16 && out_len > ssk::kB && out_len <= 3 * ssk::kB;
 }
 
 // ss_audio_obs_spec_f32 for rows of 2 or 3 partition blocks, from a half bank: the same routing (k_obs_blocks while the grid fits
@@ -1273,27 +1347,9 @@ int ss_audio_obs_rows_spec16_f32(const float* spec, const void* hspec16, const f
                                  float* audiogoal, float* spectrogram, int n_units, int h_blocks, int n_valid, int out_len,
                                  int pad_mode, int flags, void* stream) {
     if (n_units == 0) return 0;
-    if (!spectrogram || !spec16_rows_args_ok(spec, hspec16, hscale, rir_len, unit_desc, n_units, h_blocks, n_valid, out_len, pad_mode, flags))
-        return SS_EINVAL;
-    const bool fused = obs_rows_ok(out_len, n_valid, h_blocks, flags, true, audiogoal != nullptr);
-    if (!fused && !audiogoal) return SS_EINVAL;
-    if (!fused) {
-        const int rc = ss_fftconv_binaural_spec16_f32(spec, hspec16, hscale, rir_len, unit_desc, audiogoal, n_units, h_blocks, n_valid,
-                                                      out_len, flags, stream);
-        if (rc) return rc;
-        return spectrogram_of_rows(audiogoal, spectrogram, n_units, out_len, n_valid, pad_mode, stream);
-    }
-    ssk::ConvParams p;
-    int n_cus = 1;
-    int rc = fill_conv(p, &n_cus, spec, nullptr, rir_len, unit_desc, 0, 0, 1, 0, n_valid, out_len, false);
-    if (rc) return rc;
-    p.pad_mode = pad_mode;
-    p.hspec = static_cast<const ssk::f32x4*>(hspec16);
-    p.h_blocks = h_blocks;
-    p.out = audiogoal;
-    p.sgram = spectrogram;
-    return launch_obs_rows<true, false, true>(p, n_units, flags, n_cus, static_cast<hipStream_t>(stream), ssk::UnitTab<false>(),
-                                              ssk::SpecScale<true>{hscale});
+    if (!spec16_rows_args_ok(hspec16, hscale, n_units, h_blocks, out_len, flags)) return SS_EINVAL;
+    return render(spec_bank(hspec16, h_blocks, hscale), true, Launch::kObs, spec, rir_len, unit_desc, audiogoal, spectrogram, nullptr,
+                  n_units, n_valid, out_len, pad_mode, flags, stateless(stream));
 }
 
 // ss_audio_obs_logmel_rows_spec_f32 from a half bank
@@ -1302,21 +1358,11 @@ int ss_audio_obs_logmel_rows_spec16_f32(const float* spec, const void* hspec16, 
                                         const int* mel_start, const float* mel_w, int n_mels, int max_len, float mel_eps, int n_units,
                                         int h_blocks, int n_valid, int out_len, int pad_mode, int flags, void* stream) {
     if (n_units == 0) return 0;
-    if (!spec16_rows_args_ok(spec, hspec16, hscale, rir_len, unit_desc, n_units, h_blocks, n_valid, out_len, pad_mode, flags) ||
-        !mel_args_ok(logmel, mel_start, mel_w, n_mels, max_len, mel_eps))
-        return SS_EINVAL;
-    if (!obs_logmel_rows_shape_ok(out_len, n_valid, h_blocks, flags)) return SS_EINVAL;
-    ssk::ConvParams p;
-    int n_cus = 1;
-    int rc = fill_conv(p, &n_cus, spec, nullptr, rir_len, unit_desc, 0, 0, 1, 0, n_valid, out_len, false);
-    if (rc) return rc;
-    p.pad_mode = pad_mode;
-    p.hspec = static_cast<const ssk::f32x4*>(hspec16);
-    p.h_blocks = h_blocks;
-    p.out = audiogoal;
-    p.sgram = spectrogram;
+    if (!spec16_rows_args_ok(hspec16, hscale, n_units, h_blocks, out_len, flags)) return SS_EINVAL;
+    if (!mel_args_ok(logmel, mel_start, mel_w, n_mels, max_len, mel_eps)) return SS_EINVAL;
     const ssk::MelArgs m{logmel, mel_start, mel_w, n_mels, max_len, mel_eps};
-    return launch_obs_rows<true, true, true>(p, n_units, flags, n_cus, static_cast<hipStream_t>(stream), m, ssk::SpecScale<true>{hscale});
+    return render(spec_bank(hspec16, h_blocks, hscale), true, Launch::kMelRows, spec, rir_len, unit_desc, audiogoal, spectrogram, &m,
+                  n_units, n_valid, out_len, pad_mode, flags, stateless(stream));
 }
 
 // ---- pose memo: the row copies (k_memo_rows) ---------------------------------------------------------------------------
@@ -1646,6 +1692,30 @@ static int ctx_ensure_pool(ssctx::Context& c, hipStream_t st) {
     return 0;
 }
 
+// What is bound to the context: as the routing sees it (ss_route.hpp) ...
+static ssroute::Bank route_bank_of(const ssctx::Context& c) {
+    ssroute::Bank b;
+    b.rows = c.rir != nullptr;
+    b.spectra = c.hspec != nullptr;
+    b.half = c.hscale != nullptr;
+    b.buckets = !c.buckets.empty();
+    b.buckets_spectra = b.buckets && buckets_spectral(c.buckets.data(), static_cast<int>(c.buckets.size()), 0);
+    b.spec_buckets = !c.spec_buckets.empty();
+    b.spec_buckets_half = b.spec_buckets && c.spec_buckets[0].hscale != nullptr;
+    b.rir_cap = c.rir_cap;
+    b.h_blocks = c.h_blocks;
+    return b;
+}
+
+// ... and as the launches read it
+static Bank bank_of(const ssctx::Context& c) {
+    if (!c.spec_buckets.empty()) return spec_buckets_bank(c.spec_buckets.data(), static_cast<int>(c.spec_buckets.size()));
+    if (!c.buckets.empty()) return buckets_bank(c.buckets.data(), static_cast<int>(c.buckets.size()));
+    Bank b = rows_bank(c.rir, c.rir_us, c.rir_cs, c.rir_es, c.rir_cap);
+    b.hspec = c.hspec; b.hscale = c.hscale; b.h_blocks = c.h_blocks;
+    return b;
+}
+
 // One step: plan the units (host), compute the missing source-window spectra, render.  `units` are HOST arrays.
 // audiogoal / spectrogram are DEVICE buffers [n,2,sr] / [n,65,T4,2]; either may be NULL (not both).
 // `lane` >= 0: the step runs on internal stream `lane` of the overlap mode (stream == c.lane_stream[lane])
@@ -1733,11 +1803,13 @@ static int ctx_observe_on(ss_ctx* h, const ss_units* units, int n, float* audiog
     SS_PROF_MARK(2);                                           // ring slot: group event synchronise
     rc = ssctx::plan_units(c, units, n, hd, &res);
     if (rc) return rc;                                         // (refused before the cache or the ring was touched)
-    // a spectral-only bank (spectra bound, no rows: ss_ctx_set_rir_bank(ctx, NULL, ...) + ss_ctx_set_rir_spectra) cannot serve a
-    // step whose route reads the time-domain rows (a cross-fade): refused before any upload or launch, the plan's keys given back
-    // (spectral length buckets, ss_ctx_set_rir_spec_buckets, are such a bank)
-    const bool spec_bk = !c.spec_buckets.empty();
-    if (!c.rir && c.buckets.empty() && ((!c.hspec && !spec_bk) || (res.flags & SS_FLAG_CROSSFADE))) {
+    // the step's route, decided once (ss_route.hpp): which launch body, from the rows or the spectra, into whose buffers
+    ssroute::Wants wants;
+    wants.waveform = audiogoal != nullptr; wants.spectrogram = spectrogram != nullptr; wants.mel = mel != nullptr;
+    const ssroute::Route route = ssroute::route_step(route_bank_of(c), c.out_len, c.n_valid, c.policy, n, res.flags, wants, route_switches());
+    // a spectral-only bank cannot serve a step whose route reads the time-domain rows (a cross-fade): refused before any upload
+    // or launch, the plan's keys given back
+    if (route.refused) {
         ssctx::cache_rollback(c);
         return SS_EINVAL;
     }
@@ -1795,46 +1867,13 @@ static int ctx_observe_on(ss_ctx* h, const ss_units* units, int n, float* audiog
         e = hipMemcpyAsync(dd, hd, sizeof(int) * 8 * static_cast<size_t>(n), hipMemcpyHostToDevice, st);
         if (e != hipSuccess) return fail(hip_err(e));
     }
-    // cross-faded steps take the time-domain rows; so do LARGE steps of one-block rows when the caller keeps both forms and said
-    // so (ss_ctx_set_spectral_policy): there the forward FFT hides under the row's load and the spectral rows are twice the bytes
-    // (... unless its units carry a second term - a distractor, simulator.py:649-664: two forward transforms per row do not hide
-    // under one row's load; savi's 256-env step: 87.9 against 96.3 us)
-    const bool spectral = (c.hspec || spec_bk) && !(res.flags & SS_FLAG_CROSSFADE) &&
-                          !(c.spectral_max_units > 0 && c.rir && c.out_len <= ssk::kB && n > c.spectral_max_units &&
-                            (res.flags & SS_FLAG_NO_DISTRACTOR));
-    const int nbh_bank = spectral && !spec_bk ? c.h_blocks : (c.rir_cap > 0 ? ssctx::ceil_div(c.rir_cap, c.kb) : 1);
-    // log-mel without a waveform buffer: one fused launch for one-block rows of a single-allocation bank in a step without a
-    // cross-fade, inside the units range the measured policy gives (ss_ctx_set_logmel_policy); everything else renders into the
-    // context's own waveform scratch and runs the feature kernel over it
-    const bool mel_fused = mel && c.buckets.empty() && !spec_bk && obs_logmel_shape_ok(c.out_len, res.flags) &&
-                           n >= c.mel_fused_min_units && n <= c.mel_fused_max_units;
-    // rows of 2 or 3 blocks (44.1 / 48 kHz): the log-mel form of k_obs_rows / k_obs_blocks under the same conditions, inside the
-    // range of ss_ctx_set_logmel_rows_policy (default: never - the scratch route is bit-equal to observe-then-features, the
-    // fused arithmetic only to rounding)
-    // (a half bank: only the one bound by ss_ctx_set_rir_spectra16_rows has rows this long)
-    const bool mel_rows = mel && !mel_fused && (!c.hscale || c.out_len > c.kb) && c.buckets.empty() && !spec_bk && (spectral || (c.rir && c.rir_cap > 0)) &&
-                          obs_logmel_rows_shape_ok(c.out_len, c.n_valid, nbh_bank, res.flags) &&
-                          n >= c.mel_rows_min_units && n <= c.mel_rows_max_units;
-    // SoundSpaces 2.0 steps (cross-faded one-block rows; block 0 of a 44.1 / 48 kHz row, cross-faded or not): their own fused
-    // launch from the time-domain rows of a single-allocation bank, inside the range of ss_ctx_set_logmel_ss2_policy (default:
-    // never, for the same reason)
-    const bool mel_ss2 = mel && !mel_fused && !mel_rows && c.buckets.empty() && c.rir && !spectral &&
-                         obs_logmel_ss2_shape(c.out_len, c.n_valid, res.flags) != 0 &&
-                         n >= c.mel_ss2_min_units && n <= c.mel_ss2_max_units;
-    // length-bucketed banks (ss_ctx_set_rir_buckets / ss_ctx_set_rir_spec_buckets): their own fused launch, one-block rows on every
-    // bank form and rows of 2 or 3 blocks on the fp32 forms, inside the range of ss_ctx_set_logmel_buckets_policy (default: never,
-    // for the same reason); the three policies above never apply to these contexts
-    const bool mel_bk = mel && (spec_bk || !c.buckets.empty()) &&
-                        obs_logmel_buckets_shape_ok(c.out_len, c.n_valid, c.rir_cap > 0 ? ssctx::ceil_div(c.rir_cap, c.kb) : 1, res.flags,
-                                                    spec_bk && c.spec_buckets[0].hscale != nullptr) &&
-                        n >= c.mel_bk_min_units && n <= c.mel_bk_max_units;
-    const bool mel_one_launch = mel_fused || mel_rows || mel_ss2 || mel_bk;
-    if (mel && !mel_one_launch) {
+    // log-mel without a waveform buffer, on the shapes no log-mel form serves: the step renders into the context's own waveform
+    // scratch and the feature kernel runs over it
+    if (route.wave_scratch) {
         rc = get_wave_scratch(&c, lane < 0 ? 0 : lane, st, static_cast<size_t>(n) * 2 * c.out_len, &audiogoal);
         if (rc) return fail(rc);
     }
-    if (spectrogram && !audiogoal && !mel_rows && !mel_bk && c.out_len > ssk::kB && !wide_one_block_ok(c.out_len, c.n_valid, res.flags, spectral) &&
-        !obs_rows_ok(c.out_len, c.n_valid, nbh_bank, res.flags, spectral, true)) {  // cross-faded / very long rows hand over through memory (the context's own buffer)
+    if (route.handover) {                                      // cross-faded / very long rows hand over through memory (the context's own buffer)
         const size_t need = static_cast<size_t>(n) * 2 * c.out_len;
         if (need > c.ag_cap) {
             e = hipDeviceSynchronize();
@@ -1849,83 +1888,21 @@ static int ctx_observe_on(ss_ctx* h, const ss_units* units, int n, float* audiog
     }
     static const bool no_tab = ab_flag("SS_HIP_NO_UNIT_TAB");
     SS_PROF_MARK(4);                                           // new windows (upload + k_source_windows), descriptor upload
-    g_host_desc = no_tab ? nullptr : hd;                       // (see fill_unit_tab; cleared right after the dispatch below)
-    g_tab_taken = false;
-    g_launch_share = c.chip_share > 0 ? c.chip_share : c.n_lanes;
-    if (mel_ss2) {
-        rc = ss_audio_obs_logmel_ss2_f32(c.pool, c.rir, c.rir_len, dd, nullptr, spectrogram, mel->logmel, mel->mel_start, mel->mel_w,
-                                         mel->n_mels, mel->max_len, mel->mel_eps, n, c.rir_us, c.rir_cs, c.rir_es, c.rir_cap,
-                                         c.n_valid, c.out_len, c.pad_mode, res.flags, stream);
-    } else if (mel_rows) {
-        rc = spectral && c.hscale
-                 ? ss_audio_obs_logmel_rows_spec16_f32(c.pool, c.hspec, c.hscale, c.rir_len, dd, nullptr, spectrogram, mel->logmel,
-                                                       mel->mel_start, mel->mel_w, mel->n_mels, mel->max_len, mel->mel_eps, n,
-                                                       c.h_blocks, c.n_valid, c.out_len, c.pad_mode, res.flags, stream)
-             : spectral ? ss_audio_obs_logmel_rows_spec_f32(c.pool, c.hspec, c.rir_len, dd, nullptr, spectrogram, mel->logmel,
-                                                          mel->mel_start, mel->mel_w, mel->n_mels, mel->max_len, mel->mel_eps, n,
-                                                          c.h_blocks, c.n_valid, c.out_len, c.pad_mode, res.flags, stream)
-                      : ss_audio_obs_logmel_rows_f32(c.pool, c.rir, c.rir_len, dd, nullptr, spectrogram, mel->logmel, mel->mel_start,
-                                                     mel->mel_w, mel->n_mels, mel->max_len, mel->mel_eps, n, c.rir_us, c.rir_cs,
-                                                     c.rir_es, c.rir_cap, c.n_valid, c.out_len, c.pad_mode, res.flags, stream);
-    } else if (mel_fused) {
-        rc = spectral && c.hscale
-                 ? ss_audio_obs_logmel_spec16_f32(c.pool, c.hspec, c.hscale, c.rir_len, dd, nullptr, spectrogram, mel->logmel,
-                                                  mel->mel_start, mel->mel_w, mel->n_mels, mel->max_len, mel->mel_eps, n, c.h_blocks,
-                                                  c.n_valid, c.out_len, c.pad_mode, res.flags, stream)
-             : spectral ? ss_audio_obs_logmel_spec_f32(c.pool, c.hspec, c.rir_len, dd, nullptr, spectrogram, mel->logmel, mel->mel_start,
-                                                     mel->mel_w, mel->n_mels, mel->max_len, mel->mel_eps, n, c.h_blocks, c.n_valid,
-                                                     c.out_len, c.pad_mode, res.flags, stream)
-                      : ss_audio_obs_logmel_f32(c.pool, c.rir, c.rir_len, dd, nullptr, spectrogram, mel->logmel, mel->mel_start,
-                                                mel->mel_w, mel->n_mels, mel->max_len, mel->mel_eps, n, c.rir_us, c.rir_cs, c.rir_es,
-                                                c.rir_cap, c.n_valid, c.out_len, c.pad_mode, res.flags, stream);
-    } else if (mel_bk) {
-        rc = spec_bk ? ss_audio_obs_logmel_spec_buckets_f32(c.pool, c.spec_buckets.data(), static_cast<int>(c.spec_buckets.size()),
-                                                            c.rir_len, dd, nullptr, spectrogram, mel->logmel, mel->mel_start, mel->mel_w,
-                                                            mel->n_mels, mel->max_len, mel->mel_eps, n, c.n_valid, c.out_len, c.pad_mode,
-                                                            res.flags, stream)
-                     : ss_audio_obs_logmel_buckets_f32(c.pool, c.buckets.data(), static_cast<int>(c.buckets.size()), c.rir_len, dd,
-                                                       nullptr, spectrogram, mel->logmel, mel->mel_start, mel->mel_w, mel->n_mels,
-                                                       mel->max_len, mel->mel_eps, n, c.n_valid, c.out_len, c.pad_mode, res.flags, stream);
-    } else if (spec_bk) {
-        const int nb = static_cast<int>(c.spec_buckets.size());
-        rc = spectrogram ? ss_audio_obs_spec_buckets_f32(c.pool, c.spec_buckets.data(), nb, c.rir_len, dd, audiogoal, spectrogram, n,
-                                                         c.n_valid, c.out_len, c.pad_mode, res.flags, stream)
-                         : ss_fftconv_binaural_spec_buckets_f32(c.pool, c.spec_buckets.data(), nb, c.rir_len, dd, audiogoal, n,
-                                                                c.n_valid, c.out_len, res.flags, stream);
-    } else if (!c.buckets.empty()) {
-        const int nb = static_cast<int>(c.buckets.size());
-        rc = spectrogram ? ss_audio_obs_buckets_f32(c.pool, c.buckets.data(), nb, c.rir_len, dd, audiogoal, spectrogram, n,
-                                                    c.n_valid, c.out_len, c.pad_mode, res.flags, stream)
-                         : ss_fftconv_binaural_buckets_f32(c.pool, c.buckets.data(), nb, c.rir_len, dd, audiogoal, n, c.n_valid,
-                                                           c.out_len, res.flags, stream);
-    } else if (spectrogram && spectral && c.hscale && c.out_len > c.kb)      // (bound by ss_ctx_set_rir_spectra16_rows)
-        rc = ss_audio_obs_rows_spec16_f32(c.pool, c.hspec, c.hscale, c.rir_len, dd, audiogoal, spectrogram, n, c.h_blocks, c.n_valid,
-                                          c.out_len, c.pad_mode, res.flags, stream);
-    else if (spectrogram && spectral && c.hscale)
-        rc = ss_audio_obs_spec16_f32(c.pool, c.hspec, c.hscale, c.rir_len, dd, audiogoal, spectrogram, n, c.h_blocks, c.n_valid,
-                                     c.out_len, c.pad_mode, res.flags, stream);
-    else if (spectral && c.hscale)
-        rc = ss_fftconv_binaural_spec16_f32(c.pool, c.hspec, c.hscale, c.rir_len, dd, audiogoal, n, c.h_blocks, c.n_valid, c.out_len,
-                                            res.flags, stream);
-    else if (spectrogram && spectral)
-        rc = ss_audio_obs_spec_f32(c.pool, c.hspec, c.rir_len, dd, audiogoal, spectrogram, n, c.h_blocks, c.n_valid,
-                                   c.out_len, c.pad_mode, res.flags, stream);
-    else if (spectrogram)
-        rc = ss_audio_obs_f32(c.pool, c.rir, c.rir_len, dd, audiogoal, spectrogram, n, c.rir_us, c.rir_cs, c.rir_es,
-                              c.rir_cap, c.n_valid, c.out_len, c.pad_mode, res.flags, stream);
-    else if (spectral)
-        rc = ss_fftconv_binaural_spec_f32(c.pool, c.hspec, c.rir_len, dd, audiogoal, n, c.h_blocks, c.n_valid, c.out_len,
-                                          res.flags, stream);
-    else
-        rc = ss_fftconv_binaural_f32(c.pool, c.rir, c.rir_len, dd, audiogoal, n, c.rir_us, c.rir_cs, c.rir_es, c.rir_cap,
-                                     c.n_valid, c.out_len, res.flags, stream);
-    g_host_desc = nullptr;
-    g_launch_share = 1;
+    bool tab_taken = false;
+    LaunchEnv env;
+    env.st = st;
+    env.host_desc = no_tab ? nullptr : hd;                     // (see fill_unit_tab)
+    env.share = c.chip_share > 0 ? c.chip_share : c.n_lanes;
+    env.tab_taken = &tab_taken;
+    ssk::MelArgs m{};
+    if (mel) m = ssk::MelArgs{mel->logmel, mel->mel_start, mel->mel_w, mel->n_mels, mel->max_len, mel->mel_eps};
+    rc = render(bank_of(c), route.spectral, route.launch, c.pool, c.rir_len, dd, audiogoal, spectrogram,
+                mel && !route.wave_scratch ? &m : nullptr, n, c.n_valid, c.out_len, c.pad_mode, res.flags, env);
     // what the device may read from this step's ring slot after the call: descriptors in place (no unit table), the source of
     // their upload, the source of the window upload
-    slot_read = !direct || res.n_new_windows > 0 || !g_tab_taken;
+    slot_read = !direct || res.n_new_windows > 0 || !tab_taken;
     SS_PROF_MARK(5);                                           // the launch entry (unit table + hipLaunchKernel)
-    if (!rc && mel && !mel_one_launch)                         // scratch route: the features of the waveform just rendered
+    if (!rc && route.wave_scratch)                             // scratch route: the features of the waveform just rendered
         rc = ss_audio_features_f32(audiogoal, n, c.out_len, c.pad_mode, nullptr, mel->logmel, mel->mel_start, mel->mel_w,
                                    mel->n_mels, mel->max_len, mel->mel_eps, nullptr, 1, 1.f, stream);
     if (rc) return fail(rc);
@@ -1970,35 +1947,35 @@ int ss_ctx_set_overlap(ss_ctx* h, int n_streams) {
 
 int ss_ctx_set_spectral_policy(ss_ctx* h, int max_units) {
     if (!h || max_units < 0) return SS_EINVAL;
-    h->c.spectral_max_units = max_units;
+    h->c.policy.spectral_max_units = max_units;
     return 0;
 }
 
 int ss_ctx_set_logmel_policy(ss_ctx* h, int min_units, int max_units) {
     if (!h || min_units < 0 || max_units < 0) return SS_EINVAL;
-    h->c.mel_fused_min_units = min_units;
-    h->c.mel_fused_max_units = max_units;
+    h->c.policy.mel_fused_min = min_units;
+    h->c.policy.mel_fused_max = max_units;
     return 0;
 }
 
 int ss_ctx_set_logmel_rows_policy(ss_ctx* h, int min_units, int max_units) {
     if (!h || min_units < 0 || max_units < 0) return SS_EINVAL;
-    h->c.mel_rows_min_units = min_units;
-    h->c.mel_rows_max_units = max_units;
+    h->c.policy.mel_rows_min = min_units;
+    h->c.policy.mel_rows_max = max_units;
     return 0;
 }
 
 int ss_ctx_set_logmel_ss2_policy(ss_ctx* h, int min_units, int max_units) {
     if (!h || min_units < 0 || max_units < 0) return SS_EINVAL;
-    h->c.mel_ss2_min_units = min_units;
-    h->c.mel_ss2_max_units = max_units;
+    h->c.policy.mel_ss2_min = min_units;
+    h->c.policy.mel_ss2_max = max_units;
     return 0;
 }
 
 int ss_ctx_set_logmel_buckets_policy(ss_ctx* h, int min_units, int max_units) {
     if (!h || min_units < 0 || max_units < 0) return SS_EINVAL;
-    h->c.mel_bk_min_units = min_units;
-    h->c.mel_bk_max_units = max_units;
+    h->c.policy.mel_bk_min = min_units;
+    h->c.policy.mel_bk_max = max_units;
     return 0;
 }
 
@@ -2641,7 +2618,7 @@ int ss_ctx_observe_requests_load(ss_ctx* h, const long long* recs, int n, ss_req
         // a launch that reads the SPECTRAL rows needs the new rows' block spectra first (built behind the scatter)
         bool any_dis = false;
         for (int i = 0; i < n && !any_dis; ++i) any_dis = recs[static_cast<size_t>(i) * SS_REQ_WORDS] == 0 && recs[static_cast<size_t>(i) * SS_REQ_WORDS + 6] >= 0;
-        const bool spectral = c.hspec && !(c.spectral_max_units > 0 && c.rir && c.out_len <= ssk::kB && n > c.spectral_max_units && !any_dis);
+        const bool spectral = c.hspec && !(c.policy.spectral_max_units > 0 && c.rir && c.out_len <= ssk::kB && n > c.policy.spectral_max_units && !any_dis);
         if (!ld || !miss_out || c.rir != ld->bank) return 0;
         std::vector<int> miss(miss_out, miss_out + (*n_miss < n ? *n_miss : n));
         rc = serve_pose_misses(h, recs, n, tb, ld, miss.data(), static_cast<int>(miss.size()), static_cast<hipStream_t>(stream), spectral);
@@ -2661,96 +2638,22 @@ int ss_ctx_observe_requests_load(ss_ctx* h, const long long* recs, int n, ss_req
 
 }  // extern "C"
 
-// ---- length-bucketed RIR bank (SURVEY 8(f)2) ---------------------------------------------------------------------------
-// buckets[0..n): HOST array; bucket b holds bank entries [first_b, first_b + n_entries_b) as planar rows of cap_b samples
-// in an allocation of its own.  Bucket 0 fills the legacy fields of ConvParams, the others p.bk[].
-static int fill_buckets(ssk::ConvParams& p, const ss_rir_bucket* bk, int n_buckets, bool spectral, int* nbh_max) {
-    if (!bk || n_buckets < 1 || n_buckets > ssk::kMaxBuckets) return SS_EINVAL;
-    int hb_max = 1;
-    for (int b = 0; b < n_buckets; ++b) {
-        if (!bk[b].rir || bk[b].cap < 2 || (bk[b].cap & 1) || bk[b].n_entries < 0 || bk[b].first < 0) return SS_EINVAL;
-        if (b && bk[b].first < bk[b - 1].first + bk[b - 1].n_entries) return SS_EINVAL;     // ascending, disjoint ranges
-        if (spectral && !bk[b].hspec) return SS_EINVAL;
-        hb_max = std::max(hb_max, (bk[b].cap + ssk::kB - 1) / ssk::kB);
-    }
-    if (bk[0].first != 0) return SS_EINVAL;
-    p.rir = bk[0].rir;
-    p.rir_unit_stride = 2LL * bk[0].cap;
-    p.rir_chan_stride = bk[0].cap;
-    p.rir_elem_stride = 1;
-    p.rir_cap = bk[0].cap;
-    p.hspec = spectral ? reinterpret_cast<const ssk::f32x4*>(bk[0].hspec) : nullptr;
-    p.h_blocks = spectral ? (bk[0].cap + ssk::kB - 1) / ssk::kB : 0;
-    p.n_buckets = n_buckets;
-    for (int b = 1; b < n_buckets; ++b)
-        p.bk[b - 1] = ssk::BankBucket{bk[b].rir, reinterpret_cast<const ssk::f32x4*>(bk[b].hspec), bk[b].first, bk[b].cap,
-                                      (bk[b].cap + ssk::kB - 1) / ssk::kB, 0};
-    *nbh_max = hb_max;
-    return 0;
-}
-
-static bool buckets_spectral(const ss_rir_bucket* bk, int n_buckets, int flags) {
-    if (!bk || (flags & SS_FLAG_CROSSFADE)) return false;
-    for (int b = 0; b < n_buckets; ++b) if (!bk[b].hspec) return false;
-    return n_buckets > 0;
-}
-
 extern "C" {
 
 int ss_fftconv_binaural_buckets_f32(const float* spec, const ss_rir_bucket* buckets, int n_buckets, const int* rir_len,
                                     const int* unit_desc, float* out, int n_units, int n_valid, int out_len, int flags,
                                     void* stream) {
     if (n_units == 0) return 0;
-    if (!out || n_units < 0 || !buckets || n_buckets < 1) return SS_EINVAL;
-    const bool spectral = buckets_spectral(buckets, n_buckets, flags);
-    ssk::ConvParams p;
-    int n_cus = 1, nbh_max = 1;
-    int rc = fill_conv(p, &n_cus, spec, buckets[0].rir, rir_len, unit_desc, 2LL * buckets[0].cap, buckets[0].cap, 1,
-                       buckets[0].cap, n_valid, out_len);
-    if (rc == 0) rc = fill_buckets(p, buckets, n_buckets, spectral, &nbh_max);
-    if (rc) return rc;
-    p.out = out;
-    const int nb_y = n_valid == 0 ? 1 : (n_valid + ssk::kB - 1) / ssk::kB;
-    if (spectral) return launch_conv_spec<false>(p, n_units, nb_y, flags, static_cast<hipStream_t>(stream), n_cus);
-    return launch_conv<false>(p, n_units, nb_y, flags, n_cus, static_cast<hipStream_t>(stream));
+    return render(buckets_bank(buckets, n_buckets), false, Launch::kConv, spec, rir_len, unit_desc, out, nullptr, nullptr, n_units,
+                  n_valid, out_len, SS_PAD_REFLECT, flags, stateless(stream));
 }
 
 int ss_audio_obs_buckets_f32(const float* spec, const ss_rir_bucket* buckets, int n_buckets, const int* rir_len,
                              const int* unit_desc, float* audiogoal, float* spectrogram, int n_units, int n_valid,
                              int out_len, int pad_mode, int flags, void* stream) {
     if (n_units == 0) return 0;
-    if (!spectrogram || n_units < 0 || !buckets || n_buckets < 1) return SS_EINVAL;
-    if (pad_mode != SS_PAD_REFLECT && pad_mode != SS_PAD_CONSTANT) return SS_EINVAL;
-    if (out_len < ssk::kNfft / 2 + 1) return SS_EINVAL;
-    const bool spectral = buckets_spectral(buckets, n_buckets, flags);
-    ssk::ConvParams p;
-    int n_cus = 1, nbh_max = 1;
-    int rc = fill_conv(p, &n_cus, spec, buckets[0].rir, rir_len, unit_desc, 2LL * buckets[0].cap, buckets[0].cap, 1,
-                       buckets[0].cap, n_valid, out_len);
-    if (rc == 0) rc = fill_buckets(p, buckets, n_buckets, spectral, &nbh_max);
-    if (rc) return rc;
-    p.pad_mode = pad_mode;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (out_len <= ssk::kB && p.t4 <= 26) {
-        p.out = audiogoal;
-        p.sgram = spectrogram;
-        return spectral ? launch_conv_spec<true>(p, n_units, 1, flags, st, n_cus) : launch_conv<true>(p, n_units, 1, flags, n_cus, st);
-    }
-    if (wide_one_block_ok(out_len, n_valid, flags, spectral)) {
-        p.out = audiogoal;
-        p.sgram = spectrogram;
-        return launch_conv<true>(p, n_units, 1, flags, n_cus, st, true);
-    }
-    if (obs_rows_ok(out_len, n_valid, nbh_max, flags, spectral, audiogoal != nullptr)) {
-        p.out = audiogoal;
-        p.sgram = spectrogram;
-        return spectral ? launch_obs_rows<true>(p, n_units, flags, n_cus, st) : launch_obs_rows<false>(p, n_units, flags, n_cus, st);
-    }
-    if (!audiogoal) return SS_EINVAL;                   // cross-faded long rows hand over through memory
-    rc = ss_fftconv_binaural_buckets_f32(spec, buckets, n_buckets, rir_len, unit_desc, audiogoal, n_units, n_valid, out_len,
-                                         flags, stream);
-    if (rc) return rc;
-    return spectrogram_of_rows(audiogoal, spectrogram, n_units, out_len, n_valid, pad_mode, stream);
+    return render(buckets_bank(buckets, n_buckets), false, Launch::kObs, spec, rir_len, unit_desc, audiogoal, spectrogram, nullptr,
+                  n_units, n_valid, out_len, pad_mode, flags, stateless(stream));
 }
 
 // Log-mel observation from a length-bucketed bank in ONE launch, no waveform buffer needed: the log-mel forms of the kernels
@@ -2763,30 +2666,10 @@ int ss_audio_obs_logmel_buckets_f32(const float* spec, const ss_rir_bucket* buck
                                     const float* mel_w, int n_mels, int max_len, float mel_eps, int n_units, int n_valid, int out_len,
                                     int pad_mode, int flags, void* stream) {
     if (n_units == 0) return 0;
-    if (n_units < 0 || !spec || !rir_len || !unit_desc || !mel_args_ok(logmel, mel_start, mel_w, n_mels, max_len, mel_eps)) return SS_EINVAL;
-    if (pad_mode != SS_PAD_REFLECT && pad_mode != SS_PAD_CONSTANT) return SS_EINVAL;
-    const bool spectral = buckets_spectral(buckets, n_buckets, flags);
-    int nbh_max = 1;
-    {
-        ssk::ConvParams probe;                              // (the bucket array's own refusals, without the device's tables)
-        const int rc = fill_buckets(probe, buckets, n_buckets, spectral, &nbh_max);
-        if (rc) return rc;
-    }
-    if (!obs_logmel_buckets_shape_ok(out_len, n_valid, nbh_max, flags, false)) return SS_EINVAL;
-    ssk::ConvParams p;
-    int n_cus = 1;
-    int rc = fill_conv(p, &n_cus, spec, buckets[0].rir, rir_len, unit_desc, 2LL * buckets[0].cap, buckets[0].cap, 1,
-                       buckets[0].cap, n_valid, out_len);
-    if (rc == 0) rc = fill_buckets(p, buckets, n_buckets, spectral, &nbh_max);
-    if (rc) return rc;
-    if (flags & SS_FLAG_FIRST_BUCKET) p.n_buckets = 1;
-    p.pad_mode = pad_mode;
-    p.out = audiogoal;
-    p.sgram = spectrogram;
+    if (!mel_args_ok(logmel, mel_start, mel_w, n_mels, max_len, mel_eps)) return SS_EINVAL;
     const ssk::MelArgs m{logmel, mel_start, mel_w, n_mels, max_len, mel_eps};
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (out_len <= ssk::kB) return spectral ? launch_conv_spec_mel(p, m, n_units, flags, st) : launch_conv_mel(p, m, n_units, flags, st);
-    return spectral ? launch_obs_rows<true, true>(p, n_units, flags, n_cus, st, m) : launch_obs_rows<false, true>(p, n_units, flags, n_cus, st, m);
+    return render(buckets_bank(buckets, n_buckets), false, out_len <= ssk::kB ? Launch::kMelOneBlock : Launch::kMelRows, spec, rir_len,
+                  unit_desc, audiogoal, spectrogram, &m, n_units, n_valid, out_len, pad_mode, flags, stateless(stream));
 }
 
 // The context's bank as length buckets (replaces ss_ctx_set_rir_bank + ss_ctx_set_rir_spectra for such banks; borrowed
@@ -2822,129 +2705,22 @@ int ss_ctx_set_rir_buckets(ss_ctx* h, const ss_rir_bucket* buckets, int n_bucket
 
 }  // extern "C"
 
-// ---- length-bucketed bank without time-domain rows: fp32 spectra ("only") or fp16 spectra + scales ("half") --------------
-// (include/ss_hip.h "Spectral length buckets").  Everything here is checked on the host before a device is touched.
-// *half = the form (every bucket carries scales / none does), *hb_max = the longest bucket's blocks.
-static int spec_buckets_check(const ss_spec_bucket* bk, int n_buckets, bool* half, int* hb_max) {
-    if (!bk || n_buckets < 1 || n_buckets > ssk::kMaxBuckets) return SS_EINVAL;
-    const bool h = bk[0].hscale != nullptr;
-    int hb = 1;
-    for (int b = 0; b < n_buckets; ++b) {
-        if (!bk[b].hspec || (bk[b].hscale != nullptr) != h) return SS_EINVAL;                   // one form in every bucket
-        if (reinterpret_cast<size_t>(bk[b].hspec) & (h ? 7 : 15)) return SS_EINVAL;             // h16x4 / f32x4 loads
-        if (bk[b].cap < 2 || (bk[b].cap & 1) || bk[b].n_entries < 0 || bk[b].first < 0) return SS_EINVAL;
-        if (b && bk[b].first < bk[b - 1].first + bk[b - 1].n_entries) return SS_EINVAL;         // ascending, disjoint ranges
-        const int blocks = (bk[b].cap + ssk::kB - 1) / ssk::kB;
-        if (blocks > 16) return SS_EINVAL;
-        hb = std::max(hb, blocks);
-    }
-    if (bk[0].first != 0) return SS_EINVAL;
-    *half = h;
-    *hb_max = hb;
-    return 0;
-}
-
-// the arguments fill_conv refuses, before it reaches for the device's tables
-static bool spec_buckets_launch_args_ok(const float* spec, const int* rir_len, const int* unit_desc, int n_units, int n_valid, int out_len,
-                                        int flags) {
-    return spec && rir_len && unit_desc && n_units > 0 && !(flags & SS_FLAG_CROSSFADE) && out_len >= 1 && n_valid >= 0 &&
-           n_valid <= out_len && n_valid <= 3 * ssk::kB;
-}
-
-// bucket 0 into the single-bank fields, the others into p.bk[] (no rows anywhere); the half form's scales into hs
-static void fill_spec_buckets(ssk::ConvParams& p, ssk::SpecScale<true, true>& hs, const ss_spec_bucket* bk, int n_buckets) {
-    p.hspec = static_cast<const ssk::f32x4*>(bk[0].hspec);
-    p.h_blocks = (bk[0].cap + ssk::kB - 1) / ssk::kB;
-    p.n_buckets = n_buckets;
-    hs.hscale = bk[0].hscale;
-    for (auto& s : hs.bk) s = nullptr;
-    for (int b = 1; b < n_buckets; ++b) {
-        p.bk[b - 1] = ssk::BankBucket{nullptr, static_cast<const ssk::f32x4*>(bk[b].hspec), bk[b].first, bk[b].cap,
-                                      (bk[b].cap + ssk::kB - 1) / ssk::kB, 0};
-        hs.bk[b - 1] = bk[b].hscale;
-    }
-}
-
-// Half buckets.  Launches that only touch bucket 0 (one bucket, or SS_FLAG_FIRST_BUCKET) are single-allocation launches on
-// bucket 0's arrays: the existing HALF kernels, the loop-free ones included.  Everything else: k_conv_spec<.., HALF, HBK>.
-template <bool FUSE>
-static int launch_conv_spec16_buckets(ssk::ConvParams p, const ssk::SpecScale<true, true>& hs, int n_units, int nb_y, int flags,
-                                      hipStream_t st, int n_cus) {
-    if (p.n_buckets == 1 || (flags & SS_FLAG_FIRST_BUCKET)) return launch_conv_spec16<FUSE>(p, hs.hscale, n_units, nb_y, flags, st, n_cus);
-    if (nb_y < 1 || nb_y > 3 || (FUSE && nb_y != 1) || (flags & SS_FLAG_CROSSFADE)) return SS_EINVAL;
-    p.nb_y = nb_y;
-    p.parts_log2 = FUSE && n_cus > 0 ? parts_log2_for(2 * n_units, n_cus) : 0;
-    const dim3 grid((2 * n_units * nb_y) << p.parts_log2), block(ssk::kT);
-    hipLaunchKernelGGL((ssk::k_conv_spec<FUSE, false, false, false, true, true>), grid, block, 0, st, p, ssk::UnitTab<false>(), hs);
-    return hip_err(hipGetLastError());
-}
-
 extern "C" {
 
 int ss_fftconv_binaural_spec_buckets_f32(const float* spec, const ss_spec_bucket* buckets, int n_buckets, const int* rir_len,
                                          const int* unit_desc, float* out, int n_units, int n_valid, int out_len, int flags,
                                          void* stream) {
     if (n_units == 0) return 0;
-    bool half = false;
-    int hb_max = 1;
-    if (!out || spec_buckets_check(buckets, n_buckets, &half, &hb_max) ||
-        !spec_buckets_launch_args_ok(spec, rir_len, unit_desc, n_units, n_valid, out_len, flags))
-        return SS_EINVAL;
-    ssk::ConvParams p;
-    int n_cus = 1;
-    int rc = fill_conv(p, &n_cus, spec, nullptr, rir_len, unit_desc, 0, 0, 1, 0, n_valid, out_len, false);
-    if (rc) return rc;
-    ssk::SpecScale<true, true> hs;
-    fill_spec_buckets(p, hs, buckets, n_buckets);
-    p.out = out;
-    const int nb_y = n_valid == 0 ? 1 : (n_valid + ssk::kB - 1) / ssk::kB;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    return half ? launch_conv_spec16_buckets<false>(p, hs, n_units, nb_y, flags, st, n_cus)
-                : launch_conv_spec<false>(p, n_units, nb_y, flags, st, n_cus);
+    return render(spec_buckets_bank(buckets, n_buckets), true, Launch::kConv, spec, rir_len, unit_desc, out, nullptr, nullptr, n_units,
+                  n_valid, out_len, SS_PAD_REFLECT, flags, stateless(stream));
 }
 
 int ss_audio_obs_spec_buckets_f32(const float* spec, const ss_spec_bucket* buckets, int n_buckets, const int* rir_len,
                                   const int* unit_desc, float* audiogoal, float* spectrogram, int n_units, int n_valid, int out_len,
                                   int pad_mode, int flags, void* stream) {
     if (n_units == 0) return 0;
-    bool half = false;
-    int hb_max = 1;
-    if (!spectrogram || spec_buckets_check(buckets, n_buckets, &half, &hb_max) ||
-        !spec_buckets_launch_args_ok(spec, rir_len, unit_desc, n_units, n_valid, out_len, flags))
-        return SS_EINVAL;
-    if (pad_mode != SS_PAD_REFLECT && pad_mode != SS_PAD_CONSTANT) return SS_EINVAL;
-    if (out_len < ssk::kNfft / 2 + 1) return SS_EINVAL;
-    // half: rows of one partition block (the fused row kernels do not read half bucketed banks)
-    if (half && (out_len > ssk::kB || t4_of(out_len) > 26)) return SS_EINVAL;
-    ssk::ConvParams p;
-    int n_cus = 1;
-    int rc = fill_conv(p, &n_cus, spec, nullptr, rir_len, unit_desc, 0, 0, 1, 0, n_valid, out_len, false);
-    if (rc) return rc;
-    ssk::SpecScale<true, true> hs;
-    fill_spec_buckets(p, hs, buckets, n_buckets);
-    p.pad_mode = pad_mode;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (half) {
-        p.out = audiogoal;
-        p.sgram = spectrogram;
-        return launch_conv_spec16_buckets<true>(p, hs, n_units, 1, flags, st, n_cus);
-    }
-    // fp32: the routes ss_audio_obs_buckets_f32 takes when every bucket carries its spectra
-    if (out_len <= ssk::kB && p.t4 <= 26) {
-        p.out = audiogoal;
-        p.sgram = spectrogram;
-        return launch_conv_spec<true>(p, n_units, 1, flags, st, n_cus);
-    }
-    if (obs_rows_ok(out_len, n_valid, hb_max, flags, true, audiogoal != nullptr)) {
-        p.out = audiogoal;
-        p.sgram = spectrogram;
-        return launch_obs_rows<true>(p, n_units, flags, n_cus, st);
-    }
-    if (!audiogoal) return SS_EINVAL;
-    rc = ss_fftconv_binaural_spec_buckets_f32(spec, buckets, n_buckets, rir_len, unit_desc, audiogoal, n_units, n_valid, out_len,
-                                              flags, stream);
-    if (rc) return rc;
-    return spectrogram_of_rows(audiogoal, spectrogram, n_units, out_len, n_valid, pad_mode, stream);
+    return render(spec_buckets_bank(buckets, n_buckets), true, Launch::kObs, spec, rir_len, unit_desc, audiogoal, spectrogram, nullptr,
+                  n_units, n_valid, out_len, pad_mode, flags, stateless(stream));
 }
 
 // ss_audio_obs_logmel_buckets_f32 on spectral length buckets.  fp32: the log-mel forms of the kernels
@@ -2955,35 +2731,10 @@ int ss_audio_obs_logmel_spec_buckets_f32(const float* spec, const ss_spec_bucket
                                          const int* mel_start, const float* mel_w, int n_mels, int max_len, float mel_eps, int n_units,
                                          int n_valid, int out_len, int pad_mode, int flags, void* stream) {
     if (n_units == 0) return 0;
-    bool half = false;
-    int hb_max = 1;
-    if (spec_buckets_check(buckets, n_buckets, &half, &hb_max) ||
-        !spec_buckets_launch_args_ok(spec, rir_len, unit_desc, n_units, n_valid, out_len, flags) ||
-        !mel_args_ok(logmel, mel_start, mel_w, n_mels, max_len, mel_eps))
-        return SS_EINVAL;
-    if (pad_mode != SS_PAD_REFLECT && pad_mode != SS_PAD_CONSTANT) return SS_EINVAL;
-    if (!obs_logmel_buckets_shape_ok(out_len, n_valid, hb_max, flags, half)) return SS_EINVAL;
-    ssk::ConvParams p;
-    int n_cus = 1;
-    int rc = fill_conv(p, &n_cus, spec, nullptr, rir_len, unit_desc, 0, 0, 1, 0, n_valid, out_len, false);
-    if (rc) return rc;
-    ssk::SpecScale<true, true> hs;
-    fill_spec_buckets(p, hs, buckets, n_buckets);
-    if (flags & SS_FLAG_FIRST_BUCKET) p.n_buckets = 1;
-    p.pad_mode = pad_mode;
-    p.out = audiogoal;
-    p.sgram = spectrogram;
+    if (!mel_args_ok(logmel, mel_start, mel_w, n_mels, max_len, mel_eps)) return SS_EINVAL;
     const ssk::MelArgs m{logmel, mel_start, mel_w, n_mels, max_len, mel_eps};
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (half) {
-        if (p.n_buckets == 1) return launch_conv_spec16_mel(p, m, hs.hscale, n_units, flags, st);
-        p.nb_y = 1;
-        p.parts_log2 = 0;
-        hipLaunchKernelGGL((ssk::k_conv_spec<true, false, false, true, true, true>), dim3(2 * n_units), dim3(ssk::kT), 0, st, p, m, hs);
-        return hip_err(hipGetLastError());
-    }
-    if (out_len <= ssk::kB) return launch_conv_spec_mel(p, m, n_units, flags, st);
-    return launch_obs_rows<true, true>(p, n_units, flags, n_cus, st, m);
+    return render(spec_buckets_bank(buckets, n_buckets), true, out_len <= ssk::kB ? Launch::kMelOneBlock : Launch::kMelRows, spec,
+                  rir_len, unit_desc, audiogoal, spectrogram, &m, n_units, n_valid, out_len, pad_mode, flags, stateless(stream));
 }
 
 // The context's bank as spectral length buckets: replaces any earlier binding (rows, spectra of either form, ss_rir_bucket

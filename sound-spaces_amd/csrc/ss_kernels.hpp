@@ -78,9 +78,7 @@ __device__ __forceinline__ void st_stream(T* p, T v) {
 #endif
 }
 
-// STFT geometry of SpectrogramSensor.compute_spectrogram (nav.py:88-93)
-constexpr int kNfft = 512, kHop = 160, kPool = 4, kBins4 = 65;   // 257 bins -> 65 pooled rows
-constexpr int kPrevPairs = 1208;          // XFADE: packed pairs of the cross-fade ramp kept per row (fade_len <= 2414: 48 kHz)
+// (the STFT geometry - kNfft, kHop, kPool, kBins4 - and kPrevPairs: ss_consts.hpp)
 constexpr int kFrameStride = 272;         // transpose tiles (16 x 17 complex per frame); = 16 mod 32 so that the four
                                           // frames of a wave start 32 banks apart (ds_read/write_b64 rules)
 constexpr int kNatStride = 288;           // natural-order spectra per frame; = 0 mod 32 (ds_read_b128 lane groups)
@@ -364,14 +362,7 @@ struct SpecParams {
     int live;             // pooled blocks >= live are KNOWN to be zero (rows rendered up to n_valid < len: see live_blocks);
 };                        // t4 when nothing is known about the rows
 
-// pooled time blocks that can be non-zero when a row of `len` samples is zero from sample n_valid on: block b is exactly
-// zero once all of its frames start behind the rendered samples (640 b - 256 >= n_valid) - provided the right centre
-// padding mirrors zeros as well (n_valid <= len - 512); |STFT| of zeros is 0 and log1p(0) = 0
-__host__ __device__ constexpr int live_blocks(int n_valid, int len, int t4) {
-    return n_valid <= len - kNfft ? ((n_valid + kNfft / 2 + kHop * kPool - 1) / (kHop * kPool) < t4
-                                         ? (n_valid + kNfft / 2 + kHop * kPool - 1) / (kHop * kPool) : t4)
-                                  : t4;
-}
+// (live_blocks, the pooled time blocks of a row that can be non-zero: ss_consts.hpp)
 
 // stand-alone spectrogram: 512 threads = 8 waves = {ear 0, ear 1} x 4 consecutive pooled time blocks of one unit.
 // (Ablation of the previous one-wave-per-block layout, profiles/r1/NOTES.md: 58 of 200 us were the per-lane frame

@@ -122,7 +122,7 @@ def live_pooled_blocks(n_valid: int, length: int) -> int:
 def wide_one_block(out_len: int, n_valid: int, spectral: bool = False) -> bool:
     """Rows longer than one block of which only block 0 is rendered and whose live columns fit the fused phase (SS2.0 steps
     at 44.1 kHz): the library serves them with the fused loop kernel in ONE launch, waveform buffer or not
-    (csrc/ss_hip.hip::wide_one_block_ok)."""
+    (csrc/ss_route.hpp::wide_one_block_ok)."""
     return (not spectral) and out_len > KB and 0 <= n_valid <= KB and live_pooled_blocks(n_valid, out_len) <= 26
 
 

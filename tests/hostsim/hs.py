@@ -19,7 +19,7 @@ def lib():
         so = os.path.join(HERE, "libss_hostsim.so")
         srcs = [os.path.join(HERE, f) for f in ("hostsim.cpp", "hip_shim.h")]
         csrc = os.path.join(HERE, "..", "..", "sound-spaces_amd", "csrc")
-        srcs += [os.path.join(csrc, f) for f in ("ss_kernels.hpp", "ss_fft_core.hpp", "ss_tables.hpp", "ss_kernels32.hpp", "ss_fft_core32.hpp", "ss_features.hpp")]
+        srcs += [os.path.join(csrc, f) for f in ("ss_kernels.hpp", "ss_fft_core.hpp", "ss_consts.hpp", "ss_tables.hpp", "ss_kernels32.hpp", "ss_fft_core32.hpp", "ss_features.hpp")]
         if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
             cxx = os.environ.get("SS_HOSTSIM_CXX", "/opt/rocm/lib/llvm/bin/clang++")   # needs ext_vector_type
             subprocess.check_call([cxx, "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas",
