@@ -312,8 +312,8 @@ int ss_audio_obs_logmel_buckets_f32(const float* spec, const ss_rir_bucket* buck
  * keep the loop-free kernels.
  *   ss_fftconv_binaural_spec_buckets_f32   every row length ss_fftconv_binaural_spec_f32 / _spec16_f32 serve (n_valid <= 3 kB);
  *   ss_audio_obs_spec_buckets_f32          fp32: the shapes ss_audio_obs_buckets_f32 serves from spectra; half: rows of one
- *                                          partition block, 257 <= out_len <= kB (the fused 44.1 / 48 kHz row kernels do not read
- *                                          half bucketed banks);
+ *                                          partition block, 257 <= out_len <= kB (rows of 2 or 3 blocks: the entries of their own
+ *                                          below, ss_audio_obs_rows_spec16_buckets_f32);
  *   ss_audio_obs_logmel_spec_buckets_f32   ss_audio_obs_logmel_buckets_f32 on these buckets, same outputs, shapes and refusals:
  *                                          fp32 - one-block rows (k_conv_spec<loop, MEL>) and rows of 2 or 3 blocks (k_obs_blocks /
  *                                          k_obs_rows <true, .., BUCKETS, MEL>); half - one-block rows only
@@ -339,6 +339,31 @@ int ss_audio_obs_logmel_spec_buckets_f32(const float* spec, const ss_spec_bucket
                                          const int* unit_desc, float* audiogoal, float* spectrogram, float* logmel,
                                          const int* mel_start, const float* mel_w, int n_mels, int max_len, float mel_eps,
                                          int n_units, int n_valid, int out_len, int pad_mode, int flags, void* stream);
+
+/* ---- Half spectral length buckets, rows of 2 or 3 partition blocks (44.1 / 48 kHz) -------------------------------------------
+ * The two fused entries above refuse half buckets with out_len > kB; these two serve exactly that: HALF ss_spec_bucket[] arrays
+ * (hscale non-NULL in every bucket), kB < out_len <= 3 kB, 0 <= n_valid <= out_len, every bucket at most 16 blocks.  Arguments
+ * as their single-allocation siblings ss_audio_obs_rows_spec16_f32 / ss_audio_obs_logmel_rows_spec16_f32 take them, with
+ * (buckets, n_buckets) in place of (hspec16, hscale, h_blocks), and routed as those route: k_obs_blocks<true, MEL, HALF, HBK>
+ * while rows x blocks fit the chip at one workgroup per CU and n_valid == out_len, k_obs_rows<true, false, BUCKETS, MEL, HALF>
+ * beyond - both resolve halves, scales and depth of a term's bucket once per term from the wave-uniform bank index
+ * (nbh = min(ceil(rir_len / kB), the bucket's blocks)); shapes the fp32 entry renders unfused (n_valid <= kB with a waveform
+ * buffer) go to ss_fftconv_binaural_spec_buckets_f32 + the spectrogram kernel.
+ *   ss_audio_obs_rows_spec16_buckets_f32          audiogoal may be NULL, spectrogram required;
+ *   ss_audio_obs_logmel_rows_spec16_buckets_f32   logmel required (the mel limits of ss_audio_features_f32), audiogoal and
+ *                                                 spectrogram optional, any combination in one launch.
+ * Launches with one bucket or SS_FLAG_FIRST_BUCKET are single-allocation launches on bucket 0: bit for bit what the siblings
+ * give on its arrays.  Values: those of the fp32 spectral buckets fed float(q) * hscale, to the rounding of the products' order.
+ * SS_EINVAL before a device is touched: fp32 or mixed buckets, every refusal of ss_spec_bucket, SS_FLAG_CROSSFADE, out_len <= kB
+ * or > 3 kB, n_valid outside [0, out_len], a bad pad_mode, a NULL required output.  n_units == 0 returns 0.  A k_obs_blocks
+ * launch must not be replayed from a captured graph (see ss_audio_obs_rows_spec16_f32). */
+int ss_audio_obs_rows_spec16_buckets_f32(const float* spec, const ss_spec_bucket* buckets, int n_buckets, const int* rir_len,
+                                         const int* unit_desc, float* audiogoal, float* spectrogram, int n_units, int n_valid,
+                                         int out_len, int pad_mode, int flags, void* stream);
+int ss_audio_obs_logmel_rows_spec16_buckets_f32(const float* spec, const ss_spec_bucket* buckets, int n_buckets, const int* rir_len,
+                                                const int* unit_desc, float* audiogoal, float* spectrogram, float* logmel,
+                                                const int* mel_start, const float* mel_w, int n_mels, int max_len, float mel_eps,
+                                                int n_units, int n_valid, int out_len, int pad_mode, int flags, void* stream);
 
 /* EXTENSION, one pass for every STFT-derived feature (BASELINE.json configs[4] "GCC-PHAT + log-mel fused sensor"): each
  * (unit, ear, frame) of x [n_units, 2, len] is framed, windowed and transformed ONCE (both ears in one wave), and from that
@@ -482,6 +507,13 @@ int ss_ctx_set_rir_buckets(ss_ctx* ctx, const ss_rir_bucket* buckets, int n_buck
  * ss_ctx_observe_requests_load returns 0 with the unresolved requests reported in miss_out / n_miss and no launch made, as
  * ss_ctx_observe_requests reports them (a step without misses is rendered).  Call again whenever a bucket is (re)allocated. */
 int ss_ctx_set_rir_spec_buckets(ss_ctx* ctx, const ss_spec_bucket* buckets, int n_buckets, const int* rir_len);
+/* HALF spectral length buckets on a context whose rows are 2 or 3 partition blocks (kB < sampling_rate <= 3 kB: 44.1 / 48 kHz).
+ * Preconditions, replacement rules and the loaders' "not served" as ss_ctx_set_rir_spec_buckets; on top, SS_EINVAL (nothing
+ * changed) for fp32 buckets and on a context of one-block rows.  Spectrogram steps take ss_audio_obs_rows_spec16_buckets_f32,
+ * log-mel steps inside ss_ctx_set_logmel_buckets_policy's range ss_audio_obs_logmel_rows_spec16_buckets_f32 (outside it: the
+ * context's waveform scratch, as always), waveform-only steps ss_fftconv_binaural_spec_buckets_f32.  Cross-faded steps are
+ * SS_EINVAL and leave no keys behind. */
+int ss_ctx_set_rir_spec_buckets_rows(ss_ctx* ctx, const ss_spec_bucket* buckets, int n_buckets, const int* rir_len);
 /* One step.  audiogoal [n,2,sr] and spectrogram [n,65,T4,2] are device buffers; either may be NULL (not both).
  * Asynchronous on `stream`; the host arrays of `units` may be reused as soon as the call returns. */
 int ss_ctx_observe(ss_ctx* ctx, const ss_units* units, int n, float* audiogoal, float* spectrogram, void* stream);

@@ -81,6 +81,7 @@ struct Context {
     int h_blocks = 0;
     std::vector<ss_rir_bucket> buckets;   // length-bucketed bank (ss_ctx_set_rir_buckets); empty: the single bank above
     std::vector<ss_spec_bucket> spec_buckets;   // ... without time-domain rows (ss_ctx_set_rir_spec_buckets): rir / hspec are NULL then
+    bool spec_buckets_rows = false;             // ... half ones bound for rows of 2 or 3 blocks (ss_ctx_set_rir_spec_buckets_rows)
     // window-spectra cache
     int stride = 1;               // pool slots per entry = nbh_max + nby - 1
     int n_entries = 0;            // host bookkeeping (may run ahead of the device pool, see cache_grow)

@@ -293,10 +293,11 @@ void drop_stash(hipStream_t st) {
 // phase of a block split 2 / 4 / 8 ways).  Returns 1 when the launch does not qualify (the caller falls through to k_obs_rows).
 // MEL: the log-mel instantiations (ss_audio_obs_logmel_rows_f32 / _spec_f32), same rule, same hand-off area.
 // HALF: the half-bank instantiations (ss_audio_obs_rows_spec16_f32 / ss_audio_obs_logmel_rows_spec16_f32), likewise.
-template <bool SPECTRAL, bool MEL = false, bool HALF = false>
+// HBK: a half bank in length buckets (ss_audio_obs_rows_spec16_buckets_f32 / ss_audio_obs_logmel_rows_spec16_buckets_f32), likewise.
+template <bool SPECTRAL, bool MEL = false, bool HALF = false, bool HBK = false>
 int launch_obs_blocks(ssk::ConvParams p, int n_units, int flags, int n_cus, const LaunchEnv& env,
                       const ssk::UnitTab<false, MEL>& mel = ssk::UnitTab<false, MEL>(),
-                      const ssk::SpecScale<HALF>& hs = ssk::SpecScale<HALF>()) {
+                      const ssk::SpecScale<HALF, HBK>& hs = ssk::SpecScale<HALF, HBK>()) {
     const hipStream_t st = env.st;
     static const bool off = ab_flag("SS_HIP_NO_OBS_BLOCKS");   // (A/B builds only)
     const int n_rows = 2 * n_units, nb = (p.out_len + ssk::kB - 1) / ssk::kB;
@@ -316,7 +317,10 @@ int launch_obs_blocks(ssk::ConvParams p, int n_units, int flags, int n_cus, cons
     int rc = get_block_sync(st, &tails, &fl, &epoch);
     if (rc) return rc;
     const int grid = (n_rows * nb) << k;
-    if constexpr (HALF) {
+    if constexpr (HBK) {
+        hipLaunchKernelGGL((ssk::k_obs_blocks<SPECTRAL, MEL, true, true>), dim3(grid), dim3(ssk::kT), 0, st, p, n_rows, tails, fl, epoch, mel, hs);
+        return hip_err(hipGetLastError());
+    } else if constexpr (HALF) {
         hipLaunchKernelGGL((ssk::k_obs_blocks<SPECTRAL, MEL, true>), dim3(grid), dim3(ssk::kT), 0, st, p, n_rows, tails, fl, epoch, mel, hs);
         return hip_err(hipGetLastError());
     }
@@ -325,17 +329,18 @@ int launch_obs_blocks(ssk::ConvParams p, int n_units, int flags, int n_cus, cons
     return hip_err(hipGetLastError());
 }
 
-template <bool SPECTRAL, bool MEL = false, bool HALF = false>
+template <bool SPECTRAL, bool MEL = false, bool HALF = false, bool HBK = false>
 int launch_obs_rows(ssk::ConvParams p, int n_units, int flags, int n_cus, const LaunchEnv& env,
                     const ssk::UnitTab<false, MEL>& mel = ssk::UnitTab<false, MEL>(),
-                    const ssk::SpecScale<HALF>& hs = ssk::SpecScale<HALF>()) {
+                    const ssk::SpecScale<HALF, HBK>& hs = ssk::SpecScale<HALF, HBK>()) {
     const hipStream_t st = env.st;
     static_assert(!HALF || SPECTRAL, "half bank: the spectral form");
+    static_assert(!HBK || HALF, "bucketed half bank: a half form");
     const int n_rows = 2 * n_units;
     if ((MEL || HALF) && (flags & SS_FLAG_CROSSFADE)) return SS_EINVAL;                            // (the log-mel and half forms: plain rows)
-    if (HALF && p.n_buckets != 1) return SS_EINVAL;                                                 // (half: one allocation)
+    if (HALF && !HBK && p.n_buckets != 1) return SS_EINVAL;                                         // (half: one allocation, or the HBK form)
     {
-        const int rc = launch_obs_blocks<SPECTRAL, MEL, HALF>(p, n_units, flags, n_cus, env, mel, hs);
+        const int rc = launch_obs_blocks<SPECTRAL, MEL, HALF, HBK>(p, n_units, flags, n_cus, env, mel, hs);
         if (rc != 1) return rc;
     }
     // small steps (the reference steps 5-10 envs per GPU at this rate): a row on 2 / 4 / 8 CUs, each rendering the row and
@@ -372,7 +377,10 @@ int launch_obs_rows(ssk::ConvParams p, int n_units, int flags, int n_cus, const 
             return hip_err(hipGetLastError());
         }
     }
-    if constexpr (HALF) {
+    if constexpr (HBK) {
+        hipLaunchKernelGGL((ssk::k_obs_rows<true, false, true, MEL, true>), dim3(grid), dim3(ssk::kT), 0, st, p, n_rows, mel, hs);
+        return hip_err(hipGetLastError());
+    } else if constexpr (HALF) {
         hipLaunchKernelGGL((ssk::k_obs_rows<true, false, false, MEL, true>), dim3(grid), dim3(ssk::kT), 0, st, p, n_rows, mel, hs);
         return hip_err(hipGetLastError());
     }
@@ -707,6 +715,7 @@ struct Bank {
     const ss_rir_bucket* bk = nullptr;      // length buckets that keep rows (every bucket may carry its fp32 spectra as well) ...
     const ss_spec_bucket* sbk = nullptr;    // ... or hold spectra only, fp32 or half
     int n_buckets = 0;
+    bool sbk_rows = false;                  // half `sbk` that also serves rows of 2 or 3 blocks (the *_rows_spec16_buckets entries)
 };
 inline Bank rows_bank(const float* rir, long long us, int cs, int es, int cap) {
     Bank b;
@@ -723,9 +732,9 @@ inline Bank buckets_bank(const ss_rir_bucket* bk, int n_buckets) {
     b.bk = bk; b.n_buckets = n_buckets;
     return b;
 }
-inline Bank spec_buckets_bank(const ss_spec_bucket* sbk, int n_buckets) {
+inline Bank spec_buckets_bank(const ss_spec_bucket* sbk, int n_buckets, bool half_rows = false) {
     Bank b;
-    b.sbk = sbk; b.n_buckets = n_buckets;
+    b.sbk = sbk; b.n_buckets = n_buckets; b.sbk_rows = half_rows;
     return b;
 }
 
@@ -743,7 +752,13 @@ template <bool MEL>
 int launch_rows_any(const ssk::ConvParams& p, const ssk::SpecScale<true, true>& hs, bool spectral, int n_units, int flags, int n_cus,
                     const LaunchEnv& env, const ssk::UnitTab<false, MEL>& mel = ssk::UnitTab<false, MEL>()) {
     if (!spectral) return launch_obs_rows<false, MEL>(p, n_units, flags, n_cus, env, mel);
-    if (hs.hscale) return launch_obs_rows<true, MEL, true>(p, n_units, flags, n_cus, env, mel, ssk::SpecScale<true>{hs.hscale});
+    // half buckets: launches that only touch bucket 0 (one bucket, or SS_FLAG_FIRST_BUCKET) are single-allocation launches on its arrays
+    if (hs.hscale && p.n_buckets > 1 && !(flags & SS_FLAG_FIRST_BUCKET)) return launch_obs_rows<true, MEL, true, true>(p, n_units, flags, n_cus, env, mel, hs);
+    if (hs.hscale) {
+        ssk::ConvParams p1 = p;
+        p1.n_buckets = 1;
+        return launch_obs_rows<true, MEL, true>(p1, n_units, flags, n_cus, env, mel, ssk::SpecScale<true>{hs.hscale});
+    }
     return launch_obs_rows<true, MEL>(p, n_units, flags, n_cus, env, mel);
 }
 
@@ -788,7 +803,8 @@ int render(const Bank& b, bool spectral, ssroute::Launch want, const float* spec
         case Launch::kObs:
             if (!spectrogram) return SS_EINVAL;
             // half spectral buckets: rows of one partition block (the fused row kernels do not read half bucketed banks)
-            if (b.sbk && half && (out_len > ssk::kB || t4_of(out_len) > 26)) return SS_EINVAL;
+            // (... but through the entries of their own: Bank::sbk_rows)
+            if (b.sbk && half && !b.sbk_rows && (out_len > ssk::kB || t4_of(out_len) > 26)) return SS_EINVAL;
             chain = ssroute::obs_chain(out_len, n_valid, nbh_max, flags, spectral, audiogoal != nullptr, route_switches());
             if (chain == Chain::kTwo && !audiogoal) return SS_EINVAL;      // cross-faded long rows hand over through HBM/L2
             break;
@@ -800,7 +816,7 @@ int render(const Bank& b, bool spectral, ssroute::Launch want, const float* spec
             if (!mel || spectral || bucketed || !ss2_shape) return SS_EINVAL;
             break;
         case Launch::kMelRows:
-            if (!mel || (half && bucketed) || (!spectral && !bucketed && b.cap < 1) ||
+            if (!mel || (half && bucketed && !b.sbk_rows) || (!spectral && !bucketed && b.cap < 1) ||
                 !ssroute::obs_logmel_rows_shape_ok(out_len, n_valid, nbh_max, flags))
                 return SS_EINVAL;
             break;
@@ -1702,6 +1718,7 @@ static ssroute::Bank route_bank_of(const ssctx::Context& c) {
     b.buckets_spectra = b.buckets && buckets_spectral(c.buckets.data(), static_cast<int>(c.buckets.size()), 0);
     b.spec_buckets = !c.spec_buckets.empty();
     b.spec_buckets_half = b.spec_buckets && c.spec_buckets[0].hscale != nullptr;
+    b.spec_buckets_half_rows = b.spec_buckets_half && c.spec_buckets_rows;
     b.rir_cap = c.rir_cap;
     b.h_blocks = c.h_blocks;
     return b;
@@ -1709,7 +1726,7 @@ static ssroute::Bank route_bank_of(const ssctx::Context& c) {
 
 // ... and as the launches read it
 static Bank bank_of(const ssctx::Context& c) {
-    if (!c.spec_buckets.empty()) return spec_buckets_bank(c.spec_buckets.data(), static_cast<int>(c.spec_buckets.size()));
+    if (!c.spec_buckets.empty()) return spec_buckets_bank(c.spec_buckets.data(), static_cast<int>(c.spec_buckets.size()), c.spec_buckets_rows);
     if (!c.buckets.empty()) return buckets_bank(c.buckets.data(), static_cast<int>(c.buckets.size()));
     Bank b = rows_bank(c.rir, c.rir_us, c.rir_cs, c.rir_es, c.rir_cap);
     b.hspec = c.hspec; b.hscale = c.hscale; b.h_blocks = c.h_blocks;
@@ -2737,16 +2754,70 @@ int ss_audio_obs_logmel_spec_buckets_f32(const float* spec, const ss_spec_bucket
                   rir_len, unit_desc, audiogoal, spectrogram, &m, n_units, n_valid, out_len, pad_mode, flags, stateless(stream));
 }
 
+// ---- half spectral length buckets, rows of 2 or 3 partition blocks (44.1 / 48 kHz): k_obs_blocks<true, MEL, HALF, HBK> /
+// k_obs_rows<true, false, BUCKETS, MEL, HALF> ----
+// what the two entries refuse on top of render(): anything but the half form, rows the fused row kernels do not serve
+static bool spec16_buckets_rows_args_ok(const ss_spec_bucket* buckets, int n_buckets, int n_units, int n_valid, int out_len, int pad_mode,
+                                        int flags) {
+    bool half = false;
+    int hb_max = 1;
+    if (n_units < 0 || spec_buckets_check(buckets, n_buckets, &half, &hb_max) || !half || (flags & SS_FLAG_CROSSFADE)) return false;
+    if (pad_mode != SS_PAD_REFLECT && pad_mode != SS_PAD_CONSTANT) return false;
+    return out_len > ssk::kB && out_len <= 3 * ssk::kB && n_valid >= 0 && n_valid <= out_len;
+}
+
+// ss_audio_obs_rows_spec16_f32 on half spectral length buckets: the same routing (k_obs_blocks while the grid fits the chip,
+// k_obs_rows beyond; shapes the fp32 entry hands to the unfused convolution + k_spectrogram go to the half convolution).
+// Launches that only touch bucket 0 (one bucket, or SS_FLAG_FIRST_BUCKET) are single-allocation launches on bucket 0's arrays.
+int ss_audio_obs_rows_spec16_buckets_f32(const float* spec, const ss_spec_bucket* buckets, int n_buckets, const int* rir_len,
+                                         const int* unit_desc, float* audiogoal, float* spectrogram, int n_units, int n_valid,
+                                         int out_len, int pad_mode, int flags, void* stream) {
+    if (n_units == 0) return 0;
+    if (!spectrogram || !spec16_buckets_rows_args_ok(buckets, n_buckets, n_units, n_valid, out_len, pad_mode, flags)) return SS_EINVAL;
+    return render(spec_buckets_bank(buckets, n_buckets, true), true, Launch::kObs, spec, rir_len, unit_desc, audiogoal, spectrogram,
+                  nullptr, n_units, n_valid, out_len, pad_mode, flags, stateless(stream));
+}
+
+// ss_audio_obs_logmel_rows_spec16_f32 on half spectral length buckets
+int ss_audio_obs_logmel_rows_spec16_buckets_f32(const float* spec, const ss_spec_bucket* buckets, int n_buckets, const int* rir_len,
+                                                const int* unit_desc, float* audiogoal, float* spectrogram, float* logmel,
+                                                const int* mel_start, const float* mel_w, int n_mels, int max_len, float mel_eps,
+                                                int n_units, int n_valid, int out_len, int pad_mode, int flags, void* stream) {
+    if (n_units == 0) return 0;
+    if (!spec16_buckets_rows_args_ok(buckets, n_buckets, n_units, n_valid, out_len, pad_mode, flags)) return SS_EINVAL;
+    if (!mel_args_ok(logmel, mel_start, mel_w, n_mels, max_len, mel_eps)) return SS_EINVAL;
+    const ssk::MelArgs m{logmel, mel_start, mel_w, n_mels, max_len, mel_eps};
+    return render(spec_buckets_bank(buckets, n_buckets, true), true, Launch::kMelRows, spec, rir_len, unit_desc, audiogoal, spectrogram,
+                  &m, n_units, n_valid, out_len, pad_mode, flags, stateless(stream));
+}
+
+static int ctx_bind_spec_buckets(ss_ctx* h, const ss_spec_bucket* buckets, int n_buckets, const int* rir_len, bool rows);
+
 // The context's bank as spectral length buckets: replaces any earlier binding (rows, spectra of either form, ss_rir_bucket
 // buckets); the descriptor array is copied, the device pointers are borrowed.  Planning depth as ss_ctx_set_rir_buckets.
 int ss_ctx_set_rir_spec_buckets(ss_ctx* h, const ss_spec_bucket* buckets, int n_buckets, const int* rir_len) {
+    return ctx_bind_spec_buckets(h, buckets, n_buckets, rir_len, false);
+}
+
+// ... HALF buckets on a context whose rows are 2 or 3 partition blocks (kB < sampling_rate <= 3 kB): spectrogram steps go to
+// ss_audio_obs_rows_spec16_buckets_f32, log-mel steps inside ss_ctx_set_logmel_buckets_policy's range to
+// ss_audio_obs_logmel_rows_spec16_buckets_f32, waveform-only steps to ss_fftconv_binaural_spec_buckets_f32.  Same preconditions
+// otherwise; refused on a context of one-block rows and for fp32 buckets.
+int ss_ctx_set_rir_spec_buckets_rows(ss_ctx* h, const ss_spec_bucket* buckets, int n_buckets, const int* rir_len) {
+    return ctx_bind_spec_buckets(h, buckets, n_buckets, rir_len, true);
+}
+
+static int ctx_bind_spec_buckets(ss_ctx* h, const ss_spec_bucket* buckets, int n_buckets, const int* rir_len, bool rows) {
     bool half = false;
     int hb_max = 1;
     if (!h || !rir_len || spec_buckets_check(buckets, n_buckets, &half, &hb_max)) return SS_EINVAL;
     ssctx::Context& c = h->c;
-    if (half && c.out_len > c.kb) return SS_EINVAL;            // (ss_audio_obs_spec_buckets_f32: half serves one-block rows)
+    if (rows) {
+        if (!half || c.out_len <= c.kb || c.out_len > 3 * c.kb) return SS_EINVAL;
+    } else if (half && c.out_len > c.kb) return SS_EINVAL;     // (ss_audio_obs_spec_buckets_f32: half serves one-block rows)
     const int nbh_old = c.rir_cap > 0 ? ssctx::ceil_div(c.rir_cap, c.kb) : 1;
     c.spec_buckets.assign(buckets, buckets + n_buckets);
+    c.spec_buckets_rows = rows;
     c.buckets.clear();
     c.rir = nullptr; c.rir_len = rir_len; c.rir_us = 0; c.rir_cs = 0; c.rir_es = 1;
     c.rir_cap = hb_max * c.kb;                                 // planning depth: the longest bucket's blocks

@@ -2382,11 +2382,15 @@ __device__ __forceinline__ void mel_fill_quiet(const MelArgs& m, const ConvParam
 // resolves it: 124 / 122 VGPRs, no VGPR spills, no scratch (profiles/r7/NOTES.md).
 // HALF (a half bank, see k_conv_spec<.., HALF>): the pairs in memory are fp16 block spectra with one scale per block
 // (rows_product16); the scales ride in a kernel argument of their own.
+// HALF with BUCKETS (a half bank in length buckets, see k_conv_spec<.., HBK>): the bucket of a term - its fp16 base, its scale base
+// and its depth - is resolved once per term and row (bank_spec16: scalar compares on the wave-uniform index); block i of the
+// term is then hp + i * (kSpecComplex / 2) and sp + i.
 template <bool SPECTRAL, bool XFADE = false, bool BUCKETS = true, bool MEL = false, bool HALF = false>
 __global__ __launch_bounds__(1024) void k_obs_rows(ConvParams p, int n_rows, UnitTab<false, MEL> ut = UnitTab<false, MEL>(),
-                                                   SpecScale<HALF> hs = SpecScale<HALF>()) {
+                                                   SpecScale<HALF, HALF && BUCKETS> hs = SpecScale<HALF, HALF && BUCKETS>()) {
     static_assert(!(SPECTRAL && XFADE), "cross-faded rows are rendered from the time-domain bank");
-    static_assert(!HALF || (SPECTRAL && !XFADE && !BUCKETS), "half bank: plain rows of a single-allocation spectral bank");
+    static_assert(!HALF || (SPECTRAL && !XFADE), "half bank: plain rows of a spectral bank (one allocation, or length buckets)");
+    constexpr bool HBK = HALF && BUCKETS;
     static_assert(!MEL || !XFADE, "log-mel: plain rows (of one allocation, or of a length-bucketed fp32 bank)");
     __shared__ c32 lds[16 * kWaveScratch > kLdsComplex ? 16 * kWaveScratch : kLdsComplex];
     __shared__ float s_win[kNfft];
@@ -2435,7 +2439,12 @@ __global__ __launch_bounds__(1024) void k_obs_rows(ConvParams p, int n_rows, Uni
         int nbh0 = 0, nbh1 = 0;
         if (dws[0].x >= 0) nbh0 = min(kRowsMaxNbh, (uniform_load(p.rir_len + dws[0].x) + kB - 1) / kB);
         if (dws[1].x >= 0) nbh1 = min(kRowsMaxNbh, (uniform_load(p.rir_len + dws[1].x) + kB - 1) / kB);
-        if (SPECTRAL) {
+        // a half bank in length buckets: each term's first block (halves, scale) of this ear, in scalar registers for the row
+        BankSpec16 h16_0{nullptr, nullptr, 0}, h16_1{nullptr, nullptr, 0};
+        if constexpr (HBK) {
+            if (dws[0].x >= 0) { h16_0 = bank_spec16(p, hs, dws[0].x, ch); nbh0 = min(nbh0, h16_0.h_blocks); }
+            if (dws[1].x >= 0) { h16_1 = bank_spec16(p, hs, dws[1].x, ch); nbh1 = min(nbh1, h16_1.h_blocks); }
+        } else if (SPECTRAL) {
             if (dws[0].x >= 0) nbh0 = min(nbh0, bank_spec<BUCKETS>(p, dws[0].x, 0).h_blocks);
             if (dws[1].x >= 0) nbh1 = min(nbh1, bank_spec<BUCKETS>(p, dws[1].x, 0).h_blocks);
         } else {                                          // (never more blocks than the entry's row - and the stash - holds)
@@ -2570,9 +2579,14 @@ __global__ __launch_bounds__(1024) void k_obs_rows(ConvParams p, int n_rows, Uni
                         mp &= mp - 1;
                         const int term = pr >> 4, i = pr & 15;
                         const i32x4 dw = term ? dws[1] : dws[0];
+                        const f32x4* sp = p.spec + (size_t)(dw.y + (j - i - dw.z)) * blk_f4;
+                        if constexpr (HBK) {              // length buckets: the term's first block was resolved with the row
+                            const BankSpec16& hb = term ? h16_1 : h16_0;
+                            rows_product16(hb.hp + (size_t)i * blk_f4 + ti, hb.sp + i, sp + ti, ti, s, v);
+                            continue;
+                        }
                         const f32x4* hp = SPECTRAL ? bank_spec<BUCKETS>(p, dw.x, ch).hp + (size_t)i * blk_f4
                                                    : stash + (size_t)(term * p.stash_nbh + i) * blk_f4;
-                        const f32x4* sp = p.spec + (size_t)(dw.y + (j - i - dw.z)) * blk_f4;
                         if constexpr (HALF) {             // one allocation: same f32x4 index, 8-byte elements (see k_conv_spec)
                             const size_t blk = ((size_t)dw.x * 2 + ch) * (size_t)p.h_blocks + i;
                             rows_product16(reinterpret_cast<const h16x4*>(p.hspec) + blk * blk_f4 + ti, hs.hscale + blk, sp + ti, ti, s, v);
@@ -2684,11 +2698,13 @@ __global__ __launch_bounds__(1024) void k_obs_rows(ConvParams p, int n_rows, Uni
 // MEL (log-mel form, as k_obs_rows<.., MEL>): a workgroup writes the log-mel frames of its own pooled blocks, the silent row's
 // early return its block's share of frames; p.sgram may be null.
 // HALF (a half bank, see k_conv_spec<.., HALF>): the spectral branch reads fp16 block spectra and their scales.
-template <bool SPECTRAL, bool MEL = false, bool HALF = false>
+// HBK (a half bank in length buckets, see k_conv_spec<.., HBK>): the term's bucket gives the fp16 base, the scale base and the depth.
+template <bool SPECTRAL, bool MEL = false, bool HALF = false, bool HBK = false>
 __global__ __launch_bounds__(1024) void k_obs_blocks(ConvParams p, int n_rows, float* tails, int* flags, int epoch,
                                                      UnitTab<false, MEL> ut = UnitTab<false, MEL>(),
-                                                     SpecScale<HALF> hs = SpecScale<HALF>()) {
+                                                     SpecScale<HALF, HBK> hs = SpecScale<HALF, HBK>()) {
     static_assert(!HALF || SPECTRAL, "half bank: the spectral form");
+    static_assert(!HBK || HALF, "bucketed half bank: a half form");
     __shared__ c32 lds[16 * kWaveScratch > kLdsComplex ? 16 * kWaveScratch : kLdsComplex];
     __shared__ float s_win[kNfft];
     __shared__ c32 s_tw512[kTw512Lds];
@@ -2748,14 +2764,19 @@ __global__ __launch_bounds__(1024) void k_obs_blocks(ConvParams p, int n_rows, f
         const int L = uniform_load(p.rir_len + ridx);
         int nbh = (L + kB - 1) / kB;
         if (SPECTRAL) {
-            const BankSpec bs = bank_spec(p, ridx, ch);
-            nbh = min(nbh, bs.h_blocks);
+            BankSpec bs{nullptr, 0};
+            BankSpec16 b16{nullptr, nullptr, 0};
+            if constexpr (HBK) b16 = bank_spec16(p, hs, ridx, ch);
+            else bs = bank_spec(p, ridx, ch);
+            nbh = min(nbh, HBK ? b16.h_blocks : bs.h_blocks);
             for (int i = 0; i < nbh; ++i) {
                 const int m = j - i;
                 if (m < m_min || m >= m_min + m_cnt) continue;
                 int tl = t;
                 SSK_OPAQUE1(tl);
-                if constexpr (HALF) {                     // one allocation (the launcher checks): see k_conv_spec
+                if constexpr (HBK) {
+                    spec_block_product16(p.spec, tl, b16.hp + (size_t)i * (kSpecComplex / 2) + tl, b16.sp + i, spec0 + (m - m_min), any, acc);
+                } else if constexpr (HALF) {                     // one allocation (the launcher checks): see k_conv_spec
                     const size_t blk = ((size_t)ridx * 2 + ch) * (size_t)p.h_blocks + i;
                     spec_block_product16(p.spec, tl, reinterpret_cast<const h16x4*>(p.hspec) + blk * (kSpecComplex / 2) + tl,
                                          hs.hscale + blk, spec0 + (m - m_min), any, acc);

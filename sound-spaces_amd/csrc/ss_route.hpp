@@ -64,11 +64,12 @@ inline bool obs_logmel_rows_shape_ok(int out_len, int n_valid, int nbh_max, int 
 }
 
 // rows the log-mel entries of the length-bucketed banks serve (ss_audio_obs_logmel_buckets_f32 / _spec_buckets_f32): one partition
-// block on every bank form; 2 or 3 blocks on the fp32 forms, with the deepest bucket's blocks inside the row kernels' limit
-inline bool obs_logmel_buckets_shape_ok(int out_len, int n_valid, int nbh_max, int flags, bool half) {
+// block on every bank form; 2 or 3 blocks on the fp32 forms - and on half spectral buckets bound for such rows (half_rows:
+// ss_ctx_set_rir_spec_buckets_rows) - with the deepest bucket's blocks inside the row kernels' limit
+inline bool obs_logmel_buckets_shape_ok(int out_len, int n_valid, int nbh_max, int flags, bool half, bool half_rows = false) {
     if (n_valid < 0 || n_valid > out_len) return false;
     if (obs_logmel_shape_ok(out_len, flags)) return true;
-    return !half && obs_logmel_rows_shape_ok(out_len, n_valid, nbh_max, flags);
+    return (!half || half_rows) && obs_logmel_rows_shape_ok(out_len, n_valid, nbh_max, flags);
 }
 
 // One value per distinct launch body (not per C entry: every bank form has the same bodies).
@@ -97,7 +98,7 @@ inline Chain obs_chain(int out_len, int n_valid, int nbh_max, int flags, bool sp
     return Chain::kTwo;                                                               // cross-faded / very long rows
 }
 
-// What is bound to a context (ss_ctx_set_rir_bank / _spectra / _spectra16 / _spectra16_rows / _buckets / _spec_buckets)
+// What is bound to a context (ss_ctx_set_rir_bank / _spectra / _spectra16 / _spectra16_rows / _buckets / _spec_buckets / _spec_buckets_rows)
 struct Bank {
     bool rows = false;                // time-domain rows (of a length-bucketed bank: bucket 0's)
     bool spectra = false;             // block spectra of a single-allocation bank, fp32 or ...
@@ -108,6 +109,7 @@ struct Bank {
     bool spec_buckets_half = false;   // ... half
     int rir_cap = 0;                  // samples per row (length buckets: the deepest bucket's blocks * kB)
     int h_blocks = 0;                 // blocks of `spectra`
+    bool spec_buckets_half_rows = false;      // half `spec_buckets` bound for rows of 2 or 3 blocks (ss_ctx_set_rir_spec_buckets_rows)
 };
 
 struct Policies {
@@ -173,7 +175,7 @@ inline Route route_step(const Bank& b, int out_len, int n_valid, const Policies&
         else if (b.rows && !r.spectral && obs_logmel_ss2_shape(out_len, n_valid, flags, sw) != 0 &&
                  within(pol.mel_ss2_min, pol.mel_ss2_max))
             r.launch = Launch::kMelSs2;
-    } else if (w.mel && obs_logmel_buckets_shape_ok(out_len, n_valid, nbh_cap, flags, b.spec_buckets_half) &&
+    } else if (w.mel && obs_logmel_buckets_shape_ok(out_len, n_valid, nbh_cap, flags, b.spec_buckets_half, b.spec_buckets_half_rows) &&
                within(pol.mel_bk_min, pol.mel_bk_max)) {
         r.launch = out_len <= kB ? Launch::kMelOneBlock : Launch::kMelRows;
     }

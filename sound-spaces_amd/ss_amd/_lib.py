@@ -25,6 +25,7 @@ EXPORTS = ("ss_block_len", "ss_spec_floats", "ss_version", "ss_init", "ss_source
            "ss_audio_obs_rows_spec16_f32", "ss_audio_obs_logmel_rows_spec16_f32", "ss_ctx_set_rir_spectra16_rows",
            "ss_fftconv_binaural_spec_buckets_f32", "ss_audio_obs_spec_buckets_f32", "ss_ctx_set_rir_spec_buckets",
            "ss_audio_obs_logmel_buckets_f32", "ss_audio_obs_logmel_spec_buckets_f32", "ss_ctx_set_logmel_buckets_policy",
+           "ss_audio_obs_rows_spec16_buckets_f32", "ss_audio_obs_logmel_rows_spec16_buckets_f32", "ss_ctx_set_rir_spec_buckets_rows",
            "ss_memo_rows_f32", "ss_ctx_memo_enable", "ss_ctx_memo_reset", "ss_ctx_memo_stats", "ss_ctx_observe_sims_memo",
            "ss_ctx_sims_memo_plan")
 # entries that return a size_t, not a status (EXPORTS: every `int ss_*` of include/ss_hip.h)
@@ -192,6 +193,10 @@ def load() -> ctypes.CDLL:
                                                     c_int, c_int, c_int, c_int, vp]
     lib.ss_audio_obs_logmel_spec_buckets_f32.argtypes = lib.ss_audio_obs_logmel_buckets_f32.argtypes
     lib.ss_ctx_set_logmel_buckets_policy.argtypes = [vp, c_int, c_int]
+    # half spectral length buckets for rows of 2 or 3 partition blocks (44.1 / 48 kHz)
+    lib.ss_audio_obs_rows_spec16_buckets_f32.argtypes = lib.ss_audio_obs_spec_buckets_f32.argtypes
+    lib.ss_audio_obs_logmel_rows_spec16_buckets_f32.argtypes = lib.ss_audio_obs_logmel_spec_buckets_f32.argtypes
+    lib.ss_ctx_set_rir_spec_buckets_rows.argtypes = [vp, vp, c_int, vp]
     # pose memo of the column path
     lib.ss_memo_rows_f32.argtypes = [vp, c_int, vp, c_int, c_int, vp]
     lib.ss_ctx_memo_enable.argtypes = [vp, c_int]

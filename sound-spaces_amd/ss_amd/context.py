@@ -170,13 +170,16 @@ class AudioContext:
         self.rir_cap = int(bank.cap)
         self._spectra = None
 
-    def set_rir_spec_buckets(self, bank) -> None:
+    def set_rir_spec_buckets(self, bank, rows: bool = False) -> None:
         """A SPECTRAL-ONLY length-bucketed bank (``BucketedRirBank`` whose buckets keep block spectra - float32, or float16 with
         scales - and no rows; include/ss_hip.h ``ss_ctx_set_rir_spec_buckets``).  Replaces any earlier binding.  The library
-        refuses (SS_EINVAL) half buckets on a context whose rows exceed one partition block, and cross-faded steps."""
+        refuses (SS_EINVAL) half buckets on a context whose rows exceed one partition block, and cross-faded steps.
+        rows=True: HALF buckets on a context whose rows have 2 or 3 partition blocks (44.1 / 48 kHz;
+        ``ss_ctx_set_rir_spec_buckets_rows``): steps read them through k_obs_blocks / k_obs_rows in their bucketed half forms;
+        refused for float32 buckets and on a context of one-block rows."""
         arr = bank.spec_c_array()
-        _lib.check(self.lib.ss_ctx_set_rir_spec_buckets(self._h, ctypes.cast(arr, ctypes.c_void_p), len(bank.banks),
-                                                        bank.lengths.data_ptr()), "ss_ctx_set_rir_spec_buckets")
+        name = "ss_ctx_set_rir_spec_buckets_rows" if rows else "ss_ctx_set_rir_spec_buckets"
+        _lib.check(getattr(self.lib, name)(self._h, ctypes.cast(arr, ctypes.c_void_p), len(bank.banks), bank.lengths.data_ptr()), name)
         self._bank = (bank, arr)
         self.rir_cap = int(bank.cap)
         self._spectra = None
@@ -234,7 +237,8 @@ class AudioContext:
     def set_logmel_buckets_policy(self, min_units: int, max_units: int) -> None:
         """``set_logmel_policy`` for contexts bound by ``set_rir_buckets`` / ``set_rir_spec_buckets``: log-mel steps without a
         waveform buffer of ``min_units`` .. ``max_units`` units, without a cross-fade, take the one-launch fused kernels of the
-        length-bucketed banks (one-block rows on every bank form, 44.1 / 48 kHz rows on the fp32 forms;
+        length-bucketed banks (one-block rows on every bank form, 44.1 / 48 kHz rows on the fp32 forms and on half buckets
+        bound with ``set_rir_spec_buckets(bank, rows=True)``;
         ss_ctx_set_logmel_buckets_policy).  The three setters above never apply to such a context.  Default (1, 0): never -
         the scratch route is bit-equal to observe-then-features, the fused launch only to rounding.  (1, 2**31 - 1): whenever
         the shape allows - the range the measurements support at 16 kHz; at 44.1 kHz they support (1, 42) for log-mel alone

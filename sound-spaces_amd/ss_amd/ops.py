@@ -561,6 +561,31 @@ def audio_obs_spec_buckets_into(spec, buckets, n_buckets: int, rir_len, unit_des
                    "ss_audio_obs_spec_buckets_f32")
 
 
+def audio_obs_rows_spec16_buckets_into(spec, buckets, n_buckets: int, rir_len, unit_desc, audiogoal, spectrogram_out, n_valid: int,
+                                       out_len: int, pad_mode="reflect", flags: int = 0) -> None:
+    """``audio_obs_spec_buckets_into`` for rows of 2 or 3 partition blocks (KB < out_len <= 3 KB: 44.1 / 48 kHz) on HALF spectral
+    length buckets (``ss_audio_obs_rows_spec16_buckets_f32``; ``buckets`` = ``spec_bucket_array(...)`` of a half bank).
+    ``audiogoal`` may be None; spectrogram_out None: the waveform alone (ss_fftconv_binaural_spec_buckets_f32)."""
+    if spectrogram_out is None:
+        fftconv_binaural_spec_buckets_into(spec, buckets, n_buckets, rir_len, unit_desc, audiogoal, n_valid, flags)
+        return
+    _chk(spec, torch.float32, "spec"); _chk(rir_len, torch.int32, "rir_len"); _chk(unit_desc, torch.int32, "unit_desc")
+    _chk(spectrogram_out, torch.float32, "spectrogram_out")
+    N = unit_desc.shape[0]
+    assert tuple(spectrogram_out.shape) == (N,) + spectrogram_shape(out_len)
+    ag_ptr = None
+    if audiogoal is not None:
+        _chk(audiogoal, torch.float32, "audiogoal")
+        assert tuple(audiogoal.shape) == (N, 2, out_len)
+        ag_ptr = audiogoal.data_ptr()
+    with torch.cuda.device(spec.device):
+        _lib.check(_lib.load().ss_audio_obs_rows_spec16_buckets_f32(spec.data_ptr(), ctypes_ref(buckets), n_buckets,
+                                                                    rir_len.data_ptr(), unit_desc.data_ptr(), ag_ptr,
+                                                                    spectrogram_out.data_ptr(), N, n_valid, out_len, _PAD[pad_mode],
+                                                                    flags, _stream(spec)),
+                   "ss_audio_obs_rows_spec16_buckets_f32")
+
+
 def _obs_logmel_buckets(entry: str, spec, buckets, n_buckets, rir_len, unit_desc, audiogoal, spectrogram_out, logmel_out, mel_start,
                         mel_w, n_valid, out_len, mel_eps, pad_mode, flags) -> None:
     _chk(spec, torch.float32, "spec"); _chk(rir_len, torch.int32, "rir_len")
@@ -588,6 +613,15 @@ def audio_obs_logmel_spec_buckets_into(spec, buckets, n_buckets: int, rir_len, u
     """``audio_obs_logmel_buckets_into`` on spectral length buckets (``ss_audio_obs_logmel_spec_buckets_f32``; ``buckets`` =
     ``spec_bucket_array(...)``).  A half bank serves rows of one partition block here."""
     _obs_logmel_buckets("ss_audio_obs_logmel_spec_buckets_f32", spec, buckets, n_buckets, rir_len, unit_desc, audiogoal,
+                        spectrogram_out, logmel_out, mel_start, mel_w, n_valid, out_len, mel_eps, pad_mode, flags)
+
+
+def audio_obs_logmel_rows_spec16_buckets_into(spec, buckets, n_buckets: int, rir_len, unit_desc, audiogoal, spectrogram_out,
+                                              logmel_out, mel_start, mel_w, n_valid: int, out_len: int, mel_eps: float = 1e-6,
+                                              pad_mode="reflect", flags: int = 0) -> None:
+    """``audio_obs_logmel_spec_buckets_into`` for rows of 2 or 3 partition blocks on HALF spectral length buckets
+    (``ss_audio_obs_logmel_rows_spec16_buckets_f32``): ONE launch, whichever outputs are asked for next to ``logmel_out``."""
+    _obs_logmel_buckets("ss_audio_obs_logmel_rows_spec16_buckets_f32", spec, buckets, n_buckets, rir_len, unit_desc, audiogoal,
                         spectrogram_out, logmel_out, mel_start, mel_w, n_valid, out_len, mel_eps, pad_mode, flags)
 
 

@@ -433,7 +433,11 @@ class BatchedAudioRenderer:
         sg = spectrogram_out
         if sg is None:
             sg = torch.empty((N,) + self.spectrogram_shape, dtype=torch.float32, device=self.device)
-        if isinstance(self.rirs, BucketedRirBank) and self.rirs.spectral_only:
+        if isinstance(self.rirs, BucketedRirBank) and self.rirs.spectral_only and self.rirs.half and self.out_len > P.KB:
+            # (half buckets, rows of 2 or 3 blocks: the entry of their own; AudioEngine(rir_half_bucket_rows=True) builds such a bank)
+            ops.audio_obs_rows_spec16_buckets_into(self._spec, self.rirs.spec_c_array(), len(self.rirs.banks), self.rirs.lengths,
+                                                   plan.desc, ag, sg, self.n_valid, self.out_len, self.pad_mode, flags=plan.flags)
+        elif isinstance(self.rirs, BucketedRirBank) and self.rirs.spectral_only:
             ops.audio_obs_spec_buckets_into(self._spec, self.rirs.spec_c_array(), len(self.rirs.banks), self.rirs.lengths,
                                             plan.desc, ag, sg, self.n_valid, self.out_len, self.pad_mode, flags=plan.flags)
         elif isinstance(self.rirs, BucketedRirBank):
@@ -1612,7 +1616,7 @@ class AudioEngine:
                  rir_max_cap: int = 1 << 18, rir_group: int = 1, rir_spectral: Union[None, bool, str] = None,
                  rir_buckets: Optional[Sequence[Tuple[int, int]]] = None, spectral_hbm_fraction: float = 0.5,
                  spectral_max_units: int = 0, rir_half_rows: bool = False, rir_spectral_buckets: bool = False,
-                 **renderer_kwargs):
+                 rir_half_bucket_rows: bool = False, **renderer_kwargs):
         """rir_spectral: keep the RIR rows' block spectra in HBM as well (2x the bytes per row) and run k_conv_spec /
         k_obs_rows<SPECTRAL> (no forward FFT per step): for STATIC banks (SoundSpaces 1.0 RIR files); live SS2.0 RIRs change
         every step and stay on the time-domain kernels.  None (default) = decided here: ON for file-backed stores at rates
@@ -1652,7 +1656,15 @@ class AudioEngine:
         serves sampling rates up to KB (the fused 44.1 / 48 kHz row kernels do not read half bucketed banks yet).  A GPU device;
         step_time / wrap and spectral_max_units > 0 stay refused.  The last bucket grows up to min(rir_max_cap, 16 KB): a bucket
         holds at most 16 partition blocks per row, so a larger rir_max_cap is clamped here (a bucket capacity above 16 KB is the
-        store's ValueError)."""
+        store's ValueError).
+
+        rir_half_bucket_rows=True (with rir_spectral="half", rir_buckets and rir_spectral_buckets=True only; opt-in): half length
+        buckets for rows of 2 or 3 partition blocks (sampling rates in (KB, 3 KB]: 44.1 / 48 kHz) - the bucketed half forms of
+        the fused row kernels (ss_audio_obs_rows_spec16_buckets_f32 and its log-mel sibling) and the context binding
+        ss_ctx_set_rir_spec_buckets_rows.  A three-block entry costs 393 244 bytes against 786 436 of "only" buckets.  Same loss
+        and refusals as the other half forms; time against "only" buckets: INTEGRATION.md "Spectral length buckets"."""
+        if rir_half_bucket_rows and not (rir_buckets and rir_spectral_buckets and rir_spectral == "half"):
+            raise ValueError("rir_half_bucket_rows goes with rir_spectral='half', rir_buckets and rir_spectral_buckets=True")
         if rir_spectral_buckets and not (rir_buckets and rir_spectral in ("only", "half")):
             raise ValueError("rir_spectral_buckets goes with rir_buckets and rir_spectral='only' or 'half'")
         if rir_half_rows and rir_spectral != "half":
@@ -1668,12 +1680,15 @@ class AudioEngine:
             if spectral_max_units > 0:
                 raise ValueError(f"rir_spectral={rir_spectral!r} keeps no time-domain rows for the spectral_max_units policy to "
                                  "send large steps to")
-            if rir_spectral_buckets and rir_spectral == "half" and int(sampling_rate) > P.KB:
+            if rir_half_bucket_rows and int(sampling_rate) > 3 * P.KB:
+                raise ValueError(f"rir_half_bucket_rows serves rows of up to three partition blocks (sampling rates up to "
+                                 f"{3 * P.KB}), not {sampling_rate}")
+            if rir_spectral_buckets and rir_spectral == "half" and int(sampling_rate) > P.KB and not rir_half_bucket_rows:
                 raise ValueError(f"rir_spectral='half' on length buckets serves sampling rates up to {P.KB}, not {sampling_rate}: "
                                  "the fused row kernels do not read half bucketed banks yet")
             if rir_spectral_buckets and torch.device(device).type != "cuda":
                 raise ValueError(f"rir_spectral={rir_spectral!r} needs a GPU device: the spectral-only bank has no CPU fallback")
-            if rir_spectral == "half" and int(sampling_rate) > P.KB and not rir_half_rows:
+            if rir_spectral == "half" and int(sampling_rate) > P.KB and not (rir_half_rows or rir_half_bucket_rows):
                 raise ValueError(f"rir_spectral='half' serves rows of one partition block (sampling rates up to {P.KB}), "
                                  f"not {sampling_rate}; rir_half_rows=True opts in to the half forms of the 44.1 / 48 kHz row kernels")
             if rir_spectral == "half" and int(sampling_rate) > 3 * P.KB:
@@ -1773,8 +1788,8 @@ class AudioEngine:
         if isinstance(bank, BucketedRirBank):                    # length buckets: ss_ctx_set_rir_buckets (every bucket's rows, and
             now = tuple(b.data for b in bank.banks) + tuple(b.spectra for b in bank.banks)      # its block spectra when kept)
             if n_sync or cur is None or len(cur) != len(now) or any(a is not b for a, b in zip(cur, now)):
-                if bank.spectral_only:                           # (no rows: ss_ctx_set_rir_spec_buckets, either form)
-                    ctx.set_rir_spec_buckets(bank)
+                if bank.spectral_only:                           # (no rows: ss_ctx_set_rir_spec_buckets, either form; half buckets
+                    ctx.set_rir_spec_buckets(bank, rows=bank.half and self.renderer.out_len > P.KB)  # under longer rows: _rows)
                 else:
                     ctx.set_rir_buckets(bank, spectral=bool(self.store.spectral and bank.spectra))
                 self._ctx_bank = now
