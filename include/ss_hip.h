@@ -210,6 +210,42 @@ int ss_audio_obs_logmel_rows_spec16_f32(const float* spec, const void* hspec16, 
                                         const int* mel_start, const float* mel_w, int n_mels, int max_len, float mel_eps,
                                         int n_units, int h_blocks, int n_valid, int out_len, int pad_mode, int flags, void* stream);
 
+/* ---- Half-precision time-domain rows (EXTENSION, opt-in, LOSSY) ---------------------------------------------------------------
+ * The TIME-DOMAIN bank stored as IEEE fp16 with one power-of-two fp32 scale per (entry r, ear c): half the bytes of the plain row,
+ * the cheapest form a bank has.  rir16 is [entries][2][cap] halves, planar, cap even, the base 4-byte aligned; rscale is
+ * [entries][2] floats.  For a row v[0 .. cap), zero behind its length (the rule of the half spectral bank above, per row):
+ *     mx = max |v[k]|;  mx == 0: every half is +0 and rscale = 1;
+ *     otherwise, 2^(e-1) <= mx < 2^e:  q[k] = fp16(v[k] * 2^(15-e)) rounded to nearest even,  rscale = 2^(e-15).
+ * float(q) * rscale is the sample the kernels transform, exact in fp32.  BOTH arrays of a bank must be zero-initialised: an unused
+ * or empty entry then multiplies out to exact zeros (the table-form kernel never reads rir_len).  Rows are finite.
+ * Bytes per entry: 16 kHz (cap 16 000) 2 x 32 000 + 8 = 64 008 (fp32 row 128 000, half spectra 131 080, fp32 spectra only 262 144,
+ * rows and spectra 390 144); 44.1 kHz (cap 44 100) 176 408 (fp32 row 352 800, half spectra 393 244).  Rows are not padded to whole
+ * partition blocks as the spectral forms are.
+ * Accuracy (a property of the FORMAT, measured on a float64 model on the CPU - tests/rir16_ref.py: direct convolution of synthetic
+ * clips with synthetic RIRs put through the rule above, against the same RIRs unquantised; 16 kHz at 9 000 / 16 000 taps and
+ * 44.1 kHz at 9 000 / 44 100 taps, entries scaled by 1, 32 768 and 1e-6): the waveform moves by 1.7-2.3e-4 of its peak, the pooled
+ * log1p spectrogram by 0.4-1.8e-4 (INTEGRATION.md "Half-precision time-domain rows") - outside the library's 1e-4 parity budget,
+ * which is why the form is never a default.
+ * Producers: ss_rir_rows16_f32 (a planar fp32 device bank -> its half form, entry r to entry r; k_rows_half) and
+ * ss_bank_scatter_rows16_f32 (staged rows, the contract of ss_bank_scatter_rows_f32; below).  Both give the same bits for the same rows.
+ * Consumers (k_conv<.., HALF>: only the loads in front of the first FFT pass differ, so the results equal those of the fp32
+ * entries fed float(q) * rscale):
+ *   ss_fftconv_binaural_rir16_f32   every shape ss_fftconv_binaural_f32 serves on a planar bank without SS_FLAG_CROSSFADE;
+ *   ss_audio_obs_rir16_f32          the one-launch fused form, 257 <= out_len <= kB (and at most 26 pooled blocks); `audiogoal` may
+ *                                   be NULL.  Longer rows: ss_fftconv_binaural_rir16_f32 + ss_spectrogram_f32 (what a context does).
+ * Not served: SS_FLAG_CROSSFADE, length buckets, a one-launch log-mel form, the fused 44.1 / 48 kHz row kernels, the in-call
+ * loaders.  SS_EINVAL before a device is touched: NULL halves or scales, a base that is not 4-byte aligned, odd rir_cap or
+ * rir_cap < 2, more than 16 partition blocks, SS_FLAG_CROSSFADE, out_len outside the fused entry's range, a bad pad_mode, a NULL
+ * required output.  n_units == 0 (n_entries == 0) returns 0. */
+int ss_rir_rows16_f32(const float* rir, void* rir16_out, float* rscale_out, int n_entries, long long rir_unit_stride,
+                      int rir_chan_stride, int rir_cap, void* stream);
+int ss_fftconv_binaural_rir16_f32(const float* spec, const void* rir16, const float* rscale, const int* rir_len,
+                                  const int* unit_desc, float* out, int n_units, int rir_cap, int n_valid, int out_len, int flags,
+                                  void* stream);
+int ss_audio_obs_rir16_f32(const float* spec, const void* rir16, const float* rscale, const int* rir_len, const int* unit_desc,
+                           float* audiogoal, float* spectrogram, int n_units, int rir_cap, int n_valid, int out_len, int pad_mode,
+                           int flags, void* stream);
+
 /* The same for rows of 2 or 3 partition blocks (kB < out_len <= 3 kB: 44.1 / 48 kHz, the reference's Replica rate; EXTENSION):
  * the log-mel form of the fused row kernels (k_obs_rows / k_obs_blocks), the STFT phase behind every output block emits the
  * frames it completes.  Arguments and outputs as ss_audio_obs_logmel_f32 / _spec_f32 (which keep refusing rows longer than kB);
@@ -492,6 +528,16 @@ int ss_ctx_set_rir_spectra16(ss_ctx* ctx, const void* hspec16, const float* hsca
  * ss_fftconv_binaural_spec16_f32.  Cross-faded steps are SS_EINVAL and leave no keys behind.  hspec16 = NULL unbinds.  The
  * in-call loaders serve the binding through ss_bank_scatter_spectra16_f32. */
 int ss_ctx_set_rir_spectra16_rows(ss_ctx* ctx, const void* hspec16, const float* hscale, int h_blocks);
+/* Half-precision time-domain rows as the context's bank ("Half-precision time-domain rows" above).  Replaces ANY earlier binding
+ * and is replaced by every other bank call; while it is bound ss_ctx_set_rir_spectra / _spectra16 / _spectra16_rows with a bank are
+ * SS_EINVAL.  rir16 = NULL unbinds.  Steps of one-block rows (257 <= sampling_rate <= kB) take the fused half kernels, every longer
+ * row (44.1 / 48 kHz) the half convolution into the caller's waveform buffer - or the context's hand-over buffer - and the
+ * spectrogram kernel over it; log-mel steps render into the context's waveform scratch.  A cross-faded step is SS_EINVAL and
+ * leaves no keys behind.  The in-call loaders do not serve this form: ss_ctx_load_rir_files returns 1,
+ * ss_ctx_observe_requests_load reports the misses (the caller scatters with ss_bank_scatter_rows16_f32 and calls again).  The pose
+ * memo, the overlap mode and the column / request entries run on it unchanged.  SS_EINVAL, nothing changed: the bank refusals of
+ * the stateless entries, rir_len == NULL. */
+int ss_ctx_set_rir_bank16(ss_ctx* ctx, const void* rir16, const float* rscale, const int* rir_len, int rir_cap);
 /* The bank as length buckets (see ss_rir_bucket; replaces the two calls above for such banks; the descriptor array is copied,
  * the device pointers are borrowed).  Call again whenever a bucket is (re)allocated. */
 int ss_ctx_set_rir_buckets(ss_ctx* ctx, const ss_rir_bucket* buckets, int n_buckets, const int* rir_len);
@@ -853,6 +899,13 @@ int ss_bank_scatter_spectra_f32(const float* staged, long long staged_row_stride
 /* ... into a HALF bank (fp16 spectra + scales, "Half-precision spectral bank"): same staging rules, same lengths table. */
 int ss_bank_scatter_spectra16_f32(const float* staged, long long staged_row_stride, int planar, const int* slots, const int* lens,
                                   int n, void* hspec16, float* hscale, int h_blocks, int* bank_len, void* stream);
+/* ... and into a bank of HALF-PRECISION TIME-DOMAIN ROWS ("Half-precision time-domain rows"): the contract of
+ * ss_bank_scatter_rows_f32 - wav-layout rows in pinned host or device memory (pageable: SS_EINVAL), 8-byte aligned, an even
+ * staged_row_stride >= 2 cap - into halves + scale of both ears in entry slots[i], +0 halves behind the row's length up to `cap`,
+ * lens[i] (clamped to [0, cap]) into bank_len[slots[i]] (may be NULL).  Bit-identical to ss_rir_rows16_f32 over the rows
+ * ss_bank_scatter_rows_f32 would have written.  One launch; a row is read twice (maxima, then quantisation), never staged. */
+int ss_bank_scatter_rows16_f32(const float* staged, long long staged_row_stride, const int* slots, const int* lens, int n,
+                               void* rir16, float* rscale, int cap, int* bank_len, void* stream);
 /* n HOST arrays -> n rows of a (pinned) staging block: row i = src[i][0 .. n_floats[i]) followed by zeros up to row_floats,
  * rows row_stride floats apart, on up to n_threads plain threads.  The live RIRs of a SoundSpaces 2.0 step (one new RIR per
  * env and step from the ray tracer, soundspaces/continuous_simulator.py:419) travel to the bank this way: one block, one

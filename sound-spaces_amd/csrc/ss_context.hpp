@@ -79,6 +79,8 @@ struct Context {
     const float* hspec = nullptr; // spectral form of the same bank (optional, borrowed)
     const float* hscale = nullptr; // != nullptr: hspec holds a HALF bank (fp16 spectra), these are its per-block scales (borrowed)
     int h_blocks = 0;
+    const void* rir16 = nullptr;   // half-precision time-domain rows (ss_ctx_set_rir_bank16; borrowed): rir / hspec / buckets are unset then
+    const float* rscale = nullptr; // ... and their scales, one per (entry, ear)
     std::vector<ss_rir_bucket> buckets;   // length-bucketed bank (ss_ctx_set_rir_buckets); empty: the single bank above
     std::vector<ss_spec_bucket> spec_buckets;   // ... without time-domain rows (ss_ctx_set_rir_spec_buckets): rir / hspec are NULL then
     bool spec_buckets_rows = false;             // ... half ones bound for rows of 2 or 3 blocks (ss_ctx_set_rir_spec_buckets_rows)

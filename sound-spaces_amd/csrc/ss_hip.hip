@@ -209,6 +209,32 @@ int launch_conv(ssk::ConvParams p, int n_units, int nb_y, int flags, int n_cus, 
     return hip_err(hipGetLastError());
 }
 
+// ---- half-precision time-domain rows (include/ss_hip.h "Half-precision time-domain rows") ----------------------------------------
+// The launch body of launch_conv for a bank of fp16 rows + one scale per (entry, ear): the same decisions (loop-free kernel for
+// one-block rows without a distractor term, unit table when the host knows the descriptors, rows split over idle CUs, XCD map),
+// k_conv<.., HALF> for every launch - no cross-fade, no wide form, no persistent row kernel.
+template <bool FUSE>
+int launch_conv16(ssk::ConvParams p, const ssk::RowScale<true>& rs, int n_units, int nb_y, int flags, int n_cus, const LaunchEnv& env) {
+    const hipStream_t st = env.st;
+    if (nb_y < 1 || nb_y > 3 || (FUSE && nb_y != 1) || (flags & SS_FLAG_CROSSFADE)) return SS_EINVAL;
+    p.nb_y = nb_y;
+    p.parts_log2 = FUSE ? parts_log2_for(2 * n_units, n_cus, env.share) : 0;
+    const bool simple = (flags & SS_FLAG_NO_DISTRACTOR) && nb_y == 1 && p.rir_cap <= ssk::kB;
+    const dim3 grid((2 * n_units) << p.parts_log2, nb_y), block(ssk::kT);
+    if (simple) {
+        ssk::UnitTab<true> ut;
+        if (fill_unit_tab(ut, env, n_units))
+            hipLaunchKernelGGL((ssk::k_conv<FUSE, true, false, true, false, false, true>), grid, block, 0, st, p, ut, rs);
+        else hipLaunchKernelGGL((ssk::k_conv<FUSE, true, false, false, false, false, true>), grid, block, 0, st, p, ssk::UnitTab<false>(), rs);
+    } else hipLaunchKernelGGL((ssk::k_conv<FUSE, false, false, false, false, false, true>), grid, block, 0, st, p, ssk::UnitTab<false>(), rs);
+    return hip_err(hipGetLastError());
+}
+
+// the arguments every half-rows entry refuses before a device is touched
+inline bool rows16_bank_ok(const void* rir16, const float* rscale, int cap) {
+    return rir16 && rscale && !(reinterpret_cast<size_t>(rir16) & 3) && cap >= 2 && !(cap & 1) && (cap + ssk::kB - 1) / ssk::kB <= 16;
+}
+
 // ---- k_obs_rows: fused observation for rows longer than one partition block -------------------------------------
 // The kernel's workgroups keep the block spectra of the row they are rendering in a private stash (see k_obs_rows).
 // Launches on ONE stream run one after the other, so the stash is owned by (device, stream): two streams never share
@@ -716,7 +742,14 @@ struct Bank {
     const ss_spec_bucket* sbk = nullptr;    // ... or hold spectra only, fp32 or half
     int n_buckets = 0;
     bool sbk_rows = false;                  // half `sbk` that also serves rows of 2 or 3 blocks (the *_rows_spec16_buckets entries)
+    const void* rir16 = nullptr;            // half-precision time-domain rows [entries][2][cap] + ...
+    const float* rscale = nullptr;          // ... one scale per (entry, ear); nothing else is set then but `cap`
 };
+inline Bank rows16_bank(const void* rir16, const float* rscale, int cap) {
+    Bank b;
+    b.rir16 = rir16; b.rscale = rscale; b.cap = cap;
+    return b;
+}
 inline Bank rows_bank(const float* rir, long long us, int cs, int es, int cap) {
     Bank b;
     b.rir = rir; b.us = us; b.cs = cs; b.es = es; b.cap = cap;
@@ -777,7 +810,12 @@ int render(const Bank& b, bool spectral, ssroute::Launch want, const float* spec
     bool half = b.hscale != nullptr;
     int nbh_max = 1;
     if (n_units < 0) return SS_EINVAL;
-    if (b.sbk) {                                            // (no rows anywhere: a cross-fade has nothing to read)
+    const bool rows16 = b.rir16 || b.rscale;
+    if (rows16) {                                           // (one allocation of half rows: no cross-fade, no log-mel form)
+        if (!rows16_bank_ok(b.rir16, b.rscale, b.cap) || (flags & SS_FLAG_CROSSFADE) || spectral) return SS_EINVAL;
+        if (want != Launch::kConv && want != Launch::kObs) return SS_EINVAL;
+        nbh_max = (b.cap + ssk::kB - 1) / ssk::kB;
+    } else if (b.sbk) {                                            // (no rows anywhere: a cross-fade has nothing to read)
         if (spec_buckets_check(b.sbk, b.n_buckets, &half, &nbh_max) || (flags & SS_FLAG_CROSSFADE)) return SS_EINVAL;
         spectral = true;
     } else if (b.bk) {
@@ -806,6 +844,7 @@ int render(const Bank& b, bool spectral, ssroute::Launch want, const float* spec
             // (... but through the entries of their own: Bank::sbk_rows)
             if (b.sbk && half && !b.sbk_rows && (out_len > ssk::kB || t4_of(out_len) > 26)) return SS_EINVAL;
             chain = ssroute::obs_chain(out_len, n_valid, nbh_max, flags, spectral, audiogoal != nullptr, route_switches());
+            if (rows16 && chain != Chain::kFused) chain = Chain::kTwo;     // half rows: no wide / row kernels
             if (chain == Chain::kTwo && !audiogoal) return SS_EINVAL;      // cross-faded long rows hand over through HBM/L2
             break;
         case Launch::kMelOneBlock:
@@ -825,7 +864,7 @@ int render(const Bank& b, bool spectral, ssroute::Launch want, const float* spec
     }
     ssk::ConvParams p;
     int n_cus = 1;
-    const bool rows = !spectral || b.bk;                    // (length buckets that keep rows always describe them)
+    const bool rows = (!spectral || b.bk) && !rows16;       // (length buckets that keep rows always describe them)
     int rc = rows ? fill_conv(p, &n_cus, spec, b.rir, rir_len, unit_desc, b.us, b.cs, b.es, b.cap, n_valid, out_len)
                   : fill_conv(p, &n_cus, spec, nullptr, rir_len, unit_desc, 0, 0, 1, 0, n_valid, out_len, false);
     if (rc) return rc;
@@ -838,6 +877,18 @@ int render(const Bank& b, bool spectral, ssroute::Launch want, const float* spec
     if (rc) return rc;
     p.out = audiogoal;
     const int nb_y = n_valid == 0 ? 1 : (n_valid + ssk::kB - 1) / ssk::kB;
+    if (rows16) {
+        const ssk::RowScale<true> rs{static_cast<const ssk::h16x2*>(b.rir16), b.rscale};
+        p.rir_cap = b.cap;
+        if (want == Launch::kObs && chain == Chain::kFused) {
+            p.pad_mode = pad_mode;
+            p.sgram = spectrogram;
+            return launch_conv16<true>(p, rs, n_units, 1, flags, n_cus, env);
+        }
+        rc = launch_conv16<false>(p, rs, n_units, nb_y, flags, n_cus, env);
+        if (rc || want == Launch::kConv) return rc;
+        return spectrogram_of_rows(audiogoal, spectrogram, n_units, out_len, n_valid, pad_mode, env.st);
+    }
     if (want == Launch::kConv) return launch_conv_any<false>(p, hs, spectral, n_units, nb_y, flags, n_cus, env);
     if (want == Launch::kObs && chain == Chain::kTwo) {     // (pad_mode, sgram: as the convolution alone leaves them)
         rc = launch_conv_any<false>(p, hs, spectral, n_units, nb_y, flags, n_cus, env);
@@ -1381,6 +1432,27 @@ int ss_audio_obs_logmel_rows_spec16_f32(const float* spec, const void* hspec16, 
                   n_units, n_valid, out_len, pad_mode, flags, stateless(stream));
 }
 
+// ---- half-precision time-domain rows: the stateless entries ---------------------------------------------------------------
+// ss_fftconv_binaural_f32 on a planar bank of half rows (k_conv<.., HALF>: loop-free or loop kernel, as launch_conv16 decides)
+int ss_fftconv_binaural_rir16_f32(const float* spec, const void* rir16, const float* rscale, const int* rir_len, const int* unit_desc,
+                                  float* out, int n_units, int rir_cap, int n_valid, int out_len, int flags, void* stream) {
+    if (n_units == 0) return 0;
+    if (!rows16_bank_ok(rir16, rscale, rir_cap) || (flags & SS_FLAG_CROSSFADE)) return SS_EINVAL;
+    return render(rows16_bank(rir16, rscale, rir_cap), false, Launch::kConv, spec, rir_len, unit_desc, out, nullptr, nullptr, n_units,
+                  n_valid, out_len, SS_PAD_REFLECT, flags, stateless(stream));
+}
+
+// ss_audio_obs_f32's one-launch fused form (the rows the chain calls kFused) from half rows; `audiogoal` may be NULL
+int ss_audio_obs_rir16_f32(const float* spec, const void* rir16, const float* rscale, const int* rir_len, const int* unit_desc,
+                           float* audiogoal, float* spectrogram, int n_units, int rir_cap, int n_valid, int out_len, int pad_mode,
+                           int flags, void* stream) {
+    if (n_units == 0) return 0;
+    if (!rows16_bank_ok(rir16, rscale, rir_cap) || (flags & SS_FLAG_CROSSFADE)) return SS_EINVAL;
+    if (out_len < ssk::kNfft / 2 + 1 || out_len > ssk::kB || t4_of(out_len) > 26) return SS_EINVAL;
+    return render(rows16_bank(rir16, rscale, rir_cap), false, Launch::kObs, spec, rir_len, unit_desc, audiogoal, spectrogram, nullptr,
+                  n_units, n_valid, out_len, pad_mode, flags, stateless(stream));
+}
+
 // ---- pose memo: the row copies (k_memo_rows) ---------------------------------------------------------------------------
 static bool memo_io_ok(const ss_memo_io* io, int n_io) {
     if (!io || n_io < 1 || n_io > ssk::kMemoArrays) return false;
@@ -1539,6 +1611,7 @@ int ss_ctx_set_rir_bank(ss_ctx* h, const float* rir, const int* rir_len, long lo
     const int nbh_new = rir_cap > 0 ? ssctx::ceil_div(rir_cap, c.kb) : 1;
     c.rir = rir; c.rir_len = rir_len; c.rir_us = unit_stride; c.rir_cs = chan_stride; c.rir_es = elem_stride;
     c.rir_cap = rir_cap;
+    c.rir16 = nullptr; c.rscale = nullptr;                     // (half rows, ss_ctx_set_rir_bank16: replaced like any other bank)
     // the spectral form described the PREVIOUS bank (its entries, its capacity): back to the time-domain kernels until
     // ss_ctx_set_rir_spectra is called for this one (a swapped / grown bank kept rendering the old spectra)
     c.hspec = nullptr;
@@ -1567,7 +1640,7 @@ int ss_ctx_set_rir_spectra(ss_ctx* h, const float* hspec, int h_blocks) {
     if (!h || (hspec && h_blocks < 1)) return SS_EINVAL;
     ssctx::Context& c = h->c;
     if (hspec && h_blocks != (c.rir_cap > 0 ? ssctx::ceil_div(c.rir_cap, c.kb) : 1)) return SS_EINVAL;
-    if (hspec && (c.hscale || !c.spec_buckets.empty())) return SS_EINVAL;     // a half bank (ss_ctx_set_rir_spectra16) or spectral buckets are bound: one form at a time
+    if (hspec && (c.hscale || !c.spec_buckets.empty() || c.rir16)) return SS_EINVAL;     // a half bank (ss_ctx_set_rir_spectra16) or spectral buckets are bound: one form at a time
     c.hspec = hspec;
     c.hscale = nullptr;
     c.h_blocks = hspec ? h_blocks : 0;
@@ -1586,7 +1659,7 @@ int ss_ctx_set_rir_spectra16(ss_ctx* h, const void* hspec16, const float* hscale
         return 0;
     }
     if (!hscale || h_blocks < 1 || (reinterpret_cast<size_t>(hspec16) & 7)) return SS_EINVAL;
-    if (c.out_len > c.kb || c.rir || !c.buckets.empty() || !c.spec_buckets.empty() || !c.rir_len || (c.hspec && !c.hscale)) return SS_EINVAL;
+    if (c.out_len > c.kb || c.rir || c.rir16 || !c.buckets.empty() || !c.spec_buckets.empty() || !c.rir_len || (c.hspec && !c.hscale)) return SS_EINVAL;
     if (h_blocks != (c.rir_cap > 0 ? ssctx::ceil_div(c.rir_cap, c.kb) : 1)) return SS_EINVAL;
     c.hspec = static_cast<const float*>(hspec16);              // (read as halves wherever hscale is set)
     c.hscale = hscale;
@@ -1606,11 +1679,28 @@ int ss_ctx_set_rir_spectra16_rows(ss_ctx* h, const void* hspec16, const float* h
     }
     if (!hscale || h_blocks < 1 || h_blocks > 16 || (reinterpret_cast<size_t>(hspec16) & 7)) return SS_EINVAL;
     if (c.out_len <= c.kb || c.out_len > 3 * c.kb) return SS_EINVAL;
-    if (c.rir || !c.buckets.empty() || !c.spec_buckets.empty() || !c.rir_len || (c.hspec && !c.hscale)) return SS_EINVAL;
+    if (c.rir || c.rir16 || !c.buckets.empty() || !c.spec_buckets.empty() || !c.rir_len || (c.hspec && !c.hscale)) return SS_EINVAL;
     if (h_blocks != (c.rir_cap > 0 ? ssctx::ceil_div(c.rir_cap, c.kb) : 1)) return SS_EINVAL;
     c.hspec = static_cast<const float*>(hspec16);              // (read as halves wherever hscale is set)
     c.hscale = hscale;
     c.h_blocks = h_blocks;
+    return 0;
+}
+
+// Half-precision time-domain rows as the context's bank (include/ss_hip.h "Half-precision time-domain rows"): replaces whatever
+// bank was bound (rows, spectra, buckets), rir16 = NULL unbinds.  One-block rows take the fused half kernels, longer ones the half
+// convolution + k_spectrogram, log-mel steps the waveform scratch; a cross-faded step is refused (ss_route.hpp, Bank::rows16).
+int ss_ctx_set_rir_bank16(ss_ctx* h, const void* rir16, const float* rscale, const int* rir_len, int rir_cap) {
+    if (!h) return SS_EINVAL;
+    if (!rir16) {
+        h->c.rir16 = nullptr; h->c.rscale = nullptr;
+        return 0;
+    }
+    if (!rir_len || !rows16_bank_ok(rir16, rscale, rir_cap)) return SS_EINVAL;
+    const int rc = ss_ctx_set_rir_bank(h, nullptr, rir_len, 0, 0, 1, rir_cap);      // (window keys, pool, every other form: as for any new bank)
+    if (rc) return rc;
+    h->c.rir16 = rir16;
+    h->c.rscale = rscale;
     return 0;
 }
 
@@ -1721,6 +1811,7 @@ static ssroute::Bank route_bank_of(const ssctx::Context& c) {
     b.spec_buckets_half_rows = b.spec_buckets_half && c.spec_buckets_rows;
     b.rir_cap = c.rir_cap;
     b.h_blocks = c.h_blocks;
+    b.rows16 = c.rir16 != nullptr;
     return b;
 }
 
@@ -1728,6 +1819,7 @@ static ssroute::Bank route_bank_of(const ssctx::Context& c) {
 static Bank bank_of(const ssctx::Context& c) {
     if (!c.spec_buckets.empty()) return spec_buckets_bank(c.spec_buckets.data(), static_cast<int>(c.spec_buckets.size()), c.spec_buckets_rows);
     if (!c.buckets.empty()) return buckets_bank(c.buckets.data(), static_cast<int>(c.buckets.size()));
+    if (c.rir16) return rows16_bank(c.rir16, c.rscale, c.rir_cap);
     Bank b = rows_bank(c.rir, c.rir_us, c.rir_cs, c.rir_es, c.rir_cap);
     b.hspec = c.hspec; b.hscale = c.hscale; b.h_blocks = c.h_blocks;
     return b;
@@ -2074,7 +2166,7 @@ static int ctx_observe_any(ss_ctx* h, const ss_units* units, int n, float* audio
         return SS_EINVAL;
     if (n == 0) return 0;
     ssctx::Context& c = h->c;
-    if ((!c.rir && !c.hspec && c.buckets.empty() && c.spec_buckets.empty()) || !c.rir_len || !c.src_dev) return SS_EINVAL;
+    if ((!c.rir && !c.hspec && !c.rir16 && c.buckets.empty() && c.spec_buckets.empty()) || !c.rir_len || !c.src_dev) return SS_EINVAL;
     const bool sg_late = features_take_spectrogram(f, audiogoal, spectrogram);
     if (c.n_lanes <= 1) {
         if (mel_only) return ctx_observe_on(h, units, n, nullptr, spectrogram, stream, -1, f);
@@ -2614,6 +2706,7 @@ int ss_ctx_load_rir_files(ss_ctx* h, ss_miss_loader* ld, const char* const* path
     ld->n_loaded = 0; ld->n_evicted = 0;
     if (k == 0) return 0;
     ssctx::Context& c = h->c;
+    if (c.rir16) return 1;                                     // half rows: not served here (the caller's own path scatters them)
     const bool spec_only = !ld->bank && !c.rir && c.hspec && c.buckets.empty();     // spectral-only bank (see loader_load_paths)
     if (!ld->free_slots || (!ld->bank && !spec_only) || !ld->dev_len || !ld->host_len || !ld->clipped || !ld->stage || !ld->stage_slot ||
         !ld->stage_len || !ld->loaded_slot || !ld->loaded_frames || ld->cap < 2 || (ld->cap & 1) || c.rir != ld->bank)
@@ -2636,7 +2729,7 @@ int ss_ctx_observe_requests_load(ss_ctx* h, const long long* recs, int n, ss_req
         bool any_dis = false;
         for (int i = 0; i < n && !any_dis; ++i) any_dis = recs[static_cast<size_t>(i) * SS_REQ_WORDS] == 0 && recs[static_cast<size_t>(i) * SS_REQ_WORDS + 6] >= 0;
         const bool spectral = c.hspec && !(c.policy.spectral_max_units > 0 && c.rir && c.out_len <= ssk::kB && n > c.policy.spectral_max_units && !any_dis);
-        if (!ld || !miss_out || c.rir != ld->bank) return 0;
+        if (!ld || !miss_out || c.rir != ld->bank || c.rir16) return 0;     // (half rows: the misses are reported, never served here)
         std::vector<int> miss(miss_out, miss_out + (*n_miss < n ? *n_miss : n));
         rc = serve_pose_misses(h, recs, n, tb, ld, miss.data(), static_cast<int>(miss.size()), static_cast<hipStream_t>(stream), spectral);
         if (rc == 1) return 0;                                 // reported as ss_ctx_observe_requests reports it
@@ -2703,6 +2796,7 @@ int ss_ctx_set_rir_buckets(ss_ctx* h, const ss_rir_bucket* buckets, int n_bucket
     c.buckets.assign(buckets, buckets + n_buckets);
     c.spec_buckets.clear();
     c.rir = buckets[0].rir; c.rir_len = rir_len; c.rir_us = 2LL * buckets[0].cap; c.rir_cs = buckets[0].cap; c.rir_es = 1;
+    c.rir16 = nullptr; c.rscale = nullptr;
     c.rir_cap = hb_max * c.kb;                                 // planning depth: the longest bucket's blocks
     c.hspec = nullptr; c.hscale = nullptr; c.h_blocks = 0;
     if (hb_max != nbh_old) {                                   // the set of partition offsets per key changes
@@ -2820,6 +2914,7 @@ static int ctx_bind_spec_buckets(ss_ctx* h, const ss_spec_bucket* buckets, int n
     c.spec_buckets_rows = rows;
     c.buckets.clear();
     c.rir = nullptr; c.rir_len = rir_len; c.rir_us = 0; c.rir_cs = 0; c.rir_es = 1;
+    c.rir16 = nullptr; c.rscale = nullptr;
     c.rir_cap = hb_max * c.kb;                                 // planning depth: the longest bucket's blocks
     c.hspec = nullptr; c.hscale = nullptr; c.h_blocks = 0;
     if (hb_max != nbh_old) {                                   // the set of partition offsets per key changes
@@ -2971,4 +3066,41 @@ extern "C" int ss_rows_gather_f32(const float* const* src, const int* n_floats, 
     if (!src || !n_floats || !dst || n < 0 || row_floats < 0 || row_stride < row_floats) return SS_EINVAL;
     sswav::gather_rows(src, n_floats, n, dst, row_stride, row_floats, n_threads);
     return 0;
+}
+
+// ---- half-precision time-domain rows: the producers -----------------------------------------------------------------------
+// A planar fp32 device bank -> its half form, entry r to entry r (k_rows_half: one workgroup per (entry, ear))
+extern "C" int ss_rir_rows16_f32(const float* rir, void* rir16_out, float* rscale_out, int n_entries, long long rir_unit_stride,
+                                 int rir_chan_stride, int rir_cap, void* stream) {
+    if (n_entries == 0) return 0;
+    if (!rir || n_entries < 0 || rir_unit_stride < 0 || rir_chan_stride < 0 || !rows16_bank_ok(rir16_out, rscale_out, rir_cap))
+        return SS_EINVAL;
+    ssk::RowsHalfParams p;
+    p.rir = rir; p.rir16 = static_cast<ssk::h16x2*>(rir16_out); p.rscale = rscale_out;
+    p.unit_stride = rir_unit_stride; p.chan_stride = rir_chan_stride; p.cap = rir_cap;
+    for (int lo = 0; lo < n_entries; lo += 65535) {            // (grid.y limit)
+        const int m = n_entries - lo < 65535 ? n_entries - lo : 65535;
+        ssk::RowsHalfParams q = p;
+        q.rir += static_cast<size_t>(lo) * rir_unit_stride;
+        q.rir16 += static_cast<size_t>(lo) * rir_cap;          // (2 ears x cap / 2 pairs per entry)
+        q.rscale += static_cast<size_t>(lo) * 2;
+        hipLaunchKernelGGL(ssk::k_rows_half, dim3(2, m), dim3(256), 0, static_cast<hipStream_t>(stream), q);
+    }
+    return hip_err(hipGetLastError());
+}
+
+// Staged rows (wav layout, pinned host or device memory) -> halves + scales of a half-rows bank + their lengths, one launch
+// (k_scatter_rows16); the staging contract of ss_bank_scatter_rows_f32
+extern "C" int ss_bank_scatter_rows16_f32(const float* staged, long long staged_row_stride, const int* slots, const int* lens, int n,
+                                          void* rir16, float* rscale, int cap, int* bank_len, void* stream) {
+    if (n == 0) return 0;
+    if (!staged || !slots || !lens || n < 0 || !rows16_bank_ok(rir16, rscale, cap) || staged_row_stride < 2LL * cap) return SS_EINVAL;
+    if ((reinterpret_cast<size_t>(staged) & 7) || (staged_row_stride & 1)) return SS_EINVAL;      // a frame is one 8-byte load
+    for (const void* ptr : {static_cast<const void*>(staged), static_cast<const void*>(slots), static_cast<const void*>(lens)})
+        if (!device_accessible(ptr)) return SS_EINVAL;
+    ssk::ScatterRows16Params p;
+    p.staged = staged; p.slots = slots; p.lens = lens; p.rir16 = static_cast<ssk::h16x2*>(rir16); p.rscale = rscale;
+    p.bank_len = bank_len; p.staged_stride = staged_row_stride; p.cap = cap;
+    hipLaunchKernelGGL(ssk::k_scatter_rows16, dim3(n), dim3(256), 0, static_cast<hipStream_t>(stream), p);
+    return hip_err(hipGetLastError());
 }

@@ -1120,7 +1120,23 @@ __device__ __forceinline__ int row_slot(int b, int G, int on) {
 }
 
 // Time-domain row of bank entry ridx, ear ch: address, row capacity and element stride (wave-uniform).
-struct BankRow { const float* h; int cap, es; };
+struct BankRow { const float* h; int cap, es; static constexpr bool kHalf = false; };
+// Half-precision time-domain rows (include/ss_hip.h "Half-precision time-domain rows"): rir16 [entries][2][cap] IEEE halves,
+// planar, cap even, 4-byte aligned, zero behind each row's length; rscale [entries][2] fp32, one power of two per (entry, ear).
+// float(q) * scale - exact in fp32 - is the sample the forward FFT gets, so everything behind pass 1 is the fp32 kernels' code.
+// The pointers travel in a kernel argument of their own, passed to the HALF instantiations of k_conv only (as SpecScale is for
+// k_conv_spec): ConvParams keeps its size.  Of ConvParams' bank fields those kernels read rir_cap alone.
+typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
+template <bool HALF>
+struct RowScale { };
+template <>
+struct RowScale<true> { const h16x2* rir16; const float* rscale; };
+struct BankRow16 { const h16x2* h2; float scale; int cap; static constexpr bool kHalf = true; };
+__device__ __forceinline__ BankRow16 bank_row16(const RowScale<true>& rs, int cap, int ridx, int ch) {
+    const size_t row = (size_t)ridx * 2 + ch;
+    return BankRow16{rs.rir16 + row * (size_t)(cap >> 1), rs.rscale[row], cap};
+}
+__device__ __forceinline__ c32 row16_pair(h16x2 q, float scale) { return mk2((float)q.x * scale, (float)q.y * scale); }
 // BUCKETS = false: the launch's bank is ONE allocation (n_buckets == 1: the launcher checks) - the three bucket descriptors
 // (24 scalar registers) and the compare chains never enter the kernel (k_obs_rows: 81-118 -> SGPR spills)
 template <bool BUCKETS = true>
@@ -1152,10 +1168,9 @@ __device__ __forceinline__ BankSpec bank_spec(const ConvParams& p, int ridx, int
 }
 
 // forward FFT of RIR block i of one ear + multiply by the window spectrum `slot` -> acc (= or +=)
-template <bool ACCUMULATE, bool PREFETCH>
-__device__ __forceinline__ void conv_block(c32* lds, const ConvParams& p, const ThreadTw& tw, int t, const BankRow& br,
+template <bool ACCUMULATE, bool PREFETCH, class ROW = BankRow>
+__device__ __forceinline__ void conv_block(c32* lds, const ConvParams& p, const ThreadTw& tw, int t, const ROW& br,
                                            int L, int i, int slot, c32 (&acc)[2][8]) {
-    const float* h = br.h;
     // PREFETCH = issue the 8 window-spectrum loads (L2/MALL hits) at the start of pass 3 instead of at the item
     // stage, so their latency hides under pass 3.  (Issuing them before pass 1 was measured SLOWER, +1.2 us:
     // 128 KB of L2 reads queue ahead of the RIR's HBM loads on the in-order vmcnt path.)  Only the loop-free
@@ -1163,17 +1178,35 @@ __device__ __forceinline__ void conv_block(c32* lds, const ConvParams& p, const 
     const f32x4* sp = p.spec + (size_t)slot * (kSpecComplex / 2) + t;
     f32x4 sv[2][4];
     // bank rows are zero-padded to rir_cap, so the only bound is the row capacity (L is used for block counts)
-    const int lo = i * kB, es = br.es, cap = br.cap;
+    const int lo = i * kB, cap = br.cap;
     (void)L;
-    if (es == 1 && !(cap & 1) && !(reinterpret_cast<size_t>(h) & 7)) {       // planar, 8-byte aligned rows
-        const c32* h2 = reinterpret_cast<const c32*>(h + lo);
+    if constexpr (ROW::kHalf) {                                              // half rows: one 4-byte load per packed pair
+        const h16x2* h2 = br.h2 + (lo >> 1);
         const int m_end = (cap - lo) >> 1;
-        pass1_fwd<true>(lds, tw.p1, t, [&](int m) { return m < m_end ? ld_stream(h2 + m) : mk2(0.f, 0.f); });
+        const float sc = br.scale;
+        // the eight loads go out as one batch of raw words and are converted behind it: with the conversion inside the
+        // predicated load, each load is waited for on its own - eight HBM round trips in a row, 36.4 against 29.8 us per 5 units
+        // at 44.1 kHz (clamped instead of predicated, the eight addresses cost the fused kernel 5 spilled VGPRs)
+        const unsigned* u2 = reinterpret_cast<const unsigned*>(h2);
+        unsigned raw[8];
+#pragma unroll
+        for (int a = 0; a < 8; ++a) raw[a] = t + 1024 * a < m_end ? ld_stream(u2 + t + 1024 * a) : 0u;
+#pragma unroll
+        for (int a = 0; a < 8; ++a) SSK_OPAQUE1(raw[a]);         // (the conversions stay behind the batch)
+        pass1_fwd<true>(lds, tw.p1, t, [&](int m) { return row16_pair(__builtin_bit_cast(h16x2, raw[(m - t) >> 10]), sc); });
     } else {
-        pass1_fwd<true>(lds, tw.p1, t, [&](int m) {
-            const int n = lo + 2 * m;
-            return mk2(n < cap ? h[(size_t)n * es] : 0.f, n + 1 < cap ? h[(size_t)(n + 1) * es] : 0.f);
-        });
+        const float* h = br.h;
+        const int es = br.es;
+        if (es == 1 && !(cap & 1) && !(reinterpret_cast<size_t>(h) & 7)) {       // planar, 8-byte aligned rows
+            const c32* h2 = reinterpret_cast<const c32*>(h + lo);
+            const int m_end = (cap - lo) >> 1;
+            pass1_fwd<true>(lds, tw.p1, t, [&](int m) { return m < m_end ? ld_stream(h2 + m) : mk2(0.f, 0.f); });
+        } else {
+            pass1_fwd<true>(lds, tw.p1, t, [&](int m) {
+                const int n = lo + 2 * m;
+                return mk2(n < cap ? h[(size_t)n * es] : 0.f, n + 1 < cap ? h[(size_t)(n + 1) * es] : 0.f);
+            });
+        }
     }
     lds_barrier();
     pass2<false>(lds, tw.p2, t);
@@ -1433,9 +1466,13 @@ __device__ __forceinline__ void fused_stft_phase(c32* lds, const ConvParams& p, 
 // of that result (at most two packed pairs per thread) are kept in registers, then the row is convolved with the
 // current RIR (term 0) and the head of the row becomes prev*(fade-n)/fade + cur*n/fade.  One launch, and in the
 // fused kernel the spectrogram is taken from the blended row without it ever leaving the CU.
-template <bool FUSE, bool SIMPLE, bool XFADE = false, bool TAB = false, bool WIDE = false, bool MEL = false>
-__global__ __launch_bounds__(1024) void k_conv(ConvParams p, UnitTab<TAB, MEL> ut = UnitTab<TAB, MEL>()) {
+// HALF: the bank is fp16 rows + one scale per (entry, ear) (RowScale above), one allocation; only the loads in front of pass 1
+// differ - 4 bytes per packed pair, converted and multiplied by the wave-uniform scale.
+template <bool FUSE, bool SIMPLE, bool XFADE = false, bool TAB = false, bool WIDE = false, bool MEL = false, bool HALF = false>
+__global__ __launch_bounds__(1024) void k_conv(ConvParams p, UnitTab<TAB, MEL> ut = UnitTab<TAB, MEL>(),
+                                               RowScale<HALF> rs = RowScale<HALF>()) {
     static_assert(!(SIMPLE && XFADE), "the cross-fade needs the two-term loop kernel");
+    static_assert(!HALF || (!XFADE && !WIDE && !MEL), "half rows: the plain loop-free and loop kernels");
     static_assert(!MEL || (FUSE && !TAB), "log-mel: the fused kernels without a unit table (launched with parts_log2 = 0)");
     static_assert(!WIDE || (FUSE && !SIMPLE), "WIDE: fused loop kernel for rows of which only block 0 is rendered");
     static_assert(!TAB || SIMPLE, "the unit table serves the loop-free kernel");
@@ -1473,12 +1510,21 @@ __global__ __launch_bounds__(1024) void k_conv(ConvParams p, UnitTab<TAB, MEL> u
         if constexpr (TAB) ridx = ut.tab[kTabWords * unit]; else ridx = __builtin_amdgcn_readfirstlane(d[0]);
         bool active = false;
         if (ridx >= 0) {
-            const float* h = p.rir + (size_t)ridx * p.rir_unit_stride + (size_t)ch * p.rir_chan_stride;
+            const float* h = HALF ? nullptr : p.rir + (size_t)ridx * p.rir_unit_stride + (size_t)ch * p.rir_chan_stride;
             const int es = p.rir_elem_stride, cap = p.rir_cap;
-            const bool planar = es == 1 && !(cap & 1) && !(reinterpret_cast<size_t>(h) & 7);   // 8-byte aligned rows
+            const bool planar = HALF || (es == 1 && !(cap & 1) && !(reinterpret_cast<size_t>(h) & 7));   // 8-byte aligned rows
             // the row's address needs only ridx: its loads go out BEFORE the length / window words are waited for
             c32 hraw[8];
-            if (planar) {
+            h16x2 hq[HALF ? 8 : 1];
+            float sc = 1.f;
+            if constexpr (HALF) {                               // (the launcher checks: cap even, >= 2, 4-byte aligned base)
+                const size_t row16 = (size_t)ridx * 2 + ch;
+                const h16x2* h2 = rs.rir16 + row16 * (size_t)(cap >> 1);
+                const int m_end = cap >> 1;
+#pragma unroll
+                for (int a = 0; a < 8; ++a) hq[a] = ld_stream(h2 + min(t + 1024 * a, m_end - 1));     // clamped as below
+                sc = rs.rscale[row16];                          // wave-uniform: behind the row's loads
+            } else if (planar) {
                 const c32* h2 = reinterpret_cast<const c32*>(h);
                 const int m_end = cap >> 1;
 #pragma unroll
@@ -1499,7 +1545,10 @@ __global__ __launch_bounds__(1024) void k_conv(ConvParams p, UnitTab<TAB, MEL> u
                 ok = L > 0 && m_min <= 0 && m_min + m_cnt > 0;
             }
             if (ok) {
-                if (planar) {
+                if constexpr (HALF) {
+                    const int m_end = cap >> 1;
+                    pass1_fwd<true>(lds, tw.p1, t, [&](int m) { return m < m_end ? row16_pair(hq[(m - t) >> 10], sc) : mk2(0.f, 0.f); });
+                } else if (planar) {
                     const int m_end = cap >> 1;
                     pass1_fwd<true>(lds, tw.p1, t, [&](int m) { return m < m_end ? hraw[(m - t) >> 10] : mk2(0.f, 0.f); });
                 } else {
@@ -1546,7 +1595,10 @@ __global__ __launch_bounds__(1024) void k_conv(ConvParams p, UnitTab<TAB, MEL> u
                 present = true;
                 const int L = uniform_load(p.rir_len + ridx);
                 const int spec0 = dw.y, m_min = dw.z, m_cnt = dw.w;
-                const BankRow br = bank_row(p, ridx, ch);
+                auto br = [&] {
+                    if constexpr (HALF) return bank_row16(rs, p.rir_cap, ridx, ch);
+                    else return bank_row(p, ridx, ch);
+                }();
                 const int nbh = (L + kB - 1) / kB;
                 for (int i = 0; i < nbh; ++i) {
                     const int m = j - i;
@@ -2927,6 +2979,94 @@ __global__ __launch_bounds__(256) void k_scatter_rows(ScatterRowsParams p) {
     } else {
         dl[j] = v.x; dr[j] = v.y;
         if (j + 1 < p.cap) { dl[j + 1] = v.z; dr[j + 1] = v.w; }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Producers of the half-precision time-domain rows (RowScale above; the rule is stage_block_spectrum16's, per row instead of per
+// block spectrum):  mx = max |v| over the row;  mx = 0: halves +0, scale 1;  2^(e-1) <= mx < 2^e: q = RNE_fp16(v * 2^(15-e)),
+// scale 2^(e-15).  A maximum does not depend on the order it is taken in, so the two kernels below - and any grid - agree bit
+// for bit on the same samples.  Rows are finite.
+__device__ __forceinline__ float block_max256(float v, int t, float* part) { return block_reduce256<0>(v, t, part); }
+__device__ __forceinline__ int row16_exponent(float mx) {
+    int ex = 15;                                             // mx = 0: scale 1, every half +0
+    if (mx > 0.f) (void)frexpf(mx, &ex);
+    return ex;
+}
+__device__ __forceinline__ h16x2 row16_quantise(float a, float b, float mx, int ex) {
+    h16x2 q = {(_Float16)0.f, (_Float16)0.f};
+    if (mx > 0.f) {                                          // (float -> _Float16 is round-to-nearest-even)
+        q.x = (_Float16)ldexpf(a, 15 - ex);
+        q.y = (_Float16)ldexpf(b, 15 - ex);
+    }
+    return q;
+}
+
+// k_rows_half: a planar fp32 device bank -> its half form, entry r to entry r.  One workgroup of 256 threads per (entry, ear):
+// one max reduction over the row's `cap` samples, then one quantising pass (the row's second read comes from L2 for every
+// capacity the kernels serve).  Grid (2, entries of the launch).
+struct RowsHalfParams {
+    const float* rir;          // rir[r * unit_stride + c * chan_stride + j], zero behind each row's length
+    h16x2* rir16;              // [entries][2][cap / 2]
+    float* rscale;             // [entries][2]
+    long long unit_stride;
+    int chan_stride, cap;      // cap even
+};
+__global__ __launch_bounds__(256) void k_rows_half(RowsHalfParams p) {
+    __shared__ float part[4];
+    const int t = threadIdx.x, c = blockIdx.x;
+    const size_t r = blockIdx.y;
+    const float* row = p.rir + r * p.unit_stride + (size_t)c * p.chan_stride;
+    float mx = 0.f;
+    for (int j = t; j < p.cap; j += 256) mx = fmaxf(mx, fabsf(row[j]));
+    mx = block_max256(mx, t, part);
+    const int ex = row16_exponent(mx);
+    if (t == 0) p.rscale[r * 2 + c] = ldexpf(1.0f, ex - 15);
+    h16x2* o = p.rir16 + (r * 2 + c) * (size_t)(p.cap >> 1);
+    for (int m = t; m < (p.cap >> 1); m += 256) o[m] = row16_quantise(row[2 * m], row[2 * m + 1], mx, ex);
+}
+
+// k_scatter_rows16: the miss path's last hop for this form, the staging contract of k_scatter_rows: n staged rows in wav layout
+// ([frames][2], PINNED HOST or device memory) -> halves + scale of both ears in entry slots[i], +0 halves behind the row's own
+// length up to `cap`, the length into bank_len.  One workgroup of 256 threads per row, both ears at once (a frame is one 8-byte
+// load).  The row is READ TWICE - once for the two maxima, once to quantise: frames behind the length are never read, nothing
+// is staged (a 44.1 kHz row, 345 KiB, does not fit the 160 KiB of LDS; a row in pinned host memory crosses the link twice -
+// 128 KiB more per 16 kHz miss, against a staging buffer and a second launch).
+struct ScatterRows16Params {
+    const float* staged;       // [n][staged_stride] floats, row i = frames j < lens[i] as (L, R) pairs; 8-byte aligned, stride even
+    const int* slots;
+    const int* lens;
+    h16x2* rir16;              // [entries][2][cap / 2]
+    float* rscale;             // [entries][2]
+    int* bank_len;             // may be nullptr
+    long long staged_stride;
+    int cap;                   // even
+};
+__global__ __launch_bounds__(256) void k_scatter_rows16(ScatterRows16Params p) {
+    __shared__ float part[4];
+    const int t = threadIdx.x, i = blockIdx.x;
+    const size_t slot = (size_t)p.slots[i];
+    const int len = min(max(p.lens[i], 0), p.cap);
+    if (t == 0 && p.bank_len) p.bank_len[slot] = len;
+    const c32* src = reinterpret_cast<const c32*>(p.staged + (size_t)i * p.staged_stride);     // frame j = (L, R)
+    float ml = 0.f, mr = 0.f;
+    for (int j = t; j < len; j += 256) {
+        const c32 f = src[j];
+        ml = fmaxf(ml, fabsf(f.x));
+        mr = fmaxf(mr, fabsf(f.y));
+    }
+    ml = block_max256(ml, t, part);
+    mr = block_max256(mr, t, part);
+    const int el = row16_exponent(ml), er = row16_exponent(mr);
+    if (t == 0) { p.rscale[slot * 2] = ldexpf(1.0f, el - 15); p.rscale[slot * 2 + 1] = ldexpf(1.0f, er - 15); }
+    h16x2* ol = p.rir16 + slot * 2 * (size_t)(p.cap >> 1);
+    h16x2* orr = ol + (p.cap >> 1);
+    for (int m = t; m < (p.cap >> 1); m += 256) {
+        c32 f0 = mk2(0.f, 0.f), f1 = mk2(0.f, 0.f);
+        if (2 * m < len) f0 = src[2 * m];
+        if (2 * m + 1 < len) f1 = src[2 * m + 1];
+        ol[m] = row16_quantise(f0.x, f1.x, ml, el);
+        orr[m] = row16_quantise(f0.y, f1.y, mr, er);
     }
 }
 

@@ -110,6 +110,7 @@ struct Bank {
     int rir_cap = 0;                  // samples per row (length buckets: the deepest bucket's blocks * kB)
     int h_blocks = 0;                 // blocks of `spectra`
     bool spec_buckets_half_rows = false;      // half `spec_buckets` bound for rows of 2 or 3 blocks (ss_ctx_set_rir_spec_buckets_rows)
+    bool rows16 = false;              // half-precision time-domain rows (ss_ctx_set_rir_bank16): nothing else is bound then
 };
 
 struct Policies {
@@ -143,6 +144,24 @@ inline Route route_step(const Bank& b, int out_len, int n_valid, const Policies&
     Route r;
     const bool xfade = (flags & SS_FLAG_CROSSFADE) != 0;
     const bool bucketed = b.buckets || b.spec_buckets;
+    // half-precision time-domain rows: the fused half kernels for one-block rows, every longer row the half convolution into the
+    // caller's waveform buffer or the context's hand-over buffer and k_spectrogram over it (no wide / row kernels read halves);
+    // log-mel steps render into the waveform scratch; no cross-fade (refused as on the spectral-only banks)
+    if (b.rows16) {
+        if (xfade) {
+            r.refused = true;
+            return r;
+        }
+        r.wave_scratch = w.mel;
+        if (!w.spectrogram) {
+            r.launch = Launch::kConv;
+            return r;
+        }
+        r.launch = Launch::kObs;
+        r.chain = out_len <= kB && t4_of(out_len) <= 26 ? Chain::kFused : Chain::kTwo;
+        r.handover = r.chain == Chain::kTwo && !w.waveform && !r.wave_scratch;
+        return r;
+    }
     // a spectral-only bank (spectra bound, no rows: ss_ctx_set_rir_bank(ctx, NULL, ...) + ss_ctx_set_rir_spectra) cannot serve a
     // step whose route reads the time-domain rows (a cross-fade)
     // (spectral length buckets, ss_ctx_set_rir_spec_buckets, are such a bank)

@@ -27,7 +27,9 @@ EXPORTS = ("ss_block_len", "ss_spec_floats", "ss_version", "ss_init", "ss_source
            "ss_audio_obs_logmel_buckets_f32", "ss_audio_obs_logmel_spec_buckets_f32", "ss_ctx_set_logmel_buckets_policy",
            "ss_audio_obs_rows_spec16_buckets_f32", "ss_audio_obs_logmel_rows_spec16_buckets_f32", "ss_ctx_set_rir_spec_buckets_rows",
            "ss_memo_rows_f32", "ss_ctx_memo_enable", "ss_ctx_memo_reset", "ss_ctx_memo_stats", "ss_ctx_observe_sims_memo",
-           "ss_ctx_sims_memo_plan")
+           "ss_ctx_sims_memo_plan",
+           "ss_rir_rows16_f32", "ss_bank_scatter_rows16_f32", "ss_fftconv_binaural_rir16_f32", "ss_audio_obs_rir16_f32",
+           "ss_ctx_set_rir_bank16")
 # entries that return a size_t, not a status (EXPORTS: every `int ss_*` of include/ss_hip.h)
 EXPORTS_SIZE = ("ss_ctx_wave_scratch_bytes",)
 
@@ -197,6 +199,12 @@ def load() -> ctypes.CDLL:
     lib.ss_audio_obs_rows_spec16_buckets_f32.argtypes = lib.ss_audio_obs_spec_buckets_f32.argtypes
     lib.ss_audio_obs_logmel_rows_spec16_buckets_f32.argtypes = lib.ss_audio_obs_logmel_spec_buckets_f32.argtypes
     lib.ss_ctx_set_rir_spec_buckets_rows.argtypes = [vp, vp, c_int, vp]
+    # half-precision time-domain rows (fp16 rows + one scale per (entry, ear))
+    lib.ss_rir_rows16_f32.argtypes = [vp, vp, vp, c_int, c_ll, c_int, c_int, vp]
+    lib.ss_bank_scatter_rows16_f32.argtypes = [vp, c_ll, vp, vp, c_int, vp, vp, c_int, vp, vp]
+    lib.ss_fftconv_binaural_rir16_f32.argtypes = [vp, vp, vp, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, vp]
+    lib.ss_audio_obs_rir16_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, vp]
+    lib.ss_ctx_set_rir_bank16.argtypes = [vp, vp, vp, vp, c_int]
     # pose memo of the column path
     lib.ss_memo_rows_f32.argtypes = [vp, c_int, vp, c_int, c_int, vp]
     lib.ss_ctx_memo_enable.argtypes = [vp, c_int]

@@ -159,6 +159,28 @@ class AudioContext:
         _lib.check(getattr(self.lib, name)(self._h, hspec16.data_ptr(), hscale.data_ptr(), int(hspec16.shape[2])), name)
         self._spectra = (hspec16, hscale)
 
+    def set_rir_bank16(self, rir16, rscale, lengths) -> None:
+        """A bank of HALF-PRECISION TIME-DOMAIN ROWS (``RirStore(rows="half")``: float16 rir16 [R,2,cap], float32 scales rscale
+        [R,2], CUDA int32 lengths [R]; ss_ctx_set_rir_bank16).  Replaces any earlier binding; rir16 = None unbinds.  One-block rows
+        take the fused half kernels, longer ones the half convolution + the spectrogram kernel; the library refuses (SS_EINVAL)
+        cross-faded steps, and its in-call loaders report their misses instead of serving them."""
+        import torch
+        if rir16 is None:
+            _lib.check(self.lib.ss_ctx_set_rir_bank16(self._h, None, None, None, 0), "ss_ctx_set_rir_bank16")
+            self._bank = None
+            self._spectra = None
+            return
+        if rir16.dtype != torch.float16 or rscale.dtype != torch.float32 or not rir16.is_contiguous() or not rscale.is_contiguous():
+            raise ValueError("set_rir_bank16: contiguous float16 rows and float32 scales expected")
+        if rir16.dim() != 3 or rir16.shape[1] != 2 or tuple(rscale.shape) != tuple(rir16.shape[:2]):
+            raise ValueError("set_rir_bank16: rows [R, 2, cap] and one scale per (entry, ear) expected")
+        cap = int(rir16.shape[2])
+        _lib.check(self.lib.ss_ctx_set_rir_bank16(self._h, rir16.data_ptr(), rscale.data_ptr(), lengths.data_ptr(), cap),
+                   "ss_ctx_set_rir_bank16")
+        self._bank = (rir16, rscale, lengths)
+        self.rir_cap = cap
+        self._spectra = None
+
     def set_rir_buckets(self, bank, spectral: bool = False) -> None:
         """A length-bucketed bank (``ss_amd.renderer.BucketedRirBank``; include/ss_hip.h ``ss_ctx_set_rir_buckets``):
         steps whose units all sit in bucket 0 keep the loop-free kernel, long RIRs live in buckets of their own.

@@ -345,6 +345,84 @@ def audio_obs_spec_into(spec, hspec, rir_len, unit_desc, audiogoal, spectrogram_
                    "ss_audio_obs_spec_f32")
 
 
+# ---- half-precision time-domain rows ------------------------------------------------------------------------------
+def _chk_rows16(rir16: torch.Tensor, rscale: torch.Tensor) -> int:
+    """the bank argument of the *_rir16_* ops (include/ss_hip.h "Half-precision time-domain rows"): float16 [R,2,cap] with its
+    float32 scales [R,2].  -> cap"""
+    _chk(rir16, torch.float16, "rir16"); _chk(rscale, torch.float32, "rscale")
+    assert rir16.dim() == 3 and rir16.shape[1] == 2 and tuple(rscale.shape) == tuple(rir16.shape[:2])
+    assert rscale.device == rir16.device
+    return int(rir16.shape[2])
+
+
+def rir_rows16(rir_bank: torch.Tensor):
+    """Half form of a planar bank [R,2,cap] (``ss_rir_rows16_f32``, on the current stream) -> (float16 [R,2,cap], float32 scales
+    [R,2]): per (entry, ear) row q = fp16(v * 2^(15-e)) rounded to nearest even, scale = 2^(e-15).  Opt-in and LOSSY: the waveform
+    moves by about 2e-4 of its peak (include/ss_hip.h)."""
+    _chk(rir_bank, torch.float32, "rir_bank")
+    R, two, cap = rir_bank.shape
+    assert two == 2
+    rir16 = torch.zeros((R, 2, cap), dtype=torch.float16, device=rir_bank.device)
+    rscale = torch.zeros((R, 2), dtype=torch.float32, device=rir_bank.device)
+    if R:
+        with torch.cuda.device(rir_bank.device):
+            _lib.check(_lib.load().ss_rir_rows16_f32(rir_bank.data_ptr(), rir16.data_ptr(), rscale.data_ptr(), R, 2 * cap, cap, cap,
+                                                     _stream(rir_bank)), "ss_rir_rows16_f32")
+    return rir16, rscale
+
+
+def scatter_rows16_into(staged: torch.Tensor, slots: torch.Tensor, lens: torch.Tensor, n: int, rir16: torch.Tensor,
+                        rscale: torch.Tensor, bank_len: torch.Tensor) -> None:
+    """Rows [0, n) of a wav-layout staging block (float32 [*, >= cap, 2], pinned host or device memory) -> halves + scales of
+    entries slots[i] of the half-rows bank (rir16 [R,2,cap], rscale [R,2]) and lens[i] into bank_len[slots[i]]
+    (``ss_bank_scatter_rows16_f32``: one launch on the current stream of the bank's device).  slots / lens: int32, pinned host
+    or device memory.  The caller keeps all three alive and unchanged until the launch has run."""
+    cap = _chk_rows16(rir16, rscale); _chk(bank_len, torch.int32, "bank_len")
+    for t, dt, name in ((staged, torch.float32, "staged"), (slots, torch.int32, "slots"), (lens, torch.int32, "lens")):
+        if not (t.is_cuda or t.is_pinned()):
+            raise ValueError(f"{name}: pinned host or device memory expected (the kernel reads it in place)")
+        if t.dtype != dt or not t.is_contiguous():
+            raise ValueError(f"{name}: expected contiguous {dt}, got {t.dtype} contiguous={t.is_contiguous()}")
+    assert staged.dim() == 3 and staged.shape[2] == 2 and staged.shape[1] >= cap and staged.shape[0] >= n
+    if n == 0:
+        return
+    with torch.cuda.device(rir16.device):
+        _lib.check(_lib.load().ss_bank_scatter_rows16_f32(staged.data_ptr(), staged[0].numel(), slots.data_ptr(), lens.data_ptr(), n,
+                                                          rir16.data_ptr(), rscale.data_ptr(), cap, bank_len.data_ptr(),
+                                                          _stream(rir16)), "ss_bank_scatter_rows16_f32")
+
+
+def fftconv_binaural_rir16_into(spec, rir16, rscale, rir_len, unit_desc, out, n_valid: int, flags: int = 0) -> None:
+    """``fftconv_binaural_into`` from a bank of half rows (``ss_fftconv_binaural_rir16_f32``); no cross-fade."""
+    _chk(spec, torch.float32, "spec"); cap = _chk_rows16(rir16, rscale); _chk(rir_len, torch.int32, "rir_len")
+    _chk(unit_desc, torch.int32, "unit_desc"); _chk(out, torch.float32, "out")
+    N, two, out_len = out.shape
+    assert two == 2 and unit_desc.shape == (N, 8)
+    with torch.cuda.device(out.device):
+        _lib.check(_lib.load().ss_fftconv_binaural_rir16_f32(spec.data_ptr(), rir16.data_ptr(), rscale.data_ptr(), rir_len.data_ptr(),
+                                                             unit_desc.data_ptr(), out.data_ptr(), N, cap, n_valid, out_len, flags,
+                                                             _stream(spec)), "ss_fftconv_binaural_rir16_f32")
+
+
+def audio_obs_rir16_into(spec, rir16, rscale, rir_len, unit_desc, audiogoal, spectrogram_out, n_valid: int, out_len: int,
+                         pad_mode="reflect", flags: int = 0) -> None:
+    """The fused observation of one-block rows (257 <= out_len <= KB) from a bank of half rows (``ss_audio_obs_rir16_f32``);
+    ``audiogoal`` may be None."""
+    _chk(spec, torch.float32, "spec"); cap = _chk_rows16(rir16, rscale); _chk(rir_len, torch.int32, "rir_len")
+    _chk(unit_desc, torch.int32, "unit_desc"); _chk(spectrogram_out, torch.float32, "spectrogram_out")
+    N = unit_desc.shape[0]
+    assert tuple(spectrogram_out.shape) == (N,) + spectrogram_shape(out_len)
+    ag_ptr = None
+    if audiogoal is not None:
+        _chk(audiogoal, torch.float32, "audiogoal")
+        assert tuple(audiogoal.shape) == (N, 2, out_len)
+        ag_ptr = audiogoal.data_ptr()
+    with torch.cuda.device(spec.device):
+        _lib.check(_lib.load().ss_audio_obs_rir16_f32(spec.data_ptr(), rir16.data_ptr(), rscale.data_ptr(), rir_len.data_ptr(),
+                                                      unit_desc.data_ptr(), ag_ptr, spectrogram_out.data_ptr(), N, cap, n_valid,
+                                                      out_len, _PAD[pad_mode], flags, _stream(spec)), "ss_audio_obs_rir16_f32")
+
+
 # ---- log-mel observation in one launch (no waveform buffer) ---------------------------------------------------------
 def _obs_logmel_args(unit_desc, audiogoal, spectrogram_out, logmel_out, mel_start, mel_w, out_len):
     _chk(unit_desc, torch.int32, "unit_desc"); _chk(logmel_out, torch.float32, "logmel_out")

@@ -69,20 +69,31 @@ class RirBank:
 
     A HALF bank (``RirStore(spectral="half")``) is a spectral-only bank whose ``spectra`` are float16 with one float32 scale per
     (entry, ear, block) in ``scales`` ``[R, 2, ceil(cap/KB)]`` (include/ss_hip.h "Half-precision spectral bank"); ``spectra16``
-    is that tensor (None on every other bank).  Lossy: about 2e-4 of peak on the waveform."""
+    is that tensor (None on every other bank).  Lossy: about 2e-4 of peak on the waveform.
 
-    def __init__(self, data: torch.Tensor, lengths: torch.Tensor, cap: Optional[int] = None):
-        assert data.dim() == 3 and data.shape[1] == 2 and data.dtype == torch.float32 and data.is_contiguous()
+    A bank of HALF-PRECISION TIME-DOMAIN ROWS (``RirStore(rows="half")``; include/ss_hip.h "Half-precision time-domain rows"):
+    ``data`` is float16 ``[R, 2, cap]`` with one float32 scale per (entry, ear) in ``scales`` ``[R, 2]``, ``rows_half`` is True and
+    there are no spectra.  Half the bytes of the float32 rows; lossy in the same class (about 2e-4 of peak on the waveform)."""
+
+    def __init__(self, data: torch.Tensor, lengths: torch.Tensor, cap: Optional[int] = None, scales: Optional[torch.Tensor] = None):
+        assert data.dim() == 3 and data.shape[1] == 2 and data.is_contiguous()
+        assert data.dtype == (torch.float32 if scales is None else torch.float16)
+        assert scales is None or (scales.dtype == torch.float32 and tuple(scales.shape) == tuple(data.shape[:2]) and cap is None)
         assert lengths.dtype == torch.int32 and lengths.shape == (data.shape[0],)
         assert cap is None or data.shape[2] == 0, "cap is only given for a spectral-only bank (no rows)"
         self.data, self.lengths = data, lengths
         self.cap = int(data.shape[2]) if cap is None else int(cap)
         self.spectra: Optional[torch.Tensor] = None      # [R, 2, ceil(cap/KB), SPEC_FLOATS]: see build_spectra()
-        self.scales: Optional[torch.Tensor] = None       # [R, 2, ceil(cap/KB)] float32: `spectra` is float16 (a half bank)
+        # [R, 2, ceil(cap/KB)] float32: `spectra` is float16 (a half bank); [R, 2]: `data` is float16 (half time-domain rows)
+        self.scales: Optional[torch.Tensor] = scales
 
     @property
     def spectral_only(self) -> bool:
         return self.data.shape[2] == 0 and self.cap > 0
+
+    @property
+    def rows_half(self) -> bool:
+        return self.data.dtype == torch.float16
 
     @property
     def spectra16(self) -> Optional[torch.Tensor]:
@@ -94,6 +105,7 @@ class RirBank:
         the renderer runs k_conv_spec (no forward FFT; 2x the bytes per RIR).  For banks whose entries change after
         this call, call it again (or use RirStore(spectral=True), which keeps the two forms in step)."""
         assert not self.spectral_only, "a spectral-only bank has no rows to transform"
+        assert not self.rows_half, "a bank of half-precision rows has no spectral form"
         self.spectra = ops.rir_spectra(self.data)
         return self.spectra
 
@@ -423,7 +435,9 @@ class BatchedAudioRenderer:
         xfade = bool(plan.flags & ops.FLAG_CROSSFADE)
         spectral = (self.rirs.spectra is not None if not isinstance(self.rirs, BucketedRirBank) else bool(self.rirs.spectra)) \
             and not xfade and self._spectral_for(N, not (plan.flags & ops.FLAG_NO_DISTRACTOR))
-        self._check_rows(spectral)
+        self._check_rows(spectral, xfade)
+        if getattr(self.rirs, "rows_half", False):
+            return self._render_rows16(plan, want_audiogoal, audiogoal_out, spectrogram_out)
         need_ag = (want_audiogoal or audiogoal_out is not None or
                    (self.out_len > P.KB and not P.wide_one_block(self.out_len, self.n_valid, spectral)
                     and (xfade or self.n_valid <= P.KB or self.out_len > 3 * P.KB)))
@@ -451,18 +465,45 @@ class BatchedAudioRenderer:
                                self.out_len, self.pad_mode, flags=plan.flags)
         return (ag if (want_audiogoal or audiogoal_out is not None) else None), sg
 
-    def _check_rows(self, spectral: bool) -> None:
+    def _check_rows(self, spectral: bool, xfade: bool = False) -> None:
         if not spectral and getattr(self.rirs, "spectral_only", False):
             raise ValueError("this RIR bank keeps block spectra only (spectral-only): a cross-faded step, or one the "
                              "spectral_max_units policy sends to the time-domain rows, cannot be rendered from it")
+        if xfade and getattr(self.rirs, "rows_half", False):
+            raise ValueError("this RIR bank keeps half-precision rows: a cross-faded step cannot be rendered from it")
+
+    def _render_rows16(self, plan: Plan, want_audiogoal: bool, audiogoal_out, spectrogram_out):
+        """render() from a bank of half-precision time-domain rows: one fused launch for one-block rows, the half convolution
+        and the spectrogram kernel (two launches, the waveform handed over through memory) for every longer row."""
+        N = len(plan)
+        fused = self.out_len <= P.KB and self.spectrogram_shape[1] <= 26
+        ag = audiogoal_out
+        if ag is None and (want_audiogoal or not fused):
+            ag = torch.empty((N, 2, self.out_len), dtype=torch.float32, device=self.device)
+        sg = spectrogram_out
+        if sg is None:
+            sg = torch.empty((N,) + self.spectrogram_shape, dtype=torch.float32, device=self.device)
+        b = self.rirs
+        if fused:
+            ops.audio_obs_rir16_into(self._spec, b.data, b.scales, b.lengths, plan.desc, ag, sg, self.n_valid, self.out_len,
+                                     self.pad_mode, flags=plan.flags)
+        else:
+            ops.fftconv_binaural_rir16_into(self._spec, b.data, b.scales, b.lengths, plan.desc, ag, self.n_valid, flags=plan.flags)
+            ops.spectrogram_into(ag, sg, self.pad_mode)
+        return (ag if (want_audiogoal or audiogoal_out is not None) else None), sg
 
     def render_audiogoal(self, plan: Plan, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """AudioGoalSensor-only configurations (soundspaces/tasks/nav.py:37-60)."""
         if not isinstance(self.rirs, BucketedRirBank):
             self._check_rows(self.rirs.spectra is not None and not (plan.flags & ops.FLAG_CROSSFADE) and
-                             self._spectral_for(len(plan), not (plan.flags & ops.FLAG_NO_DISTRACTOR)))
+                             self._spectral_for(len(plan), not (plan.flags & ops.FLAG_NO_DISTRACTOR)),
+                             bool(plan.flags & ops.FLAG_CROSSFADE))
         if out is None:
             out = torch.empty((len(plan), 2, self.out_len), dtype=torch.float32, device=self.device)
+        if getattr(self.rirs, "rows_half", False):
+            ops.fftconv_binaural_rir16_into(self._spec, self.rirs.data, self.rirs.scales, self.rirs.lengths, plan.desc, out,
+                                            self.n_valid, flags=plan.flags)
+            return out
         if isinstance(self.rirs, BucketedRirBank):
             spectral = bool(self.rirs.spectra) and not (plan.flags & ops.FLAG_CROSSFADE) and \
                 self._spectral_for(len(plan), not (plan.flags & ops.FLAG_NO_DISTRACTOR))
@@ -516,10 +557,22 @@ class RirStore:
     pair: SURVEY 8(f)2), loaded and evicted together; ``slot()`` then returns the first slot of the group."""
 
     def __init__(self, slots: int, cap: int, device, truncate_to: Optional[int] = None, max_cap: int = 1 << 18,
-                 on_grow=None, group: int = 1, spectral: Union[bool, str] = False):
+                 on_grow=None, group: int = 1, spectral: Union[bool, str] = False, rows: Optional[str] = None):
         cap += cap & 1
         assert slots % group == 0
         self.device = torch.device(device)
+        # rows="half": the time-domain rows as float16 with one power-of-two float32 scale per (entry, ear) (RirBank.rows_half:
+        # bank.data is float16 [slots, 2, cap], bank.scales float32 [slots, 2]; include/ss_hip.h "Half-precision time-domain rows"):
+        # half the bytes of the plain rows, the cheapest form.  No float32 row is kept: like the spectral-only stores, every upload
+        # path stages the rows and quantises them on their way in (ss_bank_scatter_rows16_f32, one launch).  Lossy (about 2e-4 of
+        # peak on the waveform); no spectral form, no cross-fade, no CPU store.
+        if rows not in (None, "half"):
+            raise ValueError(f"RirStore: rows must be None or 'half', not {rows!r}")
+        self.rows_half = rows == "half"
+        if self.rows_half and spectral:
+            raise ValueError("RirStore(rows='half') keeps no spectral form: it does not go with spectral")
+        if self.rows_half and self.device.type != "cuda":
+            raise ValueError("RirStore(rows='half') needs a GPU device: the half-precision rows have no CPU fallback")
         # spectral="only": the block spectra and the lengths, NO time-domain rows (RirBank.spectral_only: bank.data is a zero-size
         # [slots, 2, 0] tensor).  Every upload path stages the rows and transforms them on their way in (ss_bank_scatter_spectra_f32,
         # one launch): 1.49x the entries of a both-forms store per byte of HBM at 16 kHz, 1.45x at 44.1 kHz.  Only the *_spec_*
@@ -536,6 +589,9 @@ class RirStore:
         lengths = torch.zeros((slots,), dtype=torch.int32, device=self.device)
         if self.spectral_only:
             self.bank = RirBank(torch.zeros((slots, 2, 0), dtype=torch.float32, device=self.device), lengths, cap=cap)
+        elif self.rows_half:                                    # (both arrays zero-initialised: an unused entry is exact zeros)
+            self.bank = RirBank(torch.zeros((slots, 2, cap), dtype=torch.float16, device=self.device), lengths,
+                                scales=torch.zeros((slots, 2), dtype=torch.float32, device=self.device))
         else:
             self.bank = RirBank(torch.zeros((slots, 2, cap), dtype=torch.float32, device=self.device), lengths)
         self.slots, self.cap, self.group = slots, cap, group
@@ -572,6 +628,7 @@ class RirStore:
         self.spectral = bool(spectral)
         self._stale = np.zeros((slots,), bool)
         self._stale_mark = not self.spectral_only               # (a spectral-only store's rows are transformed as they arrive)
+        self._staged_only = self.spectral_only or self.rows_half       # no float32 rows on the device: every upload is staged
         if spectral and self.device.type == "cuda":
             self.bank.spectra = torch.zeros((slots, 2, P.ceil_div(cap, P.KB), P.SPEC_FLOATS),
                                             dtype=torch.float16 if self.spectral_half else torch.float32, device=self.device)
@@ -657,6 +714,16 @@ class RirStore:
             if self.on_grow is not None:
                 self.on_grow(self.bank)
             return
+        if self.rows_half:                                       # the halves are copied, the new tail is +0; the scales stand
+            data = torch.zeros((self.slots, 2, new_cap), dtype=torch.float16, device=self.device)
+            data[:, :, :self.cap] = self.bank.data
+            self.bank = RirBank(data, self.bank.lengths, scales=self.bank.scales)
+            self.cap = new_cap
+            self._stage = None
+            self.grown += 1
+            if self.on_grow is not None:
+                self.on_grow(self.bank)
+            return
         data = torch.zeros((self.slots, 2, new_cap), dtype=torch.float32, device=self.device)
         data[:, :, :self.cap] = self.bank.data
         self.bank = RirBank(data, self.bank.lengths)
@@ -690,7 +757,7 @@ class RirStore:
         n = self._kept_len(r.shape[1])
         self._clipped[slot] = n < r.shape[1]
         self._ensure_cap(n)
-        if self.defer_uploads or self.spectral_only:
+        if self.defer_uploads or self._staged_only:
             # batched mode (AudioEngine): the row crosses PCIe with the step's other new rows, as ONE pinned block and ONE
             # H2D copy, when the engine flushes before its launch (flush_uploads).  SoundSpaces 2.0 hands every env a new
             # RIR every step (continuous_simulator.py:419): 128 single-row copies + 128 one-element length fills per step
@@ -770,11 +837,11 @@ class RirStore:
                 continue
             k = len(which)
             sl = [slots[j] for j in which]
-            if self.spectral_only:                             # staged rows -> block spectra + lengths, one launch per block
+            if self._staged_only:                              # staged rows -> block spectra (or half rows) + lengths, one launch per block
                 pidx, plen = self._pinned_meta("_flush_meta_" + blk_name, k)
                 pidx.numpy()[:k] = sl
                 plen.numpy()[:k] = lens[which]
-                self._scatter_spectra(getattr(self, blk_name), not transpose, pidx, plen, k)
+                self._scatter_form(getattr(self, blk_name), not transpose, pidx, plen, k)
                 self._dev_len[np.asarray(sl)] = lens[which]
                 continue
             dev_blk = getattr(self, blk_name)[:k].to(self.device, non_blocking=True)
@@ -983,14 +1050,15 @@ class RirStore:
                     torch.cuda.synchronize(self.device)          # (a scatter may still be reading the old block)
                 d["stage"] = torch.zeros((L.stage_rows, self.cap, 2), dtype=torch.float32, pin_memory=True)
                 L.stage = d["stage"].data_ptr()
-                if self.spectral_only:                           # (no rows: the library transforms the staged rows directly)
+                if self._staged_only:                            # (no rows: the library transforms the staged rows directly)
                     d["stage_desc"], L.stage_desc = None, None
                 else:
                     d["stage_desc"] = torch.zeros((L.stage_rows * 2 * P.ceil_div(self.cap, P.KB) * 5,), dtype=torch.int32,
                                                   pin_memory=True)
                     L.stage_desc = d["stage_desc"].data_ptr() if self.spectral else None
             d["bank"], d["cap"] = bank.data, self.cap
-            if self.spectral_only:                               # ss_miss_loader.bank = NULL: the context's spectra are written
+            if self._staged_only:                                # ss_miss_loader.bank = NULL: the context's spectra are written
+                # (half rows: the library's loaders do not serve them - they answer "not served" and load_files does the work)
                 L.bank, L.bank_unit_stride, L.bank_chan_stride, L.cap = None, 0, 0, self.cap
             else:
                 L.bank, L.bank_unit_stride, L.bank_chan_stride, L.cap = (bank.data.data_ptr(), bank.data.stride(0),
@@ -1139,11 +1207,11 @@ class RirStore:
                     stage_np[j * G + g, :, :n] = r[:, :n]
                     slots.append(sl + g)
             self._about_to_write()
-            if self.spectral_only:
+            if self._staged_only:
                 pidx, plen = self._pinned_meta("_many_meta", len(slots))
                 pidx.numpy()[:len(slots)] = slots
                 plen.numpy()[:len(slots)] = lens
-                self._scatter_spectra(stage, True, pidx, plen, len(slots))
+                self._scatter_form(stage, True, pidx, plen, len(slots))
             else:
                 idx = torch.as_tensor(slots, dtype=torch.long, device=self.device)
                 self.bank.data.index_copy_(0, idx, stage.to(self.device, non_blocking=True))
@@ -1175,8 +1243,8 @@ class RirStore:
             self.bank.data.index_copy_(0, idx, stage[:n_rows].permute(0, 2, 1))
             self.bank.lengths.index_copy_(0, idx, plen[:n_rows])
             return None
-        if self.spectral_only:
-            return self._scatter_spectra(stage, False, pidx, plen, n_rows)
+        if self._staged_only:
+            return self._scatter_form(stage, False, pidx, plen, n_rows)
         from . import _lib
         data = self.bank.data
         di = self.device.index if self.device.index is not None else torch.cuda.current_device()
@@ -1220,6 +1288,29 @@ class RirStore:
         src = stage if pull else stage[:n_rows].to(self.device, non_blocking=True)
         with torch.cuda.device(self.device):
             ops.scatter_spectra_into(src, planar, pidx, plen, n_rows, self.bank.spectra, self.bank.lengths, hscale=self.bank.scales)
+            ev = torch.cuda.Event()
+            ev.record()
+        return ev
+
+    def _scatter_form(self, stage, planar: bool, pidx, plen, n_rows: int):
+        """the staged transform of a store that keeps no float32 rows: block spectra (spectral-only) or half rows"""
+        if self.rows_half:
+            return self._scatter_rows16(stage, planar, pidx, plen, n_rows)
+        return self._scatter_spectra(stage, planar, pidx, plen, n_rows)
+
+    def _scatter_rows16(self, stage, planar: bool, pidx, plen, n_rows: int):
+        """half-rows stores: rows [0, n_rows) of the pinned staging block `stage` ([*, cap, 2] wav layout, or [*, 2, cap] with
+        planar) -> halves + scales of bank entries pidx[i] and their lengths plen[i] (ss_bank_scatter_rows16_f32: one launch,
+        k_scatter_rows16, which reads wav layout: a planar block is copied and transposed on the device first).  Wav blocks are
+        pulled over the host link by the kernel itself (``scatter_from_host`` False: one H2D copy first).  Returns the event
+        behind the launch (the block may be refilled after it)."""
+        self._about_to_write()
+        with torch.cuda.device(self.device):
+            if planar:
+                src = stage[:n_rows].to(self.device, non_blocking=True).permute(0, 2, 1).contiguous()
+            else:
+                src = stage if self.scatter_from_host else stage[:n_rows].to(self.device, non_blocking=True)
+            ops.scatter_rows16_into(src, pidx, plen, n_rows, self.bank.data, self.bank.scales, self.bank.lengths)
             ev = torch.cuda.Event()
             ev.record()
         return ev
@@ -1616,7 +1707,7 @@ class AudioEngine:
                  rir_max_cap: int = 1 << 18, rir_group: int = 1, rir_spectral: Union[None, bool, str] = None,
                  rir_buckets: Optional[Sequence[Tuple[int, int]]] = None, spectral_hbm_fraction: float = 0.5,
                  spectral_max_units: int = 0, rir_half_rows: bool = False, rir_spectral_buckets: bool = False,
-                 rir_half_bucket_rows: bool = False, **renderer_kwargs):
+                 rir_half_bucket_rows: bool = False, rir_rows: Optional[str] = None, **renderer_kwargs):
         """rir_spectral: keep the RIR rows' block spectra in HBM as well (2x the bytes per row) and run k_conv_spec /
         k_obs_rows<SPECTRAL> (no forward FFT per step): for STATIC banks (SoundSpaces 1.0 RIR files); live SS2.0 RIRs change
         every step and stay on the time-domain kernels.  None (default) = decided here: ON for file-backed stores at rates
@@ -1663,6 +1754,27 @@ class AudioEngine:
         the fused row kernels (ss_audio_obs_rows_spec16_buckets_f32 and its log-mel sibling) and the context binding
         ss_ctx_set_rir_spec_buckets_rows.  A three-block entry costs 393 244 bytes against 786 436 of "only" buckets.  Same loss
         and refusals as the other half forms; time against "only" buckets: INTEGRATION.md "Spectral length buckets"."""
+        if rir_rows not in (None, "half"):
+            raise ValueError(f"rir_rows must be None or 'half', not {rir_rows!r}")
+        if rir_rows == "half":
+            # rir_rows="half" (opt-in, LOSSY: about 2e-4 of peak on the waveform): the TIME-DOMAIN rows as float16 with one
+            # power-of-two scale per (entry, ear) (RirStore(rows="half"), include/ss_hip.h "Half-precision time-domain rows") - half
+            # the bytes of the plain rows, 64 008 per 16 kHz entry, the cheapest form.  Every sampling rate up to 3 KB: one-block
+            # rows take the fused half kernels, 44.1 / 48 kHz the half convolution + the spectrogram kernel.  Not served: SS2.0
+            # (step_time / wrap: live RIRs and the cross-fade), length buckets, any spectral form, a CPU device.
+            if rir_spectral:
+                raise ValueError("rir_rows='half' keeps no spectral form: it does not go with rir_spectral")
+            if rir_buckets:
+                raise ValueError("rir_rows='half' does not support length-bucketed banks (rir_buckets)")
+            if renderer_kwargs.get("step_time") is not None or renderer_kwargs.get("wrap"):
+                raise ValueError("rir_rows='half' cannot serve SoundSpaces 2.0 (step_time / wrap): live RIRs and the cross-fade "
+                                 "need float32 rows")
+            if torch.device(device).type != "cuda":
+                raise ValueError("rir_rows='half' needs a GPU device: the half-precision rows have no CPU fallback")
+            if int(sampling_rate) > 3 * P.KB:
+                raise ValueError(f"rir_rows='half' serves rows of up to three partition blocks (sampling rates up to {3 * P.KB}), "
+                                 f"not {sampling_rate}")
+            rir_spectral = False
         if rir_half_bucket_rows and not (rir_buckets and rir_spectral_buckets and rir_spectral == "half"):
             raise ValueError("rir_half_bucket_rows goes with rir_spectral='half', rir_buckets and rir_spectral_buckets=True")
         if rir_spectral_buckets and not (rir_buckets and rir_spectral in ("only", "half")):
@@ -1708,6 +1820,7 @@ class AudioEngine:
         self.rir_spectral = bool(rir_spectral) and not full
         self.rir_spectral_only = rir_spectral in ("only", "half")
         self.rir_spectral_half = rir_spectral == "half"
+        self.rir_rows_half = rir_rows == "half"
         if rir_buckets and rir_spectral_buckets:
             rir_max_cap = min(int(rir_max_cap), 16 * P.KB)         # (ss_spec_bucket: at most 16 blocks per row)
         if rir_buckets:
@@ -1722,7 +1835,8 @@ class AudioEngine:
         self.store = RirStore(rir_slots, rir_cap or sampling_rate, self.renderer.device,
                               truncate_to=None if full else int(sampling_rate), max_cap=rir_max_cap,
                               on_grow=self.renderer.set_rir_bank, group=rir_group,
-                              spectral=rir_spectral if self.rir_spectral_only else bool(rir_spectral) and not full)
+                              spectral=rir_spectral if self.rir_spectral_only else bool(rir_spectral) and not full,
+                              **(dict(rows="half") if self.rir_rows_half else {}))
         self.store.defer_uploads = True            # single-row uploads of a step travel as one block (flushed before every launch)
         self.renderer.set_rir_bank(self.store.bank)
 
@@ -1795,6 +1909,10 @@ class AudioEngine:
                 self._ctx_bank = now
             return ctx
         if n_sync or cur is None or cur[0] is not bank.data or cur[1] is not bank.spectra:   # two data_ptr() calls per step)
+            if bank.rows_half:                                   # (half-precision time-domain rows: ss_ctx_set_rir_bank16)
+                ctx.set_rir_bank16(bank.data, bank.scales, bank.lengths)
+                self._ctx_bank = (bank.data, bank.spectra)
+                return ctx
             if bank.spectral_only:                               # (no rows: the context's spectral-only binding)
                 if bank.scales is not None:                      # (a half bank: fp16 spectra + scales)
                     ctx.set_rir_spectra16(bank.spectra, bank.scales, bank.lengths, bank.cap, rows=self.renderer.out_len > P.KB)
