@@ -232,11 +232,23 @@ int ss_audio_obs_logmel_rows_spec16_f32(const float* spec, const void* hspec16, 
  * entries fed float(q) * rscale):
  *   ss_fftconv_binaural_rir16_f32   every shape ss_fftconv_binaural_f32 serves on a planar bank without SS_FLAG_CROSSFADE;
  *   ss_audio_obs_rir16_f32          the one-launch fused form, 257 <= out_len <= kB (and at most 26 pooled blocks); `audiogoal` may
- *                                   be NULL.  Longer rows: ss_fftconv_binaural_rir16_f32 + ss_spectrogram_f32 (what a context does).
- * Not served: SS_FLAG_CROSSFADE, length buckets, a one-launch log-mel form, the fused 44.1 / 48 kHz row kernels, the in-call
- * loaders.  SS_EINVAL before a device is touched: NULL halves or scales, a base that is not 4-byte aligned, odd rir_cap or
- * rir_cap < 2, more than 16 partition blocks, SS_FLAG_CROSSFADE, out_len outside the fused entry's range, a bad pad_mode, a NULL
- * required output.  n_units == 0 (n_entries == 0) returns 0. */
+ *                                   be NULL.  Longer rows: ss_fftconv_binaural_rir16_f32 + ss_spectrogram_f32 (what a context
+ *                                   bound by ss_ctx_set_rir_bank16 does), or
+ *   ss_audio_obs_rows_rir16_f32     rows of 2 or 3 partition blocks (kB < out_len <= 3 kB: 44.1 / 48 kHz) in one launch, as
+ *                                   ss_audio_obs_rows_spec16_f32 serves them from half spectra: small steps take k_obs_blocks (one
+ *                                   workgroup per output block, launch_obs_blocks' rule), larger ones k_obs_rows - the ROWS16
+ *                                   instantiations, whose forward transforms load halves; the stash, the products, the inverse
+ *                                   passes and the STFT phases are the fp32 time-domain form's.  `audiogoal` may be NULL.  Given a
+ *                                   waveform buffer and n_valid <= kB (one rendered block) the step takes the half convolution +
+ *                                   k_spectrogram, as the fp32 entry does (obs_rows_ok); that shape needs `audiogoal`.  Small steps
+ *                                   run k_obs_blocks, whose hand-off flags carry a launch counter: do not replay this entry from
+ *                                   a captured graph (the note on ss_audio_obs_rows_f32).
+ * Not served, by any entry: SS_FLAG_CROSSFADE, length buckets, a one-launch log-mel form (the time-domain log-mel instantiation of
+ * the row kernels is at its register limit: log-mel steps render a waveform and run the feature kernel over it), k_conv_rows, the
+ * wide form and the 512-thread core, the in-call loaders, the TORCH_LIBRARY ops; no default selects the form or its row kernels.
+ * SS_EINVAL before a device is touched: NULL halves or scales, a base that is not 4-byte aligned, odd rir_cap or rir_cap < 2, more
+ * than 16 partition blocks, SS_FLAG_CROSSFADE, out_len outside the entry's range, a bad pad_mode, a NULL required output.
+ * n_units == 0 (n_entries == 0) returns 0. */
 int ss_rir_rows16_f32(const float* rir, void* rir16_out, float* rscale_out, int n_entries, long long rir_unit_stride,
                       int rir_chan_stride, int rir_cap, void* stream);
 int ss_fftconv_binaural_rir16_f32(const float* spec, const void* rir16, const float* rscale, const int* rir_len,
@@ -245,6 +257,9 @@ int ss_fftconv_binaural_rir16_f32(const float* spec, const void* rir16, const fl
 int ss_audio_obs_rir16_f32(const float* spec, const void* rir16, const float* rscale, const int* rir_len, const int* unit_desc,
                            float* audiogoal, float* spectrogram, int n_units, int rir_cap, int n_valid, int out_len, int pad_mode,
                            int flags, void* stream);
+int ss_audio_obs_rows_rir16_f32(const float* spec, const void* rir16, const float* rscale, const int* rir_len, const int* unit_desc,
+                                float* audiogoal, float* spectrogram, int n_units, int rir_cap, int n_valid, int out_len,
+                                int pad_mode, int flags, void* stream);
 
 /* The same for rows of 2 or 3 partition blocks (kB < out_len <= 3 kB: 44.1 / 48 kHz, the reference's Replica rate; EXTENSION):
  * the log-mel form of the fused row kernels (k_obs_rows / k_obs_blocks), the STFT phase behind every output block emits the
@@ -538,6 +553,15 @@ int ss_ctx_set_rir_spectra16_rows(ss_ctx* ctx, const void* hspec16, const float*
  * memo, the overlap mode and the column / request entries run on it unchanged.  SS_EINVAL, nothing changed: the bank refusals of
  * the stateless entries, rir_len == NULL. */
 int ss_ctx_set_rir_bank16(ss_ctx* ctx, const void* rir16, const float* rscale, const int* rir_len, int rir_cap);
+/* The same binding, opted in to the fused row kernels (EXTENSION): ss_ctx_set_rir_bank16 in every respect - replace and unbind
+ * rules, refusals, loaders, pose memo, overlap mode, column / request entries - except that steps of rows of 2 or 3 partition
+ * blocks (44.1 / 48 kHz) take ONE launch (k_obs_blocks / k_obs_rows<.., ROWS16>, what ss_audio_obs_rows_rir16_f32 runs) wherever the
+ * fp32 time-domain bank would: not with a waveform buffer and one rendered block (n_valid <= kB), not past 3 kB samples - those keep
+ * the two launches.  A spectrogram-only step then needs no hand-over buffer.  Log-mel steps keep the waveform scratch whatever the
+ * log-mel policies say (no one-launch log-mel form reads half rows); with a spectrogram asked as well and n_valid > kB, the row
+ * kernel writes the scratch and the spectrogram and the feature kernel runs over the scratch.  One-block rates: the same routes
+ * as ss_ctx_set_rir_bank16.  A later ss_ctx_set_rir_bank16 on the context clears the opt-in. */
+int ss_ctx_set_rir_bank16_rows(ss_ctx* ctx, const void* rir16, const float* rscale, const int* rir_len, int rir_cap);
 /* The bank as length buckets (see ss_rir_bucket; replaces the two calls above for such banks; the descriptor array is copied,
  * the device pointers are borrowed).  Call again whenever a bucket is (re)allocated. */
 int ss_ctx_set_rir_buckets(ss_ctx* ctx, const ss_rir_bucket* buckets, int n_buckets, const int* rir_len);

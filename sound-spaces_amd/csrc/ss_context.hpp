@@ -81,6 +81,7 @@ struct Context {
     int h_blocks = 0;
     const void* rir16 = nullptr;   // half-precision time-domain rows (ss_ctx_set_rir_bank16; borrowed): rir / hspec / buckets are unset then
     const float* rscale = nullptr; // ... and their scales, one per (entry, ear)
+    bool rir16_rows = false;       // ... bound for the fused row kernels as well (ss_ctx_set_rir_bank16_rows)
     std::vector<ss_rir_bucket> buckets;   // length-bucketed bank (ss_ctx_set_rir_buckets); empty: the single bank above
     std::vector<ss_spec_bucket> spec_buckets;   // ... without time-domain rows (ss_ctx_set_rir_spec_buckets): rir / hspec are NULL then
     bool spec_buckets_rows = false;             // ... half ones bound for rows of 2 or 3 blocks (ss_ctx_set_rir_spec_buckets_rows)

@@ -320,10 +320,12 @@ void drop_stash(hipStream_t st) {
 // MEL: the log-mel instantiations (ss_audio_obs_logmel_rows_f32 / _spec_f32), same rule, same hand-off area.
 // HALF: the half-bank instantiations (ss_audio_obs_rows_spec16_f32 / ss_audio_obs_logmel_rows_spec16_f32), likewise.
 // HBK: a half bank in length buckets (ss_audio_obs_rows_spec16_buckets_f32 / ss_audio_obs_logmel_rows_spec16_buckets_f32), likewise.
-template <bool SPECTRAL, bool MEL = false, bool HALF = false, bool HBK = false>
+// ROWS16: half-precision time-domain rows (ss_audio_obs_rows_rir16_f32), likewise.
+template <bool SPECTRAL, bool MEL = false, bool HALF = false, bool HBK = false, bool ROWS16 = false>
 int launch_obs_blocks(ssk::ConvParams p, int n_units, int flags, int n_cus, const LaunchEnv& env,
                       const ssk::UnitTab<false, MEL>& mel = ssk::UnitTab<false, MEL>(),
-                      const ssk::SpecScale<HALF, HBK>& hs = ssk::SpecScale<HALF, HBK>()) {
+                      const ssk::SpecScale<HALF, HBK>& hs = ssk::SpecScale<HALF, HBK>(),
+                      const ssk::RowScale<ROWS16>& rs = ssk::RowScale<ROWS16>()) {
     const hipStream_t st = env.st;
     static const bool off = ab_flag("SS_HIP_NO_OBS_BLOCKS");   // (A/B builds only)
     const int n_rows = 2 * n_units, nb = (p.out_len + ssk::kB - 1) / ssk::kB;
@@ -343,6 +345,11 @@ int launch_obs_blocks(ssk::ConvParams p, int n_units, int flags, int n_cus, cons
     int rc = get_block_sync(st, &tails, &fl, &epoch);
     if (rc) return rc;
     const int grid = (n_rows * nb) << k;
+    if constexpr (ROWS16) {
+        hipLaunchKernelGGL((ssk::k_obs_blocks<false, false, false, false, true>), dim3(grid), dim3(ssk::kT), 0, st, p, n_rows, tails, fl, epoch,
+                           mel, hs, rs);
+        return hip_err(hipGetLastError());
+    }
     if constexpr (HBK) {
         hipLaunchKernelGGL((ssk::k_obs_blocks<SPECTRAL, MEL, true, true>), dim3(grid), dim3(ssk::kT), 0, st, p, n_rows, tails, fl, epoch, mel, hs);
         return hip_err(hipGetLastError());
@@ -355,18 +362,20 @@ int launch_obs_blocks(ssk::ConvParams p, int n_units, int flags, int n_cus, cons
     return hip_err(hipGetLastError());
 }
 
-template <bool SPECTRAL, bool MEL = false, bool HALF = false, bool HBK = false>
+template <bool SPECTRAL, bool MEL = false, bool HALF = false, bool HBK = false, bool ROWS16 = false>
 int launch_obs_rows(ssk::ConvParams p, int n_units, int flags, int n_cus, const LaunchEnv& env,
                     const ssk::UnitTab<false, MEL>& mel = ssk::UnitTab<false, MEL>(),
-                    const ssk::SpecScale<HALF, HBK>& hs = ssk::SpecScale<HALF, HBK>()) {
+                    const ssk::SpecScale<HALF, HBK>& hs = ssk::SpecScale<HALF, HBK>(),
+                    const ssk::RowScale<ROWS16>& rs = ssk::RowScale<ROWS16>()) {
     const hipStream_t st = env.st;
     static_assert(!HALF || SPECTRAL, "half bank: the spectral form");
     static_assert(!HBK || HALF, "bucketed half bank: a half form");
+    static_assert(!ROWS16 || (!SPECTRAL && !MEL && !HALF), "half rows: plain rows of one time-domain allocation");
     const int n_rows = 2 * n_units;
-    if ((MEL || HALF) && (flags & SS_FLAG_CROSSFADE)) return SS_EINVAL;                            // (the log-mel and half forms: plain rows)
-    if (HALF && !HBK && p.n_buckets != 1) return SS_EINVAL;                                         // (half: one allocation, or the HBK form)
+    if ((MEL || HALF || ROWS16) && (flags & SS_FLAG_CROSSFADE)) return SS_EINVAL;                  // (the log-mel and half forms: plain rows)
+    if (((HALF && !HBK) || ROWS16) && p.n_buckets != 1) return SS_EINVAL;                           // (half: one allocation, or the HBK form)
     {
-        const int rc = launch_obs_blocks<SPECTRAL, MEL, HALF, HBK>(p, n_units, flags, n_cus, env, mel, hs);
+        const int rc = launch_obs_blocks<SPECTRAL, MEL, HALF, HBK, ROWS16>(p, n_units, flags, n_cus, env, mel, hs, rs);
         if (rc != 1) return rc;
     }
     // small steps (the reference steps 5-10 envs per GPU at this rate): a row on 2 / 4 / 8 CUs, each rendering the row and
@@ -396,6 +405,10 @@ int launch_obs_rows(ssk::ConvParams p, int n_units, int flags, int n_cus, const 
         int rc = get_stash(st, per_wg * static_cast<size_t>(grid), &buf);
         if (rc) return rc;
         p.stash = reinterpret_cast<ssk::f32x4*>(buf);
+    }
+    if constexpr (ROWS16) {                                     // (the stash above: sized from rir_cap and n_terms, as for fp32 rows)
+        hipLaunchKernelGGL((ssk::k_obs_rows<false, false, false, false, false, true>), dim3(grid), dim3(ssk::kT), 0, st, p, n_rows, mel, hs, rs);
+        return hip_err(hipGetLastError());
     }
     if constexpr (!SPECTRAL) {
         if (xfade) {
@@ -744,10 +757,11 @@ struct Bank {
     bool sbk_rows = false;                  // half `sbk` that also serves rows of 2 or 3 blocks (the *_rows_spec16_buckets entries)
     const void* rir16 = nullptr;            // half-precision time-domain rows [entries][2][cap] + ...
     const float* rscale = nullptr;          // ... one scale per (entry, ear); nothing else is set then but `cap`
+    bool rows16_rows = false;               // ... that also serve the fused row kernels (ss_audio_obs_rows_rir16_f32, ss_ctx_set_rir_bank16_rows)
 };
-inline Bank rows16_bank(const void* rir16, const float* rscale, int cap) {
+inline Bank rows16_bank(const void* rir16, const float* rscale, int cap, bool fused_rows = false) {
     Bank b;
-    b.rir16 = rir16; b.rscale = rscale; b.cap = cap;
+    b.rir16 = rir16; b.rscale = rscale; b.cap = cap; b.rows16_rows = fused_rows;
     return b;
 }
 inline Bank rows_bank(const float* rir, long long us, int cs, int es, int cap) {
@@ -844,7 +858,10 @@ int render(const Bank& b, bool spectral, ssroute::Launch want, const float* spec
             // (... but through the entries of their own: Bank::sbk_rows)
             if (b.sbk && half && !b.sbk_rows && (out_len > ssk::kB || t4_of(out_len) > 26)) return SS_EINVAL;
             chain = ssroute::obs_chain(out_len, n_valid, nbh_max, flags, spectral, audiogoal != nullptr, route_switches());
-            if (rows16 && chain != Chain::kFused) chain = Chain::kTwo;     // half rows: no wide / row kernels
+            // half rows: no wide kernel; the row kernels only for a bank bound for them, on the shapes obs_rows_ok gives them
+            if (rows16 && chain != Chain::kFused)
+                chain = b.rows16_rows && ssroute::obs_rows_ok(out_len, n_valid, nbh_max, flags, false, audiogoal != nullptr) ? Chain::kRows
+                                                                                                                            : Chain::kTwo;
             if (chain == Chain::kTwo && !audiogoal) return SS_EINVAL;      // cross-faded long rows hand over through HBM/L2
             break;
         case Launch::kMelOneBlock:
@@ -884,6 +901,12 @@ int render(const Bank& b, bool spectral, ssroute::Launch want, const float* spec
             p.pad_mode = pad_mode;
             p.sgram = spectrogram;
             return launch_conv16<true>(p, rs, n_units, 1, flags, n_cus, env);
+        }
+        if (want == Launch::kObs && chain == Chain::kRows) {
+            p.pad_mode = pad_mode;
+            p.sgram = spectrogram;
+            return launch_obs_rows<false, false, false, false, true>(p, n_units, flags, n_cus, env, ssk::UnitTab<false, false>(),
+                                                                     ssk::SpecScale<false, false>(), rs);
         }
         rc = launch_conv16<false>(p, rs, n_units, nb_y, flags, n_cus, env);
         if (rc || want == Launch::kConv) return rc;
@@ -1453,6 +1476,18 @@ int ss_audio_obs_rir16_f32(const float* spec, const void* rir16, const float* rs
                   n_units, n_valid, out_len, pad_mode, flags, stateless(stream));
 }
 
+// ss_audio_obs_rows_f32 from half rows: rows of 2 or 3 partition blocks in one launch (k_obs_blocks / k_obs_rows<.., ROWS16>), the
+// shapes obs_rows_ok leaves to two launches (a waveform buffer and one rendered block) through the half convolution + k_spectrogram
+int ss_audio_obs_rows_rir16_f32(const float* spec, const void* rir16, const float* rscale, const int* rir_len, const int* unit_desc,
+                                float* audiogoal, float* spectrogram, int n_units, int rir_cap, int n_valid, int out_len, int pad_mode,
+                                int flags, void* stream) {
+    if (n_units == 0) return 0;
+    if (!rows16_bank_ok(rir16, rscale, rir_cap) || (flags & SS_FLAG_CROSSFADE)) return SS_EINVAL;
+    if (out_len <= ssk::kB || out_len > 3 * ssk::kB) return SS_EINVAL;
+    return render(rows16_bank(rir16, rscale, rir_cap, true), false, Launch::kObs, spec, rir_len, unit_desc, audiogoal, spectrogram,
+                  nullptr, n_units, n_valid, out_len, pad_mode, flags, stateless(stream));
+}
+
 // ---- pose memo: the row copies (k_memo_rows) ---------------------------------------------------------------------------
 static bool memo_io_ok(const ss_memo_io* io, int n_io) {
     if (!io || n_io < 1 || n_io > ssk::kMemoArrays) return false;
@@ -1693,14 +1728,23 @@ int ss_ctx_set_rir_spectra16_rows(ss_ctx* h, const void* hspec16, const float* h
 int ss_ctx_set_rir_bank16(ss_ctx* h, const void* rir16, const float* rscale, const int* rir_len, int rir_cap) {
     if (!h) return SS_EINVAL;
     if (!rir16) {
-        h->c.rir16 = nullptr; h->c.rscale = nullptr;
+        h->c.rir16 = nullptr; h->c.rscale = nullptr; h->c.rir16_rows = false;
         return 0;
     }
     if (!rir_len || !rows16_bank_ok(rir16, rscale, rir_cap)) return SS_EINVAL;
     const int rc = ss_ctx_set_rir_bank(h, nullptr, rir_len, 0, 0, 1, rir_cap);      // (window keys, pool, every other form: as for any new bank)
     if (rc) return rc;
     h->c.rir16 = rir16;
+    h->c.rir16_rows = false;                                   // (ss_ctx_set_rir_bank16_rows sets it behind this call)
     h->c.rscale = rscale;
+    return 0;
+}
+
+// ... bound for the fused row kernels as well: ss_ctx_set_rir_bank16 plus the route field (ss_route.hpp, Bank::rows16_rows)
+int ss_ctx_set_rir_bank16_rows(ss_ctx* h, const void* rir16, const float* rscale, const int* rir_len, int rir_cap) {
+    const int rc = ss_ctx_set_rir_bank16(h, rir16, rscale, rir_len, rir_cap);
+    if (rc) return rc;
+    h->c.rir16_rows = rir16 != nullptr;
     return 0;
 }
 
@@ -1812,6 +1856,7 @@ static ssroute::Bank route_bank_of(const ssctx::Context& c) {
     b.rir_cap = c.rir_cap;
     b.h_blocks = c.h_blocks;
     b.rows16 = c.rir16 != nullptr;
+    b.rows16_rows = b.rows16 && c.rir16_rows;
     return b;
 }
 
@@ -1819,7 +1864,7 @@ static ssroute::Bank route_bank_of(const ssctx::Context& c) {
 static Bank bank_of(const ssctx::Context& c) {
     if (!c.spec_buckets.empty()) return spec_buckets_bank(c.spec_buckets.data(), static_cast<int>(c.spec_buckets.size()), c.spec_buckets_rows);
     if (!c.buckets.empty()) return buckets_bank(c.buckets.data(), static_cast<int>(c.buckets.size()));
-    if (c.rir16) return rows16_bank(c.rir16, c.rscale, c.rir_cap);
+    if (c.rir16) return rows16_bank(c.rir16, c.rscale, c.rir_cap, c.rir16_rows);
     Bank b = rows_bank(c.rir, c.rir_us, c.rir_cs, c.rir_es, c.rir_cap);
     b.hspec = c.hspec; b.hscale = c.hscale; b.h_blocks = c.h_blocks;
     return b;

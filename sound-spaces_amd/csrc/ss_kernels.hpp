@@ -2205,6 +2205,26 @@ __device__ __forceinline__ void rows_forward(c32* lds, const ThreadTw& tw, int t
     lds_barrier();
 }
 
+// ... of a bank of half-precision time-domain rows (BankRow16): the loader of conv_block<.., BankRow16> - the thread's eight packed
+// pairs go out as one batch of raw words, predicated on the row's capacity, and are converted behind it (inside the predicated
+// load every conversion waited for its own load: eight HBM round trips in a row, see conv_block).  8 live words against the fp32
+// loader's 16.
+__device__ __forceinline__ void rows_forward(c32* lds, const ThreadTw& tw, int t, const BankRow16& br, int i) {
+    const int lo = i * kB, cap = br.cap;
+    const unsigned* u2 = reinterpret_cast<const unsigned*>(br.h2 + (lo >> 1));
+    const int m_end = (cap - lo) >> 1;
+    const float sc = br.scale;
+    unsigned raw[8];
+#pragma unroll
+    for (int a = 0; a < 8; ++a) raw[a] = t + 1024 * a < m_end ? ld_stream(u2 + t + 1024 * a) : 0u;
+#pragma unroll
+    for (int a = 0; a < 8; ++a) SSK_OPAQUE1(raw[a]);             // (the conversions stay behind the batch)
+    pass1_fwd<true>(lds, tw.p1, t, [&](int m) { return row16_pair(__builtin_bit_cast(h16x2, raw[(m - t) >> 10]), sc); });
+    lds_barrier();
+    pass2<false>(lds, tw.p2, t);
+    lds_barrier();
+}
+
 // v += H'[item s] * S'[item s] for one pair in memory (hp / sp: per-thread pointers of the two block spectra)
 __device__ __forceinline__ void rows_product(const f32x4* hp, const f32x4* sp, int t, int s, c32 (&v)[8]) {
     f32x4 hv[4], sv[4];
@@ -2437,10 +2457,15 @@ __device__ __forceinline__ void mel_fill_quiet(const MelArgs& m, const ConvParam
 // HALF with BUCKETS (a half bank in length buckets, see k_conv_spec<.., HBK>): the bucket of a term - its fp16 base, its scale base
 // and its depth - is resolved once per term and row (bank_spec16: scalar compares on the wave-uniform index); block i of the
 // term is then hp + i * (kSpecComplex / 2) and sp + i.
-template <bool SPECTRAL, bool XFADE = false, bool BUCKETS = true, bool MEL = false, bool HALF = false>
+// ROWS16 (half-precision time-domain rows, RowScale above; one allocation): the time-domain branch resolves a term's row with
+// bank_row16 and the forward transform loads halves (rows_forward for BankRow16); of ConvParams' bank fields only rir_cap is
+// read.  Everything behind pass 1 - stash, products, inverse passes, STFT phases - is the fp32 time-domain form's code.
+template <bool SPECTRAL, bool XFADE = false, bool BUCKETS = true, bool MEL = false, bool HALF = false, bool ROWS16 = false>
 __global__ __launch_bounds__(1024) void k_obs_rows(ConvParams p, int n_rows, UnitTab<false, MEL> ut = UnitTab<false, MEL>(),
-                                                   SpecScale<HALF, HALF && BUCKETS> hs = SpecScale<HALF, HALF && BUCKETS>()) {
+                                                   SpecScale<HALF, HALF && BUCKETS> hs = SpecScale<HALF, HALF && BUCKETS>(),
+                                                   RowScale<ROWS16> rs = RowScale<ROWS16>()) {
     static_assert(!(SPECTRAL && XFADE), "cross-faded rows are rendered from the time-domain bank");
+    static_assert(!ROWS16 || (!SPECTRAL && !XFADE && !BUCKETS && !MEL && !HALF), "half rows: plain rows of one time-domain allocation");
     static_assert(!HALF || (SPECTRAL && !XFADE), "half bank: plain rows of a spectral bank (one allocation, or length buckets)");
     constexpr bool HBK = HALF && BUCKETS;
     static_assert(!MEL || !XFADE, "log-mel: plain rows (of one allocation, or of a length-bucketed fp32 bank)");
@@ -2499,6 +2524,9 @@ __global__ __launch_bounds__(1024) void k_obs_rows(ConvParams p, int n_rows, Uni
         } else if (SPECTRAL) {
             if (dws[0].x >= 0) nbh0 = min(nbh0, bank_spec<BUCKETS>(p, dws[0].x, 0).h_blocks);
             if (dws[1].x >= 0) nbh1 = min(nbh1, bank_spec<BUCKETS>(p, dws[1].x, 0).h_blocks);
+        } else if constexpr (ROWS16) {                    // (one allocation: every row holds rir_cap samples)
+            if (dws[0].x >= 0) nbh0 = min(nbh0, min(p.stash_nbh, (p.rir_cap + kB - 1) / kB));
+            if (dws[1].x >= 0) nbh1 = min(nbh1, min(p.stash_nbh, (p.rir_cap + kB - 1) / kB));
         } else {                                          // (never more blocks than the entry's row - and the stash - holds)
             if (dws[0].x >= 0) nbh0 = min(nbh0, min(p.stash_nbh, (bank_row<BUCKETS>(p, dws[0].x, 0).cap + kB - 1) / kB));
             if (dws[1].x >= 0) nbh1 = min(nbh1, min(p.stash_nbh, (bank_row<BUCKETS>(p, dws[1].x, 0).cap + kB - 1) / kB));
@@ -2556,7 +2584,10 @@ __global__ __launch_bounds__(1024) void k_obs_rows(ConvParams p, int n_rows, Uni
                     const int term = pr >> 4, i = pr & 15;
                     int ti = tl;
                     SSK_OPAQUE1(ti);                      // per transform: see k_conv
-                    const BankRow br = bank_row<BUCKETS>(p, term ? dws[1].x : dws[0].x, ch);
+                    const auto br = [&] {
+                        if constexpr (ROWS16) return bank_row16(rs, p.rir_cap, term ? dws[1].x : dws[0].x, ch);
+                        else return bank_row<BUCKETS>(p, term ? dws[1].x : dws[0].x, ch);
+                    }();
                     if (last_new >= 0 || b0 > 0 || j > 0) lds_barrier();      // (the LDS buffer's previous readers are done)
                     rows_forward(lds, tw, ti, br, i);
                     if (fresh) {                          // not the last one: its spectrum just goes to the stash
@@ -2695,8 +2726,13 @@ __global__ __launch_bounds__(1024) void k_obs_rows(ConvParams p, int n_rows, Uni
             // (time-domain bank: -1.3 ... -1.7 % in three alternating runs at 64 / 128 / 512 units; the same for the spectral
             // bank's block spectra measured +2.5 % at 128 / 512 units and is not done: profiles/r6/kbench_l2warm_44k.txt)
             if (!SPECTRAL && !XFADE && j + 1 < p.nb_y && dws[0].x >= 0 && j + 1 < nbh0) {
-                const BankRow br = bank_row<BUCKETS>(p, dws[0].x, ch);
-                if (br.es == 1) l2_touch(br.h + (size_t)(j + 1) * kB, min(kB, br.cap - (j + 1) * kB) * 4, tl, s_dummy);
+                if constexpr (ROWS16) {                   // (2 bytes per sample)
+                    const BankRow16 br = bank_row16(rs, p.rir_cap, dws[0].x, ch);
+                    l2_touch(br.h2 + (size_t)(j + 1) * (kB / 2), min(kB, br.cap - (j + 1) * kB) * 2, tl, s_dummy);
+                } else {
+                    const BankRow br = bank_row<BUCKETS>(p, dws[0].x, ch);
+                    if (br.es == 1) l2_touch(br.h + (size_t)(j + 1) * kB, min(kB, br.cap - (j + 1) * kB) * 4, tl, s_dummy);
+                }
             }
 #endif
             if (kRowsAbl & 1) {
@@ -2751,11 +2787,14 @@ __global__ __launch_bounds__(1024) void k_obs_rows(ConvParams p, int n_rows, Uni
 // early return its block's share of frames; p.sgram may be null.
 // HALF (a half bank, see k_conv_spec<.., HALF>): the spectral branch reads fp16 block spectra and their scales.
 // HBK (a half bank in length buckets, see k_conv_spec<.., HBK>): the term's bucket gives the fp16 base, the scale base and the depth.
-template <bool SPECTRAL, bool MEL = false, bool HALF = false, bool HBK = false>
+// ROWS16 (half-precision time-domain rows, see k_obs_rows<.., ROWS16>): the time-domain branch transforms a BankRow16.
+template <bool SPECTRAL, bool MEL = false, bool HALF = false, bool HBK = false, bool ROWS16 = false>
 __global__ __launch_bounds__(1024) void k_obs_blocks(ConvParams p, int n_rows, float* tails, int* flags, int epoch,
                                                      UnitTab<false, MEL> ut = UnitTab<false, MEL>(),
-                                                     SpecScale<HALF, HBK> hs = SpecScale<HALF, HBK>()) {
+                                                     SpecScale<HALF, HBK> hs = SpecScale<HALF, HBK>(),
+                                                     RowScale<ROWS16> rs = RowScale<ROWS16>()) {
     static_assert(!HALF || SPECTRAL, "half bank: the spectral form");
+    static_assert(!ROWS16 || (!SPECTRAL && !MEL && !HALF && !HBK), "half rows: plain rows of one time-domain allocation");
     static_assert(!HBK || HALF, "bucketed half bank: a half form");
     __shared__ c32 lds[16 * kWaveScratch > kLdsComplex ? 16 * kWaveScratch : kLdsComplex];
     __shared__ float s_win[kNfft];
@@ -2836,7 +2875,10 @@ __global__ __launch_bounds__(1024) void k_obs_blocks(ConvParams p, int n_rows, f
                 any = true;
             }
         } else {
-            const BankRow br = bank_row(p, ridx, ch);
+            const auto br = [&] {
+                if constexpr (ROWS16) return bank_row16(rs, p.rir_cap, ridx, ch);
+                else return bank_row(p, ridx, ch);
+            }();
             nbh = min(nbh, (br.cap + kB - 1) / kB);
             for (int i = 0; i < nbh; ++i) {
                 const int m = j - i;

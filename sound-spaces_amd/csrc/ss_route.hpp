@@ -111,6 +111,7 @@ struct Bank {
     int h_blocks = 0;                 // blocks of `spectra`
     bool spec_buckets_half_rows = false;      // half `spec_buckets` bound for rows of 2 or 3 blocks (ss_ctx_set_rir_spec_buckets_rows)
     bool rows16 = false;              // half-precision time-domain rows (ss_ctx_set_rir_bank16): nothing else is bound then
+    bool rows16_rows = false;         // ... bound for the fused row kernels as well (ss_ctx_set_rir_bank16_rows; only with rows16)
 };
 
 struct Policies {
@@ -145,8 +146,11 @@ inline Route route_step(const Bank& b, int out_len, int n_valid, const Policies&
     const bool xfade = (flags & SS_FLAG_CROSSFADE) != 0;
     const bool bucketed = b.buckets || b.spec_buckets;
     // half-precision time-domain rows: the fused half kernels for one-block rows, every longer row the half convolution into the
-    // caller's waveform buffer or the context's hand-over buffer and k_spectrogram over it (no wide / row kernels read halves);
-    // log-mel steps render into the waveform scratch; no cross-fade (refused as on the spectral-only banks)
+    // caller's waveform buffer or the context's hand-over buffer and k_spectrogram over it (no wide kernel reads halves);
+    // log-mel steps render into the waveform scratch; no cross-fade (refused as on the spectral-only banks).
+    // Bound by ss_ctx_set_rir_bank16_rows (rows16_rows), rows of 2 or 3 blocks take k_obs_blocks / k_obs_rows<.., ROWS16> wherever
+    // obs_rows_ok hands the shape to them - a log-mel step's scratch counts as its waveform buffer (there is no one-launch
+    // log-mel form on half rows, whatever the log-mel policies say) - and need no hand-over buffer there.
     if (b.rows16) {
         if (xfade) {
             r.refused = true;
@@ -158,8 +162,11 @@ inline Route route_step(const Bank& b, int out_len, int n_valid, const Policies&
             return r;
         }
         r.launch = Launch::kObs;
+        const bool have_wave = w.waveform || r.wave_scratch;
         r.chain = out_len <= kB && t4_of(out_len) <= 26 ? Chain::kFused : Chain::kTwo;
-        r.handover = r.chain == Chain::kTwo && !w.waveform && !r.wave_scratch;
+        if (r.chain == Chain::kTwo && b.rows16_rows && obs_rows_ok(out_len, n_valid, ceil_div(b.rir_cap, kB), flags, false, have_wave))
+            r.chain = Chain::kRows;
+        r.handover = r.chain == Chain::kTwo && !have_wave;
         return r;
     }
     // a spectral-only bank (spectra bound, no rows: ss_ctx_set_rir_bank(ctx, NULL, ...) + ss_ctx_set_rir_spectra) cannot serve a

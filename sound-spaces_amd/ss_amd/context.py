@@ -159,12 +159,15 @@ class AudioContext:
         _lib.check(getattr(self.lib, name)(self._h, hspec16.data_ptr(), hscale.data_ptr(), int(hspec16.shape[2])), name)
         self._spectra = (hspec16, hscale)
 
-    def set_rir_bank16(self, rir16, rscale, lengths) -> None:
+    def set_rir_bank16(self, rir16, rscale, lengths, rows: bool = False) -> None:
         """A bank of HALF-PRECISION TIME-DOMAIN ROWS (``RirStore(rows="half")``: float16 rir16 [R,2,cap], float32 scales rscale
         [R,2], CUDA int32 lengths [R]; ss_ctx_set_rir_bank16).  Replaces any earlier binding; rir16 = None unbinds.  One-block rows
         take the fused half kernels, longer ones the half convolution + the spectrogram kernel; the library refuses (SS_EINVAL)
-        cross-faded steps, and its in-call loaders report their misses instead of serving them."""
+        cross-faded steps, and its in-call loaders report their misses instead of serving them.
+        ``rows=True`` (opt-in; ss_ctx_set_rir_bank16_rows): rows of 2 or 3 partition blocks (44.1 / 48 kHz) take the fused row
+        kernels' half-rows forms in one launch wherever a float32 time-domain bank would; everything else as above."""
         import torch
+        name = "ss_ctx_set_rir_bank16_rows" if rows else "ss_ctx_set_rir_bank16"
         if rir16 is None:
             _lib.check(self.lib.ss_ctx_set_rir_bank16(self._h, None, None, None, 0), "ss_ctx_set_rir_bank16")
             self._bank = None
@@ -175,8 +178,7 @@ class AudioContext:
         if rir16.dim() != 3 or rir16.shape[1] != 2 or tuple(rscale.shape) != tuple(rir16.shape[:2]):
             raise ValueError("set_rir_bank16: rows [R, 2, cap] and one scale per (entry, ear) expected")
         cap = int(rir16.shape[2])
-        _lib.check(self.lib.ss_ctx_set_rir_bank16(self._h, rir16.data_ptr(), rscale.data_ptr(), lengths.data_ptr(), cap),
-                   "ss_ctx_set_rir_bank16")
+        _lib.check(getattr(self.lib, name)(self._h, rir16.data_ptr(), rscale.data_ptr(), lengths.data_ptr(), cap), name)
         self._bank = (rir16, rscale, lengths)
         self.rir_cap = cap
         self._spectra = None

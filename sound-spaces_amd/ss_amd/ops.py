@@ -423,6 +423,28 @@ def audio_obs_rir16_into(spec, rir16, rscale, rir_len, unit_desc, audiogoal, spe
                                                       out_len, _PAD[pad_mode], flags, _stream(spec)), "ss_audio_obs_rir16_f32")
 
 
+def audio_obs_rows_rir16_into(spec, rir16, rscale, rir_len, unit_desc, audiogoal, spectrogram_out, n_valid: int, out_len: int,
+                              pad_mode="reflect", flags: int = 0) -> None:
+    """The fused observation of rows of 2 or 3 partition blocks (KB < out_len <= 3 KB: 44.1 / 48 kHz) from a bank of half rows
+    (``ss_audio_obs_rows_rir16_f32``: k_obs_blocks for small steps, k_obs_rows beyond); ``audiogoal`` may be None - except with
+    n_valid <= KB, which the library serves in two launches when it is given one and in one when it is not.  Small steps must
+    not be replayed from a captured graph (include/ss_hip.h)."""
+    _chk(spec, torch.float32, "spec"); cap = _chk_rows16(rir16, rscale); _chk(rir_len, torch.int32, "rir_len")
+    _chk(unit_desc, torch.int32, "unit_desc"); _chk(spectrogram_out, torch.float32, "spectrogram_out")
+    N = unit_desc.shape[0]
+    assert tuple(spectrogram_out.shape) == (N,) + spectrogram_shape(out_len)
+    ag_ptr = None
+    if audiogoal is not None:
+        _chk(audiogoal, torch.float32, "audiogoal")
+        assert tuple(audiogoal.shape) == (N, 2, out_len)
+        ag_ptr = audiogoal.data_ptr()
+    with torch.cuda.device(spec.device):
+        _lib.check(_lib.load().ss_audio_obs_rows_rir16_f32(spec.data_ptr(), rir16.data_ptr(), rscale.data_ptr(), rir_len.data_ptr(),
+                                                           unit_desc.data_ptr(), ag_ptr, spectrogram_out.data_ptr(), N, cap, n_valid,
+                                                           out_len, _PAD[pad_mode], flags, _stream(spec)),
+                   "ss_audio_obs_rows_rir16_f32")
+
+
 # ---- log-mel observation in one launch (no waveform buffer) ---------------------------------------------------------
 def _obs_logmel_args(unit_desc, audiogoal, spectrogram_out, logmel_out, mel_start, mel_w, out_len):
     _chk(unit_desc, torch.int32, "unit_desc"); _chk(logmel_out, torch.float32, "logmel_out")

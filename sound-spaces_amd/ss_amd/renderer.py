@@ -420,6 +420,9 @@ class BatchedAudioRenderer:
     # With BOTH bank forms resident, launches of more than this many units of one-block rows (16 kHz) read the time-domain rows
     # (ss_ctx_set_spectral_policy has the numbers); 0 = the spectral form whenever it exists.  AudioEngine sets it.
     spectral_max_units = 0
+    # A bank of half-precision time-domain rows under rows of 2 or 3 partition blocks: True = the fused row kernels
+    # (ops.audio_obs_rows_rir16_into), False = the half convolution + the spectrogram kernel.  AudioEngine(rir_rows16_fused=True) sets it.
+    rows16_fused = False
 
     def _spectral_for(self, n_units: int, distractor: bool = False) -> bool:
         """(steps with distractor terms - two forward transforms per row - read the spectral rows at any size)"""
@@ -474,11 +477,13 @@ class BatchedAudioRenderer:
 
     def _render_rows16(self, plan: Plan, want_audiogoal: bool, audiogoal_out, spectrogram_out):
         """render() from a bank of half-precision time-domain rows: one fused launch for one-block rows, the half convolution
-        and the spectrogram kernel (two launches, the waveform handed over through memory) for every longer row."""
+        and the spectrogram kernel (two launches, the waveform handed over through memory) for every longer row - or, with
+        rows16_fused, the fused row kernels for rows of 2 or 3 blocks (one launch, the waveform only where it is asked for)."""
         N = len(plan)
         fused = self.out_len <= P.KB and self.spectrogram_shape[1] <= 26
+        rows = not fused and self.rows16_fused and P.KB < self.out_len <= 3 * P.KB
         ag = audiogoal_out
-        if ag is None and (want_audiogoal or not fused):
+        if ag is None and (want_audiogoal or not (fused or rows)):
             ag = torch.empty((N, 2, self.out_len), dtype=torch.float32, device=self.device)
         sg = spectrogram_out
         if sg is None:
@@ -487,6 +492,9 @@ class BatchedAudioRenderer:
         if fused:
             ops.audio_obs_rir16_into(self._spec, b.data, b.scales, b.lengths, plan.desc, ag, sg, self.n_valid, self.out_len,
                                      self.pad_mode, flags=plan.flags)
+        elif rows:
+            ops.audio_obs_rows_rir16_into(self._spec, b.data, b.scales, b.lengths, plan.desc, ag, sg, self.n_valid, self.out_len,
+                                          self.pad_mode, flags=plan.flags)
         else:
             ops.fftconv_binaural_rir16_into(self._spec, b.data, b.scales, b.lengths, plan.desc, ag, self.n_valid, flags=plan.flags)
             ops.spectrogram_into(ag, sg, self.pad_mode)
@@ -1707,7 +1715,8 @@ class AudioEngine:
                  rir_max_cap: int = 1 << 18, rir_group: int = 1, rir_spectral: Union[None, bool, str] = None,
                  rir_buckets: Optional[Sequence[Tuple[int, int]]] = None, spectral_hbm_fraction: float = 0.5,
                  spectral_max_units: int = 0, rir_half_rows: bool = False, rir_spectral_buckets: bool = False,
-                 rir_half_bucket_rows: bool = False, rir_rows: Optional[str] = None, **renderer_kwargs):
+                 rir_half_bucket_rows: bool = False, rir_rows: Optional[str] = None, rir_rows16_fused: bool = False,
+                 **renderer_kwargs):
         """rir_spectral: keep the RIR rows' block spectra in HBM as well (2x the bytes per row) and run k_conv_spec /
         k_obs_rows<SPECTRAL> (no forward FFT per step): for STATIC banks (SoundSpaces 1.0 RIR files); live SS2.0 RIRs change
         every step and stay on the time-domain kernels.  None (default) = decided here: ON for file-backed stores at rates
@@ -1753,9 +1762,17 @@ class AudioEngine:
         buckets for rows of 2 or 3 partition blocks (sampling rates in (KB, 3 KB]: 44.1 / 48 kHz) - the bucketed half forms of
         the fused row kernels (ss_audio_obs_rows_spec16_buckets_f32 and its log-mel sibling) and the context binding
         ss_ctx_set_rir_spec_buckets_rows.  A three-block entry costs 393 244 bytes against 786 436 of "only" buckets.  Same loss
-        and refusals as the other half forms; time against "only" buckets: INTEGRATION.md "Spectral length buckets"."""
+        and refusals as the other half forms; time against "only" buckets: INTEGRATION.md "Spectral length buckets".
+
+        rir_rows16_fused=True (with rir_rows="half" only; opt-in): rows of 2 or 3 partition blocks (44.1 / 48 kHz) take the
+        half-rows forms of the fused row kernels (k_obs_blocks / k_obs_rows <.., ROWS16>: ss_audio_obs_rows_rir16_f32 and the
+        context binding ss_ctx_set_rir_bank16_rows) in ONE launch instead of the half convolution + the spectrogram kernel.
+        Accepted at every rate, inert for one-block rates.  Same results to the A/B bound, same loss, same refusals; measured
+        times: INTEGRATION.md "Half-precision time-domain rows"."""
         if rir_rows not in (None, "half"):
             raise ValueError(f"rir_rows must be None or 'half', not {rir_rows!r}")
+        if rir_rows16_fused and rir_rows != "half":
+            raise ValueError("rir_rows16_fused goes with rir_rows='half'")
         if rir_rows == "half":
             # rir_rows="half" (opt-in, LOSSY: about 2e-4 of peak on the waveform): the TIME-DOMAIN rows as float16 with one
             # power-of-two scale per (entry, ear) (RirStore(rows="half"), include/ss_hip.h "Half-precision time-domain rows") - half
@@ -1821,6 +1838,8 @@ class AudioEngine:
         self.rir_spectral_only = rir_spectral in ("only", "half")
         self.rir_spectral_half = rir_spectral == "half"
         self.rir_rows_half = rir_rows == "half"
+        self.rir_rows16_fused = bool(rir_rows16_fused)
+        self.renderer.rows16_fused = self.rir_rows16_fused
         if rir_buckets and rir_spectral_buckets:
             rir_max_cap = min(int(rir_max_cap), 16 * P.KB)         # (ss_spec_bucket: at most 16 blocks per row)
         if rir_buckets:
@@ -1910,7 +1929,7 @@ class AudioEngine:
             return ctx
         if n_sync or cur is None or cur[0] is not bank.data or cur[1] is not bank.spectra:   # two data_ptr() calls per step)
             if bank.rows_half:                                   # (half-precision time-domain rows: ss_ctx_set_rir_bank16)
-                ctx.set_rir_bank16(bank.data, bank.scales, bank.lengths)
+                ctx.set_rir_bank16(bank.data, bank.scales, bank.lengths, rows=self.rir_rows16_fused)
                 self._ctx_bank = (bank.data, bank.spectra)
                 return ctx
             if bank.spectral_only:                               # (no rows: the context's spectral-only binding)
