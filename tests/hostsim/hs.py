@@ -156,11 +156,15 @@ def run(sources, rir_bank, rir_len, units, n_valid, out_len, fuse=False, want_sp
     return out, (sg if (fuse or want_spectrogram) else None)
 
 
-def spectrogram(x, pad_mode=0, gpw=1):
+def spectrogram(x, pad_mode=0, gpw=1, n_valid=None):
+    """n_valid: the rows are known to be zero from that sample on (SpecParams::live, as the library's two-launch path sets it:
+    the pooled columns behind ssk::live_blocks are written as zeros, not computed)"""
     L = lib()
     x = np.ascontiguousarray(x, np.float32)
     N, _, n = x.shape
     sg = np.full((N, 65, P.spectrogram_shape(n)[1], 2), np.nan, np.float32)
+    if n_valid is not None:
+        L.hs_set_spec_n_valid(int(n_valid))
     rc = L.hs_spectrogram(_p(x, ctypes.c_float), _p(sg, ctypes.c_float), N, n, pad_mode, gpw)
     assert rc == 0, rc
     return sg

@@ -241,7 +241,7 @@ def test_route_fields_clear_print_the_recorded_table(route_prog):
     with open(os.path.join(HERE, "golden", "route_table.txt")) as f:
         golden = [ln for ln in f.read().splitlines() if not ln.startswith("#")]
     table = _run(route_prog, "table")
-    assert len(golden) == 10 * 9 * 3 * 4 and table == golden
+    assert len(golden) == 10 * 9 * 3 * 4 + 10 * 4 * 3 * 4 and table == golden      # (the fixed grid + the n_valid seam rows)
 
 
 def test_route_of_a_plain_half_rows_binding_is_unchanged(route_prog, route_rir16_prog):

@@ -37,7 +37,7 @@ def test_field_clear_prints_the_recorded_table(prog):
     with open(os.path.join(HERE, "golden", "route_table.txt")) as f:
         golden = [ln for ln in f.read().splitlines() if not ln.startswith("#")]
     table = _run(prog, "table")
-    assert len(golden) == 10 * 9 * 3 * 4 and table == golden
+    assert len(golden) == 10 * 9 * 3 * 4 + 10 * 4 * 3 * 4 and table == golden      # (the fixed grid + the n_valid seam rows)
 
 
 def test_routes_with_the_field_set(prog):

@@ -1,9 +1,10 @@
 """The routing of a context's step (csrc/ss_route.hpp) on its own, without HIP: tests/route_host.cpp - a stand-alone program that
 prints the Route of every case of a fixed grid (ten bank forms x nine (out_len, n_valid) x 1 / 3 / 17 RIR blocks x the planner's
-flags x five sets of wanted outputs x n in {1, 200} x three policy sets), built with AddressSanitizer and UBSan and run
-directly.  Its output is compared with tests/golden/route_table.txt, which was recorded from the verbatim extraction of the
-expressions ss_ctx_observe used to carry inline, before anything in them was simplified; and every route is checked against
-the properties a route must have."""
+flags x five sets of wanted outputs x n in {1, 200} x three policy sets; appended to it: three-block rows with n_valid on the
+block seam, kB and kB + 1, at 44 100 and 48 000), built with AddressSanitizer and UBSan and run directly.  Its output is
+compared with tests/golden/route_table.txt, whose fixed grid was recorded from the verbatim extraction of the expressions
+ss_ctx_observe used to carry inline, before anything in them was simplified (the appended seam rows: from ss_route.hpp as it
+stands); and every route is checked against the properties a route must have."""
 import os
 import shutil
 import subprocess
@@ -12,6 +13,7 @@ import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 KB = 16384
+GRID, SEAMS = 10 * 9 * 3 * 4, 10 * 4 * 3 * 4               # lines of the fixed grid, of the appended seam rows
 SPECTRAL, SCRATCH, HANDOVER, REFUSED = 1, 2, 4, 8
 LAUNCHES = "-CFWRTmsr"
 SPECTRAL_ONLY = {"spec", "half", "half-rows", "specbk", "specbk-half"}
@@ -54,7 +56,7 @@ def _cases(lines):
 
 def test_every_route_of_the_grid_is_the_recorded_one(table):
     golden = _golden()
-    assert len(golden) == 10 * 9 * 3 * 4
+    assert len(golden) == GRID + SEAMS
     diff = [(a, b) for a, b in zip(golden, table) if a != b]
     assert len(table) == len(golden) and not diff, diff[:5]
 
@@ -83,4 +85,26 @@ def test_properties_of_every_route(table):
         # without a spectrogram nothing but the convolution (or a log-mel form) runs
         if not w["spectrogram"] and not bits & REFUSED:
             assert launch in "Cmsr", case
-    assert n == 10 * 9 * 3 * 4 * 5 * 6
+    assert n == (GRID + SEAMS) * 5 * 6
+
+
+def test_seam_rows_switch_between_the_wide_kernel_and_the_row_kernels(table):
+    """n_valid = kB is the wide kernel's last step, kB + 1 the first of k_obs_rows (plain) / of two launches (cross-faded, or
+    - past 16 RIR blocks - everything), with and without a waveform buffer"""
+    seams = table[GRID:]
+    assert len(seams) == SEAMS and {(c[1], c[2]) for c in _cases(seams)} == {(o, v) for o in (44100, 48000) for v in (KB, KB + 1)}
+    seen = set()
+    for bank, out_len, n_valid, blocks, flags, w, launch, bits in _cases(seams):
+        if not w["spectrogram"] or w["mel"] or bits & REFUSED:
+            continue
+        case = (bank, out_len, n_valid, blocks, flags, w, launch, bits)
+        if n_valid == KB and not bits & SPECTRAL:
+            assert launch == "W", case                   # time-domain rows: the wide kernel, buffer or not, cross-faded or not
+        elif n_valid == KB:
+            assert launch in "TR", case                  # no wide kernel reads spectra
+        elif flags & 2 or blocks > 16:
+            assert launch == "T" and bool(bits & HANDOVER) == (not w["waveform"]), case
+        else:
+            assert launch == "R", case
+        seen.add(launch)
+    assert seen == set("WRT")
