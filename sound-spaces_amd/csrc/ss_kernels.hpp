@@ -353,6 +353,190 @@ __device__ __forceinline__ void stft_block(c32* sc, int lane, c32 wq, const c32*
     }
 }
 
+#if !defined(SS_NO_STFT_PAIR)
+// ---- TWO pooled blocks of one wave as interleaved chains (stft_block_pair) ---------------------------------------------
+// stft_block is five dependent LDS round trips with butterflies between them, and a wave that owns two blocks used to run
+// them back to back: the second block's frames sat in registers for the whole first block.  The pair runs both blocks
+// through the wave's ONE scratch, each block's round trips issued under the other block's arithmetic.  That needs no
+// further LDS and no barrier: the LDS unit executes a wave's instructions in issue order (wave_sync), so a store of block B
+// issued behind a load of block A cannot overtake it.  Every value is computed by the operations of stft_block in
+// stft_block's order - only the issue order differs - so the results are the same bits.  The stages below are stft_block's,
+// cut at its LDS phases; what they do NOT keep are its lane-conditional accesses (q == 0, lane == 0): a branch ends the
+// scheduling region and the interleave with it, so Z[128] and row 64 are read by every lane (a broadcast) and used by one,
+// and the two odd slots of the partial sums are written as sixteen (slots 96..111 of a frame: 98.. are padding).
+
+// x[r] *= w^r and y[r] *= w^r from ONE power chain (twiddle16's products in twiddle16's order; the powers depend on the
+// lane alone)
+__device__ __forceinline__ void twiddle16_pair(c32 (&x)[16], c32 (&y)[16], c32 w) {
+    const c32 w2 = cmul(w, w), w3 = cmul(w2, w), w4 = cmul(w2, w2);
+    x[1] = cmul(x[1], w);    y[1] = cmul(y[1], w);    x[2] = cmul(x[2], w2);   y[2] = cmul(y[2], w2);
+    x[3] = cmul(x[3], w3);   y[3] = cmul(y[3], w3);   x[4] = cmul(x[4], w4);   y[4] = cmul(y[4], w4);
+    const c32 w5 = cmul(w4, w), w6 = cmul(w3, w3), w7 = cmul(w4, w3), w8 = cmul(w4, w4);
+    x[5] = cmul(x[5], w5);   y[5] = cmul(y[5], w5);   x[6] = cmul(x[6], w6);   y[6] = cmul(y[6], w6);
+    x[7] = cmul(x[7], w7);   y[7] = cmul(y[7], w7);   x[8] = cmul(x[8], w8);   y[8] = cmul(y[8], w8);
+    c32 p;
+    p = cmul(w8, w);   x[9] = cmul(x[9], p);    y[9] = cmul(y[9], p);
+    p = cmul(w5, w5);  x[10] = cmul(x[10], p);  y[10] = cmul(y[10], p);
+    p = cmul(w8, w3);  x[11] = cmul(x[11], p);  y[11] = cmul(y[11], p);
+    p = cmul(w6, w6);  x[12] = cmul(x[12], p);  y[12] = cmul(y[12], p);
+    p = cmul(w8, w5);  x[13] = cmul(x[13], p);  y[13] = cmul(y[13], p);
+    p = cmul(w7, w7);  x[14] = cmul(x[14], p);  y[14] = cmul(y[14], p);
+    p = cmul(w8, w7);  x[15] = cmul(x[15], p);  y[15] = cmul(y[15], p);
+}
+
+struct StftQuads { f32x4 k01[2], k23[2], p01[2], p23[2]; c32 z128; };     // a lane's bins of one block (see stft_block)
+struct StftTwQuads { f32x4 w01[2], w23[2]; };                            // its tw512 quads: the same for every block
+struct StftSums { float dsum[2], m0[2], m123[2], x128; };                // its partial sums
+struct StftGather { float a[4], b[4], c[4]; };                           // the terms of pooled row `lane` (c: of row 64)
+
+__device__ __forceinline__ void stft_tile_st(c32* fr, int q, const c32 (&x)[16]) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) lds_st(fr + r * 17 + q, x[r]);
+}
+__device__ __forceinline__ void stft_tile_ld(const c32* fr, int q, c32 (&x)[16]) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) x[r] = lds_ld(fr + q * 17 + r);
+}
+__device__ __forceinline__ void stft_nat_st(c32* fn, int q, const c32 (&x)[16]) {
+#pragma unroll
+    for (int s = 0; s < 16; ++s) lds_st(fn + q + posN(16 * s), x[s]);
+}
+__device__ __forceinline__ void stft_quads_ld(const c32* fn, int q, StftQuads& Z) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int b = q + 16 * i;
+        const f32x4* zk4 = reinterpret_cast<const f32x4*>(fn + posN(4 * b));
+        const f32x4* zp4 = reinterpret_cast<const f32x4*>(fn + posN(252 - 4 * b));
+        Z.k01[i] = zk4[0]; Z.k23[i] = zk4[1]; Z.p01[i] = zp4[0]; Z.p23[i] = zp4[1];
+    }
+    Z.z128 = fn[posN(128)];
+}
+__device__ __forceinline__ void stft_tw_quads_ld(const c32* tw512, int q, StftTwQuads& W) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const f32x4* w4 = reinterpret_cast<const f32x4*>(tw512 + posN(4 * (q + 16 * i)));
+        W.w01[i] = w4[0]; W.w23[i] = w4[1];
+    }
+}
+// Hermitian split, magnitudes and partial sums of one block: the arithmetic of stft_block, statement for statement
+__device__ __forceinline__ void stft_magnitudes(const StftQuads& Z, const StftTwQuads& W, int lane, StftSums& S) {
+    const int q = lane & 15;
+    const c32 prev0 = mk2(row_ror1(Z.p01[0].x, lane), row_ror1(Z.p01[0].y, lane));
+    const c32 prev1 = mk2(row_ror1(Z.p01[1].x, lane), row_ror1(Z.p01[1].y, lane));
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const c32 ptop = i == 0 ? (q == 0 ? Z.k01[0].xy : prev0) : (q == 0 ? prev0 : prev1);
+        const c32 zk[4] = {Z.k01[i].xy, Z.k01[i].zw, Z.k23[i].xy, Z.k23[i].zw};
+        const c32 zp[4] = {ptop, Z.p23[i].zw, Z.p23[i].xy, Z.p01[i].zw};
+        const c32 ww[4] = {W.w01[i].xy, W.w01[i].zw, W.w23[i].xy, W.w23[i].zw};
+        float d = 0.f, m = 0.f;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const c32 P = add_conj(zk[e], zp[e]), Q = sub_conj(zk[e], zp[e]);
+            const c32 wq = cmul(Q, ww[e]);
+            const c32 m2 = mag2(xy_re(P, wq), xy_im(P, wq));
+            d += fast_sqrt(m2.x);
+            const float my = fast_sqrt(m2.y);
+            if (e == 0) S.m0[i] = 0.5f * my; else m += my;
+        }
+        S.dsum[i] = 0.5f * d;
+        S.m123[i] = 0.5f * m;
+    }
+    const c32 z = Z.z128;
+    S.x128 = fast_sqrt(z.x * z.x + z.y * z.y);            // (used by q == 0 alone)
+}
+__device__ __forceinline__ void stft_sums_st(float* ps, int lane, const StftSums& S) {
+    const int f = lane >> 4, q = lane & 15;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        ps[f * kPsStride + q + 16 * i] = S.dsum[i];
+        ps[f * kPsStride + 32 + q + 16 * i] = S.m0[i];
+        ps[f * kPsStride + 64 + q + 16 * i] = S.m123[i];
+    }
+    ps[f * kPsStride + 96 + q] = q == 0 ? S.x128 : 0.f;   // slot 96: |X[128]|; 97: the gather's zero; 98..111: padding
+}
+__device__ __forceinline__ void stft_gather_ld(const float* ps, int lane, StftGather& G) {
+    const int r = lane;
+    const bool lo = r < 32, mid = r == 32;
+    const int oa = lo ? r : mid ? 64 + 31 : 64 + 63 - r;
+    const int ob = lo ? 97 : mid ? 96 : 32 + 64 - r;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) { G.a[g] = ps[g * kPsStride + oa]; G.b[g] = ps[g * kPsStride + ob]; G.c[g] = ps[g * kPsStride + 32]; }
+}
+template <class STORE>
+__device__ __forceinline__ void stft_pooled_out(const StftGather& G, int lane, STORE store) {
+    float v = 0.f;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) v += G.a[g] + G.b[g];
+    store(lane, fast_log1p(v * (1.0f / 16.0f)));
+    float v64 = 0.f;                                      // row 64 = bin 256 alone: M0[0] of the 4 frames
+#pragma unroll
+    for (int g = 0; g < 4; ++g) v64 += G.c[g];
+    const float r64 = fast_log1p(v64 * (1.0f / 16.0f));
+    if (lane == 0) store(64, r64);
+}
+static_assert(kPsStride >= 96 + 16, "stft_sums_st writes slots 96..111 of a frame's partial sums");
+
+// Block A = x0, block B = x1, both in the scratch sc; store0 / store1 take their pooled values.  Equal, value for value, to
+// stft_block(x0, store0); wave_sync(); stft_block(x1, store1).  Every wave_sync() stands where one LDS phase hands data to
+// other lanes of the wave or frees a region for the other block; the SSK_SCHED_BARRIER()s keep the compiler from sinking a
+// block's LDS operations under the arithmetic they are meant to run beneath.
+template <class STORE0, class STORE1>
+__device__ __forceinline__ void stft_block_pair(c32* sc, int lane, c32 wq, const c32* tw512, c32 (&x0)[16], c32 (&x1)[16],
+                                                STORE0 store0, STORE1 store1) {
+    const int f = lane >> 4, q = lane & 15;
+    c32* fr = sc + f * kFrameStride;
+    c32* fn = sc + f * kNatStride;
+    float* ps = reinterpret_cast<float*>(sc);
+    // 1. first radix-16 pass of both blocks, one twiddle chain
+    fft16<false>(x0);
+    fft16<false>(x1);
+    SSK_OPAQUE2(wq);
+    twiddle16_pair(x0, x1, wq);
+    // 2. both transposes in flight, B's under A's second pass
+    stft_tile_st(fr, q, x0);
+    wave_sync();
+    stft_tile_ld(fr, q, x0);
+    wave_sync();                                          // A's tiles are read: B's may overwrite them
+    stft_tile_st(fr, q, x1);
+    wave_sync();
+    stft_tile_ld(fr, q, x1);
+    SSK_SCHED_BARRIER();
+    fft16<false>(x0);                                     // x0[s] = Z_A[q + 16 s]
+    wave_sync();                                          // B's tiles are read: the natural-order spectra overlay them
+    // 3. A's spectrum out and its quads back in, B's second pass under them
+    stft_nat_st(fn, q, x0);
+    wave_sync();
+    StftQuads za, zb;
+    StftTwQuads w;
+    stft_quads_ld(fn, q, za);
+    stft_tw_quads_ld(tw512, q, w);
+    SSK_SCHED_BARRIER();
+    fft16<false>(x1);
+    wave_sync();                                          // A's quads are read: B's spectrum may overwrite A's
+    stft_nat_st(fn, q, x1);
+    wave_sync();
+    stft_quads_ld(fn, q, zb);
+    SSK_SCHED_BARRIER();
+    // 4. A's magnitudes under B's loads, B's under A's partial sums and gather
+    StftSums sa, sb;
+    StftGather ga, gb;
+    stft_magnitudes(za, w, lane, sa);
+    wave_sync();                                          // B's quads are read: the partial sums overlay frame 0's spectrum
+    stft_sums_st(ps, lane, sa);
+    wave_sync();
+    stft_gather_ld(ps, lane, ga);
+    SSK_SCHED_BARRIER();
+    stft_magnitudes(zb, w, lane, sb);
+    wave_sync();                                          // A's sums are read
+    stft_sums_st(ps, lane, sb);
+    wave_sync();
+    stft_gather_ld(ps, lane, gb);
+    stft_pooled_out(ga, lane, store0);
+    stft_pooled_out(gb, lane, store1);
+}
+#endif  // !SS_NO_STFT_PAIR
+
 struct SpecParams {
     const float* x;       // [N][2][len]
     float* out;           // [N][65][T4][2]
@@ -1439,12 +1623,21 @@ __device__ __forceinline__ void fused_stft_phase(c32* lds, const ConvParams& p, 
             for (int b = t >> 5; b < kBins4; b += kT / 32) o[2 * (b * p.t4 + k)] = k < live ? s_res[b * p.t4 + k] : 0.f;
         return;
     }
+#if defined(SS_NO_STFT_PAIR)                                       // (A/B arm: a wave's two blocks one after the other)
     if (one)
         stft_block(lds + wv * kWaveScratch, lane, wq, s_tw512, x0, [&](int b, float v) { s_res[b * rs + bw] = v; });
     if (two) {
         wave_sync();
         stft_block(lds + wv * kWaveScratch, lane, wq, s_tw512, x1, [&](int b, float v) { s_res[b * rs + bw + 16] = v; });
     }
+#else
+    // a wave with two blocks (t4 > 16: whole rows only, a split row's share is at most 13) runs them as interleaved chains
+    if (two)
+        stft_block_pair(lds + wv * kWaveScratch, lane, wq, s_tw512, x0, x1, [&](int b, float v) { s_res[b * rs + bw] = v; },
+                        [&](int b, float v) { s_res[b * rs + bw + 16] = v; });
+    else if (one)
+        stft_block(lds + wv * kWaveScratch, lane, wq, s_tw512, x0, [&](int b, float v) { s_res[b * rs + bw] = v; });
+#endif
     lds_barrier();
     float* o = p.sgram + (size_t)unit * kBins4 * p.t4 * 2 + ch;
     if (WIDE) {                                             // t4 columns per pooled row, the live ones from s_res
