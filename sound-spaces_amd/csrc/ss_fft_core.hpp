@@ -127,9 +127,7 @@ __device__ __forceinline__ void lds_st(c32* p, c32 v) {
 }
 
 constexpr int kM = 16384;            // complex points of one block FFT
-constexpr int kT = 1024;             // threads per workgroup
 constexpr int kLdsComplex = 4 * 4352;  // 17408 complex = 139264 B (layout B; layout A needs 16640)
-constexpr int kSpecComplex = 16384;  // complex values of one stored block spectrum (kernel order)
 constexpr int kTwM = 1024;           // entries of twM:  exp(-2*pi*i*t/16384), t < 1024
 constexpr int kTwItem = 2048;        // entries of twItem: exp(-2*pi*i*gA(q)/32768), q < 2048
 

@@ -17,6 +17,7 @@
 #include "ss_kernels.hpp"
 #include "ss_kernels32.hpp"
 #include "ss_route.hpp"
+#include "ss_launch.hpp"
 #include "ss_features.hpp"
 #include "ss_tables.hpp"
 #include "ss_wavio.hpp"
@@ -153,82 +154,77 @@ inline bool fill_unit_tab(ssk::UnitTab<true>& ut, const LaunchEnv& env, int n_un
     return true;
 }
 
-// Small steps (fewer rows than CUs): a fused one-block row is rendered by 2^k workgroups on as many CUs, each running the
-// row's convolution and its share of the pooled STFT blocks (ConvParams::parts_log2) - as long as the grid still fits the
-// chip in one round of one workgroup per CU.  26 pooled blocks: k <= 3 (shares of 13 / 7 / 4 blocks).
-inline int parts_log2_for(int n_rows, int n_cus, int share) {
-    static const int forced = ab_int("SS_HIP_PARTS_LOG2", -1);        // (A/B builds only: -DSS_AB)
-    if (forced >= 0) return forced < 3 ? forced : 3;
-    const int cus = n_cus / (share > 1 ? share : 1);       // overlap mode: the lanes share the chip
-    int k = 0;
-    while (k < 3 && (n_rows << (k + 1)) <= cus) ++k;
-    return k;
+// the A/B switches the launch geometry of ss_launch.hpp takes as plain values (A/B builds only: -DSS_AB)
+inline const sslaunch::Switches& launch_switches() {
+    static const sslaunch::Switches sw{ab_int("SS_HIP_PARTS_LOG2", -1), ab_flag("SS_HIP_NO_ROW_KERNEL"), ab_flag("SS_HIP_NO_OBS_BLOCKS")};
+    return sw;
 }
 
+// The convolution of whichever bank form the launch reads, fused with the STFT (FUSE) or not: sslaunch::plan_conv decides
+// refusal, kernel variant, parts and grid; here the unit table is filled where the plan allows one and the variant picks the
+// instantiation.  hs: the scales of a half spectral bank (Form::kSpec16 / kSpec16Buckets), rs: those of half rows (Form::kRows16).
+// Half-precision time-domain rows (include/ss_hip.h "Half-precision time-domain rows"): k_conv<.., HALF> for every launch - no
+// cross-fade, no wide form, no persistent row kernel.  Half bank (include/ss_hip.h "Half-precision spectral bank"): k_conv_spec
+// <.., HALF> for every launch (more rows than CUs included: the persistent k_conv_spec_rows has no half form).  Half buckets:
+// launches that only touch bucket 0 (one bucket, or SS_FLAG_FIRST_BUCKET) are single-allocation launches on bucket 0's arrays:
+// the HALF kernels, the loop-free ones included; everything else: k_conv_spec<.., HALF, HBK>.
 template <bool FUSE>
-int launch_conv(ssk::ConvParams p, int n_units, int nb_y, int flags, int n_cus, const LaunchEnv& env, bool wide = false) {
+int launch_conv(sslaunch::Form form, ssk::ConvParams p, int n_units, int nb_y, int flags, int n_cus, const LaunchEnv& env,
+                bool wide = false, const ssk::SpecScale<true, true>* hs = nullptr, const ssk::RowScale<true>* rs = nullptr) {
+    using sslaunch::Form;
+    using V = sslaunch::Variant;
     const hipStream_t st = env.st;
-    if (nb_y < 1 || nb_y > 3 || (FUSE && nb_y != 1)) return SS_EINVAL;
-    p.nb_y = nb_y;
-    p.parts_log2 = FUSE && !wide ? parts_log2_for(2 * n_units, n_cus, env.share) : 0;
-    if constexpr (FUSE) {
-        if (wide) {
-            if ((flags & SS_FLAG_CROSSFADE) && (p.fade_len < 1 || p.fade_len > 2 * ssk::kPrevPairs - 2)) return SS_EINVAL;
-            const dim3 grid(2 * n_units, 1), block(ssk::kT);
-            if (flags & SS_FLAG_CROSSFADE)
-                hipLaunchKernelGGL((ssk::k_conv<true, false, true, false, true>), grid, block, 0, st, p, ssk::UnitTab<false>());
-            else
-                hipLaunchKernelGGL((ssk::k_conv<true, false, false, false, true>), grid, block, 0, st, p, ssk::UnitTab<false>());
-            return hip_err(hipGetLastError());
-        }
-    }
-    // the loop-free kernels address bucket 0 only: a bucketed bank qualifies when the caller promises that every index
-    // of the launch lies there (SS_FLAG_FIRST_BUCKET; the context's planner works it out per step)
-    const bool bucket0 = p.n_buckets == 1 || (flags & SS_FLAG_FIRST_BUCKET);
-    const bool simple = (flags & SS_FLAG_NO_DISTRACTOR) && !(flags & SS_FLAG_CROSSFADE) && nb_y == 1 &&
-                        p.rir_cap <= ssk::kB && bucket0;
-    if ((flags & SS_FLAG_CROSSFADE) && (p.fade_len < 1 || p.fade_len > 2 * ssk::kPrevPairs - 2)) return SS_EINVAL;
-    const dim3 grid((2 * n_units) << p.parts_log2, nb_y), block(ssk::kT);
-    // more rows than CUs: persistent workgroups that prefetch the next row's RIR under the current row's FFT passes
     const bool planar = p.rir_elem_stride == 1 && !(p.rir_cap & 1) && !(reinterpret_cast<size_t>(p.rir) & 7) &&
                         !(p.rir_unit_stride & 1) && !(p.rir_chan_stride & 1) && p.rir_cap >= 2;
-    static const bool no_rows = ab_flag("SS_HIP_NO_ROW_KERNEL");
-    if constexpr (!FUSE) {              // the fused kernel gains nothing from it (measured), see k_conv_rows
-        if (simple && planar && !no_rows && 2 * n_units > n_cus) {
-            hipLaunchKernelGGL(ssk::k_conv_rows, dim3(n_cus), block, 0, st, p, 2 * n_units);
-            return hip_err(hipGetLastError());
+    const sslaunch::ConvPlan pl = sslaunch::plan_conv(form, FUSE, wide, flags, p.rir_cap, p.h_blocks, p.n_buckets, p.fade_len, planar,
+                                                      !(reinterpret_cast<size_t>(p.hspec) & 15), n_units, nb_y, n_cus, env.share,
+                                                      launch_switches());
+    if (pl.rc) return pl.rc;
+    sslaunch::apply(pl, p);
+    const dim3 grid(pl.grid_x, pl.grid_y), block(ssk::kT);
+    const ssk::UnitTab<false> nt;
+    ssk::UnitTab<true> ut;
+    const bool simple = pl.variant == V::kSimple;
+    const bool tab = pl.tab_ok && fill_unit_tab(ut, env, n_units);
+    if (form == Form::kRows) {
+        switch (pl.variant) {
+            case V::kPersistRows:
+                if constexpr (!FUSE) hipLaunchKernelGGL(ssk::k_conv_rows, grid, block, 0, st, p, 2 * n_units);
+                break;
+            case V::kWide:
+                if constexpr (FUSE) hipLaunchKernelGGL((ssk::k_conv<true, false, false, false, true>), grid, block, 0, st, p, nt);
+                break;
+            case V::kWideXfade:
+                if constexpr (FUSE) hipLaunchKernelGGL((ssk::k_conv<true, false, true, false, true>), grid, block, 0, st, p, nt);
+                break;
+            case V::kXfade: hipLaunchKernelGGL((ssk::k_conv<FUSE, false, true>), grid, block, 0, st, p, nt); break;
+            case V::kSimple:
+                if (tab) hipLaunchKernelGGL((ssk::k_conv<FUSE, true, false, true>), grid, block, 0, st, p, ut);
+                else hipLaunchKernelGGL((ssk::k_conv<FUSE, true>), grid, block, 0, st, p, nt);
+                break;
+            case V::kLoop: hipLaunchKernelGGL((ssk::k_conv<FUSE, false>), grid, block, 0, st, p, nt); break;
         }
+    } else if (form == Form::kRows16) {
+        if (tab) hipLaunchKernelGGL((ssk::k_conv<FUSE, true, false, true, false, false, true>), grid, block, 0, st, p, ut, *rs);
+        else if (simple) hipLaunchKernelGGL((ssk::k_conv<FUSE, true, false, false, false, false, true>), grid, block, 0, st, p, nt, *rs);
+        else hipLaunchKernelGGL((ssk::k_conv<FUSE, false, false, false, false, false, true>), grid, block, 0, st, p, nt, *rs);
+    } else if (form == Form::kSpec) {
+        if (pl.variant == V::kPersistRows) {
+            if constexpr (!FUSE) hipLaunchKernelGGL(ssk::k_conv_spec_rows, grid, block, 0, st, p, 2 * n_units);
+        } else if (tab) hipLaunchKernelGGL((ssk::k_conv_spec<FUSE, true, true>), grid, block, 0, st, p, ut);
+        else if (simple) hipLaunchKernelGGL((ssk::k_conv_spec<FUSE, true>), grid, block, 0, st, p, nt);
+        else hipLaunchKernelGGL((ssk::k_conv_spec<FUSE, false>), grid, block, 0, st, p, nt);
+    } else if (form == Form::kSpec16 || pl.bucket0) {
+        const ssk::SpecScale<true> hs1{hs->hscale};
+        if (tab) hipLaunchKernelGGL((ssk::k_conv_spec<FUSE, true, true, false, true>), grid, block, 0, st, p, ut, hs1);
+        else if (simple) hipLaunchKernelGGL((ssk::k_conv_spec<FUSE, true, false, false, true>), grid, block, 0, st, p, nt, hs1);
+        else hipLaunchKernelGGL((ssk::k_conv_spec<FUSE, false, false, false, true>), grid, block, 0, st, p, nt, hs1);
+    } else {
+        hipLaunchKernelGGL((ssk::k_conv_spec<FUSE, false, false, false, true, true>), grid, block, 0, st, p, nt, *hs);
     }
-    if (flags & SS_FLAG_CROSSFADE) hipLaunchKernelGGL((ssk::k_conv<FUSE, false, true>), grid, block, 0, st, p, ssk::UnitTab<false>());
-    else if (simple) {
-        ssk::UnitTab<true> ut;
-        if (fill_unit_tab(ut, env, n_units)) hipLaunchKernelGGL((ssk::k_conv<FUSE, true, false, true>), grid, block, 0, st, p, ut);
-        else hipLaunchKernelGGL((ssk::k_conv<FUSE, true>), grid, block, 0, st, p, ssk::UnitTab<false>());
-    }
-    else hipLaunchKernelGGL((ssk::k_conv<FUSE, false>), grid, block, 0, st, p, ssk::UnitTab<false>());
     return hip_err(hipGetLastError());
 }
 
-// ---- half-precision time-domain rows (include/ss_hip.h "Half-precision time-domain rows") ----------------------------------------
-// The launch body of launch_conv for a bank of fp16 rows + one scale per (entry, ear): the same decisions (loop-free kernel for
-// one-block rows without a distractor term, unit table when the host knows the descriptors, rows split over idle CUs, XCD map),
-// k_conv<.., HALF> for every launch - no cross-fade, no wide form, no persistent row kernel.
-template <bool FUSE>
-int launch_conv16(ssk::ConvParams p, const ssk::RowScale<true>& rs, int n_units, int nb_y, int flags, int n_cus, const LaunchEnv& env) {
-    const hipStream_t st = env.st;
-    if (nb_y < 1 || nb_y > 3 || (FUSE && nb_y != 1) || (flags & SS_FLAG_CROSSFADE)) return SS_EINVAL;
-    p.nb_y = nb_y;
-    p.parts_log2 = FUSE ? parts_log2_for(2 * n_units, n_cus, env.share) : 0;
-    const bool simple = (flags & SS_FLAG_NO_DISTRACTOR) && nb_y == 1 && p.rir_cap <= ssk::kB;
-    const dim3 grid((2 * n_units) << p.parts_log2, nb_y), block(ssk::kT);
-    if (simple) {
-        ssk::UnitTab<true> ut;
-        if (fill_unit_tab(ut, env, n_units))
-            hipLaunchKernelGGL((ssk::k_conv<FUSE, true, false, true, false, false, true>), grid, block, 0, st, p, ut, rs);
-        else hipLaunchKernelGGL((ssk::k_conv<FUSE, true, false, false, false, false, true>), grid, block, 0, st, p, ssk::UnitTab<false>(), rs);
-    } else hipLaunchKernelGGL((ssk::k_conv<FUSE, false, false, false, false, false, true>), grid, block, 0, st, p, ssk::UnitTab<false>(), rs);
-    return hip_err(hipGetLastError());
-}
 
 // the arguments every half-rows entry refuses before a device is touched
 inline bool rows16_bank_ok(const void* rir16, const float* rscale, int cap) {
@@ -265,10 +261,9 @@ int get_stash(hipStream_t st, size_t bytes, float** out) {
     return 0;
 }
 
-// k_obs_blocks' hand-off area per (device, stream): [kSyncRows][2] tails of kTailFloats floats + as many flag words, zeroed once;
+// k_obs_blocks' hand-off area per (device, stream): [sslaunch::kSyncRows][2] tails of kTailFloats floats + as many flag words, zeroed once;
 // `epoch` counts the launches that used it (a flag holds the epoch of the launch that set it: nothing is reset in between -
 // which is also why such a launch cannot be replayed from a captured graph: the library never captures)
-constexpr int kSyncRows = 512;                                  // (unit, ear) rows a k_obs_blocks launch may have: more than CUs / 2
 struct SyncBuf { float* tails = nullptr; int* flags = nullptr; int epoch = 0; };
 std::map<std::pair<int, hipStream_t>, SyncBuf> g_sync;
 
@@ -280,7 +275,7 @@ int get_block_sync(hipStream_t st, float** tails, int** flags, int* epoch) {
     std::lock_guard<std::mutex> lk(g_mu);
     SyncBuf& b = g_sync[std::make_pair(dev, st)];
     if (!b.tails) {
-        const size_t n_hand = static_cast<size_t>(kSyncRows) * 2;
+        const size_t n_hand = sslaunch::handoff_flags(sslaunch::kSyncRows);
         const size_t bytes = n_hand * ssk::kTailFloats * sizeof(float) + n_hand * sizeof(int);
         void* ptr = nullptr;
         e = hipMalloc(&ptr, bytes);
@@ -313,55 +308,13 @@ void drop_stash(hipStream_t st) {
     g_stash.erase(it);
 }
 
-// Small steps of rows longer than one block (the reference's Replica arrangement: 5 envs per GPU at 44.1 kHz): one workgroup
-// per OUTPUT BLOCK of a row instead of one per row (k_obs_blocks) - while the whole grid fits the launch's share of the chip at
-// one workgroup per CU, which is also what makes the kernel's inter-workgroup hand-off safe.  Spare CUs go to parts (the STFT
-// phase of a block split 2 / 4 / 8 ways).  Returns 1 when the launch does not qualify (the caller falls through to k_obs_rows).
+// k_obs_blocks / k_obs_rows behind one launcher: sslaunch::plan_obs_rows gives the refusals and the row kernel's shape,
+// sslaunch::plan_obs_blocks says whether the step is small enough for one workgroup per OUTPUT BLOCK of a row (k_obs_blocks:
+// the hand-off area of the stream) - else k_obs_rows with its stash.
 // MEL: the log-mel instantiations (ss_audio_obs_logmel_rows_f32 / _spec_f32), same rule, same hand-off area.
 // HALF: the half-bank instantiations (ss_audio_obs_rows_spec16_f32 / ss_audio_obs_logmel_rows_spec16_f32), likewise.
 // HBK: a half bank in length buckets (ss_audio_obs_rows_spec16_buckets_f32 / ss_audio_obs_logmel_rows_spec16_buckets_f32), likewise.
 // ROWS16: half-precision time-domain rows (ss_audio_obs_rows_rir16_f32), likewise.
-template <bool SPECTRAL, bool MEL = false, bool HALF = false, bool HBK = false, bool ROWS16 = false>
-int launch_obs_blocks(ssk::ConvParams p, int n_units, int flags, int n_cus, const LaunchEnv& env,
-                      const ssk::UnitTab<false, MEL>& mel = ssk::UnitTab<false, MEL>(),
-                      const ssk::SpecScale<HALF, HBK>& hs = ssk::SpecScale<HALF, HBK>(),
-                      const ssk::RowScale<ROWS16>& rs = ssk::RowScale<ROWS16>()) {
-    const hipStream_t st = env.st;
-    static const bool off = ab_flag("SS_HIP_NO_OBS_BLOCKS");   // (A/B builds only)
-    const int n_rows = 2 * n_units, nb = (p.out_len + ssk::kB - 1) / ssk::kB;
-    const int budget = n_cus / (env.share > 1 ? env.share : 1);
-    if (off || (flags & SS_FLAG_CROSSFADE) || p.n_valid != p.out_len || nb < 2 || nb > 3 || n_rows * nb > budget ||
-        n_rows > kSyncRows || st == hipStreamPerThread)
-        return 1;
-    int k = 0;
-    while (k < 3 && ((n_rows * nb) << (k + 1)) <= budget) ++k;
-    p.parts_log2 = k;
-    p.nb_y = nb;
-    p.n_terms = (flags & SS_FLAG_NO_DISTRACTOR) ? 1 : 2;
-    p.stash = nullptr; p.stash_nbh = 0; p.stash_terms = 0;
-    float* tails = nullptr;
-    int* fl = nullptr;
-    int epoch = 0;
-    int rc = get_block_sync(st, &tails, &fl, &epoch);
-    if (rc) return rc;
-    const int grid = (n_rows * nb) << k;
-    if constexpr (ROWS16) {
-        hipLaunchKernelGGL((ssk::k_obs_blocks<false, false, false, false, true>), dim3(grid), dim3(ssk::kT), 0, st, p, n_rows, tails, fl, epoch,
-                           mel, hs, rs);
-        return hip_err(hipGetLastError());
-    }
-    if constexpr (HBK) {
-        hipLaunchKernelGGL((ssk::k_obs_blocks<SPECTRAL, MEL, true, true>), dim3(grid), dim3(ssk::kT), 0, st, p, n_rows, tails, fl, epoch, mel, hs);
-        return hip_err(hipGetLastError());
-    } else if constexpr (HALF) {
-        hipLaunchKernelGGL((ssk::k_obs_blocks<SPECTRAL, MEL, true>), dim3(grid), dim3(ssk::kT), 0, st, p, n_rows, tails, fl, epoch, mel, hs);
-        return hip_err(hipGetLastError());
-    }
-    if constexpr (MEL) hipLaunchKernelGGL((ssk::k_obs_blocks<SPECTRAL, true>), dim3(grid), dim3(ssk::kT), 0, st, p, n_rows, tails, fl, epoch, mel);
-    else hipLaunchKernelGGL((ssk::k_obs_blocks<SPECTRAL>), dim3(grid), dim3(ssk::kT), 0, st, p, n_rows, tails, fl, epoch);
-    return hip_err(hipGetLastError());
-}
-
 template <bool SPECTRAL, bool MEL = false, bool HALF = false, bool HBK = false, bool ROWS16 = false>
 int launch_obs_rows(ssk::ConvParams p, int n_units, int flags, int n_cus, const LaunchEnv& env,
                     const ssk::UnitTab<false, MEL>& mel = ssk::UnitTab<false, MEL>(),
@@ -372,65 +325,54 @@ int launch_obs_rows(ssk::ConvParams p, int n_units, int flags, int n_cus, const 
     static_assert(!HBK || HALF, "bucketed half bank: a half form");
     static_assert(!ROWS16 || (!SPECTRAL && !MEL && !HALF), "half rows: plain rows of one time-domain allocation");
     const int n_rows = 2 * n_units;
-    if ((MEL || HALF || ROWS16) && (flags & SS_FLAG_CROSSFADE)) return SS_EINVAL;                  // (the log-mel and half forms: plain rows)
-    if (((HALF && !HBK) || ROWS16) && p.n_buckets != 1) return SS_EINVAL;                           // (half: one allocation, or the HBK form)
-    {
-        const int rc = launch_obs_blocks<SPECTRAL, MEL, HALF, HBK, ROWS16>(p, n_units, flags, n_cus, env, mel, hs, rs);
-        if (rc != 1) return rc;
+    const dim3 block(ssk::kT);
+    // (the log-mel and half forms: plain rows; half: one allocation, or the HBK form)
+    const sslaunch::ObsRowsPlan pr = sslaunch::plan_obs_rows(SPECTRAL, MEL || HALF || ROWS16, (HALF && !HBK) || ROWS16, flags, p.n_valid,
+                                                             p.n_buckets, sslaunch::rows_nbh_max(p), n_units, n_cus, env.share,
+                                                             launch_switches());
+    if (pr.rc) return pr.rc;
+    const sslaunch::ObsBlocksPlan pb = sslaunch::plan_obs_blocks(flags, p.out_len, p.n_valid, n_units, n_cus, env.share,
+                                                                 st != hipStreamPerThread, launch_switches());
+    if (pb.ok) {
+        float* tails = nullptr;
+        int* fl = nullptr;
+        int epoch = 0;
+        const int rc = get_block_sync(st, &tails, &fl, &epoch);
+        if (rc) return rc;
+        sslaunch::apply(pb, p);
+        const dim3 grid(pb.grid);
+        if constexpr (ROWS16)
+            hipLaunchKernelGGL((ssk::k_obs_blocks<false, false, false, false, true>), grid, block, 0, st, p, n_rows, tails, fl, epoch, mel, hs, rs);
+        else if constexpr (HBK) hipLaunchKernelGGL((ssk::k_obs_blocks<SPECTRAL, MEL, true, true>), grid, block, 0, st, p, n_rows, tails, fl, epoch, mel, hs);
+        else if constexpr (HALF) hipLaunchKernelGGL((ssk::k_obs_blocks<SPECTRAL, MEL, true>), grid, block, 0, st, p, n_rows, tails, fl, epoch, mel, hs);
+        else if constexpr (MEL) hipLaunchKernelGGL((ssk::k_obs_blocks<SPECTRAL, true>), grid, block, 0, st, p, n_rows, tails, fl, epoch, mel);
+        else hipLaunchKernelGGL((ssk::k_obs_blocks<SPECTRAL>), grid, block, 0, st, p, n_rows, tails, fl, epoch);
+        return hip_err(hipGetLastError());
     }
-    // small steps (the reference steps 5-10 envs per GPU at this rate): a row on 2 / 4 / 8 CUs, each rendering the row and
-    // its share of every phase's pooled STFT blocks - only while every (row, part) still gets a workgroup of its own
-    // Time-domain bank: every part also repeats the row's stash round trip (640 KiB per row), and the launch turns
-    // memory-bound long before the CUs run out - same box, alternating, us per launch at 1 / 5 / 10 / 16 units with up to 8
-    // parts per row: 58.7 / 62.2 / 69.5 / 75.4 against 70.8 / 71.1 / 72.1 / 72.6 with one (profiles/r5/kbench_parts_44k.txt) -
-    // so the split stops at 96 workgroups there.  The spectral bank has no stash: -20 % up to 32 units (256 workgroups).
-    p.parts_log2 = parts_log2_for(n_rows, SPECTRAL ? n_cus : std::min(n_cus, 96), env.share);
-    const int grid = (n_rows << p.parts_log2) < n_cus ? (n_rows << p.parts_log2) : n_cus;
-    p.nb_y = p.n_valid == 0 ? 0 : (p.n_valid + ssk::kB - 1) / ssk::kB;
-    p.stash = nullptr;
-    p.stash_nbh = 0;
-    p.stash_terms = 0;
-    p.n_terms = (flags & SS_FLAG_NO_DISTRACTOR) ? 1 : 2;
-    const bool xfade = (flags & SS_FLAG_CROSSFADE) != 0;
-    if (xfade && (SPECTRAL || p.n_terms != 2)) return SS_EINVAL;
-    // Time-domain bank: the kernel transforms every RIR block once per row and keeps the spectra that are needed again
-    // in a per-workgroup stash (k_obs_rows); 44.1 kHz: 2 x 128 KiB written and 3 x 128 KiB read back per row.
-    if (!SPECTRAL) {
-        int nbh_max = (p.rir_cap + ssk::kB - 1) / ssk::kB;
-        for (int b = 0; b + 1 < p.n_buckets; ++b) nbh_max = std::max(nbh_max, (p.bk[b].cap + ssk::kB - 1) / ssk::kB);
-        p.stash_terms = p.n_terms;                              // no distractor terms: half the stash
-        p.stash_nbh = nbh_max;
-        const size_t per_wg = static_cast<size_t>(p.stash_terms) * nbh_max * ssk::kSpecComplex * sizeof(ssk::c32);
+    sslaunch::apply(pr, p);
+    if constexpr (!SPECTRAL) {                                  // (sized from the deepest bucket and n_terms - half rows as fp32 rows)
         float* buf = nullptr;
-        int rc = get_stash(st, per_wg * static_cast<size_t>(grid), &buf);
+        const int rc = get_stash(st, pr.stash_bytes, &buf);
         if (rc) return rc;
         p.stash = reinterpret_cast<ssk::f32x4*>(buf);
     }
-    if constexpr (ROWS16) {                                     // (the stash above: sized from rir_cap and n_terms, as for fp32 rows)
-        hipLaunchKernelGGL((ssk::k_obs_rows<false, false, false, false, false, true>), dim3(grid), dim3(ssk::kT), 0, st, p, n_rows, mel, hs, rs);
-        return hip_err(hipGetLastError());
-    }
-    if constexpr (!SPECTRAL) {
+    const dim3 grid(pr.grid);
+    if constexpr (ROWS16) hipLaunchKernelGGL((ssk::k_obs_rows<false, false, false, false, false, true>), grid, block, 0, st, p, n_rows, mel, hs, rs);
+    else if constexpr (HBK) hipLaunchKernelGGL((ssk::k_obs_rows<true, false, true, MEL, true>), grid, block, 0, st, p, n_rows, mel, hs);
+    else if constexpr (HALF) hipLaunchKernelGGL((ssk::k_obs_rows<true, false, false, MEL, true>), grid, block, 0, st, p, n_rows, mel, hs);
+    else if constexpr (MEL) {                                   // (length buckets: the instantiation that resolves them)
+        if (p.n_buckets == 1) hipLaunchKernelGGL((ssk::k_obs_rows<SPECTRAL, false, false, true>), grid, block, 0, st, p, n_rows, mel);
+        else hipLaunchKernelGGL((ssk::k_obs_rows<SPECTRAL, false, true, true>), grid, block, 0, st, p, n_rows, mel);
+    } else {
+        bool xfade = false;
+        if constexpr (!SPECTRAL) xfade = (flags & SS_FLAG_CROSSFADE) != 0;
         if (xfade) {
-            hipLaunchKernelGGL((ssk::k_obs_rows<false, true>), dim3(grid), dim3(ssk::kT), 0, st, p, n_rows);
-            return hip_err(hipGetLastError());
+            if constexpr (!SPECTRAL) hipLaunchKernelGGL((ssk::k_obs_rows<false, true>), grid, block, 0, st, p, n_rows);
         }
+        // one bank allocation (every launch but those of a length-bucketed store): the instantiation without the bucket descriptors
+        else if (p.n_buckets == 1) hipLaunchKernelGGL((ssk::k_obs_rows<SPECTRAL, false, false>), grid, block, 0, st, p, n_rows);
+        else hipLaunchKernelGGL((ssk::k_obs_rows<SPECTRAL>), grid, block, 0, st, p, n_rows);
     }
-    if constexpr (HBK) {
-        hipLaunchKernelGGL((ssk::k_obs_rows<true, false, true, MEL, true>), dim3(grid), dim3(ssk::kT), 0, st, p, n_rows, mel, hs);
-        return hip_err(hipGetLastError());
-    } else if constexpr (HALF) {
-        hipLaunchKernelGGL((ssk::k_obs_rows<true, false, false, MEL, true>), dim3(grid), dim3(ssk::kT), 0, st, p, n_rows, mel, hs);
-        return hip_err(hipGetLastError());
-    }
-    if constexpr (MEL) {                                        // (length buckets: the instantiation that resolves them)
-        if (p.n_buckets == 1) hipLaunchKernelGGL((ssk::k_obs_rows<SPECTRAL, false, false, true>), dim3(grid), dim3(ssk::kT), 0, st, p, n_rows, mel);
-        else hipLaunchKernelGGL((ssk::k_obs_rows<SPECTRAL, false, true, true>), dim3(grid), dim3(ssk::kT), 0, st, p, n_rows, mel);
-        return hip_err(hipGetLastError());
-    }
-    // one bank allocation (every launch but those of a length-bucketed store): the instantiation without the bucket descriptors
-    if (p.n_buckets == 1) hipLaunchKernelGGL((ssk::k_obs_rows<SPECTRAL, false, false>), dim3(grid), dim3(ssk::kT), 0, st, p, n_rows);
-    else hipLaunchKernelGGL((ssk::k_obs_rows<SPECTRAL>), dim3(grid), dim3(ssk::kT), 0, st, p, n_rows);
     return hip_err(hipGetLastError());
 }
 
@@ -442,8 +384,6 @@ inline bool mel_args_ok(const float* logmel, const int* mel_start, const float* 
            !(reinterpret_cast<size_t>(mel_w) & 15);
 }
 int launch_conv_mel(ssk::ConvParams p, const ssk::MelArgs& m, int n_units, int flags, hipStream_t st) {
-    p.nb_y = 1;
-    p.parts_log2 = 0;
     const bool simple = (flags & SS_FLAG_NO_DISTRACTOR) && p.rir_cap <= ssk::kB && p.n_buckets == 1;
     const dim3 grid(2 * n_units), block(ssk::kT);
     if (simple) hipLaunchKernelGGL((ssk::k_conv<true, true, false, false, false, true>), grid, block, 0, st, p, m);
@@ -454,8 +394,6 @@ int launch_conv_mel(ssk::ConvParams p, const ssk::MelArgs& m, int n_units, int f
 // SoundSpaces 2.0 steps (ss_audio_obs_logmel_ss2_f32): the cross-faded one-block row and the WIDE row (block 0 of a longer row,
 // with or without the cross-fade) in their log-mel forms - the loop kernel, one workgroup per (unit, ear) row
 int launch_conv_mel_ss2(ssk::ConvParams p, const ssk::MelArgs& m, int n_units, int flags, bool wide, hipStream_t st) {
-    p.nb_y = 1;
-    p.parts_log2 = 0;
     const bool xfade = (flags & SS_FLAG_CROSSFADE) != 0;
     if (xfade && (p.fade_len < 1 || p.fade_len > 2 * ssk::kPrevPairs - 2)) return SS_EINVAL;
     const dim3 grid(2 * n_units), block(ssk::kT);
@@ -466,8 +404,6 @@ int launch_conv_mel_ss2(ssk::ConvParams p, const ssk::MelArgs& m, int n_units, i
 }
 
 int launch_conv_spec_mel(ssk::ConvParams p, const ssk::MelArgs& m, int n_units, int flags, hipStream_t st) {
-    p.nb_y = 1;
-    p.parts_log2 = 0;
     const bool simple = (flags & SS_FLAG_NO_DISTRACTOR) && p.h_blocks == 1 && p.n_buckets == 1;
     const dim3 grid(2 * n_units), block(ssk::kT);
     if (simple) hipLaunchKernelGGL((ssk::k_conv_spec<true, true, false, true>), grid, block, 0, st, p, m);
@@ -477,8 +413,6 @@ int launch_conv_spec_mel(ssk::ConvParams p, const ssk::MelArgs& m, int n_units, 
 
 // ... from a half bank (fp16 block spectra + one scale per block: ssk::SpecScale)
 int launch_conv_spec16_mel(ssk::ConvParams p, const ssk::MelArgs& m, const float* hscale, int n_units, int flags, hipStream_t st) {
-    p.nb_y = 1;
-    p.parts_log2 = 0;
     const bool simple = (flags & SS_FLAG_NO_DISTRACTOR) && p.h_blocks == 1;
     const dim3 grid(2 * n_units), block(ssk::kT);
     const ssk::SpecScale<true> hs{hscale};
@@ -555,24 +489,10 @@ int fill_conv(ssk::ConvParams& p, int* n_cus, const float* spec, const float* ri
     p.rir_chan_stride = cs;
     p.rir_elem_stride = es;
     p.rir_cap = cap;
-    p.n_valid = n_valid;
-    p.out_len = out_len;
-    p.n_frames = n_frames_of(out_len);
-    p.t4 = t4_of(out_len);
-    p.pad_mode = 0;
-    p.fade_len = static_cast<int>(0.05 * out_len);     // crossfade_samples = int(0.05 * sr), rows are 1 s (out_len == sr)
-    p.hspec = nullptr;
-    p.h_blocks = 0;
+    sslaunch::init_conv_params(p, n_valid, out_len);
     // default on: the two ears of a unit (same window spectrum) share an XCD's L2; SS_HIP_XCD_MAP=0 is the A/B switch
     static const int xcd_map = ab_int("SS_HIP_XCD_MAP", 1);
     p.xcd_map = xcd_map;
-    p.stash = nullptr;
-    p.stash_nbh = 0;
-    p.stash_terms = 0;
-    p.n_terms = 2;
-    p.parts_log2 = 0;
-    p.n_buckets = 1;
-    for (auto& b : p.bk) b = ssk::BankBucket{nullptr, nullptr, 0x7fffffff, 0, 0, 0};
 #if defined(SS_LADDER)                                     // profiling builds only (scripts/gpu_ladder.sh compiles with -DSS_LADDER)
     static const int dbg = getenv("SS_HIP_DBG") ? atoi(getenv("SS_HIP_DBG")) : 0;
     p.dbg = dbg;
@@ -592,65 +512,17 @@ int spectrogram_of_rows(const float* x, float* out, int n_units, int len, int n_
     p.x = x;
     p.out = out;
     p.len = len;
-    p.n_frames = n_frames_of(len);
-    p.t4 = t4_of(len);
     p.pad_mode = pad_mode;
-    p.live = ssk::live_blocks(n_valid, len, p.t4);
-    const int groups = (p.t4 + 3) / 4;                      // 4 pooled time blocks x 2 ears per round of a workgroup
     // large batches: one workgroup walks several groups (tables staged once, next segment prefetched under the math);
     // small batches keep one group per workgroup so that the launch still fills 256 CUs x 2 workgroups
-    long long gpw = (long long)n_units * groups / 2048;
-    p.gpw = gpw < 1 ? 1 : gpw > groups ? groups : (int)gpw;
-    const int chunks = (groups + p.gpw - 1) / p.gpw;
-    hipLaunchKernelGGL(ssk::k_spectrogram, dim3(n_units * chunks), dim3(512), 0,
+    const sslaunch::FramesPlan pl = sslaunch::plan_frames(sslaunch::Frames::kPooled, n_units, len, n_valid,
+                                                          (long long)n_units * sslaunch::groups_of(sslaunch::Frames::kPooled, len) / 2048);
+    p.n_frames = pl.n_frames;
+    p.t4 = pl.t4;
+    p.live = pl.live;
+    p.gpw = pl.gpw;
+    hipLaunchKernelGGL(ssk::k_spectrogram, dim3(pl.grid), dim3(512), 0,
                        static_cast<hipStream_t>(stream), p);
-    return hip_err(hipGetLastError());
-}
-
-
-template <bool FUSE>
-int launch_conv_spec(ssk::ConvParams p, int n_units, int nb_y, int flags, const LaunchEnv& env, int n_cus = 0) {
-    const hipStream_t st = env.st;
-    if (nb_y < 1 || nb_y > 3 || (FUSE && nb_y != 1) || (flags & SS_FLAG_CROSSFADE)) return SS_EINVAL;
-    p.nb_y = nb_y;
-    p.parts_log2 = FUSE && n_cus > 0 ? parts_log2_for(2 * n_units, n_cus, env.share) : 0;
-    const bool simple = (flags & SS_FLAG_NO_DISTRACTOR) && nb_y == 1 && p.h_blocks == 1 &&
-                        (p.n_buckets == 1 || (flags & SS_FLAG_FIRST_BUCKET));
-    static const bool no_rows = ab_flag("SS_HIP_NO_ROW_KERNEL");
-    if constexpr (!FUSE) {              // more rows than CUs: persistent workgroups prefetching the next row's H'
-        if (simple && !no_rows && n_cus > 0 && n_units > n_cus && !(reinterpret_cast<size_t>(p.hspec) & 15)) {
-            hipLaunchKernelGGL(ssk::k_conv_spec_rows, dim3(n_cus), dim3(ssk::kT), 0, st, p, 2 * n_units);
-            return hip_err(hipGetLastError());
-        }
-    }
-    const dim3 grid((2 * n_units * nb_y) << p.parts_log2), block(ssk::kT);
-    if (simple) {
-        ssk::UnitTab<true> ut;
-        if (fill_unit_tab(ut, env, n_units)) hipLaunchKernelGGL((ssk::k_conv_spec<FUSE, true, true>), grid, block, 0, st, p, ut);
-        else hipLaunchKernelGGL((ssk::k_conv_spec<FUSE, true>), grid, block, 0, st, p, ssk::UnitTab<false>());
-    } else hipLaunchKernelGGL((ssk::k_conv_spec<FUSE, false>), grid, block, 0, st, p, ssk::UnitTab<false>());
-    return hip_err(hipGetLastError());
-}
-
-
-// ---- half bank: fp16 block spectra + one fp32 scale per (entry, ear, block) (include/ss_hip.h "Half-precision spectral bank") ----
-// k_conv_spec<.., HALF> for every launch (one workgroup per row and output block; more rows than CUs included: the persistent
-// k_conv_spec_rows has no half form)
-template <bool FUSE>
-int launch_conv_spec16(ssk::ConvParams p, const float* hscale, int n_units, int nb_y, int flags, const LaunchEnv& env, int n_cus) {
-    const hipStream_t st = env.st;
-    if (nb_y < 1 || nb_y > 3 || (FUSE && nb_y != 1) || (flags & SS_FLAG_CROSSFADE)) return SS_EINVAL;
-    p.nb_y = nb_y;
-    p.parts_log2 = FUSE && n_cus > 0 ? parts_log2_for(2 * n_units, n_cus, env.share) : 0;
-    const bool simple = (flags & SS_FLAG_NO_DISTRACTOR) && nb_y == 1 && p.h_blocks == 1;
-    const dim3 grid((2 * n_units * nb_y) << p.parts_log2), block(ssk::kT);
-    const ssk::SpecScale<true> hs{hscale};
-    if (simple) {
-        ssk::UnitTab<true> ut;
-        if (fill_unit_tab(ut, env, n_units))
-            hipLaunchKernelGGL((ssk::k_conv_spec<FUSE, true, true, false, true>), grid, block, 0, st, p, ut, hs);
-        else hipLaunchKernelGGL((ssk::k_conv_spec<FUSE, true, false, false, true>), grid, block, 0, st, p, ssk::UnitTab<false>(), hs);
-    } else hipLaunchKernelGGL((ssk::k_conv_spec<FUSE, false, false, false, true>), grid, block, 0, st, p, ssk::UnitTab<false>(), hs);
     return hip_err(hipGetLastError());
 }
 
@@ -726,22 +598,6 @@ void fill_spec_buckets(ssk::ConvParams& p, ssk::SpecScale<true, true>& hs, const
     }
 }
 
-// Half buckets.  Launches that only touch bucket 0 (one bucket, or SS_FLAG_FIRST_BUCKET) are single-allocation launches on
-// bucket 0's arrays: the existing HALF kernels, the loop-free ones included.  Everything else: k_conv_spec<.., HALF, HBK>.
-template <bool FUSE>
-int launch_conv_spec16_buckets(ssk::ConvParams p, const ssk::SpecScale<true, true>& hs, int n_units, int nb_y, int flags,
-                               const LaunchEnv& env, int n_cus) {
-    if (p.n_buckets == 1 || (flags & SS_FLAG_FIRST_BUCKET)) return launch_conv_spec16<FUSE>(p, hs.hscale, n_units, nb_y, flags, env, n_cus);
-    const hipStream_t st = env.st;
-    if (nb_y < 1 || nb_y > 3 || (FUSE && nb_y != 1) || (flags & SS_FLAG_CROSSFADE)) return SS_EINVAL;
-    p.nb_y = nb_y;
-    p.parts_log2 = FUSE && n_cus > 0 ? parts_log2_for(2 * n_units, n_cus, env.share) : 0;
-    const dim3 grid((2 * n_units * nb_y) << p.parts_log2), block(ssk::kT);
-    hipLaunchKernelGGL((ssk::k_conv_spec<FUSE, false, false, false, true, true>), grid, block, 0, st, p, ssk::UnitTab<false>(), hs);
-    return hip_err(hipGetLastError());
-}
-
-
 // ---- one launch body behind the observation entries -------------------------------------------------------------------
 // A RIR bank in whichever form its holder keeps it: built from the arguments of a C entry, or from a Context (bank_of).
 struct Bank {
@@ -789,9 +645,8 @@ inline Bank spec_buckets_bank(const ss_spec_bucket* sbk, int n_buckets, bool hal
 template <bool FUSE>
 int launch_conv_any(const ssk::ConvParams& p, const ssk::SpecScale<true, true>& hs, bool spectral, int n_units, int nb_y, int flags,
                     int n_cus, const LaunchEnv& env) {
-    if (!spectral) return launch_conv<FUSE>(p, n_units, nb_y, flags, n_cus, env);
-    if (hs.hscale) return launch_conv_spec16_buckets<FUSE>(p, hs, n_units, nb_y, flags, env, n_cus);
-    return launch_conv_spec<FUSE>(p, n_units, nb_y, flags, env, n_cus);
+    if (!spectral) return launch_conv<FUSE>(sslaunch::Form::kRows, p, n_units, nb_y, flags, n_cus, env);
+    return launch_conv<FUSE>(hs.hscale ? sslaunch::Form::kSpec16Buckets : sslaunch::Form::kSpec, p, n_units, nb_y, flags, n_cus, env, false, &hs);
 }
 
 // ... and k_obs_blocks / k_obs_rows likewise (launch_obs_rows' own choice, hand-off area and stash)
@@ -820,6 +675,7 @@ int render(const Bank& b, bool spectral, ssroute::Launch want, const float* spec
            int flags, const LaunchEnv& env) {
     using ssroute::Chain;
     using ssroute::Launch;
+    using sslaunch::Form;
     const bool bucketed = b.bk || b.sbk;
     bool half = b.hscale != nullptr;
     int nbh_max = 1;
@@ -893,14 +749,14 @@ int render(const Bank& b, bool spectral, ssroute::Launch want, const float* spec
     else if (spectral) { p.hspec = static_cast<const ssk::f32x4*>(b.hspec); p.h_blocks = b.h_blocks; }
     if (rc) return rc;
     p.out = audiogoal;
-    const int nb_y = n_valid == 0 ? 1 : (n_valid + ssk::kB - 1) / ssk::kB;
+    const int nb_y = sslaunch::nb_y_of(n_valid);
     if (rows16) {
         const ssk::RowScale<true> rs{static_cast<const ssk::h16x2*>(b.rir16), b.rscale};
         p.rir_cap = b.cap;
         if (want == Launch::kObs && chain == Chain::kFused) {
             p.pad_mode = pad_mode;
             p.sgram = spectrogram;
-            return launch_conv16<true>(p, rs, n_units, 1, flags, n_cus, env);
+            return launch_conv<true>(Form::kRows16, p, n_units, 1, flags, n_cus, env, false, nullptr, &rs);
         }
         if (want == Launch::kObs && chain == Chain::kRows) {
             p.pad_mode = pad_mode;
@@ -908,7 +764,7 @@ int render(const Bank& b, bool spectral, ssroute::Launch want, const float* spec
             return launch_obs_rows<false, false, false, false, true>(p, n_units, flags, n_cus, env, ssk::UnitTab<false, false>(),
                                                                      ssk::SpecScale<false, false>(), rs);
         }
-        rc = launch_conv16<false>(p, rs, n_units, nb_y, flags, n_cus, env);
+        rc = launch_conv<false>(Form::kRows16, p, n_units, nb_y, flags, n_cus, env, false, nullptr, &rs);
         if (rc || want == Launch::kConv) return rc;
         return spectrogram_of_rows(audiogoal, spectrogram, n_units, out_len, n_valid, pad_mode, env.st);
     }
@@ -922,7 +778,7 @@ int render(const Bank& b, bool spectral, ssroute::Launch want, const float* spec
     p.sgram = spectrogram;
     if (want == Launch::kObs) {
         if (chain == Chain::kFused) return launch_conv_any<true>(p, hs, spectral, n_units, 1, flags, n_cus, env);
-        if (chain == Chain::kWide) return launch_conv<true>(p, n_units, 1, flags, n_cus, env, true);
+        if (chain == Chain::kWide) return launch_conv<true>(Form::kRows, p, n_units, 1, flags, n_cus, env, true);
         return launch_rows_any<false>(p, hs, spectral, n_units, flags, n_cus, env);
     }
     // the log-mel forms.  Launches that only touch bucket 0 (one bucket, or SS_FLAG_FIRST_BUCKET) are single-allocation launches
@@ -933,8 +789,6 @@ int render(const Bank& b, bool spectral, ssroute::Launch want, const float* spec
     if (!spectral) return launch_conv_mel(p, *mel, n_units, flags, env.st);
     if (!half) return launch_conv_spec_mel(p, *mel, n_units, flags, env.st);
     if (p.n_buckets == 1) return launch_conv_spec16_mel(p, *mel, hs.hscale, n_units, flags, env.st);
-    p.nb_y = 1;
-    p.parts_log2 = 0;
     hipLaunchKernelGGL((ssk::k_conv_spec<true, false, false, true, true, true>), dim3(2 * n_units), dim3(ssk::kT), 0, env.st, p, *mel, hs);
     return hip_err(hipGetLastError());
 }
@@ -1063,11 +917,11 @@ int ss_logmel_f32(const float* x, float* out, int n_units, int len, int pad_mode
     p.n_mels = n_mels;
     p.max_len = max_len;
     p.eps = eps;
-    const int groups = (p.n_frames + ssk::kSegFrames - 1) / ssk::kSegFrames;
-    long long gpw = (long long)n_units * groups / 1024;     // one 111 KB workgroup per CU: ~4 rounds of 256
-    p.gpw = gpw < 1 ? 1 : gpw > groups ? groups : (int)gpw;
-    const int chunks = (groups + p.gpw - 1) / p.gpw;
-    hipLaunchKernelGGL(ssk::k_logmel, dim3(n_units * chunks), dim3(512), 0, static_cast<hipStream_t>(stream), p);
+    // (one 111 KB workgroup per CU: ~4 rounds of 256)
+    const sslaunch::FramesPlan pl = sslaunch::plan_frames(sslaunch::Frames::kSegments, n_units, len, len,
+                                                          (long long)n_units * sslaunch::groups_of(sslaunch::Frames::kSegments, len) / 1024);
+    p.gpw = pl.gpw;
+    hipLaunchKernelGGL(ssk::k_logmel, dim3(pl.grid), dim3(512), 0, static_cast<hipStream_t>(stream), p);
     return hip_err(hipGetLastError());
 }
 
@@ -1087,11 +941,10 @@ int ss_gccphat_f32(const float* x, float* out, int n_units, int len, int pad_mod
     p.pad_mode = pad_mode;
     p.max_lag = max_lag;
     p.eps = eps;
-    const int groups = (p.n_frames + ssk::kSegFrames - 1) / ssk::kSegFrames;
-    long long gpw = (long long)n_units * groups / 2048;
-    p.gpw = gpw < 1 ? 1 : gpw > groups ? groups : (int)gpw;
-    const int chunks = (groups + p.gpw - 1) / p.gpw;
-    hipLaunchKernelGGL(ssk::k_gccphat, dim3(n_units * chunks), dim3(256), 0, static_cast<hipStream_t>(stream), p);
+    const sslaunch::FramesPlan pl = sslaunch::plan_frames(sslaunch::Frames::kSegments, n_units, len, len,
+                                                          (long long)n_units * sslaunch::groups_of(sslaunch::Frames::kSegments, len) / 2048);
+    p.gpw = pl.gpw;
+    hipLaunchKernelGGL(ssk::k_gccphat, dim3(pl.grid), dim3(256), 0, static_cast<hipStream_t>(stream), p);
     return hip_err(hipGetLastError());
 }
 
@@ -1114,14 +967,12 @@ int ss_audio_features_f32(const float* x, int n_units, int len, int pad_mode, fl
     p.len = len; p.n_frames = n_frames_of(len); p.t4 = t4_of(len); p.pad_mode = pad_mode;
     p.n_mels = logmel ? n_mels : 0; p.max_len = logmel ? max_len : 4; p.max_lag = gccphat ? max_lag : 1;
     p.mel_eps = mel_eps; p.gcc_eps = gcc_eps;
-    const int groups = (p.n_frames + ssk::kSegFrames - 1) / ssk::kSegFrames;
     // two ~80 KiB workgroups per CU: one wave of resident workgroups that share the (unit, group) rounds round-robin (tables
     // staged once per workgroup, the next round's segments prefetched under the current round's math)
     int n_cus = 256;
     { ssk::Tables unused; (void)get_tables(&unused, &n_cus); }
     p.n_units = n_units;
-    const long long tasks = (long long)n_units * groups;
-    const dim3 grid(static_cast<unsigned>(tasks < 2LL * n_cus ? tasks : 2LL * n_cus)), block(256);
+    const dim3 grid(static_cast<unsigned>(sslaunch::features_grid(n_units, len, 2LL * n_cus))), block(256);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int which = (logmel ? 1 : 0) | (spectrogram ? 2 : 0) | (gccphat ? 4 : 0);
     switch (which) {

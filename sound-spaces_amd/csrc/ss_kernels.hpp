@@ -557,7 +557,7 @@ struct SpecParams {
 //      dead and is overlaid by the per-wave STFT scratch;
 //   3. the 65 x (4 blocks x 2 ears) results are collected in LDS and written as contiguous 32-byte runs of the
 //      channel-last output instead of 4-byte scatters.
-constexpr int kSegFrames = 16, kSegLen = kHop * (kSegFrames - 1) + kNfft;     // 2912 samples
+constexpr int kSegLen = kHop * (kSegFrames - 1) + kNfft;     // 2912 samples (kSegFrames = 16: ss_consts.hpp)
 constexpr int kSegQuads = kSegLen / 4;                                         // 728 float4 per ear
 
 // librosa / np.pad(mode="reflect") centre padding at ANY row length: position i of the padded row reads sample
@@ -1206,8 +1206,7 @@ __global__ __launch_bounds__(256) void k_gccphat(GccParams p) {
 // Y_j = sum over (term, RIR block i) of H_i * S_{j-i}; one accumulator per workgroup, so multi-block rows
 // (44.1 kHz: 3 output blocks) re-run the forward FFTs per output block instead of holding 3 accumulators
 // (96 VGPRs) that a 1024-thread workgroup does not have.
-constexpr int kMaxBuckets = 4;
-constexpr int kTabUnits = 256;
+// (kMaxBuckets, kTabUnits: ss_consts.hpp)
 // words per unit of the kernel-argument table: {bank index | -1, window-spectrum slot, OUTPUT unit}.  The host deals the
 // units out sorted by window spectrum (one group of sounds per XCD: row_slot), so the rows that read one 128-KiB spectrum sit
 // on one XCD and find it in that L2; word 2 says where the row's results go (the caller's unit order is untouched)
@@ -2369,10 +2368,8 @@ constexpr int kRowsAbl = SS_ROWS_ABL;
 #else
 constexpr int kRowsAbl = 0;
 #endif
-constexpr int kTailFloats = 640;            // context handed from output block j to j+1 (nb_rows <= 3: 640, 384)
 constexpr int kRowsMaxBlocks = 27;          // pooled blocks behind one output block (32768-sample rows: 25 + 27)
 constexpr int kRowsResFloats = kBins4 * kRowsMaxBlocks;
-constexpr int kRowsMaxNbh = 16;             // RIR blocks per term the pair masks can hold (2 terms x 16 bits)
 
 // pooled time blocks that are complete once the row is known up to sample `known` (not the row's end)
 __host__ __device__ constexpr int pooled_blocks_complete(int known) {

@@ -12,6 +12,7 @@
 #include "../../sound-spaces_amd/csrc/ss_kernels32.hpp"
 #include "../../sound-spaces_amd/csrc/ss_features.hpp"
 #include "../../sound-spaces_amd/csrc/ss_tables.hpp"
+#include "../../sound-spaces_amd/csrc/ss_launch.hpp"
 
 dim3 threadIdx, blockIdx, blockDim, gridDim;
 
@@ -95,6 +96,104 @@ ssk::Tables host_tables() {
     tb.twP2 = reinterpret_cast<const ssk::c32*>(tab.data() + ssk_host::kTwP2Off);
     return tb;
 }
+
+// one launch: the workgroups of a grid one after the other, blockIdx.x fastest (reversed: the last workgroup first)
+int run_grid(int grid_x, int grid_y, int nthreads, const std::function<void()>& body, bool reversed = false) {
+    gridDim = dim3{(unsigned)grid_x, (unsigned)grid_y, 1};
+    const int n = grid_x * grid_y;
+    for (int i = 0; i < n; ++i) {
+        const int b = reversed ? n - 1 - i : i;
+        blockIdx = dim3{(unsigned)(b % grid_x), (unsigned)(b / grid_x), 0};
+        const int rc = run_block(nthreads, body);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+// The launch geometry is the library's (sound-spaces_amd/csrc/ss_launch.hpp).  What a test chooses freely arrives as a plan
+// INPUT: the parts of a row as the forced parts_log2 (the library's A/B switch), persistent workgroups as the chip's CUs.
+constexpr int kBigChip = 1 << 20;                     // more CUs than any launch here has rows: never the persistent kernels
+sslaunch::Switches forced_parts(int parts_log2) { return sslaunch::Switches{parts_log2, false, false}; }
+
+// ConvParams as the library's fill_conv leaves them (xcd_map off, the host's tables), without a bank
+ssk::ConvParams conv_params(const float* spec, const int* rir_len, const int* desc, float* out, float* sgram, int n_valid,
+                            int out_len, int pad_mode) {
+    ssk::ConvParams p;
+    p.spec = reinterpret_cast<const ssk::f32x4*>(spec); p.rir = nullptr; p.rir_len = rir_len; p.desc = desc;
+    p.out = out; p.sgram = sgram; p.tb = host_tables();
+    p.rir_unit_stride = 0; p.rir_chan_stride = 0; p.rir_elem_stride = 1; p.rir_cap = 0;
+    sslaunch::init_conv_params(p, n_valid, out_len);
+    p.pad_mode = pad_mode;
+    return p;
+}
+void set_rows(ssk::ConvParams& p, const float* rir, long long us, int cs, int es, int cap) {
+    p.rir = rir; p.rir_unit_stride = us; p.rir_chan_stride = cs; p.rir_elem_stride = es; p.rir_cap = cap;
+}
+void set_spectra(ssk::ConvParams& p, const void* hspec, int h_blocks) {
+    p.hspec = static_cast<const ssk::f32x4*>(hspec); p.h_blocks = h_blocks;
+}
+// buckets 1.. of a length-bucketed bank (bucket 0: set_rows / set_spectra); rows / hspec: per bucket, or nullptr
+void set_buckets(ssk::ConvParams& p, const float* const* rows, const void* const* hspec, const int* first, const int* cap, int n_buckets) {
+    p.n_buckets = n_buckets;
+    for (int b = 1; b < n_buckets; ++b)
+        p.bk[b - 1] = ssk::BankBucket{rows ? rows[b] : nullptr, hspec ? static_cast<const ssk::f32x4*>(hspec[b]) : nullptr, first[b], cap[b],
+                                      ssroute::ceil_div(cap[b], ssk::kB), 0};
+}
+// the scales of a half bank in buckets (hscale == nullptr: none)
+ssk::SpecScale<true, true> bucket_scales(const float* const* hscale, int n_buckets) {
+    ssk::SpecScale<true, true> hs;
+    hs.hscale = hscale ? hscale[0] : nullptr;
+    for (int b = 0; b < ssk::kMaxBuckets - 1; ++b) hs.bk[b] = hscale && b + 1 < n_buckets ? hscale[b + 1] : nullptr;
+    return hs;
+}
+// the unit table with launch slot k rendering unit n - 1 - k (the library deals the units out sorted by window spectrum:
+// word 2 = where the results go)
+void fill_tab_reversed(ssk::UnitTab<true>& ut, const int* desc, int n_units) {
+    for (int k = 0; k < n_units; ++k) {
+        const int i = n_units - 1 - k;
+        const int* d = desc + 8 * i;
+        const bool ok = d[0] >= 0 && d[2] <= 0 && d[2] + d[3] > 0;
+        ut.tab[ssk::kTabWords * k] = ok ? d[0] : -1;
+        ut.tab[ssk::kTabWords * k + 1] = ok ? d[1] - d[2] : 0;
+        ut.tab[ssk::kTabWords * k + 2] = i;
+    }
+}
+
+// k_obs_blocks as sslaunch::plan_obs_blocks shapes it: the plan sees a chip of exactly the (row, block, part) workgroups the
+// test wants, so that its own rule arrives at `parts_log2`; the hand-off area at the plan's sizes; the workgroups run in
+// blockIdx order with xcd_map = 0 - (row, j - 1) before (row, j): producers before consumers - or reversed.
+// body(tails, flags) runs the kernel; -3: the plan does not take the launch (a cross-fade, n_valid < out_len).
+template <class Body>
+int run_obs_blocks(ssk::ConvParams& p, int n_units, int flags, int parts_log2, Body body, bool reversed = false,
+                   std::vector<int>* flags_out = nullptr) {
+    const int wanted = (2 * n_units * ssroute::ceil_div(p.out_len, ssk::kB)) << parts_log2;
+    const sslaunch::ObsBlocksPlan pl = sslaunch::plan_obs_blocks(flags, p.out_len, p.n_valid, n_units, wanted, 1, true, sslaunch::Switches());
+    if (!pl.ok) return -3;
+    sslaunch::apply(pl, p);
+    p.xcd_map = 0;
+    std::vector<float> tails(pl.handoff_floats, 12345.0f);
+    std::vector<int> fl(pl.handoff_flags, 0);
+    const int rc = run_grid(pl.grid, 1, ssk::kT, [&] { body(tails.data(), fl.data()); }, reversed);
+    if (flags_out) flags_out->swap(fl);
+    return rc;
+}
+
+// k_obs_rows as sslaunch::plan_obs_rows shapes it: `wgs` persistent workgroups are the plan's CUs (parts_log2 > 0: one workgroup
+// per (row, part), whatever `wgs` says), the stash of a time-domain bank at the plan's size, filled with `fill`.
+// -2: the plan refuses the launch.
+template <class Body>
+int run_obs_rows(ssk::ConvParams& p, bool spectral, int n_units, int flags, int wgs, int parts_log2, float fill, Body body,
+                 int xcd_map = -1) {
+    const sslaunch::ObsRowsPlan pl = sslaunch::plan_obs_rows(spectral, false, false, flags, p.n_valid, p.n_buckets, sslaunch::rows_nbh_max(p),
+                                                             n_units, parts_log2 ? (2 * n_units) << parts_log2 : wgs, 1,
+                                                             forced_parts(parts_log2));
+    if (pl.rc) return -2;
+    sslaunch::apply(pl, p);
+    p.xcd_map = xcd_map >= 0 ? xcd_map : pl.grid >= 8;
+    std::vector<float> stash(pl.stash_bytes / sizeof(float), fill);
+    if (!spectral) p.stash = reinterpret_cast<ssk::f32x4*>(stash.data());
+    return run_grid(pl.grid, 1, ssk::kT, body);
+}
 }  // namespace
 
 // a second length bucket for the next hs_conv / hs_obs_rows call (cleared by it): entries >= first live in `rir` [n,2,cap]
@@ -103,11 +202,9 @@ static int g_parts_log2 = 0;          // the next fused hs_conv / hs_conv_spec /
 static const float* g_b2_rir = nullptr;
 static int g_b2_first = 0, g_b2_cap = 0;
 static void apply_bucket2(ssk::ConvParams& p) {
-    p.n_buckets = 1;
-    for (auto& b : p.bk) b = ssk::BankBucket{nullptr, nullptr, 0x7fffffff, 0, 0, 0};
     if (g_b2_rir) {
         p.n_buckets = 2;
-        p.bk[0] = ssk::BankBucket{g_b2_rir, nullptr, g_b2_first, g_b2_cap, (g_b2_cap + ssk::kB - 1) / ssk::kB, 0};
+        p.bk[0] = ssk::BankBucket{g_b2_rir, nullptr, g_b2_first, g_b2_cap, ssroute::ceil_div(g_b2_cap, ssk::kB), 0};
     }
     g_b2_rir = nullptr;
 }
@@ -124,6 +221,15 @@ float hostsim_lane_read(float v, int src_lane) {
     return r;
 }
 
+// window spectra / block spectra: one workgroup per descriptor row
+static int run_source_windows(const float* src, const int* desc, float* spec, int n_windows, float scale, bool core32) {
+    ssk::SrcParams p;
+    p.src = src; p.desc = desc; p.spec = reinterpret_cast<ssk::f32x4*>(spec); p.tb = host_tables();
+    p.desc_stride = 4; p.scale = scale;
+    if (core32) return run_grid(n_windows, 1, ssk::kT32, [&] { ssk::k_source_windows32(p); });
+    return run_grid(n_windows, 1, ssk::kT, [&] { ssk::k_source_windows(p); });
+}
+
 extern "C" {
 
 void hs_set_bucket2(const float* rir, int first, int cap) { g_b2_rir = rir; g_b2_first = first; g_b2_cap = cap; }
@@ -135,128 +241,70 @@ static int g_obs_blocks = 0;
 void hs_set_obs_blocks(int on) { g_obs_blocks = on; }
 
 int hs_source_windows(const float* src, const int* desc, float* spec, int n_windows) {
-    ssk::SrcParams p;
-    p.src = src; p.desc = desc; p.spec = reinterpret_cast<ssk::f32x4*>(spec); p.tb = host_tables();
-    p.desc_stride = 4; p.scale = ssk::kWindowScale;
-    gridDim = dim3{(unsigned)n_windows, 1, 1};
-    for (int w = 0; w < n_windows; ++w) {
-        blockIdx = dim3{(unsigned)w, 0, 0};
-        int rc = run_block(ssk::kT, [&] { ssk::k_source_windows(p); });
-        if (rc) return rc;
-    }
-    return 0;
+    return run_source_windows(src, desc, spec, n_windows, ssk::kWindowScale, false);
 }
 
 int hs_conv(int fuse, int simple, const float* spec, const float* rir, const int* rir_len, const int* desc, float* out,
             float* sgram, int n_units, long long us, int cs, int es, int cap, int n_valid, int out_len, int pad_mode,
             int persist) {
-    ssk::ConvParams p;
-    p.spec = reinterpret_cast<const ssk::f32x4*>(spec); p.rir = rir; p.rir_len = rir_len; p.desc = desc;
-    p.out = out; p.sgram = sgram; p.tb = host_tables();
-    p.rir_unit_stride = us; p.rir_chan_stride = cs; p.rir_elem_stride = es; p.rir_cap = cap;
-    p.n_valid = n_valid; p.out_len = out_len;
-    p.n_frames = 1 + out_len / ssk::kHop;
-    p.t4 = (p.n_frames + 3) / 4;
-    p.pad_mode = pad_mode;
-    p.hspec = nullptr; p.h_blocks = 0; p.xcd_map = 0; p.stash = nullptr; p.stash_nbh = 0; p.stash_terms = 0; p.n_terms = 2; p.parts_log2 = 0;
+    using V = sslaunch::Variant;
+    ssk::ConvParams p = conv_params(spec, rir_len, desc, out, sgram, n_valid, out_len, pad_mode);
+    set_rows(p, rir, us, cs, es, cap);
     apply_bucket2(p);
-    p.fade_len = static_cast<int>(0.05 * out_len);
     const bool xfade = simple == 2;                     // simple: 0 = loop kernel, 1 = SIMPLE, 2 = loop kernel + XFADE
     if (xfade) simple = 0;
-    const int nb_y = n_valid == 0 ? 1 : (n_valid + ssk::kB - 1) / ssk::kB;
-    // WIDE: a row longer than one block of which only block 0 is rendered (the library's wide_one_block_ok)
-    const bool wide = fuse && out_len > ssk::kB && n_valid <= ssk::kB && ssk::live_blocks(n_valid, out_len, p.t4) <= 26;
+    // the caller chooses the kernel; the flags under which the library's plan chooses the same one
+    const int flags = (simple ? SS_FLAG_NO_DISTRACTOR | SS_FLAG_FIRST_BUCKET : 0) | (xfade ? SS_FLAG_CROSSFADE : 0);
+    const int nb_y = sslaunch::nb_y_of(n_valid);
+    // WIDE: a row longer than one block of which only block 0 is rendered
+    const bool wide = fuse && ssroute::wide_one_block_ok(out_len, n_valid, flags, false, ssroute::Switches());
     if (wide && simple) return -3;
     if (fuse && !wide && (nb_y != 1 || out_len > ssk::kB || p.t4 > 26)) return -1;
-    if (persist > 0) {                                  // k_conv_rows: `persist` workgroups walk the 2*n_units rows
-        if (fuse || !simple || nb_y != 1 || es != 1 || (cap & 1) || cap > ssk::kB) return -2;
-        gridDim = dim3{(unsigned)persist, 1, 1};
-        for (int b = 0; b < persist && b < 2 * n_units; ++b) {
-            blockIdx = dim3{(unsigned)b, 0, 0};
-            int rc = run_block(ssk::kT, [&] {
-                ssk::k_conv_rows(p, 2 * n_units);
-            });
-            if (rc) return rc;
-        }
-        return 0;
-    }
-    p.nb_y = nb_y;
-    p.parts_log2 = fuse && !wide ? g_parts_log2 : 0;
+    // k_conv_rows: `persist` workgroups walk the 2*n_units rows - the plan's CUs
+    if (persist > 0 && (fuse || !simple || nb_y != 1 || es != 1 || (cap & 1) || cap > ssk::kB)) return -2;
+    const sslaunch::ConvPlan pl = sslaunch::plan_conv(sslaunch::Form::kRows, fuse, wide, flags, cap, 0, p.n_buckets, p.fade_len, persist > 0,
+                                                      false, n_units, nb_y, persist > 0 ? persist : kBigChip, 1, forced_parts(g_parts_log2));
+    if (pl.rc) return -1;
     g_parts_log2 = 0;
-    const int gx = (2 * n_units) << p.parts_log2;
-    gridDim = dim3{(unsigned)gx, (unsigned)nb_y, 1};
-    for (int b = 0; b < gx * nb_y; ++b) {
-        {
-            blockIdx = dim3{(unsigned)(b % gx), (unsigned)(b / gx), 0};
-            int rc = run_block(ssk::kT, [&] {
-                if (wide) { if (xfade) ssk::k_conv<true, false, true, false, true>(p); else ssk::k_conv<true, false, false, false, true>(p); }
-                else if (xfade) { if (fuse) ssk::k_conv<true, false, true>(p); else ssk::k_conv<false, false, true>(p); }
-                else if (fuse) { if (simple) ssk::k_conv<true, true>(p); else ssk::k_conv<true, false>(p); }
-                else { if (simple) ssk::k_conv<false, true>(p); else ssk::k_conv<false, false>(p); }
-            });
-            if (rc) return rc;
-        }
-    }
-    return 0;
+    sslaunch::apply(pl, p);
+    if (persist > 0)            // (forced where the plan would not take it - no more rows than workgroups: one workgroup per row)
+        return run_grid(pl.variant == V::kPersistRows ? pl.grid_x : 2 * n_units, 1, ssk::kT, [&] { ssk::k_conv_rows(p, 2 * n_units); });
+    return run_grid(pl.grid_x, pl.grid_y, ssk::kT, [&] {
+        if (wide) { if (xfade) ssk::k_conv<true, false, true, false, true>(p); else ssk::k_conv<true, false, false, false, true>(p); }
+        else if (xfade) { if (fuse) ssk::k_conv<true, false, true>(p); else ssk::k_conv<false, false, true>(p); }
+        else if (fuse) { if (simple) ssk::k_conv<true, true>(p); else ssk::k_conv<true, false>(p); }
+        else { if (simple) ssk::k_conv<false, true>(p); else ssk::k_conv<false, false>(p); }
+    });
 }
 
 // ---- 512-thread core (ss_kernels32.hpp): window spectra in ITS order + the loop-free row kernel
 int hs_source_windows32(const float* src, const int* desc, float* spec, int n_windows) {
-    ssk::SrcParams p;
-    p.src = src; p.desc = desc; p.spec = reinterpret_cast<ssk::f32x4*>(spec); p.tb = host_tables();
-    p.desc_stride = 4; p.scale = ssk::kWindowScale;
-    gridDim = dim3{(unsigned)n_windows, 1, 1};
-    for (int w = 0; w < n_windows; ++w) {
-        blockIdx = dim3{(unsigned)w, 0, 0};
-        int rc = run_block(ssk::kT32, [&] { ssk::k_source_windows32(p); });
-        if (rc) return rc;
-    }
-    return 0;
+    return run_source_windows(src, desc, spec, n_windows, ssk::kWindowScale, true);
 }
 
 int hs_conv32(int fuse, const float* spec, const float* rir, const int* rir_len, const int* desc, float* out,
               float* sgram, int n_units, long long us, int cs, int es, int cap, int n_valid, int out_len, int pad_mode,
               int use_tab) {
-    ssk::ConvParams p;
-    p.spec = reinterpret_cast<const ssk::f32x4*>(spec); p.rir = rir; p.rir_len = rir_len; p.desc = desc;
-    p.out = out; p.sgram = sgram; p.tb = host_tables();
-    p.rir_unit_stride = us; p.rir_chan_stride = cs; p.rir_elem_stride = es; p.rir_cap = cap;
-    p.n_valid = n_valid; p.out_len = out_len;
-    p.n_frames = 1 + out_len / ssk::kHop;
-    p.t4 = (p.n_frames + 3) / 4;
-    p.pad_mode = pad_mode;
-    p.hspec = nullptr; p.h_blocks = 0; p.xcd_map = 0; p.stash = nullptr; p.stash_nbh = 0; p.stash_terms = 0; p.n_terms = 1;
-    apply_bucket2(p);
+    ssk::ConvParams p = conv_params(spec, rir_len, desc, out, sgram, n_valid, out_len, pad_mode);
+    set_rows(p, rir, us, cs, es, cap);
+    p.n_terms = 1;
     p.fade_len = 0;
-    p.nb_y = 1;
+    apply_bucket2(p);
     if (n_valid > ssk::kB || cap > ssk::kB || (fuse && (out_len > ssk::kB || p.t4 > 26))) return -1;
     ssk::UnitTab<true> ut;
     if (use_tab) {
         if (n_units > ssk::kTabUnits) return -2;
-        for (int k = 0; k < n_units; ++k) {                 // launch slot k renders unit n - 1 - k (the library deals the units
-            const int i = n_units - 1 - k;                  // out sorted by window spectrum: word 2 = where the results go)
-            const int* d = desc + 8 * i;
-            const bool ok = d[0] >= 0 && d[2] <= 0 && d[2] + d[3] > 0;
-            ut.tab[ssk::kTabWords * k] = ok ? d[0] : -1;
-            ut.tab[ssk::kTabWords * k + 1] = ok ? d[1] - d[2] : 0;
-            ut.tab[ssk::kTabWords * k + 2] = i;
-        }
+        fill_tab_reversed(ut, desc, n_units);
     }
-    gridDim = dim3{(unsigned)(2 * n_units), 1, 1};
-    for (int b = 0; b < 2 * n_units; ++b) {
-        blockIdx = dim3{(unsigned)b, 0, 0};
-        int rc = run_block(ssk::kT32, [&] {
-            if (fuse) { if (use_tab) ssk::k_conv32<true, true>(p, ut); else ssk::k_conv32<true, false>(p); }
-            else { if (use_tab) ssk::k_conv32<false, true>(p, ut); else ssk::k_conv32<false, false>(p); }
-        });
-        if (rc) return rc;
-    }
-    return 0;
+    return run_grid(2 * n_units, 1, ssk::kT32, [&] {
+        if (fuse) { if (use_tab) ssk::k_conv32<true, true>(p, ut); else ssk::k_conv32<true, false>(p); }
+        else { if (use_tab) ssk::k_conv32<false, true>(p, ut); else ssk::k_conv32<false, false>(p); }
+    });
 }
 
 // spectral RIR bank: block spectra of every (entry, ear), like ss_rir_spectra_f32 (k_source_windows with scale 1)
 int hs_rir_spectra(const float* rir, float* hspec, int n_entries, long long us, int cs, int cap) {
-    const int hb = (cap + ssk::kB - 1) / ssk::kB;
+    const int hb = ssroute::ceil_div(cap, ssk::kB);
     std::vector<int> desc;
     for (int r = 0; r < n_entries; ++r)
         for (int c = 0; c < 2; ++c)
@@ -267,64 +315,36 @@ int hs_rir_spectra(const float* rir, float* hspec, int n_entries, long long us, 
                 desc.push_back(0);
                 desc.push_back(0);
             }
-    ssk::SrcParams p;
-    p.src = rir; p.desc = desc.data(); p.spec = reinterpret_cast<ssk::f32x4*>(hspec); p.tb = host_tables();
-    p.desc_stride = 4; p.scale = 1.0f;
-    const int n_windows = static_cast<int>(desc.size() / 4);
-    gridDim = dim3{(unsigned)n_windows, 1, 1};
-    for (int w = 0; w < n_windows; ++w) {
-        blockIdx = dim3{(unsigned)w, 0, 0};
-        int rc = run_block(ssk::kT, [&] { ssk::k_source_windows(p); });
-        if (rc) return rc;
-    }
-    return 0;
+    return run_source_windows(rir, desc.data(), hspec, static_cast<int>(desc.size() / 4), 1.0f, false);
 }
 
 int hs_conv_spec(int fuse, int simple, const float* spec, const float* hspec, const int* rir_len, const int* desc,
                  float* out, float* sgram, int n_units, int h_blocks, int n_valid, int out_len, int pad_mode, int persist) {
-    ssk::ConvParams p;
-    p.spec = reinterpret_cast<const ssk::f32x4*>(spec); p.rir = nullptr; p.rir_len = rir_len; p.desc = desc;
-    p.out = out; p.sgram = sgram; p.tb = host_tables();
-    p.rir_unit_stride = 0; p.rir_chan_stride = 0; p.rir_elem_stride = 1; p.rir_cap = 0;
-    p.n_valid = n_valid; p.out_len = out_len;
-    p.n_frames = 1 + out_len / ssk::kHop;
-    p.t4 = (p.n_frames + 3) / 4;
-    p.pad_mode = pad_mode;
+    using V = sslaunch::Variant;
+    ssk::ConvParams p = conv_params(spec, rir_len, desc, out, sgram, n_valid, out_len, pad_mode);
+    set_spectra(p, hspec, h_blocks);
     p.fade_len = 0;
-    p.hspec = reinterpret_cast<const ssk::f32x4*>(hspec);
-    p.h_blocks = h_blocks; p.xcd_map = 0; p.stash = nullptr; p.stash_nbh = 0; p.stash_terms = 0; p.n_terms = 2; p.parts_log2 = 0;
     apply_bucket2(p);
-    const int nb_y = n_valid == 0 ? 1 : (n_valid + ssk::kB - 1) / ssk::kB;
-    // WIDE: a row longer than one block of which only block 0 is rendered (the library's wide_one_block_ok)
-    const bool wide = fuse && out_len > ssk::kB && n_valid <= ssk::kB && ssk::live_blocks(n_valid, out_len, p.t4) <= 26;
+    const int flags = simple ? SS_FLAG_NO_DISTRACTOR | SS_FLAG_FIRST_BUCKET : 0;
+    const int nb_y = sslaunch::nb_y_of(n_valid);
+    // the shapes the WIDE rule takes are let through as well (asked as of time-domain rows: no spectral launch is wide)
+    const bool wide = fuse && ssroute::wide_one_block_ok(out_len, n_valid, flags, false, ssroute::Switches());
     if (wide && simple) return -3;
     if (fuse && !wide && (nb_y != 1 || out_len > ssk::kB || p.t4 > 26)) return -1;
     if (simple && (nb_y != 1 || h_blocks != 1)) return -2;
-    p.nb_y = nb_y;
-    if (persist > 0) {                                  // k_conv_spec_rows: `persist` workgroups walk the units
-        if (fuse || !simple) return -3;
-        gridDim = dim3{(unsigned)persist, 1, 1};
-        for (int b = 0; b < persist && b < n_units; ++b) {
-            blockIdx = dim3{(unsigned)b, 0, 0};
-            int rc = run_block(ssk::kT, [&] { ssk::k_conv_spec_rows(p, 2 * n_units); });
-            if (rc) return rc;
-        }
-        return 0;
-    }
-    p.parts_log2 = fuse ? g_parts_log2 : 0;
+    if (persist > 0 && (fuse || !simple)) return -3;    // k_conv_spec_rows: `persist` workgroups walk the units - the plan's CUs
+    const sslaunch::ConvPlan pl = sslaunch::plan_conv(sslaunch::Form::kSpec, fuse, false, flags, 0, h_blocks, p.n_buckets, p.fade_len, false,
+                                                      persist > 0, n_units, nb_y, persist > 0 ? persist : kBigChip, 1,
+                                                      forced_parts(fuse ? g_parts_log2 : 0));
+    if (pl.rc) return -1;
+    sslaunch::apply(pl, p);
+    if (persist > 0)            // (forced where the plan would not take it - no more units than workgroups: one workgroup per unit)
+        return run_grid(pl.variant == V::kPersistRows ? pl.grid_x : n_units, 1, ssk::kT, [&] { ssk::k_conv_spec_rows(p, 2 * n_units); });
     g_parts_log2 = 0;
-    gridDim = dim3{(unsigned)((2 * n_units * nb_y) << p.parts_log2), 1, 1};
-    for (int b = 0; b < (2 * n_units * nb_y) << p.parts_log2; ++b) {
-        {
-            blockIdx = dim3{(unsigned)b, 0, 0};
-            int rc = run_block(ssk::kT, [&] {
-                if (fuse) { if (simple) ssk::k_conv_spec<true, true>(p); else ssk::k_conv_spec<true, false>(p); }
-                else { if (simple) ssk::k_conv_spec<false, true>(p); else ssk::k_conv_spec<false, false>(p); }
-            });
-            if (rc) return rc;
-        }
-    }
-    return 0;
+    return run_grid(pl.grid_x, pl.grid_y, ssk::kT, [&] {
+        if (fuse) { if (simple) ssk::k_conv_spec<true, true>(p); else ssk::k_conv_spec<true, false>(p); }
+        else { if (simple) ssk::k_conv_spec<false, true>(p); else ssk::k_conv_spec<false, false>(p); }
+    });
 }
 
 // k_obs_rows: `wgs` persistent workgroups walk the (unit, ear) rows; hspec != nullptr selects the spectral-bank variant
@@ -332,171 +352,102 @@ int hs_obs_rows(const float* spec, const float* rir, const float* hspec, const i
                 float* sgram, int n_units, long long us, int cs, int es, int cap, int h_blocks, int n_valid, int out_len,
                 int pad_mode, int wgs, int no_distractor, int use_stash, int crossfade) {
     if (out_len <= ssk::kB || out_len > 3 * ssk::kB || !sgram) return -1;
-    ssk::ConvParams p;
-    p.spec = reinterpret_cast<const ssk::f32x4*>(spec); p.rir = rir; p.rir_len = rir_len; p.desc = desc;
-    p.out = out; p.sgram = sgram; p.tb = host_tables();
-    p.rir_unit_stride = us; p.rir_chan_stride = cs; p.rir_elem_stride = es; p.rir_cap = cap;
-    p.n_valid = n_valid; p.out_len = out_len;
-    p.n_frames = 1 + out_len / ssk::kHop;
-    p.t4 = (p.n_frames + 3) / 4;
-    p.pad_mode = pad_mode;
-    p.fade_len = static_cast<int>(0.05 * out_len);
+    ssk::ConvParams p = conv_params(spec, rir_len, desc, out, sgram, n_valid, out_len, pad_mode);
+    set_rows(p, rir, us, cs, es, cap);
     if (crossfade && (hspec || no_distractor || p.fade_len > 2 * ssk::kPrevPairs - 2)) return -2;
-    p.hspec = reinterpret_cast<const ssk::f32x4*>(hspec); p.h_blocks = h_blocks; p.xcd_map = wgs >= 8;
-    p.nb_y = n_valid == 0 ? 0 : (n_valid + ssk::kB - 1) / ssk::kB;
-    p.n_terms = no_distractor ? 1 : 2;
+    set_spectra(p, hspec, h_blocks);
     apply_bucket2(p);
-    p.parts_log2 = g_parts_log2;                        // split rows: one workgroup per (row, part), whatever `wgs` says
+    const int flags = (no_distractor ? SS_FLAG_NO_DISTRACTOR : 0) | (crossfade ? SS_FLAG_CROSSFADE : 0);
+    const int parts_log2 = g_parts_log2;                // split rows: one workgroup per (row, part), whatever `wgs` says
     g_parts_log2 = 0;
     const int n_rows = 2 * n_units;
+    (void)use_stash;                                    // (the time-domain path always has its stash)
     if (g_obs_blocks) {
         const bool reversed = g_obs_blocks == 2;        // consumers BEFORE producers: every hand-off wait runs out (poisoned frames)
         g_obs_blocks = 0;
-        if (crossfade || n_valid != out_len) return -3;
-        const int nb = (out_len + ssk::kB - 1) / ssk::kB, grid_b = (n_rows * nb) << p.parts_log2;
-        p.nb_y = nb;
-        p.xcd_map = 0;                                  // workgroups run in blockIdx order here: (row, j - 1) before (row, j)
-        p.stash = nullptr; p.stash_nbh = 0; p.stash_terms = 0;
-        std::vector<float> tails(static_cast<size_t>(n_rows) * 2 * ssk::kTailFloats, 12345.0f);
-        std::vector<int> fl(static_cast<size_t>(n_rows) * 2, 0);
-        gridDim = dim3{(unsigned)grid_b, 1, 1};
-        for (int bb = 0; bb < grid_b; ++bb) {
-            const int b = reversed ? grid_b - 1 - bb : bb;
-            blockIdx = dim3{(unsigned)b, 0, 0};
-            int rc = run_block(ssk::kT, [&] {
-                if (hspec) ssk::k_obs_blocks<true>(p, n_rows, tails.data(), fl.data(), 7);
-                else ssk::k_obs_blocks<false>(p, n_rows, tails.data(), fl.data(), 7);
-            });
-            if (rc) return rc;
-        }
+        std::vector<int> fl;
+        const int rc = run_obs_blocks(p, n_units, flags, parts_log2, [&](float* tails, int* flag) {
+            if (hspec) ssk::k_obs_blocks<true>(p, n_rows, tails, flag, 7);
+            else ssk::k_obs_blocks<false>(p, n_rows, tails, flag, 7);
+        }, reversed, &fl);
+        if (rc) return rc;
         for (int r = 0; r < n_rows; ++r)                // every hand-off of a non-silent row was released exactly once
-            for (int j = 0; j + 1 < nb; ++j)
-                if (fl[static_cast<size_t>(r) * (nb - 1) + j] != 7 && fl[static_cast<size_t>(r) * (nb - 1) + j] != 0) return -4;
+            for (int j = 0; j + 1 < p.nb_y; ++j)
+                if (fl[static_cast<size_t>(r) * (p.nb_y - 1) + j] != 7 && fl[static_cast<size_t>(r) * (p.nb_y - 1) + j] != 0) return -4;
         return 0;
     }
-    const int grid = p.parts_log2 ? (n_rows << p.parts_log2) : (wgs < n_rows ? wgs : n_rows);
-    std::vector<float> stash;
-    p.stash = nullptr; p.stash_nbh = 0; p.stash_terms = 0;
-    (void)use_stash;                                    // (the time-domain path always has its stash)
-    if (!hspec) {
-        p.stash_nbh = (cap + ssk::kB - 1) / ssk::kB;
-        if (p.n_buckets > 1 && p.bk[0].h_blocks > p.stash_nbh) p.stash_nbh = p.bk[0].h_blocks;
-        p.stash_terms = p.n_terms;
-        stash.assign(static_cast<size_t>(grid) * p.stash_terms * p.stash_nbh * 2 * ssk::kSpecComplex, 12345.0f);
-        p.stash = reinterpret_cast<ssk::f32x4*>(stash.data());
-    }
-    gridDim = dim3{(unsigned)grid, 1, 1};
-    for (int b = 0; b < grid; ++b) {
-        blockIdx = dim3{(unsigned)b, 0, 0};
-        int rc = run_block(ssk::kT, [&] {
-            if (hspec) ssk::k_obs_rows<true>(p, n_rows);
-            else if (crossfade) ssk::k_obs_rows<false, true>(p, n_rows);
-            else ssk::k_obs_rows<false>(p, n_rows);
-        });
-        if (rc) return rc;
-    }
-    return 0;
+    return run_obs_rows(p, hspec != nullptr, n_units, flags, wgs, parts_log2, 12345.0f, [&] {
+        if (hspec) ssk::k_obs_rows<true>(p, n_rows);
+        else if (crossfade) ssk::k_obs_rows<false, true>(p, n_rows);
+        else ssk::k_obs_rows<false>(p, n_rows);
+    }, wgs >= 8);
 }
 
+// the stand-alone feature kernels: gpw = the groups one workgroup should walk (sslaunch::plan_frames clamps it)
 int hs_spectrogram(const float* x, float* out, int n_units, int len, int pad_mode, int gpw) {
     ssk::SpecParams p;
     p.x = x; p.out = out; p.tb = host_tables();
-    p.len = len; p.n_frames = 1 + len / ssk::kHop; p.t4 = (p.n_frames + 3) / 4; p.pad_mode = pad_mode;
-    p.live = g_spec_n_valid >= 0 ? ssk::live_blocks(g_spec_n_valid, len, p.t4) : p.t4;
+    const int n_valid = g_spec_n_valid >= 0 ? g_spec_n_valid : len;
     g_spec_n_valid = -1;
     if (len < 1) return -2;                             // (the entry points' own argument checks, here and below)
-    const int groups = (p.t4 + 3) / 4;
-    p.gpw = gpw < 1 ? 1 : gpw > groups ? groups : gpw;
-    const int chunks = (groups + p.gpw - 1) / p.gpw;
-    gridDim = dim3{(unsigned)(n_units * chunks), 1, 1};
-    for (int b = 0; b < n_units * chunks; ++b) {
-        blockIdx = dim3{(unsigned)b, 0, 0};
-        int rc = run_block(512, [&] { ssk::k_spectrogram(p); });
-        if (rc) return rc;
-    }
-    return 0;
+    const sslaunch::FramesPlan pl = sslaunch::plan_frames(sslaunch::Frames::kPooled, n_units, len, n_valid, gpw);
+    p.len = len; p.n_frames = pl.n_frames; p.t4 = pl.t4; p.pad_mode = pad_mode; p.live = pl.live; p.gpw = pl.gpw;
+    return run_grid(pl.grid, 1, 512, [&] { ssk::k_spectrogram(p); });
 }
 
 int hs_logmel(const float* x, float* out, int n_units, int len, int pad_mode, const int* start, const float* w,
               int n_mels, int max_len, float eps, int gpw) {
     ssk::MelParams p;
     p.x = x; p.out = out; p.tb = host_tables(); p.start = start; p.w = w;
-    p.len = len; p.n_frames = 1 + len / ssk::kHop; p.pad_mode = pad_mode;
     p.n_mels = n_mels; p.max_len = max_len; p.eps = eps;
     if (len < 1 || n_mels < 1 || n_mels > ssk::kMelMaxBands || max_len > ssk::kMelMaxLen || (max_len & 3) || n_mels * max_len > ssk::kMelTableFloats) return -2;
-    const int groups = (p.n_frames + ssk::kSegFrames - 1) / ssk::kSegFrames;
-    p.gpw = gpw < 1 ? 1 : gpw > groups ? groups : gpw;
-    const int chunks = (groups + p.gpw - 1) / p.gpw;
-    gridDim = dim3{(unsigned)(n_units * chunks), 1, 1};
-    for (int b = 0; b < n_units * chunks; ++b) {
-        blockIdx = dim3{(unsigned)b, 0, 0};
-        int rc = run_block(512, [&] { ssk::k_logmel(p); });
-        if (rc) return rc;
-    }
-    return 0;
+    const sslaunch::FramesPlan pl = sslaunch::plan_frames(sslaunch::Frames::kSegments, n_units, len, len, gpw);
+    p.len = len; p.n_frames = pl.n_frames; p.pad_mode = pad_mode; p.gpw = pl.gpw;
+    return run_grid(pl.grid, 1, 512, [&] { ssk::k_logmel(p); });
 }
 
 int hs_gccphat(const float* x, float* out, int n_units, int len, int pad_mode, int max_lag, float eps, int gpw) {
     ssk::GccParams p;
     p.x = x; p.out = out; p.tb = host_tables();
-    p.len = len; p.n_frames = 1 + len / ssk::kHop; p.pad_mode = pad_mode; p.max_lag = max_lag; p.eps = eps;
+    p.max_lag = max_lag; p.eps = eps;
     if (len < 1 || max_lag < 1 || max_lag > ssk::kGccMaxLag) return -2;
-    const int groups = (p.n_frames + ssk::kSegFrames - 1) / ssk::kSegFrames;
-    p.gpw = gpw < 1 ? 1 : gpw > groups ? groups : gpw;
-    const int chunks = (groups + p.gpw - 1) / p.gpw;
-    gridDim = dim3{(unsigned)(n_units * chunks), 1, 1};
-    for (int b = 0; b < n_units * chunks; ++b) {
-        blockIdx = dim3{(unsigned)b, 0, 0};
-        int rc = run_block(256, [&] { ssk::k_gccphat(p); });
-        if (rc) return rc;
-    }
-    return 0;
+    const sslaunch::FramesPlan pl = sslaunch::plan_frames(sslaunch::Frames::kSegments, n_units, len, len, gpw);
+    p.len = len; p.n_frames = pl.n_frames; p.pad_mode = pad_mode; p.gpw = pl.gpw;
+    return run_grid(pl.grid, 1, 256, [&] { ssk::k_gccphat(p); });
 }
 
 int hs_features(const float* x, int n_units, int len, int pad_mode, float* sgram, float* mel, const int* start, const float* w,
                 int n_mels, int max_len, float mel_eps, float* gcc, int max_lag, float gcc_eps, int gpw) {
     ssk::FeatParams p;
     p.x = x; p.sgram = sgram; p.mel = mel; p.gcc = gcc; p.tb = host_tables(); p.mel_start = start; p.mel_w = w;
-    p.len = len; p.n_frames = 1 + len / ssk::kHop; p.t4 = (p.n_frames + 3) / 4; p.pad_mode = pad_mode;
     p.n_mels = mel ? n_mels : 0; p.max_len = mel ? max_len : 4; p.max_lag = gcc ? max_lag : 1;
     p.mel_eps = mel_eps; p.gcc_eps = gcc_eps;
     if (len < 1 || (!sgram && !mel && !gcc)) return -2;
     if (mel && (n_mels < 1 || n_mels > ssk::kFeatMaxMels || max_len > ssk::kFeatMaxLen || (max_len & 3) || n_mels * max_len > ssk::kFeatMelTable)) return -2;
     if (gcc && (max_lag < 1 || max_lag > ssk::kGccMaxLag)) return -2;
-    const int groups = (p.n_frames + ssk::kSegFrames - 1) / ssk::kSegFrames;
+    p.len = len; p.n_frames = sslaunch::n_frames_of(len); p.t4 = sslaunch::t4_of(len); p.pad_mode = pad_mode;
     p.n_units = n_units;
-    const int tasks = n_units * groups;                 // gpw: rounds per workgroup wanted -> grid = ceil(tasks / gpw)
-    const int wgs = (tasks + (gpw < 1 ? 1 : gpw) - 1) / (gpw < 1 ? 1 : gpw);
-    gridDim = dim3{(unsigned)wgs, 1, 1};
-    for (int b = 0; b < wgs; ++b) {
-        blockIdx = dim3{(unsigned)b, 0, 0};
-        int rc = run_block(256, [&] {
-            const int which = (mel ? 1 : 0) | (sgram ? 2 : 0) | (gcc ? 4 : 0);
-            switch (which) {
-                case 1: ssk::k_features<true, false, false>(p); break;
-                case 2: ssk::k_features<false, true, false>(p); break;
-                case 3: ssk::k_features<true, true, false>(p); break;
-                case 4: ssk::k_features<false, false, true>(p); break;
-                case 5: ssk::k_features<true, false, true>(p); break;
-                case 6: ssk::k_features<false, true, true>(p); break;
-                default: ssk::k_features<true, true, true>(p); break;
-            }
-        });
-        if (rc) return rc;
-    }
-    return 0;
+    // gpw: rounds per workgroup wanted -> at most ceil(tasks / gpw) resident workgroups
+    const int tasks = n_units * sslaunch::groups_of(sslaunch::Frames::kSegments, len), per_wg = gpw < 1 ? 1 : gpw;
+    const int wgs = sslaunch::features_grid(n_units, len, (tasks + per_wg - 1) / per_wg);
+    const int which = (mel ? 1 : 0) | (sgram ? 2 : 0) | (gcc ? 4 : 0);
+    return run_grid(wgs, 1, 256, [&] {
+        switch (which) {
+            case 1: ssk::k_features<true, false, false>(p); break;
+            case 2: ssk::k_features<false, true, false>(p); break;
+            case 3: ssk::k_features<true, true, false>(p); break;
+            case 4: ssk::k_features<false, false, true>(p); break;
+            case 5: ssk::k_features<true, false, true>(p); break;
+            case 6: ssk::k_features<false, true, true>(p); break;
+            default: ssk::k_features<true, true, true>(p); break;
+        }
+    });
 }
 
 int hs_intensity(const float* x, float* out, int n_units, int len, int num_frame) {
     ssk::IntensityParams p;
     p.x = x; p.out = out; p.len = len; p.num_frame = num_frame;
-    gridDim = dim3{(unsigned)n_units, 1, 1};
-    for (int b = 0; b < n_units; ++b) {
-        blockIdx = dim3{(unsigned)b, 0, 0};
-        int rc = run_block(256, [&] { ssk::k_intensity(p); });
-        if (rc) return rc;
-    }
-    return 0;
+    return run_grid(n_units, 1, 256, [&] { ssk::k_intensity(p); });
 }
 
 }  // extern "C"

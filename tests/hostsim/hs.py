@@ -10,7 +10,22 @@ import numpy as np
 from ss_amd import planning as P
 
 HERE = os.path.dirname(os.path.abspath(__file__))
+TESTS = os.path.dirname(HERE)
 _LIB = None
+
+
+def driver_command(name, so, extra=()):
+    """the ONE command line of a host build of the kernels: tests/<name>_host.cpp (hostsim.cpp included whole) -> `so`; cwd = tests/"""
+    cxx = os.environ.get("SS_HOSTSIM_CXX", "/opt/rocm/lib/llvm/bin/clang++")   # needs ext_vector_type
+    return [cxx, "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-Wno-pass-failed", "-I", TESTS,
+            "-include", os.path.join(HERE, "hip_shim.h")] + list(extra) + [f"{name}_host.cpp", "-o", so]
+
+
+def build_driver(name, out_dir, extra=()):
+    """compile tests/<name>_host.cpp into out_dir/libss_<name>_host.so -> its path"""
+    so = os.path.join(str(out_dir), f"libss_{name}_host.so")
+    subprocess.check_call(driver_command(name, so, extra), cwd=TESTS)
+    return so
 
 
 def lib():
@@ -19,7 +34,8 @@ def lib():
         so = os.path.join(HERE, "libss_hostsim.so")
         srcs = [os.path.join(HERE, f) for f in ("hostsim.cpp", "hip_shim.h")]
         csrc = os.path.join(HERE, "..", "..", "sound-spaces_amd", "csrc")
-        srcs += [os.path.join(csrc, f) for f in ("ss_kernels.hpp", "ss_fft_core.hpp", "ss_consts.hpp", "ss_tables.hpp", "ss_kernels32.hpp", "ss_fft_core32.hpp", "ss_features.hpp")]
+        srcs += [os.path.join(csrc, f) for f in ("ss_kernels.hpp", "ss_fft_core.hpp", "ss_consts.hpp", "ss_tables.hpp", "ss_kernels32.hpp", "ss_fft_core32.hpp", "ss_features.hpp",
+                                                   "ss_route.hpp", "ss_launch.hpp")]
         if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
             cxx = os.environ.get("SS_HOSTSIM_CXX", "/opt/rocm/lib/llvm/bin/clang++")   # needs ext_vector_type
             subprocess.check_call([cxx, "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas",

@@ -11,35 +11,19 @@ extern "C" int hs_obs_logmel(int spectral, int simple, const float* spec, const 
                              int pad_mode) {
     if (out_len < ssk::kNfft / 2 + 1 || out_len > ssk::kB || n_valid > out_len) return -1;
     if (simple && (spectral ? h_blocks != 1 : cap > ssk::kB)) return -2;
-    ssk::ConvParams p;
-    p.spec = reinterpret_cast<const ssk::f32x4*>(spec); p.rir_len = rir_len; p.desc = desc;
-    p.out = out; p.sgram = sgram; p.tb = host_tables();
-    p.rir = spectral ? nullptr : bank;
-    p.rir_unit_stride = spectral ? 0 : 2LL * cap; p.rir_chan_stride = spectral ? 0 : cap; p.rir_elem_stride = 1;
-    p.rir_cap = spectral ? 0 : cap;
-    p.hspec = spectral ? reinterpret_cast<const ssk::f32x4*>(bank) : nullptr;
-    p.h_blocks = spectral ? h_blocks : 0;
-    p.n_valid = n_valid; p.out_len = out_len;
-    p.n_frames = 1 + out_len / ssk::kHop;
-    p.t4 = (p.n_frames + 3) / 4;
-    p.pad_mode = pad_mode;
+    ssk::ConvParams p = conv_params(spec, rir_len, desc, out, sgram, n_valid, out_len, pad_mode);
+    if (spectral) set_spectra(p, bank, h_blocks);
+    else set_rows(p, bank, 2LL * cap, cap, 1, cap);
     p.fade_len = 0;
-    p.xcd_map = 0; p.stash = nullptr; p.stash_nbh = 0; p.stash_terms = 0; p.n_terms = 2; p.parts_log2 = 0; p.nb_y = 1;
     apply_bucket2(p);
     const ssk::MelArgs m{logmel, mel_start, mel_w, n_mels, max_len, mel_eps};
-    gridDim = dim3{(unsigned)(2 * n_units), 1, 1};
-    for (int b = 0; b < 2 * n_units; ++b) {
-        blockIdx = dim3{(unsigned)b, 0, 0};
-        int rc = run_block(ssk::kT, [&] {
-            if (spectral) {
-                if (simple) ssk::k_conv_spec<true, true, false, true>(p, m);
-                else ssk::k_conv_spec<true, false, false, true>(p, m);
-            } else {
-                if (simple) ssk::k_conv<true, true, false, false, false, true>(p, m);
-                else ssk::k_conv<true, false, false, false, false, true>(p, m);
-            }
-        });
-        if (rc) return rc;
-    }
-    return 0;
+    return run_grid(2 * n_units, 1, ssk::kT, [&] {
+        if (spectral) {
+            if (simple) ssk::k_conv_spec<true, true, false, true>(p, m);
+            else ssk::k_conv_spec<true, false, false, true>(p, m);
+        } else {
+            if (simple) ssk::k_conv<true, true, false, false, false, true>(p, m);
+            else ssk::k_conv<true, false, false, false, false, true>(p, m);
+        }
+    });
 }

@@ -11,33 +11,17 @@ extern "C" int hs_obs_logmel_ss2(int xfade, const float* spec, const float* bank
                                  float* sgram, float* logmel, const int* mel_start, const float* mel_w, int n_mels, int max_len,
                                  float mel_eps, int n_units, int cap, int n_valid, int out_len, int pad_mode) {
     if (out_len < ssk::kNfft / 2 + 1 || out_len > 3 * ssk::kB || n_valid < 0 || n_valid > out_len) return -1;
-    ssk::ConvParams p;
-    p.spec = reinterpret_cast<const ssk::f32x4*>(spec); p.rir_len = rir_len; p.desc = desc;
-    p.out = out; p.sgram = sgram; p.tb = host_tables();
-    p.rir = bank;
-    p.rir_unit_stride = 2LL * cap; p.rir_chan_stride = cap; p.rir_elem_stride = 1; p.rir_cap = cap;
-    p.hspec = nullptr; p.h_blocks = 0;
-    p.n_valid = n_valid; p.out_len = out_len;
-    p.n_frames = 1 + out_len / ssk::kHop;
-    p.t4 = (p.n_frames + 3) / 4;
-    p.pad_mode = pad_mode;
-    p.fade_len = static_cast<int>(0.05 * out_len);
-    p.xcd_map = 0; p.stash = nullptr; p.stash_nbh = 0; p.stash_terms = 0; p.n_terms = 2; p.parts_log2 = 0; p.nb_y = 1;
+    ssk::ConvParams p = conv_params(spec, rir_len, desc, out, sgram, n_valid, out_len, pad_mode);
+    set_rows(p, bank, 2LL * cap, cap, 1, cap);
     apply_bucket2(p);
     const bool wide = out_len > ssk::kB;
-    if (wide && (n_valid > ssk::kB || ssk::live_blocks(n_valid, out_len, p.t4) > 26)) return -2;
+    if (wide && !ssroute::wide_one_block_ok(out_len, n_valid, 0, false, ssroute::Switches())) return -2;      // (the shape alone)
     if (!wide && !xfade) return -3;
     if (xfade && (p.fade_len < 1 || p.fade_len > 2 * ssk::kPrevPairs - 2)) return -4;
     const ssk::MelArgs m{logmel, mel_start, mel_w, n_mels, max_len, mel_eps};
-    gridDim = dim3{(unsigned)(2 * n_units), 1, 1};
-    for (int b = 0; b < 2 * n_units; ++b) {
-        blockIdx = dim3{(unsigned)b, 0, 0};
-        int rc = run_block(ssk::kT, [&] {
-            if (!wide) ssk::k_conv<true, false, true, false, false, true>(p, m);
-            else if (xfade) ssk::k_conv<true, false, true, false, true, true>(p, m);
-            else ssk::k_conv<true, false, false, false, true, true>(p, m);
-        });
-        if (rc) return rc;
-    }
-    return 0;
+    return run_grid(2 * n_units, 1, ssk::kT, [&] {
+        if (!wide) ssk::k_conv<true, false, true, false, false, true>(p, m);
+        else if (xfade) ssk::k_conv<true, false, true, false, true, true>(p, m);
+        else ssk::k_conv<true, false, false, false, true, true>(p, m);
+    });
 }

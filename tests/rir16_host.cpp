@@ -9,14 +9,7 @@ extern "C" int hs_rows_half(const float* rir, void* rir16, float* rscale, int n_
     if (cap < 2 || (cap & 1)) return -1;
     ssk::RowsHalfParams p;
     p.rir = rir; p.rir16 = static_cast<ssk::h16x2*>(rir16); p.rscale = rscale; p.unit_stride = us; p.chan_stride = cs; p.cap = cap;
-    gridDim = dim3{2, (unsigned)n_entries, 1};
-    for (int r = 0; r < n_entries; ++r)
-        for (int c = 0; c < 2; ++c) {
-            blockIdx = dim3{(unsigned)c, (unsigned)r, 0};
-            int rc = run_block(256, [&] { ssk::k_rows_half(p); });
-            if (rc) return rc;
-        }
-    return 0;
+    return run_grid(2, n_entries, 256, [&] { ssk::k_rows_half(p); });
 }
 
 // as ss_bank_scatter_rows16_f32
@@ -26,13 +19,7 @@ extern "C" int hs_scatter_rows16(const float* staged, long long staged_stride, c
     ssk::ScatterRows16Params p;
     p.staged = staged; p.slots = slots; p.lens = lens; p.rir16 = static_cast<ssk::h16x2*>(rir16); p.rscale = rscale;
     p.bank_len = bank_len; p.staged_stride = staged_stride; p.cap = cap;
-    gridDim = dim3{(unsigned)n, 1, 1};
-    for (int i = 0; i < n; ++i) {
-        blockIdx = dim3{(unsigned)i, 0, 0};
-        int rc = run_block(256, [&] { ssk::k_scatter_rows16(p); });
-        if (rc) return rc;
-    }
-    return 0;
+    return run_grid(n, 1, 256, [&] { ssk::k_scatter_rows16(p); });
 }
 
 // k_conv over a bank of half rows (half != 0: `bank` = fp16 [R][2][cap], rscale [R][2]) or over the planar fp32 bank [R][2][cap]
@@ -41,54 +28,36 @@ extern "C" int hs_scatter_rows16(const float* staged, long long staged_stride, c
 extern "C" int hs_conv_rir16_ab(int half, int fuse, int simple, int use_tab, const float* spec, const void* bank, const float* rscale,
                                 const int* rir_len, const int* desc, float* out, float* sgram, int n_units, int cap, int n_valid,
                                 int out_len, int pad_mode, int parts_log2) {
-    const int nb_y = n_valid == 0 ? 1 : (n_valid + ssk::kB - 1) / ssk::kB;
-    if (cap < 2 || (cap & 1) || (cap + ssk::kB - 1) / ssk::kB > 16 || nb_y > 3) return -5;
+    const int nb_y = sslaunch::nb_y_of(n_valid);
+    if (cap < 2 || (cap & 1) || ssroute::ceil_div(cap, ssk::kB) > 16 || nb_y > 3) return -5;
     if (fuse && (nb_y != 1 || out_len > ssk::kB || out_len < ssk::kNfft / 2 + 1 || !sgram)) return -1;
     if (simple && (nb_y != 1 || cap > ssk::kB)) return -2;
     if (use_tab && (!simple || n_units > ssk::kTabUnits)) return -4;
     if (parts_log2 < 0 || parts_log2 > 3 || (parts_log2 && !fuse)) return -3;
-    ssk::ConvParams p;
-    p.spec = reinterpret_cast<const ssk::f32x4*>(spec); p.rir_len = rir_len; p.desc = desc;
-    p.out = out; p.sgram = sgram; p.tb = host_tables();
-    p.rir = half ? nullptr : static_cast<const float*>(bank);
-    p.rir_unit_stride = half ? 0 : 2LL * cap; p.rir_chan_stride = half ? 0 : cap; p.rir_elem_stride = 1; p.rir_cap = cap;
-    p.n_valid = n_valid; p.out_len = out_len;
-    p.n_frames = 1 + out_len / ssk::kHop;
-    p.t4 = (p.n_frames + 3) / 4;
-    p.pad_mode = pad_mode;
+    ssk::ConvParams p = conv_params(spec, rir_len, desc, out, sgram, n_valid, out_len, pad_mode);
+    if (half) p.rir_cap = cap;                          // (half rows: addressed through rs)
+    else set_rows(p, static_cast<const float*>(bank), 2LL * cap, cap, 1, cap);
     p.fade_len = 0;
-    p.hspec = nullptr; p.h_blocks = 0; p.xcd_map = 0; p.stash = nullptr; p.stash_nbh = 0; p.stash_terms = 0; p.n_terms = 2;
-    p.parts_log2 = parts_log2;
-    p.nb_y = nb_y;
     apply_bucket2(p);
+    // the caller chooses the kernel (simple); never the persistent one: the half form has none, the fp32 arm keeps the same grid
+    const sslaunch::ConvPlan pl = sslaunch::plan_conv(half ? sslaunch::Form::kRows16 : sslaunch::Form::kRows, fuse, false,
+                                                      simple ? SS_FLAG_NO_DISTRACTOR | SS_FLAG_FIRST_BUCKET : 0, cap, 0, p.n_buckets, p.fade_len,
+                                                      false, false, n_units, nb_y, kBigChip, 1, forced_parts(parts_log2));
+    if (pl.rc) return -5;
+    sslaunch::apply(pl, p);
     const ssk::RowScale<true> rs{static_cast<const ssk::h16x2*>(bank), rscale};
     ssk::UnitTab<true> ut;
-    if (use_tab)
-        for (int k = 0; k < n_units; ++k) {                 // launch slot k renders unit n - 1 - k (as hs_conv32)
-            const int i = n_units - 1 - k;
-            const int* d = desc + 8 * i;
-            const bool ok = d[0] >= 0 && d[2] <= 0 && d[2] + d[3] > 0;
-            ut.tab[ssk::kTabWords * k] = ok ? d[0] : -1;
-            ut.tab[ssk::kTabWords * k + 1] = ok ? d[1] - d[2] : 0;
-            ut.tab[ssk::kTabWords * k + 2] = i;
-        }
-    const int gx = (2 * n_units) << parts_log2;
-    gridDim = dim3{(unsigned)gx, (unsigned)nb_y, 1};
+    if (use_tab) fill_tab_reversed(ut, desc, n_units);
     const ssk::UnitTab<false> nt;
-    for (int b = 0; b < gx * nb_y; ++b) {
-        blockIdx = dim3{(unsigned)(b % gx), (unsigned)(b / gx), 0};
-        int rc = run_block(ssk::kT, [&] {
-            if (half) {
-                if (use_tab) { if (fuse) ssk::k_conv<true, true, false, true, false, false, true>(p, ut, rs); else ssk::k_conv<false, true, false, true, false, false, true>(p, ut, rs); }
-                else if (fuse) { if (simple) ssk::k_conv<true, true, false, false, false, false, true>(p, nt, rs); else ssk::k_conv<true, false, false, false, false, false, true>(p, nt, rs); }
-                else { if (simple) ssk::k_conv<false, true, false, false, false, false, true>(p, nt, rs); else ssk::k_conv<false, false, false, false, false, false, true>(p, nt, rs); }
-            } else {
-                if (use_tab) { if (fuse) ssk::k_conv<true, true, false, true>(p, ut); else ssk::k_conv<false, true, false, true>(p, ut); }
-                else if (fuse) { if (simple) ssk::k_conv<true, true>(p); else ssk::k_conv<true, false>(p); }
-                else { if (simple) ssk::k_conv<false, true>(p); else ssk::k_conv<false, false>(p); }
-            }
-        });
-        if (rc) return rc;
-    }
-    return 0;
+    return run_grid(pl.grid_x, pl.grid_y, ssk::kT, [&] {
+        if (half) {
+            if (use_tab) { if (fuse) ssk::k_conv<true, true, false, true, false, false, true>(p, ut, rs); else ssk::k_conv<false, true, false, true, false, false, true>(p, ut, rs); }
+            else if (fuse) { if (simple) ssk::k_conv<true, true, false, false, false, false, true>(p, nt, rs); else ssk::k_conv<true, false, false, false, false, false, true>(p, nt, rs); }
+            else { if (simple) ssk::k_conv<false, true, false, false, false, false, true>(p, nt, rs); else ssk::k_conv<false, false, false, false, false, false, true>(p, nt, rs); }
+        } else {
+            if (use_tab) { if (fuse) ssk::k_conv<true, true, false, true>(p, ut); else ssk::k_conv<false, true, false, true>(p, ut); }
+            else if (fuse) { if (simple) ssk::k_conv<true, true>(p); else ssk::k_conv<true, false>(p); }
+            else { if (simple) ssk::k_conv<false, true>(p); else ssk::k_conv<false, false>(p); }
+        }
+    });
 }

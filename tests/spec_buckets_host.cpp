@@ -12,51 +12,29 @@
 extern "C" int hs_conv_spec_buckets(int half, int fuse, const float* spec, const void* const* hspec, const float* const* hscale,
                                     const float* const* rows, const int* first, const int* cap, int n_buckets, const int* rir_len,
                                     const int* desc, float* out, float* sgram, int n_units, int n_valid, int out_len, int pad_mode) {
-    const int nb_y = n_valid == 0 ? 1 : (n_valid + ssk::kB - 1) / ssk::kB;
+    const int nb_y = sslaunch::nb_y_of(n_valid);
     if (n_buckets < 1 || n_buckets > ssk::kMaxBuckets || nb_y > 3) return -1;
     if (fuse && (nb_y != 1 || out_len > ssk::kB || out_len < ssk::kNfft / 2 + 1)) return -2;
     if (half && rows) return -3;
-    ssk::ConvParams p;
-    p.spec = reinterpret_cast<const ssk::f32x4*>(spec); p.rir_len = rir_len; p.desc = desc;
-    p.out = out; p.sgram = sgram; p.tb = host_tables();
-    p.rir = rows ? rows[0] : nullptr;
-    p.rir_unit_stride = rows ? 2LL * cap[0] : 0; p.rir_chan_stride = rows ? cap[0] : 0; p.rir_elem_stride = 1; p.rir_cap = rows ? cap[0] : 0;
-    p.n_valid = n_valid; p.out_len = out_len;
-    p.n_frames = 1 + out_len / ssk::kHop;
-    p.t4 = (p.n_frames + 3) / 4;
-    p.pad_mode = pad_mode;
+    ssk::ConvParams p = conv_params(spec, rir_len, desc, out, sgram, n_valid, out_len, pad_mode);
+    if (rows) set_rows(p, rows[0], 2LL * cap[0], cap[0], 1, cap[0]);
+    set_spectra(p, hspec[0], ssroute::ceil_div(cap[0], ssk::kB));
     p.fade_len = 0;
-    p.hspec = static_cast<const ssk::f32x4*>(hspec[0]);
-    p.h_blocks = (cap[0] + ssk::kB - 1) / ssk::kB;
-    p.xcd_map = 0; p.stash = nullptr; p.stash_nbh = 0; p.stash_terms = 0; p.n_terms = 2; p.parts_log2 = 0;
-    p.nb_y = nb_y;
-    p.n_buckets = n_buckets;
-    ssk::SpecScale<true, true> hs;
-    hs.hscale = half ? hscale[0] : nullptr;
-    for (int b = 0; b < ssk::kMaxBuckets - 1; ++b) {
-        p.bk[b] = ssk::BankBucket{nullptr, nullptr, 0x7fffffff, 0, 0, 0};
-        hs.bk[b] = nullptr;
-    }
-    for (int b = 1; b < n_buckets; ++b) {
-        p.bk[b - 1] = ssk::BankBucket{rows ? rows[b] : nullptr, static_cast<const ssk::f32x4*>(hspec[b]), first[b], cap[b],
-                                      (cap[b] + ssk::kB - 1) / ssk::kB, 0};
-        hs.bk[b - 1] = half ? hscale[b] : nullptr;
-    }
-    const int grid = 2 * n_units * nb_y;
-    gridDim = dim3{(unsigned)grid, 1, 1};
+    set_buckets(p, rows, hspec, first, cap, n_buckets);
+    const ssk::SpecScale<true, true> hs = bucket_scales(half ? hscale : nullptr, n_buckets);
+    // the loop kernel over every bucket (no SS_FLAG_FIRST_BUCKET), one workgroup per (row, output block): no parts
+    const sslaunch::ConvPlan pl = sslaunch::plan_conv(half ? sslaunch::Form::kSpec16Buckets : sslaunch::Form::kSpec, fuse, false, 0, p.rir_cap,
+                                                      p.h_blocks, n_buckets, p.fade_len, false, false, n_units, nb_y, kBigChip, 1, forced_parts(0));
+    if (pl.rc) return -1;
+    sslaunch::apply(pl, p);
     const ssk::UnitTab<false> nt;
-    for (int b = 0; b < grid; ++b) {
-        blockIdx = dim3{(unsigned)b, 0, 0};
-        int rc = run_block(ssk::kT, [&] {
-            if (half) {
-                if (fuse) ssk::k_conv_spec<true, false, false, false, true, true>(p, nt, hs);
-                else ssk::k_conv_spec<false, false, false, false, true, true>(p, nt, hs);
-            } else {
-                if (fuse) ssk::k_conv_spec<true, false>(p);
-                else ssk::k_conv_spec<false, false>(p);
-            }
-        });
-        if (rc) return rc;
-    }
-    return 0;
+    return run_grid(pl.grid_x, pl.grid_y, ssk::kT, [&] {
+        if (half) {
+            if (fuse) ssk::k_conv_spec<true, false, false, false, true, true>(p, nt, hs);
+            else ssk::k_conv_spec<false, false, false, false, true, true>(p, nt, hs);
+        } else {
+            if (fuse) ssk::k_conv_spec<true, false>(p);
+            else ssk::k_conv_spec<false, false>(p);
+        }
+    });
 }

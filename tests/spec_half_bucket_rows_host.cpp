@@ -24,80 +24,39 @@ extern "C" int hs_obs_rows_half_buckets(int form, int blocks, int mel, const flo
     if (blocks && n_valid != out_len) return -3;
     if (parts_log2 < 0 || parts_log2 > 3 || wgs < 1) return -2;
     for (int b = 0; b < n_buckets; ++b)
-        if (!bank[b] || (form && !hscale[b]) || cap[b] < 2 || (cap[b] + ssk::kB - 1) / ssk::kB > 16) return -4;
-    ssk::ConvParams p;
-    p.spec = reinterpret_cast<const ssk::f32x4*>(spec); p.rir_len = rir_len; p.desc = desc;
-    p.out = out; p.sgram = sgram; p.tb = host_tables();
-    p.rir = nullptr; p.rir_unit_stride = 0; p.rir_chan_stride = 0; p.rir_elem_stride = 1; p.rir_cap = 0;
-    p.hspec = static_cast<const ssk::f32x4*>(bank[0]);
-    p.h_blocks = (cap[0] + ssk::kB - 1) / ssk::kB;
-    p.n_valid = n_valid; p.out_len = out_len;
-    p.n_frames = 1 + out_len / ssk::kHop;
-    p.t4 = (p.n_frames + 3) / 4;
-    p.pad_mode = pad_mode;
+        if (!bank[b] || (form && !hscale[b]) || cap[b] < 2 || ssroute::ceil_div(cap[b], ssk::kB) > 16) return -4;
+    ssk::ConvParams p = conv_params(spec, rir_len, desc, out, sgram, n_valid, out_len, pad_mode);
+    set_spectra(p, bank[0], ssroute::ceil_div(cap[0], ssk::kB));
     p.fade_len = 0;
-    p.n_terms = no_distractor ? 1 : 2;
-    p.parts_log2 = parts_log2;
-    p.stash = nullptr; p.stash_nbh = 0; p.stash_terms = 0;
-    p.n_buckets = n_buckets;
-    ssk::SpecScale<true, true> hs;
-    hs.hscale = form ? hscale[0] : nullptr;
-    for (int b = 0; b < ssk::kMaxBuckets - 1; ++b) {
-        p.bk[b] = ssk::BankBucket{nullptr, nullptr, 0x7fffffff, 0, 0, 0};
-        hs.bk[b] = nullptr;
-    }
-    for (int b = 1; b < n_buckets; ++b) {
-        p.bk[b - 1] = ssk::BankBucket{nullptr, static_cast<const ssk::f32x4*>(bank[b]), first[b], cap[b], (cap[b] + ssk::kB - 1) / ssk::kB, 0};
-        hs.bk[b - 1] = form ? hscale[b] : nullptr;
-    }
+    set_buckets(p, nullptr, bank, first, cap, n_buckets);
+    const ssk::SpecScale<true, true> hs = bucket_scales(form ? hscale : nullptr, n_buckets);
     const ssk::SpecScale<true> hs1{hs.hscale};
     const ssk::MelArgs m{logmel, mel_start, mel_w, n_mels, max_len, mel_eps};
     const ssk::UnitTab<false> nt;
-    const int n_rows = 2 * n_units;
-    if (blocks) {
-        const int nb = (out_len + ssk::kB - 1) / ssk::kB, grid_b = (n_rows * nb) << parts_log2;
-        p.nb_y = nb;
-        p.xcd_map = 0;                                  // workgroups run in blockIdx order here: (row, j - 1) before (row, j)
-        std::vector<float> tails(static_cast<size_t>(n_rows) * 2 * ssk::kTailFloats, 12345.0f);
-        std::vector<int> fl(static_cast<size_t>(n_rows) * 2, 0);
-        gridDim = dim3{(unsigned)grid_b, 1, 1};
-        for (int b = 0; b < grid_b; ++b) {
-            blockIdx = dim3{(unsigned)b, 0, 0};
-            int rc = run_block(ssk::kT, [&] {
-                if (form == 1) {
-                    if (mel) ssk::k_obs_blocks<true, true, true, true>(p, n_rows, tails.data(), fl.data(), 7, m, hs);
-                    else ssk::k_obs_blocks<true, false, true, true>(p, n_rows, tails.data(), fl.data(), 7, nt, hs);
-                } else if (form == 2) {
-                    if (mel) ssk::k_obs_blocks<true, true, true>(p, n_rows, tails.data(), fl.data(), 7, m, hs1);
-                    else ssk::k_obs_blocks<true, false, true>(p, n_rows, tails.data(), fl.data(), 7, nt, hs1);
-                } else {
-                    if (mel) ssk::k_obs_blocks<true, true>(p, n_rows, tails.data(), fl.data(), 7, m);
-                    else ssk::k_obs_blocks<true>(p, n_rows, tails.data(), fl.data(), 7);
-                }
-            });
-            if (rc) return rc;
-        }
-        return 0;
-    }
-    const int grid = parts_log2 ? (n_rows << parts_log2) : (wgs < n_rows ? wgs : n_rows);
-    p.xcd_map = grid >= 8;
-    p.nb_y = n_valid == 0 ? 0 : (n_valid + ssk::kB - 1) / ssk::kB;
-    gridDim = dim3{(unsigned)grid, 1, 1};
-    for (int b = 0; b < grid; ++b) {
-        blockIdx = dim3{(unsigned)b, 0, 0};
-        int rc = run_block(ssk::kT, [&] {
+    const int n_rows = 2 * n_units, flags = no_distractor ? SS_FLAG_NO_DISTRACTOR : 0;
+    if (blocks)
+        return run_obs_blocks(p, n_units, flags, parts_log2, [&](float* tails, int* fl) {
             if (form == 1) {
-                if (mel) ssk::k_obs_rows<true, false, true, true, true>(p, n_rows, m, hs);
-                else ssk::k_obs_rows<true, false, true, false, true>(p, n_rows, nt, hs);
+                if (mel) ssk::k_obs_blocks<true, true, true, true>(p, n_rows, tails, fl, 7, m, hs);
+                else ssk::k_obs_blocks<true, false, true, true>(p, n_rows, tails, fl, 7, nt, hs);
             } else if (form == 2) {
-                if (mel) ssk::k_obs_rows<true, false, false, true, true>(p, n_rows, m, hs1);
-                else ssk::k_obs_rows<true, false, false, false, true>(p, n_rows, nt, hs1);
+                if (mel) ssk::k_obs_blocks<true, true, true>(p, n_rows, tails, fl, 7, m, hs1);
+                else ssk::k_obs_blocks<true, false, true>(p, n_rows, tails, fl, 7, nt, hs1);
             } else {
-                if (mel) ssk::k_obs_rows<true, false, true, true>(p, n_rows, m);
-                else ssk::k_obs_rows<true, false, true>(p, n_rows);
+                if (mel) ssk::k_obs_blocks<true, true>(p, n_rows, tails, fl, 7, m);
+                else ssk::k_obs_blocks<true>(p, n_rows, tails, fl, 7);
             }
         });
-        if (rc) return rc;
-    }
-    return 0;
+    return run_obs_rows(p, true, n_units, flags, wgs, parts_log2, 12345.0f, [&] {
+        if (form == 1) {
+            if (mel) ssk::k_obs_rows<true, false, true, true, true>(p, n_rows, m, hs);
+            else ssk::k_obs_rows<true, false, true, false, true>(p, n_rows, nt, hs);
+        } else if (form == 2) {
+            if (mel) ssk::k_obs_rows<true, false, false, true, true>(p, n_rows, m, hs1);
+            else ssk::k_obs_rows<true, false, false, false, true>(p, n_rows, nt, hs1);
+        } else {
+            if (mel) ssk::k_obs_rows<true, false, true, true>(p, n_rows, m);
+            else ssk::k_obs_rows<true, false, true>(p, n_rows);
+        }
+    });
 }

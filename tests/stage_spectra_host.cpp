@@ -11,12 +11,5 @@ extern "C" int hs_stage_spectra(const float* staged, long long staged_stride, in
     p.staged_stride = staged_stride; p.planar = planar; p.h_blocks = h_blocks;
     const long long frames = staged_stride / 2, hb_frames = static_cast<long long>(h_blocks) * ssk::kB;
     p.cap = static_cast<int>(frames < hb_frames ? frames : hb_frames);       // (as ss_bank_scatter_spectra_f32)
-    gridDim = dim3{(unsigned)h_blocks, (unsigned)n, 1};
-    for (int i = 0; i < n; ++i)
-        for (int b = 0; b < h_blocks; ++b) {
-            blockIdx = dim3{(unsigned)b, (unsigned)i, 0};
-            int rc = run_block(ssk::kT, [&] { ssk::k_stage_spectra(p); });
-            if (rc) return rc;
-        }
-    return 0;
+    return run_grid(h_blocks, n, ssk::kT, [&] { ssk::k_stage_spectra(p); });
 }

@@ -8,12 +8,11 @@ multiple of 4 - 8-byte path), 32000 and 88200 (audiogoal rows: 8 and 22 chunks p
 alignment take the narrower paths for a row size that would allow 16."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-pytest.importorskip("hostsim.hs")
+hs = pytest.importorskip("hostsim.hs")
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GUARD = 64
@@ -22,10 +21,7 @@ N_ROWS, N_SLOTS = 40, 50
 
 @pytest.fixture(scope="module")
 def lib(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("memo_rows") / "libss_memo_rows_host.so")
-    cxx = os.environ.get("SS_HOSTSIM_CXX", "/opt/rocm/lib/llvm/bin/clang++")      # (needs ext_vector_type, as hostsim)
-    subprocess.check_call([cxx, "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-Wno-pass-failed", "-I", HERE,
-                           "-include", os.path.join(HERE, "hostsim", "hip_shim.h"), "memo_rows_host.cpp", "-o", so], cwd=HERE)
+    so = hs.build_driver("memo_rows", tmp_path_factory.mktemp("memo_rows"))
     L = ctypes.CDLL(so)
     vp, ci = ctypes.c_void_p, ctypes.c_int
     L.hs_memo_rows.argtypes = [vp, vp, vp, ci, vp, ci, ci, ci]

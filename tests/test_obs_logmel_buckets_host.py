@@ -21,7 +21,6 @@ persistent workgroups and with rows split over 2, k_obs_blocks<.., MEL> over the
 Every output is pre-filled with NaN, every unit is compared."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -47,10 +46,7 @@ ROWS, SPEC, HALF = 0, 1, 2
 
 @pytest.fixture(scope="module")
 def lib(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("obs_logmel_buckets") / "libss_obs_logmel_buckets_host.so")
-    cxx = os.environ.get("SS_HOSTSIM_CXX", "/opt/rocm/lib/llvm/bin/clang++")      # (needs ext_vector_type, as hostsim)
-    subprocess.check_call([cxx, "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-Wno-pass-failed", "-I", HERE,
-                           "-include", os.path.join(HERE, "hostsim", "hip_shim.h"), "obs_logmel_buckets_host.cpp", "-o", so], cwd=HERE)
+    so = hs.build_driver("obs_logmel_buckets", tmp_path_factory.mktemp("obs_logmel_buckets"))
     L = ctypes.CDLL(so)
     vp, ci, ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
     L.hs_obs_logmel_buckets.argtypes = [ci, ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, ci, ci, ctypes.c_float,

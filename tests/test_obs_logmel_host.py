@@ -6,7 +6,6 @@ Tolerances: the project's log-mel rule (tests/test_logmel.py::check, 1e-4 of the
 spectrogram; today's two-step host path sits at 6.1e-6 against the same oracle expression."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -25,10 +24,7 @@ PAD_NAME = {0: "reflect", 1: "constant"}
 
 @pytest.fixture(scope="module")
 def mel_lib(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("obs_logmel") / "libss_obs_logmel_host.so")
-    cxx = os.environ.get("SS_HOSTSIM_CXX", "/opt/rocm/lib/llvm/bin/clang++")      # (needs ext_vector_type, as hostsim)
-    subprocess.check_call([cxx, "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-Wno-pass-failed", "-I", HERE,
-                           "-include", os.path.join(HERE, "hostsim", "hip_shim.h"), "obs_logmel_host.cpp", "-o", so], cwd=HERE)
+    so = hs.build_driver("obs_logmel", tmp_path_factory.mktemp("obs_logmel"))
     lib = ctypes.CDLL(so)
     vp, ci = ctypes.c_void_p, ctypes.c_int
     lib.hs_obs_logmel.argtypes = [ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ctypes.c_float, ci, ci, ci, ci, ci, ci]

@@ -4,7 +4,6 @@ against the oracle: compute_logmel of compute_audiogoal_continuous.  Tolerances:
 value, tests/test_obs_logmel_host.py::_check_mel), relerr <= 1e-4 for the pooled spectrogram, 1e-5 for the waveform."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -22,10 +21,7 @@ PAD_NAME = {0: "reflect", 1: "constant"}
 
 @pytest.fixture(scope="module")
 def ss2_lib(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("obs_logmel_ss2") / "libss_obs_logmel_ss2_host.so")
-    cxx = os.environ.get("SS_HOSTSIM_CXX", "/opt/rocm/lib/llvm/bin/clang++")      # (needs ext_vector_type, as hostsim)
-    subprocess.check_call([cxx, "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-Wno-pass-failed", "-I", HERE,
-                           "-include", os.path.join(HERE, "hostsim", "hip_shim.h"), "obs_logmel_ss2_host.cpp", "-o", so], cwd=HERE)
+    so = hs.build_driver("obs_logmel_ss2", tmp_path_factory.mktemp("obs_logmel_ss2"))
     lib = ctypes.CDLL(so)
     vp, ci = ctypes.c_void_p, ctypes.c_int
     lib.hs_obs_logmel_ss2.argtypes = [ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ctypes.c_float, ci, ci, ci, ci, ci]

@@ -10,7 +10,6 @@ relerr <= 1e-4 for the pooled spectrogram.  On these inputs today's two-step hos
 Every output is pre-filled with NaN, every unit is compared, nothing is masked out."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -28,10 +27,7 @@ PAD_NAME = {0: "reflect", 1: "constant"}
 
 @pytest.fixture(scope="module")
 def mel_lib(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("obs_rows_logmel") / "libss_obs_rows_logmel_host.so")
-    cxx = os.environ.get("SS_HOSTSIM_CXX", "/opt/rocm/lib/llvm/bin/clang++")      # (needs ext_vector_type, as hostsim)
-    subprocess.check_call([cxx, "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-Wno-pass-failed", "-I", HERE,
-                           "-include", os.path.join(HERE, "hostsim", "hip_shim.h"), "obs_rows_logmel_host.cpp", "-o", so], cwd=HERE)
+    so = hs.build_driver("obs_rows_logmel", tmp_path_factory.mktemp("obs_rows_logmel"))
     lib = ctypes.CDLL(so)
     vp, ci = ctypes.c_void_p, ctypes.c_int
     lib.hs_obs_rows_logmel.argtypes = [ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ctypes.c_float,

@@ -30,6 +30,7 @@ from oracle import ss_oracle as O
 from ss_amd import planning as P
 
 import rir16_ref as R
+hs = pytest.importorskip("hostsim.hs")
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 BOUND = 2e-6
@@ -40,10 +41,7 @@ WAVE, SGRAM, BOTH, MEL, MEL_SGRAM = range(5)
 
 @pytest.fixture(scope="module")
 def lib(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("rir16") / "libss_rir16_host.so")
-    cxx = os.environ.get("SS_HOSTSIM_CXX", "/opt/rocm/lib/llvm/bin/clang++")      # (needs ext_vector_type, as hostsim)
-    subprocess.check_call([cxx, "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-Wno-pass-failed", "-I", HERE,
-                           "-include", os.path.join(HERE, "hostsim", "hip_shim.h"), "rir16_host.cpp", "-o", so], cwd=HERE)
+    so = hs.build_driver("rir16", tmp_path_factory.mktemp("rir16"))
     lib = ctypes.CDLL(so)
     vp, ci, ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
     lib.hs_rows_half.argtypes = [vp, vp, vp, ci, ll, ci, ci]

@@ -32,6 +32,7 @@ from ss_amd import planning as P
 
 import rir16_ref as R
 import test_rir16_host as T
+hs = pytest.importorskip("hostsim.hs")
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 BOUND = T.BOUND
@@ -41,10 +42,7 @@ WAVE, SGRAM, BOTH, MEL, MEL_SGRAM = range(5)
 
 @pytest.fixture(scope="module")
 def lib(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("rir16_rows") / "libss_rir16_rows_host.so")
-    cxx = os.environ.get("SS_HOSTSIM_CXX", "/opt/rocm/lib/llvm/bin/clang++")      # (needs ext_vector_type, as hostsim)
-    subprocess.check_call([cxx, "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-Wno-pass-failed", "-I", HERE,
-                           "-include", os.path.join(HERE, "hostsim", "hip_shim.h"), "rir16_rows_host.cpp", "-o", so], cwd=HERE)
+    so = hs.build_driver("rir16_rows", tmp_path_factory.mktemp("rir16_rows"))
     lib = ctypes.CDLL(so)
     vp, ci = ctypes.c_void_p, ctypes.c_int
     lib.hs_obs_rows_rir16_ab.argtypes = [ci, ci, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci]

@@ -14,7 +14,6 @@ fp32 form: the launch without time-domain rows anywhere in its arguments is bit-
 the same spectra."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -37,10 +36,7 @@ BUDGET = 1e-4
 
 @pytest.fixture(scope="module")
 def lib(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("spec_buckets") / "libss_spec_buckets_host.so")
-    cxx = os.environ.get("SS_HOSTSIM_CXX", "/opt/rocm/lib/llvm/bin/clang++")      # (needs ext_vector_type, as hostsim)
-    subprocess.check_call([cxx, "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-Wno-pass-failed", "-I", HERE,
-                           "-include", os.path.join(HERE, "hostsim", "hip_shim.h"), "spec_buckets_host.cpp", "-o", so], cwd=HERE)
+    so = hs.build_driver("spec_buckets", tmp_path_factory.mktemp("spec_buckets"))
     L = ctypes.CDLL(so)
     vp, ci, ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
     L.hs_conv_spec_buckets.argtypes = [ci, ci, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, ci, ci, ci, ci]

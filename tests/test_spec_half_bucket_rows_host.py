@@ -12,7 +12,6 @@ nbh = min(ceil(rir_len / kB), the bucket's blocks): <= 1e-4 of peak.
 One bucket: the bucketed instantiation over a single bucket equals the single-allocation HALF instantiation bit for bit."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -22,6 +21,7 @@ from ss_amd import planning as P
 
 import spec_half_bucket_rows_world as W
 import spec_half_rows_ref as R
+hs = pytest.importorskip("hostsim.hs")
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 BOUND = 2e-6
@@ -32,10 +32,7 @@ EPS = 1e-6
 
 @pytest.fixture(scope="module")
 def lib(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("spec_half_bucket_rows") / "libss_spec_half_bucket_rows_host.so")
-    cxx = os.environ.get("SS_HOSTSIM_CXX", "/opt/rocm/lib/llvm/bin/clang++")      # (needs ext_vector_type, as hostsim)
-    subprocess.check_call([cxx, "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-Wno-pass-failed", "-I", HERE,
-                           "-include", os.path.join(HERE, "hostsim", "hip_shim.h"), "spec_half_bucket_rows_host.cpp", "-o", so], cwd=HERE)
+    so = hs.build_driver("spec_half_bucket_rows", tmp_path_factory.mktemp("spec_half_bucket_rows"))
     lib = ctypes.CDLL(so)
     vp, ci, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
     lib.hs_obs_rows_half_buckets.argtypes = [ci, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, ci, ci, cf, ci, ci, ci, ci,

@@ -11,7 +11,6 @@ parity record and the inputs are identical; measured 0.0 on every form (the dequ
 behind it is the same instructions) - profiles/r7/NOTES.md."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -33,10 +32,7 @@ EPS = 1e-6
 
 @pytest.fixture(scope="module")
 def half_lib(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("spec_half") / "libss_spec_half_host.so")
-    cxx = os.environ.get("SS_HOSTSIM_CXX", "/opt/rocm/lib/llvm/bin/clang++")      # (needs ext_vector_type, as hostsim)
-    subprocess.check_call([cxx, "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-Wno-pass-failed", "-I", HERE,
-                           "-include", os.path.join(HERE, "hostsim", "hip_shim.h"), "spec_half_host.cpp", "-o", so], cwd=HERE)
+    so = hs.build_driver("spec_half", tmp_path_factory.mktemp("spec_half"))
     lib = ctypes.CDLL(so)
     vp, ci, ll, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_float
     lib.hs_stage_spectra16.argtypes = [vp, ll, ci, vp, vp, ci, vp, vp, ci, vp]

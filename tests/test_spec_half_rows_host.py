@@ -15,7 +15,6 @@ Bank: 6 entries at capacity 49 152 with RIR lengths 0 / 9 000 / 16 384 / 16 385 
 entry 2 scaled by 32 768 and entry 3 by 1e-6 (scales that differ per block and per entry).  Every output is pre-filled with NaN."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -24,6 +23,7 @@ from oracle import ss_oracle as O
 from ss_amd import planning as P
 
 import spec_half_rows_ref as R
+hs = pytest.importorskip("hostsim.hs")
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CAP = 49152
@@ -35,10 +35,7 @@ EPS = 1e-6
 
 @pytest.fixture(scope="module")
 def rows_lib(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("spec_half_rows") / "libss_spec_half_rows_host.so")
-    cxx = os.environ.get("SS_HOSTSIM_CXX", "/opt/rocm/lib/llvm/bin/clang++")      # (needs ext_vector_type, as hostsim)
-    subprocess.check_call([cxx, "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-Wno-pass-failed", "-I", HERE,
-                           "-include", os.path.join(HERE, "hostsim", "hip_shim.h"), "spec_half_rows_host.cpp", "-o", so], cwd=HERE)
+    so = hs.build_driver("spec_half_rows", tmp_path_factory.mktemp("spec_half_rows"))
     lib = ctypes.CDLL(so)
     vp, ci, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
     lib.hs_obs_rows_spec_ab.argtypes = [ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, cf, ci, ci, ci, ci, ci, ci, ci, ci]

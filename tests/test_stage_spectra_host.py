@@ -3,7 +3,6 @@ against the host-sim spectral-bank entry (k_source_windows with scale 1, hostsim
 scattered planar: the spectra must be BIT-identical, in wav and planar staging, for lengths around the block edges."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -19,10 +18,7 @@ CAPS = [16000, 49152]
 
 @pytest.fixture(scope="module")
 def stage_lib(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("stage_spectra") / "libss_stage_spectra_host.so")
-    cxx = os.environ.get("SS_HOSTSIM_CXX", "/opt/rocm/lib/llvm/bin/clang++")      # (needs ext_vector_type, as hostsim)
-    subprocess.check_call([cxx, "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-Wno-pass-failed", "-I", HERE,
-                           "-include", os.path.join(HERE, "hostsim", "hip_shim.h"), "stage_spectra_host.cpp", "-o", so], cwd=HERE)
+    so = hs.build_driver("stage_spectra", tmp_path_factory.mktemp("stage_spectra"))
     lib = ctypes.CDLL(so)
     vp = ctypes.c_void_p
     lib.hs_stage_spectra.argtypes = [vp, ctypes.c_longlong, ctypes.c_int, vp, vp, ctypes.c_int, vp, ctypes.c_int, vp]

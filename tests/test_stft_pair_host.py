@@ -27,13 +27,10 @@ SR = 16000
 def libs(tmp_path_factory):
     """(pair, one after the other): the two host builds, compiled side by side"""
     d = tmp_path_factory.mktemp("stft_pair")
-    cxx = os.environ.get("SS_HOSTSIM_CXX", "/opt/rocm/lib/llvm/bin/clang++")      # (needs ext_vector_type, as hostsim)
     procs, sos = [], []
     for name, extra in (("pair", []), ("nopair", ["-DSS_NO_STFT_PAIR"])):
         so = str(d / f"libss_stft_{name}_host.so")
-        procs.append(subprocess.Popen([cxx, "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-Wno-pass-failed",
-                                       "-I", HERE, "-include", os.path.join(HERE, "hostsim", "hip_shim.h")] + extra +
-                                      ["stft_pair_host.cpp", "-o", so], cwd=HERE))
+        procs.append(subprocess.Popen(hs.driver_command("stft_pair", so, extra), cwd=HERE))
         sos.append(so)
     assert [p.wait() for p in procs] == [0, 0]
     pair, nopair = (ctypes.CDLL(so) for so in sos)
