@@ -243,7 +243,8 @@ int ss_audio_obs_logmel_rows_spec16_f32(const float* spec, const void* hspec16, 
  *                                   k_spectrogram, as the fp32 entry does (obs_rows_ok); that shape needs `audiogoal`.  Small steps
  *                                   run k_obs_blocks, whose hand-off flags carry a launch counter: do not replay this entry from
  *                                   a captured graph (the note on ss_audio_obs_rows_f32).
- * Not served, by any entry: SS_FLAG_CROSSFADE, length buckets, a one-launch log-mel form (the time-domain log-mel instantiation of
+ * Length buckets: the section "Half-precision time-domain rows in length buckets" below (entries of their own).
+ * Not served, by any entry: SS_FLAG_CROSSFADE, a one-launch log-mel form (the time-domain log-mel instantiation of
  * the row kernels is at its register limit: log-mel steps render a waveform and run the feature kernel over it), k_conv_rows, the
  * wide form and the 512-thread core, the in-call loaders, the TORCH_LIBRARY ops; no default selects the form or its row kernels.
  * SS_EINVAL before a device is touched: NULL halves or scales, a base that is not 4-byte aligned, odd rir_cap or rir_cap < 2, more
@@ -416,6 +417,46 @@ int ss_audio_obs_logmel_rows_spec16_buckets_f32(const float* spec, const ss_spec
                                                 const int* mel_start, const float* mel_w, int n_mels, int max_len, float mel_eps,
                                                 int n_units, int n_valid, int out_len, int pad_mode, int flags, void* stream);
 
+/* ---- Half-precision time-domain rows in length buckets (EXTENSION, opt-in, LOSSY) ------------------------------------------------
+ * The two capacity levers of a bank together: the half rows of "Half-precision time-domain rows" (same format, same quantiser, same
+ * loss - a property of the per-row rule, independent of the bucket: 1.7-2.3e-4 of peak on the waveform, measured there) kept in the
+ * length buckets of ss_rir_bucket.  Bucket b holds bank indices [first, first + n_entries) in two allocations of its own: rir16
+ * [n_entries, 2, cap_b] halves and rscale [n_entries, 2] floats, both zero-initialised (ss_rir_rows16_f32 /
+ * ss_bank_scatter_rows16_f32 of that bucket).  An entry of bucket b costs 4 * cap_b + 8 bytes.  Rows are NOT padded to whole
+ * partition blocks: the halves behind a row's capacity are the next entry's, and the kernel takes a row's stride and its load bound
+ * from the row's own bucket.  Ordering (`first` ascending, bucket 0 at index 0, disjoint ranges), count (1 to 4), rir_len (ONE device
+ * array over global indices) and the unit descriptors as for ss_rir_bucket; `buckets` is a HOST array, copied where it is kept.
+ * Each bucket must pass the checks of the single-allocation form: non-NULL 4-byte aligned halves, non-NULL scales, an even cap >= 2
+ * of at most 16 partition blocks.
+ * Kernel: k_conv<.., HALF, RBK> (the loop kernel), which resolves halves, scales, stride and capacity of a term's bucket from the
+ * wave-uniform bank index with scalar compares; results equal those of ss_*_buckets_f32 fed float(q) * rscale.  Launches that promise
+ * SS_FLAG_FIRST_BUCKET (or have one bucket) are single-allocation launches on bucket 0's arrays - with cap_0 <= kB the loop-free
+ * half kernels - and equal ss_fftconv_binaural_rir16_f32 / ss_audio_obs_rir16_f32 on them bit for bit.
+ *   ss_fftconv_binaural_rir16_buckets_f32   every shape ss_fftconv_binaural_rir16_f32 serves;
+ *   ss_audio_obs_rir16_buckets_f32          the shapes of ss_audio_obs_rir16_f32: 257 <= out_len <= kB, at most 26 pooled blocks,
+ *                                           `audiogoal` may be NULL.  Longer rows: the convolution entry + ss_spectrogram_f32 (what
+ *                                           a context bound by ss_ctx_set_rir16_buckets does).
+ * OUT OF SCOPE, refused or not offered: bucketed half rows under the fused row kernels (k_obs_blocks / k_obs_rows keep reading one
+ * allocation of half rows only), a one-launch log-mel form, SS_FLAG_CROSSFADE, the wide form, k_conv_rows, the 512-thread core, the
+ * in-call loaders, the TORCH_LIBRARY ops; no default selects the form.
+ * SS_EINVAL before a device is touched: a NULL bucket array, n_buckets outside [1, 4], any bucket the single-allocation checks
+ * refuse, `first` not ascending / overlapping / != 0 for bucket 0, negative n_entries, NULL rir_len, SS_FLAG_CROSSFADE, out_len
+ * outside the entry's range, a bad pad_mode, a NULL required output.  n_units == 0 returns 0. */
+typedef struct ss_rir16_bucket {
+    const void*  rir16;   /* device, [n_entries, 2, cap] halves, planar, 4-byte aligned, zero-initialised */
+    const float* rscale;  /* device, [n_entries, 2], zero-initialised */
+    int first;            /* global bank index of entry 0 of the bucket */
+    int n_entries;
+    int cap;              /* samples per (entry, ear) row, even */
+    int reserved;
+} ss_rir16_bucket;
+int ss_fftconv_binaural_rir16_buckets_f32(const float* spec, const ss_rir16_bucket* buckets, int n_buckets, const int* rir_len,
+                                          const int* unit_desc, float* out, int n_units, int n_valid, int out_len, int flags,
+                                          void* stream);
+int ss_audio_obs_rir16_buckets_f32(const float* spec, const ss_rir16_bucket* buckets, int n_buckets, const int* rir_len,
+                                   const int* unit_desc, float* audiogoal, float* spectrogram, int n_units, int n_valid,
+                                   int out_len, int pad_mode, int flags, void* stream);
+
 /* EXTENSION, one pass for every STFT-derived feature (BASELINE.json configs[4] "GCC-PHAT + log-mel fused sensor"): each
  * (unit, ear, frame) of x [n_units, 2, len] is framed, windowed and transformed ONCE (both ears in one wave), and from that
  * one spectrum the kernel writes any subset of
@@ -584,6 +625,17 @@ int ss_ctx_set_rir_spec_buckets(ss_ctx* ctx, const ss_spec_bucket* buckets, int 
  * context's waveform scratch, as always), waveform-only steps ss_fftconv_binaural_spec_buckets_f32.  Cross-faded steps are
  * SS_EINVAL and leave no keys behind. */
 int ss_ctx_set_rir_spec_buckets_rows(ss_ctx* ctx, const ss_spec_bucket* buckets, int n_buckets, const int* rir_len);
+/* Half-precision time-domain rows in length buckets as the context's bank (see ss_rir16_bucket).  Replaces ANY earlier binding and
+ * is replaced by every other bank call; buckets = NULL unbinds; while it is bound ss_ctx_set_rir_spectra / _spectra16 /
+ * _spectra16_rows with a bank are SS_EINVAL.  Planning depth is the deepest bucket's blocks, as for ss_ctx_set_rir_buckets; steps
+ * whose units all sit in bucket 0 carry SS_FLAG_FIRST_BUCKET and keep the loop-free half kernels.  Routes as ss_ctx_set_rir_bank16:
+ * one-block rows take the fused launch, longer rows (44.1 / 48 kHz) the bucketed half convolution into the caller's waveform buffer
+ * - or the context's hand-over buffer - and the spectrogram kernel over it (never the fused row kernels), log-mel steps the waveform
+ * scratch.  A cross-faded step is SS_EINVAL and leaves no keys behind.  The in-call loaders do not serve this form:
+ * ss_ctx_load_rir_files returns 1, ss_ctx_observe_requests_load reports the misses and launches nothing.  The pose memo, the overlap
+ * mode and the column / request entries run on it unchanged.  SS_EINVAL, nothing changed: the refusals of ss_rir16_bucket,
+ * rir_len == NULL.  Call again whenever a bucket is (re)allocated. */
+int ss_ctx_set_rir16_buckets(ss_ctx* ctx, const ss_rir16_bucket* buckets, int n_buckets, const int* rir_len);
 /* One step.  audiogoal [n,2,sr] and spectrogram [n,65,T4,2] are device buffers; either may be NULL (not both).
  * Asynchronous on `stream`; the host arrays of `units` may be reused as soon as the call returns. */
 int ss_ctx_observe(ss_ctx* ctx, const ss_units* units, int n, float* audiogoal, float* spectrogram, void* stream);

@@ -82,6 +82,7 @@ struct Context {
     const void* rir16 = nullptr;   // half-precision time-domain rows (ss_ctx_set_rir_bank16; borrowed): rir / hspec / buckets are unset then
     const float* rscale = nullptr; // ... and their scales, one per (entry, ear)
     bool rir16_rows = false;       // ... bound for the fused row kernels as well (ss_ctx_set_rir_bank16_rows)
+    std::vector<ss_rir16_bucket> rir16_buckets; // ... in length buckets (ss_ctx_set_rir16_buckets): rir / rir16 / hspec and the other buckets are unset then
     std::vector<ss_rir_bucket> buckets;   // length-bucketed bank (ss_ctx_set_rir_buckets); empty: the single bank above
     std::vector<ss_spec_bucket> spec_buckets;   // ... without time-domain rows (ss_ctx_set_rir_spec_buckets): rir / hspec are NULL then
     bool spec_buckets_rows = false;             // ... half ones bound for rows of 2 or 3 blocks (ss_ctx_set_rir_spec_buckets_rows)
@@ -329,6 +330,7 @@ inline int plan_units(Context& c, const ss_units* u, int n, int* desc, PlanResul
     res->flags = any_fade ? SS_FLAG_CROSSFADE : (any_dis ? 0 : SS_FLAG_NO_DISTRACTOR);
     if (c.buckets.size() > 1 && max_rir < c.buckets[1].first) res->flags |= SS_FLAG_FIRST_BUCKET;
     if (c.spec_buckets.size() > 1 && max_rir < c.spec_buckets[1].first) res->flags |= SS_FLAG_FIRST_BUCKET;
+    if (c.rir16_buckets.size() > 1 && max_rir < c.rir16_buckets[1].first) res->flags |= SS_FLAG_FIRST_BUCKET;
     res->n_new_windows = static_cast<int>(c.new_win.size() / 5);
     return 0;
 }

@@ -163,6 +163,8 @@ inline const sslaunch::Switches& launch_switches() {
 // The convolution of whichever bank form the launch reads, fused with the STFT (FUSE) or not: sslaunch::plan_conv decides
 // refusal, kernel variant, parts and grid; here the unit table is filled where the plan allows one and the variant picks the
 // instantiation.  hs: the scales of a half spectral bank (Form::kSpec16 / kSpec16Buckets), rs: those of half rows (Form::kRows16).
+// Half rows in length buckets (Form::kRows16 with p.n_buckets > 1): launches that only touch bucket 0 are single-allocation launches
+// on bucket 0's arrays (the HALF kernels, the loop-free ones included); everything else: k_conv<.., HALF, RBK>.
 // Half-precision time-domain rows (include/ss_hip.h "Half-precision time-domain rows"): k_conv<.., HALF> for every launch - no
 // cross-fade, no wide form, no persistent row kernel.  Half bank (include/ss_hip.h "Half-precision spectral bank"): k_conv_spec
 // <.., HALF> for every launch (more rows than CUs included: the persistent k_conv_spec_rows has no half form).  Half buckets:
@@ -170,7 +172,7 @@ inline const sslaunch::Switches& launch_switches() {
 // the HALF kernels, the loop-free ones included; everything else: k_conv_spec<.., HALF, HBK>.
 template <bool FUSE>
 int launch_conv(sslaunch::Form form, ssk::ConvParams p, int n_units, int nb_y, int flags, int n_cus, const LaunchEnv& env,
-                bool wide = false, const ssk::SpecScale<true, true>* hs = nullptr, const ssk::RowScale<true>* rs = nullptr) {
+                bool wide = false, const ssk::SpecScale<true, true>* hs = nullptr, const ssk::RowScale<true, true>* rs = nullptr) {
     using sslaunch::Form;
     using V = sslaunch::Variant;
     const hipStream_t st = env.st;
@@ -205,9 +207,11 @@ int launch_conv(sslaunch::Form form, ssk::ConvParams p, int n_units, int nb_y, i
             case V::kLoop: hipLaunchKernelGGL((ssk::k_conv<FUSE, false>), grid, block, 0, st, p, nt); break;
         }
     } else if (form == Form::kRows16) {
-        if (tab) hipLaunchKernelGGL((ssk::k_conv<FUSE, true, false, true, false, false, true>), grid, block, 0, st, p, ut, *rs);
-        else if (simple) hipLaunchKernelGGL((ssk::k_conv<FUSE, true, false, false, false, false, true>), grid, block, 0, st, p, nt, *rs);
-        else hipLaunchKernelGGL((ssk::k_conv<FUSE, false, false, false, false, false, true>), grid, block, 0, st, p, nt, *rs);
+        const ssk::RowScale<true> rs1{rs->rir16, rs->rscale};
+        if (!pl.bucket0) hipLaunchKernelGGL((ssk::k_conv<FUSE, false, false, false, false, false, true, true>), grid, block, 0, st, p, nt, *rs);
+        else if (tab) hipLaunchKernelGGL((ssk::k_conv<FUSE, true, false, true, false, false, true>), grid, block, 0, st, p, ut, rs1);
+        else if (simple) hipLaunchKernelGGL((ssk::k_conv<FUSE, true, false, false, false, false, true>), grid, block, 0, st, p, nt, rs1);
+        else hipLaunchKernelGGL((ssk::k_conv<FUSE, false, false, false, false, false, true>), grid, block, 0, st, p, nt, rs1);
     } else if (form == Form::kSpec) {
         if (pl.variant == V::kPersistRows) {
             if constexpr (!FUSE) hipLaunchKernelGGL(ssk::k_conv_spec_rows, grid, block, 0, st, p, 2 * n_units);
@@ -229,6 +233,35 @@ int launch_conv(sslaunch::Form form, ssk::ConvParams p, int n_units, int nb_y, i
 // the arguments every half-rows entry refuses before a device is touched
 inline bool rows16_bank_ok(const void* rir16, const float* rscale, int cap) {
     return rir16 && rscale && !(reinterpret_cast<size_t>(rir16) & 3) && cap >= 2 && !(cap & 1) && (cap + ssk::kB - 1) / ssk::kB <= 16;
+}
+
+// ---- half-precision time-domain rows in length buckets (include/ss_hip.h "... in length buckets") -------------------------------
+// the bucket rules of ss_rir_bucket, each bucket under rows16_bank_ok; *hb_max = the deepest bucket's blocks
+int rir16_buckets_check(const ss_rir16_bucket* bk, int n_buckets, int* hb_max) {
+    if (!bk || n_buckets < 1 || n_buckets > ssk::kMaxBuckets) return SS_EINVAL;
+    int hb = 1;
+    for (int b = 0; b < n_buckets; ++b) {
+        if (!rows16_bank_ok(bk[b].rir16, bk[b].rscale, bk[b].cap) || bk[b].n_entries < 0 || bk[b].first < 0) return SS_EINVAL;
+        if (b && bk[b].first < bk[b - 1].first + bk[b - 1].n_entries) return SS_EINVAL;         // ascending, disjoint ranges
+        hb = std::max(hb, (bk[b].cap + ssk::kB - 1) / ssk::kB);
+    }
+    if (bk[0].first != 0) return SS_EINVAL;
+    *hb_max = hb;
+    return 0;
+}
+
+// bucket 0 into rir_cap and the head of rs, the others into p.bk[].rir (halves, read as h16x2) and rs.bk[]
+void fill_rir16_buckets(ssk::ConvParams& p, ssk::RowScale<true, true>& rs, const ss_rir16_bucket* bk, int n_buckets) {
+    p.rir_cap = bk[0].cap;
+    p.n_buckets = n_buckets;
+    rs.rir16 = static_cast<const ssk::h16x2*>(bk[0].rir16);
+    rs.rscale = bk[0].rscale;
+    for (auto& s : rs.bk) s = nullptr;
+    for (int b = 1; b < n_buckets; ++b) {
+        p.bk[b - 1] = ssk::BankBucket{static_cast<const float*>(bk[b].rir16), nullptr, bk[b].first, bk[b].cap,
+                                      (bk[b].cap + ssk::kB - 1) / ssk::kB, 0};
+        rs.bk[b - 1] = bk[b].rscale;
+    }
 }
 
 // ---- k_obs_rows: fused observation for rows longer than one partition block -------------------------------------
@@ -614,7 +647,14 @@ struct Bank {
     const void* rir16 = nullptr;            // half-precision time-domain rows [entries][2][cap] + ...
     const float* rscale = nullptr;          // ... one scale per (entry, ear); nothing else is set then but `cap`
     bool rows16_rows = false;               // ... that also serve the fused row kernels (ss_audio_obs_rows_rir16_f32, ss_ctx_set_rir_bank16_rows)
+    const ss_rir16_bucket* rbk = nullptr;   // half-precision time-domain rows in length buckets (with n_buckets) ...
+    bool rows16_bk = false;                 // ... the form was asked for (rbk may be NULL: refused by render)
 };
+inline Bank rir16_buckets_bank(const ss_rir16_bucket* rbk, int n_buckets) {
+    Bank b;
+    b.rbk = rbk; b.n_buckets = n_buckets; b.rows16_bk = true;
+    return b;
+}
 inline Bank rows16_bank(const void* rir16, const float* rscale, int cap, bool fused_rows = false) {
     Bank b;
     b.rir16 = rir16; b.rscale = rscale; b.cap = cap; b.rows16_rows = fused_rows;
@@ -680,11 +720,12 @@ int render(const Bank& b, bool spectral, ssroute::Launch want, const float* spec
     bool half = b.hscale != nullptr;
     int nbh_max = 1;
     if (n_units < 0) return SS_EINVAL;
-    const bool rows16 = b.rir16 || b.rscale;
-    if (rows16) {                                           // (one allocation of half rows: no cross-fade, no log-mel form)
-        if (!rows16_bank_ok(b.rir16, b.rscale, b.cap) || (flags & SS_FLAG_CROSSFADE) || spectral) return SS_EINVAL;
+    const bool rows16 = b.rir16 || b.rscale || b.rows16_bk;
+    if (rows16) {                                           // (half rows, one allocation or length buckets: no cross-fade, no log-mel form)
+        if (b.rows16_bk ? rir16_buckets_check(b.rbk, b.n_buckets, &nbh_max) != 0 : !rows16_bank_ok(b.rir16, b.rscale, b.cap)) return SS_EINVAL;
+        if ((flags & SS_FLAG_CROSSFADE) || spectral) return SS_EINVAL;
         if (want != Launch::kConv && want != Launch::kObs) return SS_EINVAL;
-        nbh_max = (b.cap + ssk::kB - 1) / ssk::kB;
+        if (!b.rows16_bk) nbh_max = (b.cap + ssk::kB - 1) / ssk::kB;
     } else if (b.sbk) {                                            // (no rows anywhere: a cross-fade has nothing to read)
         if (spec_buckets_check(b.sbk, b.n_buckets, &half, &nbh_max) || (flags & SS_FLAG_CROSSFADE)) return SS_EINVAL;
         spectral = true;
@@ -751,8 +792,9 @@ int render(const Bank& b, bool spectral, ssroute::Launch want, const float* spec
     p.out = audiogoal;
     const int nb_y = sslaunch::nb_y_of(n_valid);
     if (rows16) {
-        const ssk::RowScale<true> rs{static_cast<const ssk::h16x2*>(b.rir16), b.rscale};
+        ssk::RowScale<true, true> rs{static_cast<const ssk::h16x2*>(b.rir16), b.rscale, {nullptr, nullptr, nullptr}};
         p.rir_cap = b.cap;
+        if (b.rows16_bk) fill_rir16_buckets(p, rs, b.rbk, b.n_buckets);
         if (want == Launch::kObs && chain == Chain::kFused) {
             p.pad_mode = pad_mode;
             p.sgram = spectrogram;
@@ -762,7 +804,7 @@ int render(const Bank& b, bool spectral, ssroute::Launch want, const float* spec
             p.pad_mode = pad_mode;
             p.sgram = spectrogram;
             return launch_obs_rows<false, false, false, false, true>(p, n_units, flags, n_cus, env, ssk::UnitTab<false, false>(),
-                                                                     ssk::SpecScale<false, false>(), rs);
+                                                                     ssk::SpecScale<false, false>(), ssk::RowScale<true>{rs.rir16, rs.rscale});
         }
         rc = launch_conv<false>(Form::kRows16, p, n_units, nb_y, flags, n_cus, env, false, nullptr, &rs);
         if (rc || want == Launch::kConv) return rc;
@@ -1339,6 +1381,26 @@ int ss_audio_obs_rows_rir16_f32(const float* spec, const void* rir16, const floa
                   nullptr, n_units, n_valid, out_len, pad_mode, flags, stateless(stream));
 }
 
+// ---- half-precision time-domain rows in length buckets: the stateless entries ------------------------------------------------
+// ss_fftconv_binaural_rir16_f32 on ss_rir16_bucket[] (k_conv<.., HALF, RBK>; bucket-0 launches: the single-allocation half kernels)
+int ss_fftconv_binaural_rir16_buckets_f32(const float* spec, const ss_rir16_bucket* buckets, int n_buckets, const int* rir_len,
+                                          const int* unit_desc, float* out, int n_units, int n_valid, int out_len, int flags,
+                                          void* stream) {
+    if (n_units == 0) return 0;
+    return render(rir16_buckets_bank(buckets, n_buckets), false, Launch::kConv, spec, rir_len, unit_desc, out, nullptr, nullptr, n_units,
+                  n_valid, out_len, SS_PAD_REFLECT, flags, stateless(stream));
+}
+
+// ss_audio_obs_rir16_f32 on ss_rir16_bucket[]: the one-launch fused form; `audiogoal` may be NULL
+int ss_audio_obs_rir16_buckets_f32(const float* spec, const ss_rir16_bucket* buckets, int n_buckets, const int* rir_len,
+                                   const int* unit_desc, float* audiogoal, float* spectrogram, int n_units, int n_valid, int out_len,
+                                   int pad_mode, int flags, void* stream) {
+    if (n_units == 0) return 0;
+    if (out_len < ssk::kNfft / 2 + 1 || out_len > ssk::kB || t4_of(out_len) > 26) return SS_EINVAL;
+    return render(rir16_buckets_bank(buckets, n_buckets), false, Launch::kObs, spec, rir_len, unit_desc, audiogoal, spectrogram, nullptr,
+                  n_units, n_valid, out_len, pad_mode, flags, stateless(stream));
+}
+
 // ---- pose memo: the row copies (k_memo_rows) ---------------------------------------------------------------------------
 static bool memo_io_ok(const ss_memo_io* io, int n_io) {
     if (!io || n_io < 1 || n_io > ssk::kMemoArrays) return false;
@@ -1498,6 +1560,7 @@ int ss_ctx_set_rir_bank(ss_ctx* h, const float* rir, const int* rir_len, long lo
     c.rir = rir; c.rir_len = rir_len; c.rir_us = unit_stride; c.rir_cs = chan_stride; c.rir_es = elem_stride;
     c.rir_cap = rir_cap;
     c.rir16 = nullptr; c.rscale = nullptr;                     // (half rows, ss_ctx_set_rir_bank16: replaced like any other bank)
+    c.rir16_buckets.clear();                                   // (... in length buckets, ss_ctx_set_rir16_buckets: likewise)
     // the spectral form described the PREVIOUS bank (its entries, its capacity): back to the time-domain kernels until
     // ss_ctx_set_rir_spectra is called for this one (a swapped / grown bank kept rendering the old spectra)
     c.hspec = nullptr;
@@ -1526,7 +1589,7 @@ int ss_ctx_set_rir_spectra(ss_ctx* h, const float* hspec, int h_blocks) {
     if (!h || (hspec && h_blocks < 1)) return SS_EINVAL;
     ssctx::Context& c = h->c;
     if (hspec && h_blocks != (c.rir_cap > 0 ? ssctx::ceil_div(c.rir_cap, c.kb) : 1)) return SS_EINVAL;
-    if (hspec && (c.hscale || !c.spec_buckets.empty() || c.rir16)) return SS_EINVAL;     // a half bank (ss_ctx_set_rir_spectra16) or spectral buckets are bound: one form at a time
+    if (hspec && (c.hscale || !c.spec_buckets.empty() || c.rir16 || !c.rir16_buckets.empty())) return SS_EINVAL;     // a half bank (ss_ctx_set_rir_spectra16) or spectral buckets are bound: one form at a time
     c.hspec = hspec;
     c.hscale = nullptr;
     c.h_blocks = hspec ? h_blocks : 0;
@@ -1545,7 +1608,7 @@ int ss_ctx_set_rir_spectra16(ss_ctx* h, const void* hspec16, const float* hscale
         return 0;
     }
     if (!hscale || h_blocks < 1 || (reinterpret_cast<size_t>(hspec16) & 7)) return SS_EINVAL;
-    if (c.out_len > c.kb || c.rir || c.rir16 || !c.buckets.empty() || !c.spec_buckets.empty() || !c.rir_len || (c.hspec && !c.hscale)) return SS_EINVAL;
+    if (c.out_len > c.kb || c.rir || c.rir16 || !c.rir16_buckets.empty() || !c.buckets.empty() || !c.spec_buckets.empty() || !c.rir_len || (c.hspec && !c.hscale)) return SS_EINVAL;
     if (h_blocks != (c.rir_cap > 0 ? ssctx::ceil_div(c.rir_cap, c.kb) : 1)) return SS_EINVAL;
     c.hspec = static_cast<const float*>(hspec16);              // (read as halves wherever hscale is set)
     c.hscale = hscale;
@@ -1565,7 +1628,7 @@ int ss_ctx_set_rir_spectra16_rows(ss_ctx* h, const void* hspec16, const float* h
     }
     if (!hscale || h_blocks < 1 || h_blocks > 16 || (reinterpret_cast<size_t>(hspec16) & 7)) return SS_EINVAL;
     if (c.out_len <= c.kb || c.out_len > 3 * c.kb) return SS_EINVAL;
-    if (c.rir || c.rir16 || !c.buckets.empty() || !c.spec_buckets.empty() || !c.rir_len || (c.hspec && !c.hscale)) return SS_EINVAL;
+    if (c.rir || c.rir16 || !c.rir16_buckets.empty() || !c.buckets.empty() || !c.spec_buckets.empty() || !c.rir_len || (c.hspec && !c.hscale)) return SS_EINVAL;
     if (h_blocks != (c.rir_cap > 0 ? ssctx::ceil_div(c.rir_cap, c.kb) : 1)) return SS_EINVAL;
     c.hspec = static_cast<const float*>(hspec16);              // (read as halves wherever hscale is set)
     c.hscale = hscale;
@@ -1708,6 +1771,7 @@ static ssroute::Bank route_bank_of(const ssctx::Context& c) {
     b.h_blocks = c.h_blocks;
     b.rows16 = c.rir16 != nullptr;
     b.rows16_rows = b.rows16 && c.rir16_rows;
+    b.rows16_buckets = !c.rir16_buckets.empty();
     return b;
 }
 
@@ -1716,6 +1780,7 @@ static Bank bank_of(const ssctx::Context& c) {
     if (!c.spec_buckets.empty()) return spec_buckets_bank(c.spec_buckets.data(), static_cast<int>(c.spec_buckets.size()), c.spec_buckets_rows);
     if (!c.buckets.empty()) return buckets_bank(c.buckets.data(), static_cast<int>(c.buckets.size()));
     if (c.rir16) return rows16_bank(c.rir16, c.rscale, c.rir_cap, c.rir16_rows);
+    if (!c.rir16_buckets.empty()) return rir16_buckets_bank(c.rir16_buckets.data(), static_cast<int>(c.rir16_buckets.size()));
     Bank b = rows_bank(c.rir, c.rir_us, c.rir_cs, c.rir_es, c.rir_cap);
     b.hspec = c.hspec; b.hscale = c.hscale; b.h_blocks = c.h_blocks;
     return b;
@@ -2062,7 +2127,7 @@ static int ctx_observe_any(ss_ctx* h, const ss_units* units, int n, float* audio
         return SS_EINVAL;
     if (n == 0) return 0;
     ssctx::Context& c = h->c;
-    if ((!c.rir && !c.hspec && !c.rir16 && c.buckets.empty() && c.spec_buckets.empty()) || !c.rir_len || !c.src_dev) return SS_EINVAL;
+    if ((!c.rir && !c.hspec && !c.rir16 && c.rir16_buckets.empty() && c.buckets.empty() && c.spec_buckets.empty()) || !c.rir_len || !c.src_dev) return SS_EINVAL;
     const bool sg_late = features_take_spectrogram(f, audiogoal, spectrogram);
     if (c.n_lanes <= 1) {
         if (mel_only) return ctx_observe_on(h, units, n, nullptr, spectrogram, stream, -1, f);
@@ -2602,7 +2667,7 @@ int ss_ctx_load_rir_files(ss_ctx* h, ss_miss_loader* ld, const char* const* path
     ld->n_loaded = 0; ld->n_evicted = 0;
     if (k == 0) return 0;
     ssctx::Context& c = h->c;
-    if (c.rir16) return 1;                                     // half rows: not served here (the caller's own path scatters them)
+    if (c.rir16 || !c.rir16_buckets.empty()) return 1;         // half rows: not served here (the caller's own path scatters them)
     const bool spec_only = !ld->bank && !c.rir && c.hspec && c.buckets.empty();     // spectral-only bank (see loader_load_paths)
     if (!ld->free_slots || (!ld->bank && !spec_only) || !ld->dev_len || !ld->host_len || !ld->clipped || !ld->stage || !ld->stage_slot ||
         !ld->stage_len || !ld->loaded_slot || !ld->loaded_frames || ld->cap < 2 || (ld->cap & 1) || c.rir != ld->bank)
@@ -2625,7 +2690,7 @@ int ss_ctx_observe_requests_load(ss_ctx* h, const long long* recs, int n, ss_req
         bool any_dis = false;
         for (int i = 0; i < n && !any_dis; ++i) any_dis = recs[static_cast<size_t>(i) * SS_REQ_WORDS] == 0 && recs[static_cast<size_t>(i) * SS_REQ_WORDS + 6] >= 0;
         const bool spectral = c.hspec && !(c.policy.spectral_max_units > 0 && c.rir && c.out_len <= ssk::kB && n > c.policy.spectral_max_units && !any_dis);
-        if (!ld || !miss_out || c.rir != ld->bank || c.rir16) return 0;     // (half rows: the misses are reported, never served here)
+        if (!ld || !miss_out || c.rir != ld->bank || c.rir16 || !c.rir16_buckets.empty()) return 0;     // (half rows: the misses are reported, never served here)
         std::vector<int> miss(miss_out, miss_out + (*n_miss < n ? *n_miss : n));
         rc = serve_pose_misses(h, recs, n, tb, ld, miss.data(), static_cast<int>(miss.size()), static_cast<hipStream_t>(stream), spectral);
         if (rc == 1) return 0;                                 // reported as ss_ctx_observe_requests reports it
@@ -2692,7 +2757,7 @@ int ss_ctx_set_rir_buckets(ss_ctx* h, const ss_rir_bucket* buckets, int n_bucket
     c.buckets.assign(buckets, buckets + n_buckets);
     c.spec_buckets.clear();
     c.rir = buckets[0].rir; c.rir_len = rir_len; c.rir_us = 2LL * buckets[0].cap; c.rir_cs = buckets[0].cap; c.rir_es = 1;
-    c.rir16 = nullptr; c.rscale = nullptr;
+    c.rir16 = nullptr; c.rscale = nullptr; c.rir16_buckets.clear();
     c.rir_cap = hb_max * c.kb;                                 // planning depth: the longest bucket's blocks
     c.hspec = nullptr; c.hscale = nullptr; c.h_blocks = 0;
     if (hb_max != nbh_old) {                                   // the set of partition offsets per key changes
@@ -2797,6 +2862,22 @@ int ss_ctx_set_rir_spec_buckets_rows(ss_ctx* h, const ss_spec_bucket* buckets, i
     return ctx_bind_spec_buckets(h, buckets, n_buckets, rir_len, true);
 }
 
+// Half-precision time-domain rows in length buckets as the context's bank: replaces any earlier binding (ss_ctx_set_rir_bank clears
+// every form and resets keys and pool where the depth changes), buckets = NULL unbinds.  Planning depth: the deepest bucket's blocks.
+int ss_ctx_set_rir16_buckets(ss_ctx* h, const ss_rir16_bucket* buckets, int n_buckets, const int* rir_len) {
+    if (!h) return SS_EINVAL;
+    if (!buckets) {
+        h->c.rir16_buckets.clear();
+        return 0;
+    }
+    int hb_max = 1;
+    if (!rir_len || rir16_buckets_check(buckets, n_buckets, &hb_max)) return SS_EINVAL;
+    const int rc = ss_ctx_set_rir_bank(h, nullptr, rir_len, 0, 0, 1, hb_max * h->c.kb);
+    if (rc) return rc;
+    h->c.rir16_buckets.assign(buckets, buckets + n_buckets);
+    return 0;
+}
+
 static int ctx_bind_spec_buckets(ss_ctx* h, const ss_spec_bucket* buckets, int n_buckets, const int* rir_len, bool rows) {
     bool half = false;
     int hb_max = 1;
@@ -2810,7 +2891,7 @@ static int ctx_bind_spec_buckets(ss_ctx* h, const ss_spec_bucket* buckets, int n
     c.spec_buckets_rows = rows;
     c.buckets.clear();
     c.rir = nullptr; c.rir_len = rir_len; c.rir_us = 0; c.rir_cs = 0; c.rir_es = 1;
-    c.rir16 = nullptr; c.rscale = nullptr;
+    c.rir16 = nullptr; c.rscale = nullptr; c.rir16_buckets.clear();
     c.rir_cap = hb_max * c.kb;                                 // planning depth: the longest bucket's blocks
     c.hspec = nullptr; c.hscale = nullptr; c.h_blocks = 0;
     if (hb_max != nbh_old) {                                   // the set of partition offsets per key changes

@@ -1310,14 +1310,40 @@ struct BankRow { const float* h; int cap, es; static constexpr bool kHalf = fals
 // The pointers travel in a kernel argument of their own, passed to the HALF instantiations of k_conv only (as SpecScale is for
 // k_conv_spec): ConvParams keeps its size.  Of ConvParams' bank fields those kernels read rir_cap alone.
 typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
-template <bool HALF>
+// RBK (half rows in length buckets, ss_rir16_bucket): bucket b >= 1 keeps its halves behind ConvParams::bk[b - 1].rir (read as
+// h16x2) and its scales behind bk[b - 1] HERE - three more pointers in this argument, none in ConvParams (as SpecScale<true, true>).
+template <bool HALF, bool RBK = false>
 struct RowScale { };
 template <>
-struct RowScale<true> { const h16x2* rir16; const float* rscale; };
+struct RowScale<true, false> { const h16x2* rir16; const float* rscale; };
+template <>
+struct RowScale<true, true> {
+    const h16x2* rir16;                                      // bucket 0: [n_0][2][cap_0] halves
+    const float* rscale;                                     // bucket 0: [n_0][2]
+    const float* bk[kMaxBuckets - 1];                        // bucket b + 1: [n][2]
+};
 struct BankRow16 { const h16x2* h2; float scale; int cap; static constexpr bool kHalf = true; };
 __device__ __forceinline__ BankRow16 bank_row16(const RowScale<true>& rs, int cap, int ridx, int ch) {
     const size_t row = (size_t)ridx * 2 + ch;
     return BankRow16{rs.rir16 + row * (size_t)(cap >> 1), rs.rscale[row], cap};
+}
+// ... of a bucketed bank: resolved as bank_row / bank_spec16 resolve theirs - scalar compares on the wave-uniform index, no memory
+// access besides the row's scale word.  The row's stride AND its capacity are its OWN bucket's: half rows are not padded to whole
+// partition blocks, the halves behind a row's capacity are the next entry's.
+__device__ __forceinline__ BankRow16 bank_row16(const ConvParams& p, const RowScale<true, true>& rs, int ridx, int ch) {
+    const h16x2* base = rs.rir16;
+    const float* sbase = rs.rscale;
+    int first = 0, cap = p.rir_cap;
+#pragma unroll
+    for (int b = 0; b < kMaxBuckets - 1; ++b)
+        if (b + 1 < p.n_buckets && ridx >= p.bk[b].first) {
+            base = reinterpret_cast<const h16x2*>(p.bk[b].rir);
+            sbase = rs.bk[b];
+            first = p.bk[b].first;
+            cap = p.bk[b].cap;
+        }
+    const size_t row = (size_t)(ridx - first) * 2 + ch;
+    return BankRow16{base + row * (size_t)(cap >> 1), sbase[row], cap};
 }
 __device__ __forceinline__ c32 row16_pair(h16x2 q, float scale) { return mk2((float)q.x * scale, (float)q.y * scale); }
 // BUCKETS = false: the launch's bank is ONE allocation (n_buckets == 1: the launcher checks) - the three bucket descriptors
@@ -1660,10 +1686,16 @@ __device__ __forceinline__ void fused_stft_phase(c32* lds, const ConvParams& p, 
 // fused kernel the spectrogram is taken from the blended row without it ever leaving the CU.
 // HALF: the bank is fp16 rows + one scale per (entry, ear) (RowScale above), one allocation; only the loads in front of pass 1
 // differ - 4 bytes per packed pair, converted and multiplied by the wave-uniform scale.
-template <bool FUSE, bool SIMPLE, bool XFADE = false, bool TAB = false, bool WIDE = false, bool MEL = false, bool HALF = false>
+// RBK: half rows in length buckets (RowScale<true, true>, bank_row16 above): the loop kernel resolves a term's bucket once per term;
+// launches whose units all sit in bucket 0 take the HALF instantiations on bucket 0's arrays (bucket 0 starts at global index 0).
+// Out of scope: XFADE, WIDE, MEL, k_conv_rows, the 512-thread core and the fused 44.1 / 48 kHz row kernels (k_obs_blocks /
+// k_obs_rows<.., ROWS16> keep their !BUCKETS / !HBK asserts: they read ONE allocation of half rows).
+template <bool FUSE, bool SIMPLE, bool XFADE = false, bool TAB = false, bool WIDE = false, bool MEL = false, bool HALF = false,
+          bool RBK = false>
 __global__ __launch_bounds__(1024) void k_conv(ConvParams p, UnitTab<TAB, MEL> ut = UnitTab<TAB, MEL>(),
-                                               RowScale<HALF> rs = RowScale<HALF>()) {
+                                               RowScale<HALF, RBK> rs = RowScale<HALF, RBK>()) {
     static_assert(!(SIMPLE && XFADE), "the cross-fade needs the two-term loop kernel");
+    static_assert(!RBK || (HALF && !SIMPLE), "bucketed half rows: the loop kernel (bucket-0 launches take the loop-free HALF ones)");
     static_assert(!HALF || (!XFADE && !WIDE && !MEL), "half rows: the plain loop-free and loop kernels");
     static_assert(!MEL || (FUSE && !TAB), "log-mel: the fused kernels without a unit table (launched with parts_log2 = 0)");
     static_assert(!WIDE || (FUSE && !SIMPLE), "WIDE: fused loop kernel for rows of which only block 0 is rendered");
@@ -1788,7 +1820,8 @@ __global__ __launch_bounds__(1024) void k_conv(ConvParams p, UnitTab<TAB, MEL> u
                 const int L = uniform_load(p.rir_len + ridx);
                 const int spec0 = dw.y, m_min = dw.z, m_cnt = dw.w;
                 auto br = [&] {
-                    if constexpr (HALF) return bank_row16(rs, p.rir_cap, ridx, ch);
+                    if constexpr (RBK) return bank_row16(p, rs, ridx, ch);
+                    else if constexpr (HALF) return bank_row16(rs, p.rir_cap, ridx, ch);
                     else return bank_row(p, ridx, ch);
                 }();
                 const int nbh = (L + kB - 1) / kB;

@@ -45,7 +45,7 @@ inline int parts_log2_for(int n_rows, int n_cus, int share, int forced) {
 // ---- the convolution launches (k_conv, k_conv_spec and their half forms; fused with the STFT or not) -------------------------
 enum class Form {                     // the bank form the launch reads
     kRows,                            // fp32 time-domain rows (length buckets that keep rows included)
-    kRows16,                          // half-precision time-domain rows + one scale per (entry, ear)
+    kRows16,                          // half-precision time-domain rows + one scale per (entry, ear); n_buckets > 1: in length buckets
     kSpec,                            // fp32 block spectra
     kSpec16,                          // fp16 block spectra + one scale per block, one allocation
     kSpec16Buckets,                   // ... in length buckets
@@ -62,7 +62,7 @@ struct ConvPlan {
     int rc = 0;                       // SS_EINVAL: the launch is refused and nothing else of the plan is set
     Variant variant = Variant::kLoop;
     bool tab_ok = false;              // kSimple: the unit table may be tried (the host knows the descriptors: fill_unit_tab)
-    bool bucket0 = true;              // the launch addresses bucket 0 only (kSpec16Buckets: the single-allocation half kernels)
+    bool bucket0 = true;              // the launch addresses bucket 0 only (kSpec16Buckets, bucketed kRows16: the single-allocation half kernels)
     int grid_x = 1, grid_y = 1;
     int parts_log2 = 0;
     int nb_y = 1;

@@ -112,6 +112,7 @@ struct Bank {
     bool spec_buckets_half_rows = false;      // half `spec_buckets` bound for rows of 2 or 3 blocks (ss_ctx_set_rir_spec_buckets_rows)
     bool rows16 = false;              // half-precision time-domain rows (ss_ctx_set_rir_bank16): nothing else is bound then
     bool rows16_rows = false;         // ... bound for the fused row kernels as well (ss_ctx_set_rir_bank16_rows; only with rows16)
+    bool rows16_buckets = false;      // half-precision time-domain rows in length buckets (ss_ctx_set_rir16_buckets): nothing else is bound then
 };
 
 struct Policies {
@@ -151,7 +152,9 @@ inline Route route_step(const Bank& b, int out_len, int n_valid, const Policies&
     // Bound by ss_ctx_set_rir_bank16_rows (rows16_rows), rows of 2 or 3 blocks take k_obs_blocks / k_obs_rows<.., ROWS16> wherever
     // obs_rows_ok hands the shape to them - a log-mel step's scratch counts as its waveform buffer (there is no one-launch
     // log-mel form on half rows, whatever the log-mel policies say) - and need no hand-over buffer there.
-    if (b.rows16) {
+    // Half rows in length buckets (rows16_buckets; rir_cap = the deepest bucket's blocks * kB): exactly as rows16, and never the
+    // row kernels - they do not read bucketed half rows.
+    if (b.rows16 || b.rows16_buckets) {
         if (xfade) {
             r.refused = true;
             return r;
@@ -164,7 +167,7 @@ inline Route route_step(const Bank& b, int out_len, int n_valid, const Policies&
         r.launch = Launch::kObs;
         const bool have_wave = w.waveform || r.wave_scratch;
         r.chain = out_len <= kB && t4_of(out_len) <= 26 ? Chain::kFused : Chain::kTwo;
-        if (r.chain == Chain::kTwo && b.rows16_rows && obs_rows_ok(out_len, n_valid, ceil_div(b.rir_cap, kB), flags, false, have_wave))
+        if (r.chain == Chain::kTwo && b.rows16 && b.rows16_rows && obs_rows_ok(out_len, n_valid, ceil_div(b.rir_cap, kB), flags, false, have_wave))
             r.chain = Chain::kRows;
         r.handover = r.chain == Chain::kTwo && !have_wave;
         return r;

@@ -29,7 +29,8 @@ EXPORTS = ("ss_block_len", "ss_spec_floats", "ss_version", "ss_init", "ss_source
            "ss_memo_rows_f32", "ss_ctx_memo_enable", "ss_ctx_memo_reset", "ss_ctx_memo_stats", "ss_ctx_observe_sims_memo",
            "ss_ctx_sims_memo_plan",
            "ss_rir_rows16_f32", "ss_bank_scatter_rows16_f32", "ss_fftconv_binaural_rir16_f32", "ss_audio_obs_rir16_f32",
-           "ss_ctx_set_rir_bank16", "ss_audio_obs_rows_rir16_f32", "ss_ctx_set_rir_bank16_rows")
+           "ss_ctx_set_rir_bank16", "ss_audio_obs_rows_rir16_f32", "ss_ctx_set_rir_bank16_rows",
+           "ss_fftconv_binaural_rir16_buckets_f32", "ss_audio_obs_rir16_buckets_f32", "ss_ctx_set_rir16_buckets")
 # entries that return a size_t, not a status (EXPORTS: every `int ss_*` of include/ss_hip.h)
 EXPORTS_SIZE = ("ss_ctx_wave_scratch_bytes",)
 
@@ -43,6 +44,12 @@ class SsRirBucket(ctypes.Structure):
 class SsSpecBucket(ctypes.Structure):
     """struct ss_spec_bucket of include/ss_hip.h."""
     _fields_ = [("hspec", ctypes.c_void_p), ("hscale", ctypes.c_void_p), ("first", ctypes.c_int), ("n_entries", ctypes.c_int),
+                ("cap", ctypes.c_int), ("reserved", ctypes.c_int)]
+
+
+class SsRir16Bucket(ctypes.Structure):
+    """struct ss_rir16_bucket of include/ss_hip.h."""
+    _fields_ = [("rir16", ctypes.c_void_p), ("rscale", ctypes.c_void_p), ("first", ctypes.c_int), ("n_entries", ctypes.c_int),
                 ("cap", ctypes.c_int), ("reserved", ctypes.c_int)]
 
 
@@ -207,6 +214,10 @@ def load() -> ctypes.CDLL:
     lib.ss_ctx_set_rir_bank16.argtypes = [vp, vp, vp, vp, c_int]
     lib.ss_audio_obs_rows_rir16_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, vp]
     lib.ss_ctx_set_rir_bank16_rows.argtypes = [vp, vp, vp, vp, c_int]
+    # ... in length buckets (ss_rir16_bucket): the ss_*_buckets_f32 arguments
+    lib.ss_fftconv_binaural_rir16_buckets_f32.argtypes = lib.ss_fftconv_binaural_buckets_f32.argtypes
+    lib.ss_audio_obs_rir16_buckets_f32.argtypes = lib.ss_audio_obs_buckets_f32.argtypes
+    lib.ss_ctx_set_rir16_buckets.argtypes = [vp, vp, c_int, vp]
     # pose memo of the column path
     lib.ss_memo_rows_f32.argtypes = [vp, c_int, vp, c_int, c_int, vp]
     lib.ss_ctx_memo_enable.argtypes = [vp, c_int]

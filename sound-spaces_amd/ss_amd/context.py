@@ -208,6 +208,25 @@ class AudioContext:
         self.rir_cap = int(bank.cap)
         self._spectra = None
 
+    def set_rir16_buckets(self, bank) -> None:
+        """HALF-PRECISION TIME-DOMAIN ROWS IN LENGTH BUCKETS (``BucketedRirBank`` whose sub-banks are ``rows_half``:
+        ``BucketedRirStore(rows="half")``; include/ss_hip.h ``ss_ctx_set_rir16_buckets``).  Replaces any earlier binding; bank =
+        None unbinds.  Routes as ``set_rir_bank16``: one-block rows fused, longer rows the bucketed half convolution + the
+        spectrogram kernel (never the fused row kernels), log-mel steps the waveform scratch; the library refuses (SS_EINVAL)
+        cross-faded steps and its in-call loaders report their misses.  Steps whose units all sit in bucket 0 keep the loop-free
+        half kernels."""
+        if bank is None:
+            _lib.check(self.lib.ss_ctx_set_rir16_buckets(self._h, None, 0, None), "ss_ctx_set_rir16_buckets")
+            self._bank = None
+            self._spectra = None
+            return
+        arr = bank.rir16_c_array()
+        _lib.check(self.lib.ss_ctx_set_rir16_buckets(self._h, ctypes.cast(arr, ctypes.c_void_p), len(bank.banks),
+                                                     bank.lengths.data_ptr()), "ss_ctx_set_rir16_buckets")
+        self._bank = (bank, arr)
+        self.rir_cap = int(bank.cap)
+        self._spectra = None
+
     def set_rir_spectra(self, hspec) -> None:
         """Spectral form of the bank set by set_rir_bank() (ops.rir_spectra / RirBank.build_spectra): steps without a
         cross-fade then run k_conv_spec.  None switches back to the time-domain kernels."""

@@ -604,6 +604,57 @@ def audio_obs_buckets_into(spec, buckets, n_buckets: int, rir_len, unit_desc, au
                                                         _PAD[pad_mode], flags, _stream(spec)), "ss_audio_obs_buckets_f32")
 
 
+# ---- half-precision time-domain rows in length buckets (include/ss_hip.h "... in length buckets") ---------------------------
+def rir16_bucket_array(rows16, scales, firsts):
+    """ctypes array of ss_rir16_bucket: per bucket its half rows [n,2,cap] (float16), its scales [n,2] (float32) and the global
+    index of its entry 0.  Keep the array alive with the tensors it points to."""
+    assert len(rows16) == len(scales) == len(firsts)
+    arr = (_lib.SsRir16Bucket * len(rows16))()
+    for b, (q, sc, first) in enumerate(zip(rows16, scales, firsts)):
+        cap = _chk_rows16(q, sc)
+        arr[b].rir16 = q.data_ptr()
+        arr[b].rscale = sc.data_ptr()
+        arr[b].first, arr[b].n_entries, arr[b].cap, arr[b].reserved = int(first), int(q.shape[0]), cap, 0
+    return arr
+
+
+def fftconv_binaural_rir16_buckets_into(spec, buckets, n_buckets: int, rir_len, unit_desc, out, n_valid: int, flags: int = 0) -> None:
+    """``fftconv_binaural_rir16_into`` on half rows in length buckets: ``buckets`` = ``rir16_bucket_array(...)``
+    (ss_fftconv_binaural_rir16_buckets_f32); no cross-fade."""
+    _chk(spec, torch.float32, "spec"); _chk(rir_len, torch.int32, "rir_len"); _chk(unit_desc, torch.int32, "unit_desc")
+    _chk(out, torch.float32, "out")
+    N, two, out_len = out.shape
+    assert two == 2 and unit_desc.shape == (N, 8)
+    with torch.cuda.device(out.device):
+        _lib.check(_lib.load().ss_fftconv_binaural_rir16_buckets_f32(spec.data_ptr(), ctypes_ref(buckets), n_buckets,
+                                                                     rir_len.data_ptr(), unit_desc.data_ptr(), out.data_ptr(), N,
+                                                                     n_valid, out_len, flags, _stream(spec)),
+                   "ss_fftconv_binaural_rir16_buckets_f32")
+
+
+def audio_obs_rir16_buckets_into(spec, buckets, n_buckets: int, rir_len, unit_desc, audiogoal, spectrogram_out, n_valid: int,
+                                 out_len: int, pad_mode="reflect", flags: int = 0) -> None:
+    """``audio_obs_rir16_into`` on half rows in length buckets (ss_audio_obs_rir16_buckets_f32: one-block rows, 257 <= out_len <=
+    KB; ``audiogoal`` may be None).  spectrogram_out None: the waveform alone (ss_fftconv_binaural_rir16_buckets_f32)."""
+    if spectrogram_out is None:
+        fftconv_binaural_rir16_buckets_into(spec, buckets, n_buckets, rir_len, unit_desc, audiogoal, n_valid, flags)
+        return
+    _chk(spec, torch.float32, "spec"); _chk(rir_len, torch.int32, "rir_len"); _chk(unit_desc, torch.int32, "unit_desc")
+    _chk(spectrogram_out, torch.float32, "spectrogram_out")
+    N = unit_desc.shape[0]
+    assert tuple(spectrogram_out.shape) == (N,) + spectrogram_shape(out_len)
+    ag_ptr = None
+    if audiogoal is not None:
+        _chk(audiogoal, torch.float32, "audiogoal")
+        assert tuple(audiogoal.shape) == (N, 2, out_len)
+        ag_ptr = audiogoal.data_ptr()
+    with torch.cuda.device(spec.device):
+        _lib.check(_lib.load().ss_audio_obs_rir16_buckets_f32(spec.data_ptr(), ctypes_ref(buckets), n_buckets, rir_len.data_ptr(),
+                                                              unit_desc.data_ptr(), ag_ptr, spectrogram_out.data_ptr(), N, n_valid,
+                                                              out_len, _PAD[pad_mode], flags, _stream(spec)),
+                   "ss_audio_obs_rir16_buckets_f32")
+
+
 # ---- spectral length buckets: a bucketed bank without time-domain rows (include/ss_hip.h "Spectral length buckets") --------
 def spec_bucket_array(spectra, scales, firsts, caps):
     """ctypes array of ss_spec_bucket: per bucket its block spectra [n,2,hb,SPEC_FLOATS] (float32, or float16 of a HALF bank),

@@ -144,13 +144,18 @@ class BucketedRirBank:
 
     Buckets that are all spectral-only banks (``RirStore(spectral="only" | "half")``: no rows) make a SPECTRAL-ONLY bucketed
     bank (``spectral_only``; include/ss_hip.h ``ss_spec_bucket``): ``spec_c_array()`` describes it, a half one with every
-    bucket's ``scales``."""
+    bucket's ``scales``.
+
+    Buckets that are all banks of half-precision time-domain rows (``RirStore(rows="half")``) make a bucketed bank of HALF ROWS
+    (``rows_half``; include/ss_hip.h ``ss_rir16_bucket``): ``rir16_c_array()`` describes it.  An entry of bucket b costs
+    ``4 * cap_b + 8`` bytes (``nbytes`` sums them)."""
 
     def __init__(self, banks: Sequence[RirBank], lengths: torch.Tensor, firsts: Optional[Sequence[int]] = None):
         assert 1 <= len(banks) <= 4
         only = [b.spectral_only for b in banks]
         assert all(only) or not any(only), "every bucket keeps rows or none does"
         assert len({b.scales is not None for b in banks}) == 1 or not all(only), "one spectral form in every bucket"
+        assert len({b.rows_half for b in banks}) == 1, "every bucket keeps half-precision rows or none does"
         self.banks = list(banks)
         self.first = list(firsts) if firsts is not None else list(np.cumsum([0] + [len(b) for b in banks[:-1]]))
         assert self.first[0] == 0 and all(self.first[b + 1] >= self.first[b] + len(banks[b]) for b in range(len(banks) - 1))
@@ -179,7 +184,26 @@ class BucketedRirBank:
 
     @property
     def half(self) -> bool:                     # a half bank: every bucket's spectra are float16 with scales of their own
-        return all(b.scales is not None for b in self.banks)
+        return all(b.scales is not None and not b.rows_half for b in self.banks)
+
+    @property
+    def rows_half(self) -> bool:                # every bucket keeps half-precision time-domain rows (ss_rir16_bucket)
+        return all(b.rows_half for b in self.banks)
+
+    @property
+    def nbytes(self) -> int:
+        """bytes of a bucketed bank of half rows: sum over the buckets of slots_b * (4 * cap_b + 8)"""
+        assert self.rows_half
+        return sum(len(b) * (4 * b.cap + 8) for b in self.banks)
+
+    def rir16_c_array(self):
+        """ss_rir16_bucket array of a bucketed bank of half rows (cached on the buckets' tensors, like c_array)."""
+        assert self.rows_half
+        now = [b.data.data_ptr() for b in self.banks] + [b.scales.data_ptr() for b in self.banks]
+        if self._carr is None or self._carr[1] != "rir16" or self._carr[2] != now:
+            arr = ops.rir16_bucket_array([b.data for b in self.banks], [b.scales for b in self.banks], self.first)
+            self._carr = (arr, "rir16", now)
+        return self._carr[0]
 
     def spec_c_array(self):
         """ss_spec_bucket array of a spectral-only bucketed bank (cached on the buckets' tensors, like c_array)."""
@@ -193,6 +217,7 @@ class BucketedRirBank:
 
     def c_array(self, spectral: bool):
         assert not self.spectral_only, "a spectral-only bucketed bank is described by spec_c_array()"
+        assert not self.rows_half, "a bucketed bank of half rows is described by rir16_c_array()"
         if self._carr is None or self._carr[1] != spectral or self._carr[2] != [b.data.data_ptr() for b in self.banks]:
             self._carr = (ops.bucket_array(self.banks, self.first, spectral), spectral, [b.data.data_ptr() for b in self.banks])
         return self._carr[0]
@@ -481,7 +506,7 @@ class BatchedAudioRenderer:
         rows16_fused, the fused row kernels for rows of 2 or 3 blocks (one launch, the waveform only where it is asked for)."""
         N = len(plan)
         fused = self.out_len <= P.KB and self.spectrogram_shape[1] <= 26
-        rows = not fused and self.rows16_fused and P.KB < self.out_len <= 3 * P.KB
+        rows = not fused and self.rows16_fused and P.KB < self.out_len <= 3 * P.KB and not isinstance(self.rirs, BucketedRirBank)
         ag = audiogoal_out
         if ag is None and (want_audiogoal or not (fused or rows)):
             ag = torch.empty((N, 2, self.out_len), dtype=torch.float32, device=self.device)
@@ -489,7 +514,15 @@ class BatchedAudioRenderer:
         if sg is None:
             sg = torch.empty((N,) + self.spectrogram_shape, dtype=torch.float32, device=self.device)
         b = self.rirs
-        if fused:
+        if isinstance(b, BucketedRirBank):                      # half rows in length buckets: never the fused row kernels
+            if fused:
+                ops.audio_obs_rir16_buckets_into(self._spec, b.rir16_c_array(), len(b.banks), b.lengths, plan.desc, ag, sg,
+                                                 self.n_valid, self.out_len, self.pad_mode, flags=plan.flags)
+            else:
+                ops.fftconv_binaural_rir16_buckets_into(self._spec, b.rir16_c_array(), len(b.banks), b.lengths, plan.desc, ag,
+                                                        self.n_valid, flags=plan.flags)
+                ops.spectrogram_into(ag, sg, self.pad_mode)
+        elif fused:
             ops.audio_obs_rir16_into(self._spec, b.data, b.scales, b.lengths, plan.desc, ag, sg, self.n_valid, self.out_len,
                                      self.pad_mode, flags=plan.flags)
         elif rows:
@@ -508,6 +541,12 @@ class BatchedAudioRenderer:
                              bool(plan.flags & ops.FLAG_CROSSFADE))
         if out is None:
             out = torch.empty((len(plan), 2, self.out_len), dtype=torch.float32, device=self.device)
+        if getattr(self.rirs, "rows_half", False) and isinstance(self.rirs, BucketedRirBank):
+            if plan.flags & ops.FLAG_CROSSFADE:
+                self._check_rows(False, True)
+            ops.fftconv_binaural_rir16_buckets_into(self._spec, self.rirs.rir16_c_array(), len(self.rirs.banks), self.rirs.lengths,
+                                                    plan.desc, out, self.n_valid, flags=plan.flags)
+            return out
         if getattr(self.rirs, "rows_half", False):
             ops.fftconv_binaural_rir16_into(self._spec, self.rirs.data, self.rirs.scales, self.rirs.lengths, plan.desc, out,
                                             self.n_valid, flags=plan.flags)
@@ -1453,8 +1492,13 @@ class BucketedRirStore:
 
     def __init__(self, slots: Sequence[int], caps: Sequence[int], device, truncate_to: Optional[int] = None,
                  max_cap: int = 1 << 18, on_grow=None, group: int = 1, spectral: Union[bool, str] = False,
-                 spectral_buckets: bool = False):
-        """spectral="only" | "half" with spectral_buckets=True (opt-in): every bucket is a spectral-only sub-store of that form
+                 spectral_buckets: bool = False, rows: Optional[str] = None):
+        """rows="half" (opt-in, lossy exactly as ``RirStore(rows="half")``): every bucket is a sub-store of half-precision
+        time-domain rows and the bank is served through ``ss_rir16_bucket`` - an entry of bucket b costs 4 * cap_b + 8 bytes
+        (``nbytes``).  A GPU device, no spectral argument, at most 16 partition blocks per bucket.  Staging and quantising
+        (ss_bank_scatter_rows16_f32), routing by length, re-bucketing, eviction and growth of the last bucket (halves copied, the
+        new tail +0, scales kept) are the sub-stores' own.
+        spectral="only" | "half" with spectral_buckets=True (opt-in): every bucket is a spectral-only sub-store of that form
         (``RirStore(spectral=...)``: block spectra staged as the rows arrive, no time-domain rows, a GPU device) and the bank is
         served through ``ss_spec_bucket`` - a half entry of bucket b costs 2 * h_blocks_b * (65 536 + 4) + 4 bytes, an "only"
         one 2 * h_blocks_b * 131 072 + 4.  Routing by length, re-bucketing, eviction and growth of the last bucket are the
@@ -1471,6 +1515,17 @@ class BucketedRirStore:
             if P.ceil_div(max(max_cap, caps[-1]), P.KB) > 16:
                 raise ValueError("BucketedRirStore: a spectral bucket holds at most 16 partition blocks per row "
                                  f"(max_cap <= {16 * P.KB})")
+        if rows not in (None, "half"):
+            raise ValueError(f"BucketedRirStore: rows must be None or 'half', not {rows!r}")
+        self.rows_half = rows == "half"
+        if self.rows_half:
+            if spectral or spectral_buckets:
+                raise ValueError("BucketedRirStore(rows='half') keeps no spectral form: it does not go with spectral")
+            if torch.device(device).type != "cuda":
+                raise ValueError("BucketedRirStore(rows='half') needs a GPU device: the half-precision rows have no CPU fallback")
+            if P.ceil_div(max(max_cap, caps[-1]), P.KB) > 16:
+                raise ValueError("BucketedRirStore: a bucket of half rows holds at most 16 partition blocks per row "
+                                 f"(max_cap <= {16 * P.KB})")
         self.device = torch.device(device)
         self.group, self.on_grow, self.spectral = group, on_grow, spectral
         self.first = [int(v) for v in np.cumsum([0] + list(slots[:-1]))]
@@ -1481,7 +1536,7 @@ class BucketedRirStore:
         for b, (n, cap) in enumerate(zip(slots, caps)):
             last = b == len(caps) - 1
             st = RirStore(n, cap, device, truncate_to=truncate_to, max_cap=max_cap if last else cap + (cap & 1),
-                          on_grow=self._sub_grown, group=group, spectral=spectral)
+                          on_grow=self._sub_grown, group=group, spectral=spectral, **(dict(rows="half") if self.rows_half else {}))
             st.bank.lengths = lengths[self.first[b]:self.first[b] + n]        # views of the one global array
             st.host_len = self.host_len[self.first[b]:self.first[b] + n]
             self.stores.append(st)
@@ -1502,6 +1557,11 @@ class BucketedRirStore:
     @property
     def cap(self) -> int:
         return max(st.cap for st in self.stores)
+
+    @property
+    def nbytes(self) -> int:
+        """device bytes of the bank of a rows="half" store: sum over the buckets of slots_b * (4 * cap_b + 8)"""
+        return self.bank.nbytes
 
     @property
     def hits(self) -> int:
@@ -1778,16 +1838,20 @@ class AudioEngine:
             # power-of-two scale per (entry, ear) (RirStore(rows="half"), include/ss_hip.h "Half-precision time-domain rows") - half
             # the bytes of the plain rows, 64 008 per 16 kHz entry, the cheapest form.  Every sampling rate up to 3 KB: one-block
             # rows take the fused half kernels, 44.1 / 48 kHz the half convolution + the spectrogram kernel.  Not served: SS2.0
-            # (step_time / wrap: live RIRs and the cross-fade), length buckets, any spectral form, a CPU device.
+            # (step_time / wrap: live RIRs and the cross-fade), any spectral form, a CPU device.
+            # With rir_buckets: the half rows in length buckets (BucketedRirStore(rows="half"), include/ss_hip.h "Half-precision
+            # time-domain rows in length buckets"): an entry of bucket b costs 4 * cap_b + 8 bytes; rir_max_cap is clamped to 16 KB.
+            # Not with rir_rows16_fused: the fused row kernels do not read bucketed half rows.
             if rir_spectral:
                 raise ValueError("rir_rows='half' keeps no spectral form: it does not go with rir_spectral")
-            if rir_buckets:
-                raise ValueError("rir_rows='half' does not support length-bucketed banks (rir_buckets)")
+            if rir_buckets and rir_rows16_fused:
+                raise ValueError("rir_rows16_fused does not go with rir_buckets: the fused row kernels do not read bucketed half rows")
             if renderer_kwargs.get("step_time") is not None or renderer_kwargs.get("wrap"):
                 raise ValueError("rir_rows='half' cannot serve SoundSpaces 2.0 (step_time / wrap): live RIRs and the cross-fade "
                                  "need float32 rows")
             if torch.device(device).type != "cuda":
-                raise ValueError("rir_rows='half' needs a GPU device: the half-precision rows have no CPU fallback")
+                raise ValueError("rir_rows='half'" + (" with rir_buckets" if rir_buckets else "") +
+                                 " needs a GPU device: the half-precision rows have no CPU fallback")
             if int(sampling_rate) > 3 * P.KB:
                 raise ValueError(f"rir_rows='half' serves rows of up to three partition blocks (sampling rates up to {3 * P.KB}), "
                                  f"not {sampling_rate}")
@@ -1840,15 +1904,16 @@ class AudioEngine:
         self.rir_rows_half = rir_rows == "half"
         self.rir_rows16_fused = bool(rir_rows16_fused)
         self.renderer.rows16_fused = self.rir_rows16_fused
-        if rir_buckets and rir_spectral_buckets:
-            rir_max_cap = min(int(rir_max_cap), 16 * P.KB)         # (ss_spec_bucket: at most 16 blocks per row)
+        if rir_buckets and (rir_spectral_buckets or self.rir_rows_half):
+            rir_max_cap = min(int(rir_max_cap), 16 * P.KB)         # (ss_spec_bucket / ss_rir16_bucket: at most 16 blocks per row)
         if rir_buckets:
             # length-bucketed bank: [(slots, cap samples), ...] ascending, e.g. [(4096, 16000), (256, 49152), (64, 65536)]
             self.store = BucketedRirStore([b[0] for b in rir_buckets], [b[1] for b in rir_buckets], self.renderer.device,
                                           truncate_to=None if full else int(sampling_rate), max_cap=rir_max_cap,
                                           on_grow=self.renderer.set_rir_bank, group=rir_group,
                                           spectral=False if full else rir_spectral,
-                                          **(dict(spectral_buckets=True) if rir_spectral_buckets else {}))
+                                          **(dict(spectral_buckets=True) if rir_spectral_buckets else {}),
+                                          **(dict(rows="half") if self.rir_rows_half else {}))
             self.renderer.set_rir_bank(self.store.bank)
             return
         self.store = RirStore(rir_slots, rir_cap or sampling_rate, self.renderer.device,
@@ -1921,7 +1986,9 @@ class AudioEngine:
         if isinstance(bank, BucketedRirBank):                    # length buckets: ss_ctx_set_rir_buckets (every bucket's rows, and
             now = tuple(b.data for b in bank.banks) + tuple(b.spectra for b in bank.banks)      # its block spectra when kept)
             if n_sync or cur is None or len(cur) != len(now) or any(a is not b for a, b in zip(cur, now)):
-                if bank.spectral_only:                           # (no rows: ss_ctx_set_rir_spec_buckets, either form; half buckets
+                if bank.rows_half:                               # (half-precision rows in length buckets: ss_ctx_set_rir16_buckets)
+                    ctx.set_rir16_buckets(bank)
+                elif bank.spectral_only:                         # (no rows: ss_ctx_set_rir_spec_buckets, either form; half buckets
                     ctx.set_rir_spec_buckets(bank, rows=bank.half and self.renderer.out_len > P.KB)  # under longer rows: _rows)
                 else:
                     ctx.set_rir_buckets(bank, spectral=bool(self.store.spectral and bank.spectra))
