@@ -243,12 +243,24 @@ int ss_audio_obs_logmel_rows_spec16_f32(const float* spec, const void* hspec16, 
  *                                   k_spectrogram, as the fp32 entry does (obs_rows_ok); that shape needs `audiogoal`.  Small steps
  *                                   run k_obs_blocks, whose hand-off flags carry a launch counter: do not replay this entry from
  *                                   a captured graph (the note on ss_audio_obs_rows_f32).
+ *   ss_audio_obs_logmel_rir16_f32   ss_audio_obs_logmel_f32 from half rows (k_conv<.., MEL, HALF>: loop-free when
+ *                                   SS_FLAG_NO_DISTRACTOR and rir_cap <= kB, else the loop kernel): 257 <= out_len <= kB, the mel
+ *                                   arguments and their limits as there; `audiogoal` and `spectrogram` may each be NULL, any
+ *                                   combination is ONE launch.  Silent units, empty entries and pooled blocks behind n_valid give
+ *                                   log(mel_eps), with exact zeros in the pooled spectrogram; a waveform buffer is written exactly
+ *                                   as ss_audio_obs_rir16_f32 writes it.
+ *   ss_audio_obs_logmel_rows_rir16_f32  the same for rows of 2 or 3 partition blocks (kB < out_len <= 3 kB, at most 16 RIR
+ *                                   blocks): k_obs_blocks / k_obs_rows<.., MEL, .., ROWS16>, chosen by the rule of
+ *                                   ss_audio_obs_rows_rir16_f32 (same stash, same hand-off area); a waveform buffer is written as
+ *                                   that entry writes it.  A launch that takes k_obs_blocks must not be replayed from a captured
+ *                                   graph (the note on ss_audio_obs_rows_f32).
+ *                                   The results of both equal those of ss_audio_obs_logmel_f32 / _rows_f32 fed float(q) * rscale.
  * Length buckets: the section "Half-precision time-domain rows in length buckets" below (entries of their own).
- * Not served, by any entry: SS_FLAG_CROSSFADE, a one-launch log-mel form (the time-domain log-mel instantiation of
- * the row kernels is at its register limit: log-mel steps render a waveform and run the feature kernel over it), k_conv_rows, the
- * wide form and the 512-thread core, the in-call loaders, the TORCH_LIBRARY ops; no default selects the form or its row kernels.
+ * Not served, by any entry: SS_FLAG_CROSSFADE (log-mel included), k_conv_rows, the wide form and the 512-thread core, the in-call
+ * loaders, the TORCH_LIBRARY ops; no default selects the form, its row kernels or its log-mel forms.
  * SS_EINVAL before a device is touched: NULL halves or scales, a base that is not 4-byte aligned, odd rir_cap or rir_cap < 2, more
- * than 16 partition blocks, SS_FLAG_CROSSFADE, out_len outside the entry's range, a bad pad_mode, a NULL required output.
+ * than 16 partition blocks, SS_FLAG_CROSSFADE, out_len outside the entry's range, a bad pad_mode, a NULL required output, mel
+ * arguments outside the limits of ss_audio_features_f32.
  * n_units == 0 (n_entries == 0) returns 0. */
 int ss_rir_rows16_f32(const float* rir, void* rir16_out, float* rscale_out, int n_entries, long long rir_unit_stride,
                       int rir_chan_stride, int rir_cap, void* stream);
@@ -261,6 +273,14 @@ int ss_audio_obs_rir16_f32(const float* spec, const void* rir16, const float* rs
 int ss_audio_obs_rows_rir16_f32(const float* spec, const void* rir16, const float* rscale, const int* rir_len, const int* unit_desc,
                                 float* audiogoal, float* spectrogram, int n_units, int rir_cap, int n_valid, int out_len,
                                 int pad_mode, int flags, void* stream);
+int ss_audio_obs_logmel_rir16_f32(const float* spec, const void* rir16, const float* rscale, const int* rir_len, const int* unit_desc,
+                                  float* audiogoal, float* spectrogram, float* logmel, const int* mel_start, const float* mel_w,
+                                  int n_mels, int max_len, float mel_eps, int n_units, int rir_cap, int n_valid, int out_len,
+                                  int pad_mode, int flags, void* stream);
+int ss_audio_obs_logmel_rows_rir16_f32(const float* spec, const void* rir16, const float* rscale, const int* rir_len,
+                                       const int* unit_desc, float* audiogoal, float* spectrogram, float* logmel,
+                                       const int* mel_start, const float* mel_w, int n_mels, int max_len, float mel_eps, int n_units,
+                                       int rir_cap, int n_valid, int out_len, int pad_mode, int flags, void* stream);
 
 /* The same for rows of 2 or 3 partition blocks (kB < out_len <= 3 kB: 44.1 / 48 kHz, the reference's Replica rate; EXTENSION):
  * the log-mel form of the fused row kernels (k_obs_rows / k_obs_blocks), the STFT phase behind every output block emits the
@@ -436,8 +456,13 @@ int ss_audio_obs_logmel_rows_spec16_buckets_f32(const float* spec, const ss_spec
  *   ss_audio_obs_rir16_buckets_f32          the shapes of ss_audio_obs_rir16_f32: 257 <= out_len <= kB, at most 26 pooled blocks,
  *                                           `audiogoal` may be NULL.  Longer rows: the convolution entry + ss_spectrogram_f32 (what
  *                                           a context bound by ss_ctx_set_rir16_buckets does).
+ *   ss_audio_obs_logmel_rir16_buckets_f32   ss_audio_obs_logmel_rir16_f32 on the buckets: one-block rows only (257 <= out_len <= kB;
+ *                                           longer rows are SS_EINVAL), ONE launch for any combination of `audiogoal` and
+ *                                           `spectrogram` (each may be NULL): k_conv<.., MEL, HALF, RBK>; bucket-0 launches run the
+ *                                           single-allocation log-mel kernels on bucket 0's arrays (loop-free with cap_0 <= kB and
+ *                                           SS_FLAG_NO_DISTRACTOR) and equal ss_audio_obs_logmel_rir16_f32 on them bit for bit.
  * OUT OF SCOPE, refused or not offered: bucketed half rows under the fused row kernels (k_obs_blocks / k_obs_rows keep reading one
- * allocation of half rows only), a one-launch log-mel form, SS_FLAG_CROSSFADE, the wide form, k_conv_rows, the 512-thread core, the
+ * allocation of half rows only - log-mel included), SS_FLAG_CROSSFADE, the wide form, k_conv_rows, the 512-thread core, the
  * in-call loaders, the TORCH_LIBRARY ops; no default selects the form.
  * SS_EINVAL before a device is touched: a NULL bucket array, n_buckets outside [1, 4], any bucket the single-allocation checks
  * refuse, `first` not ascending / overlapping / != 0 for bucket 0, negative n_entries, NULL rir_len, SS_FLAG_CROSSFADE, out_len
@@ -456,6 +481,10 @@ int ss_fftconv_binaural_rir16_buckets_f32(const float* spec, const ss_rir16_buck
 int ss_audio_obs_rir16_buckets_f32(const float* spec, const ss_rir16_bucket* buckets, int n_buckets, const int* rir_len,
                                    const int* unit_desc, float* audiogoal, float* spectrogram, int n_units, int n_valid,
                                    int out_len, int pad_mode, int flags, void* stream);
+int ss_audio_obs_logmel_rir16_buckets_f32(const float* spec, const ss_rir16_bucket* buckets, int n_buckets, const int* rir_len,
+                                          const int* unit_desc, float* audiogoal, float* spectrogram, float* logmel,
+                                          const int* mel_start, const float* mel_w, int n_mels, int max_len, float mel_eps,
+                                          int n_units, int n_valid, int out_len, int pad_mode, int flags, void* stream);
 
 /* EXTENSION, one pass for every STFT-derived feature (BASELINE.json configs[4] "GCC-PHAT + log-mel fused sensor"): each
  * (unit, ear, frame) of x [n_units, 2, len] is framed, windowed and transformed ONCE (both ears in one wave), and from that
@@ -588,7 +617,8 @@ int ss_ctx_set_rir_spectra16_rows(ss_ctx* ctx, const void* hspec16, const float*
  * and is replaced by every other bank call; while it is bound ss_ctx_set_rir_spectra / _spectra16 / _spectra16_rows with a bank are
  * SS_EINVAL.  rir16 = NULL unbinds.  Steps of one-block rows (257 <= sampling_rate <= kB) take the fused half kernels, every longer
  * row (44.1 / 48 kHz) the half convolution into the caller's waveform buffer - or the context's hand-over buffer - and the
- * spectrogram kernel over it; log-mel steps render into the context's waveform scratch.  A cross-faded step is SS_EINVAL and
+ * spectrogram kernel over it; log-mel steps render into the context's waveform scratch unless ss_ctx_set_logmel_rir16_policy
+ * admits them to the one-launch form (one-block rows on this binding).  A cross-faded step is SS_EINVAL and
  * leaves no keys behind.  The in-call loaders do not serve this form: ss_ctx_load_rir_files returns 1,
  * ss_ctx_observe_requests_load reports the misses (the caller scatters with ss_bank_scatter_rows16_f32 and calls again).  The pose
  * memo, the overlap mode and the column / request entries run on it unchanged.  SS_EINVAL, nothing changed: the bank refusals of
@@ -598,8 +628,9 @@ int ss_ctx_set_rir_bank16(ss_ctx* ctx, const void* rir16, const float* rscale, c
  * rules, refusals, loaders, pose memo, overlap mode, column / request entries - except that steps of rows of 2 or 3 partition
  * blocks (44.1 / 48 kHz) take ONE launch (k_obs_blocks / k_obs_rows<.., ROWS16>, what ss_audio_obs_rows_rir16_f32 runs) wherever the
  * fp32 time-domain bank would: not with a waveform buffer and one rendered block (n_valid <= kB), not past 3 kB samples - those keep
- * the two launches.  A spectrogram-only step then needs no hand-over buffer.  Log-mel steps keep the waveform scratch whatever the
- * log-mel policies say (no one-launch log-mel form reads half rows); with a spectrogram asked as well and n_valid > kB, the row
+ * the two launches.  A spectrogram-only step then needs no hand-over buffer.  Log-mel steps inside
+ * ss_ctx_set_logmel_rir16_policy's range (empty by default) take ss_audio_obs_logmel_rir16_f32 / _rows_rir16_f32; the others keep
+ * the waveform scratch: with a spectrogram asked as well and n_valid > kB, the row
  * kernel writes the scratch and the spectrogram and the feature kernel runs over the scratch.  One-block rates: the same routes
  * as ss_ctx_set_rir_bank16.  A later ss_ctx_set_rir_bank16 on the context clears the opt-in. */
 int ss_ctx_set_rir_bank16_rows(ss_ctx* ctx, const void* rir16, const float* rscale, const int* rir_len, int rir_cap);
@@ -631,7 +662,7 @@ int ss_ctx_set_rir_spec_buckets_rows(ss_ctx* ctx, const ss_spec_bucket* buckets,
  * whose units all sit in bucket 0 carry SS_FLAG_FIRST_BUCKET and keep the loop-free half kernels.  Routes as ss_ctx_set_rir_bank16:
  * one-block rows take the fused launch, longer rows (44.1 / 48 kHz) the bucketed half convolution into the caller's waveform buffer
  * - or the context's hand-over buffer - and the spectrogram kernel over it (never the fused row kernels), log-mel steps the waveform
- * scratch.  A cross-faded step is SS_EINVAL and leaves no keys behind.  The in-call loaders do not serve this form:
+ * scratch - or, one-block rows inside ss_ctx_set_logmel_rir16_policy's range, ss_audio_obs_logmel_rir16_buckets_f32.  A cross-faded step is SS_EINVAL and leaves no keys behind.  The in-call loaders do not serve this form:
  * ss_ctx_load_rir_files returns 1, ss_ctx_observe_requests_load reports the misses and launches nothing.  The pose memo, the overlap
  * mode and the column / request entries run on it unchanged.  SS_EINVAL, nothing changed: the refusals of ss_rir16_bucket,
  * rir_len == NULL.  Call again whenever a bucket is (re)allocated. */
@@ -661,6 +692,11 @@ int ss_ctx_observe(ss_ctx* ctx, const ss_units* units, int n, float* audiogoal, 
  *     ss_ctx_set_rir_spec_buckets, when the step has no cross-fade, its rows are one partition block (every bank form) or 2 or
  *     3 blocks (the fp32 forms) and its unit count lies inside ss_ctx_set_logmel_buckets_policy's range, which is empty by
  *     default for the same reason; the three ranges above never apply to such a context;
+ *   - ONE fused launch (ss_audio_obs_logmel_rir16_f32 / _rows_rir16_f32 / _rir16_buckets_f32) on a context bound by
+ *     ss_ctx_set_rir_bank16, ss_ctx_set_rir_bank16_rows or ss_ctx_set_rir16_buckets, when the step has no cross-fade, its rows are
+ *     one partition block (all three bindings) or 2 or 3 blocks (ss_ctx_set_rir_bank16_rows only) and its unit count lies inside
+ *     ss_ctx_set_logmel_rir16_policy's range, which is empty by default for the same reason; the four ranges above never apply
+ *     to such a context;
  *   - otherwise (44.1 / 48 kHz rows, cross-faded steps and bucketed banks by default, unit counts outside the range) the route ss_ctx_observe
  *     takes with an audiogoal buffer, into a waveform scratch the CONTEXT owns ([n, 2, sr] floats per overlap lane, grown on
  *     demand, freed with the context and by ss_release_scratch; a growth needed while the stream is being captured is refused
@@ -701,6 +737,15 @@ int ss_ctx_set_logmel_ss2_policy(ss_ctx* ctx, int min_units, int max_units);
  * whenever the spectrogram is asked for as well (8-29 %), but log-mel alone at 43 units costs 1.7 x the scratch route (the row
  * kernel takes over from the one-workgroup-per-block kernel) and 128 units are a tie: (1, 42) there. */
 int ss_ctx_set_logmel_buckets_policy(ss_ctx* ctx, int min_units, int max_units);
+/* The same for contexts bound to half-precision time-domain rows (ss_ctx_set_rir_bank16, ss_ctx_set_rir_bank16_rows,
+ * ss_ctx_set_rir16_buckets: ss_audio_obs_logmel_rir16_f32 / _rows_rir16_f32 / _rir16_buckets_f32 and their shapes); the four
+ * setters above keep their meaning and never apply to such a context, and this one applies to no other.  Rebinding a bank keeps
+ * the range.  Default: never (max_units < min_units) - the fused values equal the scratch route's to rounding only.  Measured
+ * against the scratch route of the same bank, ONE pass (profiles/r12/kbench_obs_logmel_rir16.txt): 16 kHz, one allocation and buckets,
+ * 1 .. 512 units: 16-45 % faster, so (1, INT_MAX) is the range a caller would pass there; 44.1 kHz: 15-34 % faster up to 42 units and
+ * whenever the spectrogram is asked for as well, but log-mel alone at 43 units is 20 % slower (the row kernel takes over from the
+ * one-workgroup-per-block kernel): (1, 42) there. */
+int ss_ctx_set_logmel_rir16_policy(ss_ctx* ctx, int min_units, int max_units);
 /* Bytes of waveform scratch the context currently holds over all overlap lanes (the scratch route above): 0 after creation and
  * after ss_release_scratch. */
 size_t ss_ctx_wave_scratch_bytes(const ss_ctx* ctx);

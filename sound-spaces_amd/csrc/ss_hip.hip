@@ -347,7 +347,7 @@ void drop_stash(hipStream_t st) {
 // MEL: the log-mel instantiations (ss_audio_obs_logmel_rows_f32 / _spec_f32), same rule, same hand-off area.
 // HALF: the half-bank instantiations (ss_audio_obs_rows_spec16_f32 / ss_audio_obs_logmel_rows_spec16_f32), likewise.
 // HBK: a half bank in length buckets (ss_audio_obs_rows_spec16_buckets_f32 / ss_audio_obs_logmel_rows_spec16_buckets_f32), likewise.
-// ROWS16: half-precision time-domain rows (ss_audio_obs_rows_rir16_f32), likewise.
+// ROWS16: half-precision time-domain rows (ss_audio_obs_rows_rir16_f32; with MEL: ss_audio_obs_logmel_rows_rir16_f32), likewise.
 template <bool SPECTRAL, bool MEL = false, bool HALF = false, bool HBK = false, bool ROWS16 = false>
 int launch_obs_rows(ssk::ConvParams p, int n_units, int flags, int n_cus, const LaunchEnv& env,
                     const ssk::UnitTab<false, MEL>& mel = ssk::UnitTab<false, MEL>(),
@@ -356,7 +356,7 @@ int launch_obs_rows(ssk::ConvParams p, int n_units, int flags, int n_cus, const 
     const hipStream_t st = env.st;
     static_assert(!HALF || SPECTRAL, "half bank: the spectral form");
     static_assert(!HBK || HALF, "bucketed half bank: a half form");
-    static_assert(!ROWS16 || (!SPECTRAL && !MEL && !HALF), "half rows: plain rows of one time-domain allocation");
+    static_assert(!ROWS16 || (!SPECTRAL && !HALF), "half rows: plain rows of one time-domain allocation");
     const int n_rows = 2 * n_units;
     const dim3 block(ssk::kT);
     // (the log-mel and half forms: plain rows; half: one allocation, or the HBK form)
@@ -375,7 +375,7 @@ int launch_obs_rows(ssk::ConvParams p, int n_units, int flags, int n_cus, const 
         sslaunch::apply(pb, p);
         const dim3 grid(pb.grid);
         if constexpr (ROWS16)
-            hipLaunchKernelGGL((ssk::k_obs_blocks<false, false, false, false, true>), grid, block, 0, st, p, n_rows, tails, fl, epoch, mel, hs, rs);
+            hipLaunchKernelGGL((ssk::k_obs_blocks<false, MEL, false, false, true>), grid, block, 0, st, p, n_rows, tails, fl, epoch, mel, hs, rs);
         else if constexpr (HBK) hipLaunchKernelGGL((ssk::k_obs_blocks<SPECTRAL, MEL, true, true>), grid, block, 0, st, p, n_rows, tails, fl, epoch, mel, hs);
         else if constexpr (HALF) hipLaunchKernelGGL((ssk::k_obs_blocks<SPECTRAL, MEL, true>), grid, block, 0, st, p, n_rows, tails, fl, epoch, mel, hs);
         else if constexpr (MEL) hipLaunchKernelGGL((ssk::k_obs_blocks<SPECTRAL, true>), grid, block, 0, st, p, n_rows, tails, fl, epoch, mel);
@@ -390,7 +390,7 @@ int launch_obs_rows(ssk::ConvParams p, int n_units, int flags, int n_cus, const 
         p.stash = reinterpret_cast<ssk::f32x4*>(buf);
     }
     const dim3 grid(pr.grid);
-    if constexpr (ROWS16) hipLaunchKernelGGL((ssk::k_obs_rows<false, false, false, false, false, true>), grid, block, 0, st, p, n_rows, mel, hs, rs);
+    if constexpr (ROWS16) hipLaunchKernelGGL((ssk::k_obs_rows<false, false, false, MEL, false, true>), grid, block, 0, st, p, n_rows, mel, hs, rs);
     else if constexpr (HBK) hipLaunchKernelGGL((ssk::k_obs_rows<true, false, true, MEL, true>), grid, block, 0, st, p, n_rows, mel, hs);
     else if constexpr (HALF) hipLaunchKernelGGL((ssk::k_obs_rows<true, false, false, MEL, true>), grid, block, 0, st, p, n_rows, mel, hs);
     else if constexpr (MEL) {                                   // (length buckets: the instantiation that resolves them)
@@ -421,6 +421,21 @@ int launch_conv_mel(ssk::ConvParams p, const ssk::MelArgs& m, int n_units, int f
     const dim3 grid(2 * n_units), block(ssk::kT);
     if (simple) hipLaunchKernelGGL((ssk::k_conv<true, true, false, false, false, true>), grid, block, 0, st, p, m);
     else hipLaunchKernelGGL((ssk::k_conv<true, false, false, false, false, true>), grid, block, 0, st, p, m);
+    return hip_err(hipGetLastError());
+}
+
+// ... from half-precision time-domain rows (k_conv<.., MEL, HALF>; ssk::RowScale): the convention of launch_conv_mel - one
+// workgroup per row, parts_log2 = 0.  Launches that only touch bucket 0 (one allocation, one bucket, or SS_FLAG_FIRST_BUCKET)
+// run the single-allocation kernels on bucket 0's arrays, the loop-free one included; everything else bucketed: k_conv<.., RBK>.
+int launch_conv16_mel(ssk::ConvParams p, const ssk::MelArgs& m, const ssk::RowScale<true, true>& rs, int n_units, int flags,
+                      hipStream_t st) {
+    const bool bucket0 = p.n_buckets == 1 || (flags & SS_FLAG_FIRST_BUCKET);
+    const bool simple = (flags & SS_FLAG_NO_DISTRACTOR) && p.rir_cap <= ssk::kB && bucket0;
+    const dim3 grid(2 * n_units), block(ssk::kT);
+    const ssk::RowScale<true> rs1{rs.rir16, rs.rscale};
+    if (!bucket0) hipLaunchKernelGGL((ssk::k_conv<true, false, false, false, false, true, true, true>), grid, block, 0, st, p, m, rs);
+    else if (simple) hipLaunchKernelGGL((ssk::k_conv<true, true, false, false, false, true, true>), grid, block, 0, st, p, m, rs1);
+    else hipLaunchKernelGGL((ssk::k_conv<true, false, false, false, false, true, true>), grid, block, 0, st, p, m, rs1);
     return hip_err(hipGetLastError());
 }
 
@@ -721,10 +736,11 @@ int render(const Bank& b, bool spectral, ssroute::Launch want, const float* spec
     int nbh_max = 1;
     if (n_units < 0) return SS_EINVAL;
     const bool rows16 = b.rir16 || b.rscale || b.rows16_bk;
-    if (rows16) {                                           // (half rows, one allocation or length buckets: no cross-fade, no log-mel form)
+    if (rows16) {                                           // (half rows, one allocation or length buckets: no cross-fade)
         if (b.rows16_bk ? rir16_buckets_check(b.rbk, b.n_buckets, &nbh_max) != 0 : !rows16_bank_ok(b.rir16, b.rscale, b.cap)) return SS_EINVAL;
         if ((flags & SS_FLAG_CROSSFADE) || spectral) return SS_EINVAL;
-        if (want != Launch::kConv && want != Launch::kObs) return SS_EINVAL;
+        // log-mel: one-block rows on both forms, rows of 2 or 3 blocks on one allocation asked for the row kernels
+        if (want == Launch::kMelSs2 || (want == Launch::kMelRows && (b.rows16_bk || !b.rows16_rows))) return SS_EINVAL;
         if (!b.rows16_bk) nbh_max = (b.cap + ssk::kB - 1) / ssk::kB;
     } else if (b.sbk) {                                            // (no rows anywhere: a cross-fade has nothing to read)
         if (spec_buckets_check(b.sbk, b.n_buckets, &half, &nbh_max) || (flags & SS_FLAG_CROSSFADE)) return SS_EINVAL;
@@ -805,6 +821,13 @@ int render(const Bank& b, bool spectral, ssroute::Launch want, const float* spec
             p.sgram = spectrogram;
             return launch_obs_rows<false, false, false, false, true>(p, n_units, flags, n_cus, env, ssk::UnitTab<false, false>(),
                                                                      ssk::SpecScale<false, false>(), ssk::RowScale<true>{rs.rir16, rs.rscale});
+        }
+        if (want == Launch::kMelOneBlock || want == Launch::kMelRows) {
+            p.pad_mode = pad_mode;
+            p.sgram = spectrogram;
+            if (want == Launch::kMelOneBlock) return launch_conv16_mel(p, *mel, rs, n_units, flags, env.st);
+            return launch_obs_rows<false, true, false, false, true>(p, n_units, flags, n_cus, env, *mel, ssk::SpecScale<false, false>(),
+                                                                    ssk::RowScale<true>{rs.rir16, rs.rscale});
         }
         rc = launch_conv<false>(Form::kRows16, p, n_units, nb_y, flags, n_cus, env, false, nullptr, &rs);
         if (rc || want == Launch::kConv) return rc;
@@ -1381,6 +1404,34 @@ int ss_audio_obs_rows_rir16_f32(const float* spec, const void* rir16, const floa
                   nullptr, n_units, n_valid, out_len, pad_mode, flags, stateless(stream));
 }
 
+// Log-mel observation of one-block rows from half rows in ONE launch (k_conv<.., MEL, HALF>), no waveform buffer needed
+int ss_audio_obs_logmel_rir16_f32(const float* spec, const void* rir16, const float* rscale, const int* rir_len, const int* unit_desc,
+                                  float* audiogoal, float* spectrogram, float* logmel, const int* mel_start, const float* mel_w,
+                                  int n_mels, int max_len, float mel_eps, int n_units, int rir_cap, int n_valid, int out_len,
+                                  int pad_mode, int flags, void* stream) {
+    if (n_units == 0) return 0;
+    if (!rows16_bank_ok(rir16, rscale, rir_cap) || (flags & SS_FLAG_CROSSFADE)) return SS_EINVAL;
+    if (!mel_args_ok(logmel, mel_start, mel_w, n_mels, max_len, mel_eps)) return SS_EINVAL;
+    const ssk::MelArgs m{logmel, mel_start, mel_w, n_mels, max_len, mel_eps};
+    return render(rows16_bank(rir16, rscale, rir_cap), false, Launch::kMelOneBlock, spec, rir_len, unit_desc, audiogoal, spectrogram, &m,
+                  n_units, n_valid, out_len, pad_mode, flags, stateless(stream));
+}
+
+// ... of rows of 2 or 3 partition blocks (k_obs_blocks / k_obs_rows<.., MEL, .., ROWS16>: launch_obs_rows' own choice, hand-off
+// area and stash)
+int ss_audio_obs_logmel_rows_rir16_f32(const float* spec, const void* rir16, const float* rscale, const int* rir_len,
+                                       const int* unit_desc, float* audiogoal, float* spectrogram, float* logmel, const int* mel_start,
+                                       const float* mel_w, int n_mels, int max_len, float mel_eps, int n_units, int rir_cap,
+                                       int n_valid, int out_len, int pad_mode, int flags, void* stream) {
+    if (n_units == 0) return 0;
+    if (!rows16_bank_ok(rir16, rscale, rir_cap) || (flags & SS_FLAG_CROSSFADE)) return SS_EINVAL;
+    if (out_len <= ssk::kB || out_len > 3 * ssk::kB) return SS_EINVAL;
+    if (!mel_args_ok(logmel, mel_start, mel_w, n_mels, max_len, mel_eps)) return SS_EINVAL;
+    const ssk::MelArgs m{logmel, mel_start, mel_w, n_mels, max_len, mel_eps};
+    return render(rows16_bank(rir16, rscale, rir_cap, true), false, Launch::kMelRows, spec, rir_len, unit_desc, audiogoal, spectrogram,
+                  &m, n_units, n_valid, out_len, pad_mode, flags, stateless(stream));
+}
+
 // ---- half-precision time-domain rows in length buckets: the stateless entries ------------------------------------------------
 // ss_fftconv_binaural_rir16_f32 on ss_rir16_bucket[] (k_conv<.., HALF, RBK>; bucket-0 launches: the single-allocation half kernels)
 int ss_fftconv_binaural_rir16_buckets_f32(const float* spec, const ss_rir16_bucket* buckets, int n_buckets, const int* rir_len,
@@ -1399,6 +1450,19 @@ int ss_audio_obs_rir16_buckets_f32(const float* spec, const ss_rir16_bucket* buc
     if (out_len < ssk::kNfft / 2 + 1 || out_len > ssk::kB || t4_of(out_len) > 26) return SS_EINVAL;
     return render(rir16_buckets_bank(buckets, n_buckets), false, Launch::kObs, spec, rir_len, unit_desc, audiogoal, spectrogram, nullptr,
                   n_units, n_valid, out_len, pad_mode, flags, stateless(stream));
+}
+
+// ss_audio_obs_logmel_rir16_f32 on ss_rir16_bucket[]: one-block rows in ONE launch (k_conv<.., MEL, HALF, RBK>; bucket-0 launches:
+// the single-allocation half kernels)
+int ss_audio_obs_logmel_rir16_buckets_f32(const float* spec, const ss_rir16_bucket* buckets, int n_buckets, const int* rir_len,
+                                          const int* unit_desc, float* audiogoal, float* spectrogram, float* logmel,
+                                          const int* mel_start, const float* mel_w, int n_mels, int max_len, float mel_eps, int n_units,
+                                          int n_valid, int out_len, int pad_mode, int flags, void* stream) {
+    if (n_units == 0) return 0;
+    if (!mel_args_ok(logmel, mel_start, mel_w, n_mels, max_len, mel_eps)) return SS_EINVAL;
+    const ssk::MelArgs m{logmel, mel_start, mel_w, n_mels, max_len, mel_eps};
+    return render(rir16_buckets_bank(buckets, n_buckets), false, Launch::kMelOneBlock, spec, rir_len, unit_desc, audiogoal, spectrogram,
+                  &m, n_units, n_valid, out_len, pad_mode, flags, stateless(stream));
 }
 
 // ---- pose memo: the row copies (k_memo_rows) ---------------------------------------------------------------------------
@@ -2046,6 +2110,13 @@ int ss_ctx_set_logmel_buckets_policy(ss_ctx* h, int min_units, int max_units) {
     if (!h || min_units < 0 || max_units < 0) return SS_EINVAL;
     h->c.policy.mel_bk_min = min_units;
     h->c.policy.mel_bk_max = max_units;
+    return 0;
+}
+
+int ss_ctx_set_logmel_rir16_policy(ss_ctx* h, int min_units, int max_units) {
+    if (!h || min_units < 0 || max_units < 0) return SS_EINVAL;
+    h->c.policy.mel_r16_min = min_units;
+    h->c.policy.mel_r16_max = max_units;
     return 0;
 }
 

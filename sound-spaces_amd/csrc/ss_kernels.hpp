@@ -787,7 +787,10 @@ __device__ __forceinline__ float mel_log(float v) {
 // LEAN (the rows kernels, which enter with the other round's 32 registers live and no VGPR to spare): the split's twiddle quads
 // are read behind the Z values' barrier, pair by pair, and the band's first bin and weight row (`band`; start / wj are ignored)
 // are looked up in front of the filter bank instead of travelling through the transforms.
-template <bool LEAN = false, class STORE, class BAND = void>
+// TIGHT (k_obs_blocks<.., MEL, .., ROWS16>, a wave's SECOND block: the first block's four log-mel values are live across it): the
+// filter-bank loop is unrolled by two at the most - unrolled by four its sixteen power quads and four weight quads pushed one
+// quad of registers into scratch memory.  Same steps in the same order: the same values.
+template <bool LEAN = false, bool TIGHT = false, class STORE, class BAND = void>
 __device__ __forceinline__ void stft_block_mel(c32* sc, int lane, c32 wq, const c32* tw512, c32 (&x)[16], int start,
                                                const f32x4* wj, int steps, float eps, bool want_sg, float (&mv)[4], STORE store,
                                                const BAND* band = nullptr) {      // (BAND: MelArgs, declared further down)
@@ -877,6 +880,18 @@ __device__ __forceinline__ void stft_block_mel(c32* sc, int lane, c32 wq, const 
         constexpr int fs = kPowStride / 4;               // quads between two frames' spectra
         c32 acc[4] = {mk2(0.f, 0.f), mk2(0.f, 0.f), mk2(0.f, 0.f), mk2(0.f, 0.f)};
         f32x4 a = wj[0];
+        if constexpr (TIGHT) {                            // the same steps in the same order, unrolled by two at the most
+#pragma unroll 2
+            for (int i = 0; i < steps; ++i) {
+                const f32x4 an = wj[i + 1 < steps ? i + 1 : i];      // next weight quad in flight under this step's math
+                const f32x4 b0 = pj[i], b1 = pj[fs + i], b2 = pj[2 * fs + i], b3 = pj[3 * fs + i];
+                acc[0] = acc[0] + mk2(a.x * b0.x, a.y * b0.y); acc[1] = acc[1] + mk2(a.x * b1.x, a.y * b1.y);
+                acc[2] = acc[2] + mk2(a.x * b2.x, a.y * b2.y); acc[3] = acc[3] + mk2(a.x * b3.x, a.y * b3.y);
+                acc[0] = acc[0] + mk2(a.z * b0.z, a.w * b0.w); acc[1] = acc[1] + mk2(a.z * b1.z, a.w * b1.w);
+                acc[2] = acc[2] + mk2(a.z * b2.z, a.w * b2.w); acc[3] = acc[3] + mk2(a.z * b3.z, a.w * b3.w);
+                a = an;
+            }
+        } else {
         for (int i = 0; i < steps; ++i) {
             const f32x4 an = wj[i + 1 < steps ? i + 1 : i];      // next weight quad in flight under this step's math
             const f32x4 b0 = pj[i], b1 = pj[fs + i], b2 = pj[2 * fs + i], b3 = pj[3 * fs + i];
@@ -885,6 +900,7 @@ __device__ __forceinline__ void stft_block_mel(c32* sc, int lane, c32 wq, const 
             acc[0] = acc[0] + mk2(a.z * b0.z, a.w * b0.w); acc[1] = acc[1] + mk2(a.z * b1.z, a.w * b1.w);
             acc[2] = acc[2] + mk2(a.z * b2.z, a.w * b2.w); acc[3] = acc[3] + mk2(a.z * b3.z, a.w * b3.w);
             a = an;
+        }
         }
 #pragma unroll
         for (int g = 0; g < 4; ++g) mv[g] = mel_log(acc[g].x + acc[g].y + eps);
@@ -1696,7 +1712,7 @@ __global__ __launch_bounds__(1024) void k_conv(ConvParams p, UnitTab<TAB, MEL> u
                                                RowScale<HALF, RBK> rs = RowScale<HALF, RBK>()) {
     static_assert(!(SIMPLE && XFADE), "the cross-fade needs the two-term loop kernel");
     static_assert(!RBK || (HALF && !SIMPLE), "bucketed half rows: the loop kernel (bucket-0 launches take the loop-free HALF ones)");
-    static_assert(!HALF || (!XFADE && !WIDE && !MEL), "half rows: the plain loop-free and loop kernels");
+    static_assert(!HALF || (!XFADE && !WIDE), "half rows: the plain loop-free and loop kernels, and their log-mel forms");
     static_assert(!MEL || (FUSE && !TAB), "log-mel: the fused kernels without a unit table (launched with parts_log2 = 0)");
     static_assert(!WIDE || (FUSE && !SIMPLE), "WIDE: fused loop kernel for rows of which only block 0 is rendered");
     static_assert(!TAB || SIMPLE, "the unit table serves the loop-free kernel");
@@ -2552,7 +2568,7 @@ __device__ __forceinline__ void l2_touch(const void* ptr, int bytes, int t, int*
 // consecutive lanes on consecutive frames, a part only the frames of its own pooled blocks, the last phase up to n_frames.  The
 // pooled spectrogram is optional there (p.sgram may be null).
 constexpr int kMelRowsStride = kPool * kRowsMaxBlocks;      // floats per band of the collected log-mel values of one phase
-template <bool GLOBAL_TAIL = false, bool MEL = false>
+template <bool GLOBAL_TAIL = false, bool MEL = false, bool TIGHT = false>
 __device__ __forceinline__ void rows_stft_phase(c32* lds, const ConvParams& p, int t, int unit, int ch, int j, int b0, int b1,
                                                 bool last, const c32 (&y)[8], const float* s_win, const c32* s_tw512,
                                                 const c32* s_wq, float* s_res, const float* tail_in, float* tail_out,
@@ -2622,7 +2638,7 @@ __device__ __forceinline__ void rows_stft_phase(c32* lds, const ConvParams& p, i
                                  [&](int b, float v) { s_res[b * cnt + kw] = v; }, &m);
         if (two) {
             wave_sync();
-            stft_block_mel<true>(sc, lane, wq, s_tw512, x1, 0, nullptr, m.max_len >> 2, m.eps, want_sg, mv1,
+            stft_block_mel<true, TIGHT>(sc, lane, wq, s_tw512, x1, 0, nullptr, m.max_len >> 2, m.eps, want_sg, mv1,
                                  [&](int b, float v) { s_res[b * cnt + kw + 16] = v; }, &m);
         }
         lds_barrier();                                      // every wave's scratch is dead: the buffer collects the bands
@@ -2688,7 +2704,7 @@ __global__ __launch_bounds__(1024) void k_obs_rows(ConvParams p, int n_rows, Uni
                                                    SpecScale<HALF, HALF && BUCKETS> hs = SpecScale<HALF, HALF && BUCKETS>(),
                                                    RowScale<ROWS16> rs = RowScale<ROWS16>()) {
     static_assert(!(SPECTRAL && XFADE), "cross-faded rows are rendered from the time-domain bank");
-    static_assert(!ROWS16 || (!SPECTRAL && !XFADE && !BUCKETS && !MEL && !HALF), "half rows: plain rows of one time-domain allocation");
+    static_assert(!ROWS16 || (!SPECTRAL && !XFADE && !BUCKETS && !HALF), "half rows: plain rows of one time-domain allocation");
     static_assert(!HALF || (SPECTRAL && !XFADE), "half bank: plain rows of a spectral bank (one allocation, or length buckets)");
     constexpr bool HBK = HALF && BUCKETS;
     static_assert(!MEL || !XFADE, "log-mel: plain rows (of one allocation, or of a length-bucketed fp32 bank)");
@@ -3017,7 +3033,7 @@ __global__ __launch_bounds__(1024) void k_obs_blocks(ConvParams p, int n_rows, f
                                                      SpecScale<HALF, HBK> hs = SpecScale<HALF, HBK>(),
                                                      RowScale<ROWS16> rs = RowScale<ROWS16>()) {
     static_assert(!HALF || SPECTRAL, "half bank: the spectral form");
-    static_assert(!ROWS16 || (!SPECTRAL && !MEL && !HALF && !HBK), "half rows: plain rows of one time-domain allocation");
+    static_assert(!ROWS16 || (!SPECTRAL && !HALF && !HBK), "half rows: plain rows of one time-domain allocation");
     static_assert(!HBK || HALF, "bucketed half bank: a half form");
     __shared__ c32 lds[16 * kWaveScratch > kLdsComplex ? 16 * kWaveScratch : kLdsComplex];
     __shared__ float s_win[kNfft];
@@ -3129,7 +3145,7 @@ __global__ __launch_bounds__(1024) void k_obs_blocks(ConvParams p, int n_rows, f
     const size_t hand = (size_t)row * (nb_rows - 1);      // the row's hand-off slots: [row][j] = block j -> block j + 1
     BlockSync sync{(!last && part == 0) ? flags + hand + j : nullptr, j > 0 ? flags + hand + (j - 1) : nullptr, epoch};
     if constexpr (MEL)
-        rows_stft_phase<true, true>(lds, p, t, unit, ch, j, b0, b1, last, y, s_win, s_tw512, s_wq, s_res,
+        rows_stft_phase<true, true, ROWS16>(lds, p, t, unit, ch, j, b0, b1, last, y, s_win, s_tw512, s_wq, s_res,
                                     j > 0 ? tails + (hand + (j - 1)) * kTailFloats : nullptr,
                                     (!last && part == 0) ? tails + (hand + j) * kTailFloats : nullptr, part, sync, ut);
     else

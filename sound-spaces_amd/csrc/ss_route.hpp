@@ -123,6 +123,8 @@ struct Policies {
     int mel_rows_min = 1, mel_rows_max = 0;
     int mel_ss2_min = 1, mel_ss2_max = 0;       // ss_ctx_set_logmel_ss2_policy: never, by default
     int mel_bk_min = 1, mel_bk_max = 0;         // ss_ctx_set_logmel_buckets_policy (length-bucketed banks): never, by default
+    // ss_ctx_set_logmel_rir16_policy (half-precision time-domain rows, one allocation or length buckets): never, by default
+    int mel_r16_min = 1, mel_r16_max = 0;
 };
 
 struct Wants {
@@ -148,16 +150,26 @@ inline Route route_step(const Bank& b, int out_len, int n_valid, const Policies&
     const bool bucketed = b.buckets || b.spec_buckets;
     // half-precision time-domain rows: the fused half kernels for one-block rows, every longer row the half convolution into the
     // caller's waveform buffer or the context's hand-over buffer and k_spectrogram over it (no wide kernel reads halves);
-    // log-mel steps render into the waveform scratch; no cross-fade (refused as on the spectral-only banks).
+    // no cross-fade (refused as on the spectral-only banks).
+    // Log-mel steps without a waveform buffer, inside the units range of ss_ctx_set_logmel_rir16_policy (default never; the four
+    // other log-mel policies never apply here): the log-mel form of the half kernels - one-block rows on both bindings
+    // (k_conv<.., MEL, HALF>), rows of 2 or 3 blocks only on a bank bound by ss_ctx_set_rir_bank16_rows (k_obs_blocks /
+    // k_obs_rows<.., MEL, .., ROWS16>).  Every other log-mel step renders into the waveform scratch.
     // Bound by ss_ctx_set_rir_bank16_rows (rows16_rows), rows of 2 or 3 blocks take k_obs_blocks / k_obs_rows<.., ROWS16> wherever
-    // obs_rows_ok hands the shape to them - a log-mel step's scratch counts as its waveform buffer (there is no one-launch
-    // log-mel form on half rows, whatever the log-mel policies say) - and need no hand-over buffer there.
+    // obs_rows_ok hands the shape to them - a log-mel step's scratch counts as its waveform buffer - and need no hand-over
+    // buffer there.
     // Half rows in length buckets (rows16_buckets; rir_cap = the deepest bucket's blocks * kB): exactly as rows16, and never the
     // row kernels - they do not read bucketed half rows.
     if (b.rows16 || b.rows16_buckets) {
         if (xfade) {
             r.refused = true;
             return r;
+        }
+        if (w.mel && !w.waveform && n >= pol.mel_r16_min && n <= pol.mel_r16_max) {
+            if (obs_logmel_shape_ok(out_len, flags)) r.launch = Launch::kMelOneBlock;
+            else if (b.rows16 && b.rows16_rows && obs_logmel_rows_shape_ok(out_len, n_valid, ceil_div(b.rir_cap, kB), flags))
+                r.launch = Launch::kMelRows;
+            if (r.launch != Launch::kNone) return r;
         }
         r.wave_scratch = w.mel;
         if (!w.spectrogram) {

@@ -30,7 +30,9 @@ EXPORTS = ("ss_block_len", "ss_spec_floats", "ss_version", "ss_init", "ss_source
            "ss_ctx_sims_memo_plan",
            "ss_rir_rows16_f32", "ss_bank_scatter_rows16_f32", "ss_fftconv_binaural_rir16_f32", "ss_audio_obs_rir16_f32",
            "ss_ctx_set_rir_bank16", "ss_audio_obs_rows_rir16_f32", "ss_ctx_set_rir_bank16_rows",
-           "ss_fftconv_binaural_rir16_buckets_f32", "ss_audio_obs_rir16_buckets_f32", "ss_ctx_set_rir16_buckets")
+           "ss_fftconv_binaural_rir16_buckets_f32", "ss_audio_obs_rir16_buckets_f32", "ss_ctx_set_rir16_buckets",
+           "ss_audio_obs_logmel_rir16_f32", "ss_audio_obs_logmel_rows_rir16_f32", "ss_audio_obs_logmel_rir16_buckets_f32",
+           "ss_ctx_set_logmel_rir16_policy")
 # entries that return a size_t, not a status (EXPORTS: every `int ss_*` of include/ss_hip.h)
 EXPORTS_SIZE = ("ss_ctx_wave_scratch_bytes",)
 
@@ -218,6 +220,12 @@ def load() -> ctypes.CDLL:
     lib.ss_fftconv_binaural_rir16_buckets_f32.argtypes = lib.ss_fftconv_binaural_buckets_f32.argtypes
     lib.ss_audio_obs_rir16_buckets_f32.argtypes = lib.ss_audio_obs_buckets_f32.argtypes
     lib.ss_ctx_set_rir16_buckets.argtypes = [vp, vp, c_int, vp]
+    # ... and their one-launch log-mel forms
+    lib.ss_audio_obs_logmel_rir16_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, c_int, c_int, ctypes.c_float, c_int, c_int,
+                                                  c_int, c_int, c_int, c_int, vp]
+    lib.ss_audio_obs_logmel_rows_rir16_f32.argtypes = lib.ss_audio_obs_logmel_rir16_f32.argtypes
+    lib.ss_audio_obs_logmel_rir16_buckets_f32.argtypes = lib.ss_audio_obs_logmel_buckets_f32.argtypes
+    lib.ss_ctx_set_logmel_rir16_policy.argtypes = [vp, c_int, c_int]
     # pose memo of the column path
     lib.ss_memo_rows_f32.argtypes = [vp, c_int, vp, c_int, c_int, vp]
     lib.ss_ctx_memo_enable.argtypes = [vp, c_int]

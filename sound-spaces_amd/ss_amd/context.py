@@ -162,8 +162,9 @@ class AudioContext:
     def set_rir_bank16(self, rir16, rscale, lengths, rows: bool = False) -> None:
         """A bank of HALF-PRECISION TIME-DOMAIN ROWS (``RirStore(rows="half")``: float16 rir16 [R,2,cap], float32 scales rscale
         [R,2], CUDA int32 lengths [R]; ss_ctx_set_rir_bank16).  Replaces any earlier binding; rir16 = None unbinds.  One-block rows
-        take the fused half kernels, longer ones the half convolution + the spectrogram kernel; the library refuses (SS_EINVAL)
-        cross-faded steps, and its in-call loaders report their misses instead of serving them.
+        take the fused half kernels, longer ones the half convolution + the spectrogram kernel; log-mel steps without a waveform
+        buffer take the waveform scratch unless ``set_logmel_rir16_policy`` admits them to the one-launch form; the library refuses
+        (SS_EINVAL) cross-faded steps, and its in-call loaders report their misses instead of serving them.
         ``rows=True`` (opt-in; ss_ctx_set_rir_bank16_rows): rows of 2 or 3 partition blocks (44.1 / 48 kHz) take the fused row
         kernels' half-rows forms in one launch wherever a float32 time-domain bank would; everything else as above."""
         import torch
@@ -212,8 +213,8 @@ class AudioContext:
         """HALF-PRECISION TIME-DOMAIN ROWS IN LENGTH BUCKETS (``BucketedRirBank`` whose sub-banks are ``rows_half``:
         ``BucketedRirStore(rows="half")``; include/ss_hip.h ``ss_ctx_set_rir16_buckets``).  Replaces any earlier binding; bank =
         None unbinds.  Routes as ``set_rir_bank16``: one-block rows fused, longer rows the bucketed half convolution + the
-        spectrogram kernel (never the fused row kernels), log-mel steps the waveform scratch; the library refuses (SS_EINVAL)
-        cross-faded steps and its in-call loaders report their misses.  Steps whose units all sit in bucket 0 keep the loop-free
+        spectrogram kernel (never the fused row kernels), log-mel steps the waveform scratch - or, one-block rows inside
+        ``set_logmel_rir16_policy``'s range, the one-launch log-mel form; the library refuses (SS_EINVAL) cross-faded steps and its in-call loaders report their misses.  Steps whose units all sit in bucket 0 keep the loop-free
         half kernels."""
         if bank is None:
             _lib.check(self.lib.ss_ctx_set_rir16_buckets(self._h, None, 0, None), "ss_ctx_set_rir16_buckets")
@@ -288,6 +289,20 @@ class AudioContext:
         (profiles/r7/NOTES.md)."""
         _lib.check(self.lib.ss_ctx_set_logmel_buckets_policy(self._h, int(min_units), int(max_units)),
                    "ss_ctx_set_logmel_buckets_policy")
+
+    def set_logmel_rir16_policy(self, min_units: int, max_units: int) -> None:
+        """``set_logmel_policy`` for contexts bound to half-precision time-domain rows (``set_rir_bank16``, also with
+        ``rows=True``, and ``set_rir16_buckets``): log-mel steps without a waveform buffer of ``min_units`` .. ``max_units``
+        units, without a cross-fade, take the one-launch log-mel form of the half kernels - one-block rows on all three
+        bindings, 44.1 / 48 kHz rows only with ``rows=True`` (ss_ctx_set_logmel_rir16_policy).  The four setters above never
+        apply to such a context, and rebinding a bank keeps the range.  Default (1, 0): never - the scratch route is bit-equal
+        to observe-then-features, the fused launch only to rounding.  (1, 2**31 - 1): whenever the shape allows.
+        One timing pass on an MI355X (profiles/r12/kbench_obs_logmel_rir16.txt; noise 3-4 %): at 16 kHz, one allocation and
+        buckets, the one-launch form beats the scratch route by 16-45 % at every size from 1 to 512 units - (1, 2**31 - 1); at
+        44.1 kHz by 15-34 % up to 42 units and whenever the spectrogram is asked for as well, but log-mel alone is 20 % SLOWER at
+        43 units (12 % faster again at 128) - (1, 42)."""
+        _lib.check(self.lib.ss_ctx_set_logmel_rir16_policy(self._h, int(min_units), int(max_units)),
+                   "ss_ctx_set_logmel_rir16_policy")
 
     def wave_scratch_bytes(self) -> int:
         """Bytes of waveform scratch the context holds over all overlap lanes (ss_ctx_wave_scratch_bytes): 0 until a log-mel

@@ -445,6 +445,36 @@ def audio_obs_rows_rir16_into(spec, rir16, rscale, rir_len, unit_desc, audiogoal
                    "ss_audio_obs_rows_rir16_f32")
 
 
+def _obs_logmel_rir16(entry: str, spec, rir16, rscale, rir_len, unit_desc, audiogoal, spectrogram_out, logmel_out, mel_start, mel_w,
+                      n_valid, out_len, mel_eps, pad_mode, flags) -> None:
+    _chk(spec, torch.float32, "spec"); cap = _chk_rows16(rir16, rscale); _chk(rir_len, torch.int32, "rir_len")
+    N, n_mels, max_len, ag_ptr, sg_ptr = _obs_logmel_args(unit_desc, audiogoal, spectrogram_out, logmel_out, mel_start, mel_w, out_len)
+    with torch.cuda.device(spec.device):
+        _lib.check(getattr(_lib.load(), entry)(spec.data_ptr(), rir16.data_ptr(), rscale.data_ptr(), rir_len.data_ptr(),
+                                               unit_desc.data_ptr(), ag_ptr, sg_ptr, logmel_out.data_ptr(), mel_start.data_ptr(),
+                                               mel_w.data_ptr(), int(n_mels), int(max_len), float(mel_eps), N, cap, n_valid, out_len,
+                                               _PAD[pad_mode], flags, _stream(spec)), entry)
+
+
+def audio_obs_logmel_rir16_into(spec, rir16, rscale, rir_len, unit_desc, audiogoal, spectrogram_out, logmel_out, mel_start, mel_w,
+                                n_valid: int, out_len: int, mel_eps: float = 1e-6, pad_mode="reflect", flags: int = 0) -> None:
+    """``audio_obs_logmel_into`` from a bank of half rows (``ss_audio_obs_logmel_rir16_f32``): ONE launch, whichever outputs are
+    asked for next to ``logmel_out``.  Rows of one partition block (257 <= out_len <= KB), no cross-fade; anything else is
+    refused (invalid argument)."""
+    _obs_logmel_rir16("ss_audio_obs_logmel_rir16_f32", spec, rir16, rscale, rir_len, unit_desc, audiogoal, spectrogram_out,
+                      logmel_out, mel_start, mel_w, n_valid, out_len, mel_eps, pad_mode, flags)
+
+
+def audio_obs_logmel_rows_rir16_into(spec, rir16, rscale, rir_len, unit_desc, audiogoal, spectrogram_out, logmel_out, mel_start,
+                                     mel_w, n_valid: int, out_len: int, mel_eps: float = 1e-6, pad_mode="reflect",
+                                     flags: int = 0) -> None:
+    """``audio_obs_logmel_rows_into`` from a bank of half rows (``ss_audio_obs_logmel_rows_rir16_f32``): rows of 2 or 3 partition
+    blocks (KB < out_len <= 3 KB), at most 16 RIR blocks, no cross-fade.  Small steps run the one-workgroup-per-output-block
+    kernel, whose launch must not be replayed from a captured graph."""
+    _obs_logmel_rir16("ss_audio_obs_logmel_rows_rir16_f32", spec, rir16, rscale, rir_len, unit_desc, audiogoal, spectrogram_out,
+                      logmel_out, mel_start, mel_w, n_valid, out_len, mel_eps, pad_mode, flags)
+
+
 # ---- log-mel observation in one launch (no waveform buffer) ---------------------------------------------------------
 def _obs_logmel_args(unit_desc, audiogoal, spectrogram_out, logmel_out, mel_start, mel_w, out_len):
     _chk(unit_desc, torch.int32, "unit_desc"); _chk(logmel_out, torch.float32, "logmel_out")
@@ -746,6 +776,15 @@ def _obs_logmel_buckets(entry: str, spec, buckets, n_buckets, rir_len, unit_desc
                                                unit_desc.data_ptr(), ag_ptr, sg_ptr, logmel_out.data_ptr(), mel_start.data_ptr(),
                                                mel_w.data_ptr(), int(n_mels), int(max_len), float(mel_eps), N, n_valid, out_len,
                                                _PAD[pad_mode], flags, _stream(spec)), entry)
+
+
+def audio_obs_logmel_rir16_buckets_into(spec, buckets, n_buckets: int, rir_len, unit_desc, audiogoal, spectrogram_out, logmel_out,
+                                        mel_start, mel_w, n_valid: int, out_len: int, mel_eps: float = 1e-6, pad_mode="reflect",
+                                        flags: int = 0) -> None:
+    """``audio_obs_logmel_rir16_into`` on half rows in length buckets (``ss_audio_obs_logmel_rir16_buckets_f32``; ``buckets`` =
+    ``rir16_bucket_array(...)``): rows of one partition block only."""
+    _obs_logmel_buckets("ss_audio_obs_logmel_rir16_buckets_f32", spec, buckets, n_buckets, rir_len, unit_desc, audiogoal,
+                        spectrogram_out, logmel_out, mel_start, mel_w, n_valid, out_len, mel_eps, pad_mode, flags)
 
 
 def audio_obs_logmel_buckets_into(spec, buckets, n_buckets: int, rir_len, unit_desc, audiogoal, spectrogram_out, logmel_out,
