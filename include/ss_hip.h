@@ -227,7 +227,8 @@ int ss_audio_obs_logmel_rows_spec16_f32(const float* spec, const void* hspec16, 
  * log1p spectrogram by 0.4-1.8e-4 (INTEGRATION.md "Half-precision time-domain rows") - outside the library's 1e-4 parity budget,
  * which is why the form is never a default.
  * Producers: ss_rir_rows16_f32 (a planar fp32 device bank -> its half form, entry r to entry r; k_rows_half) and
- * ss_bank_scatter_rows16_f32 (staged rows, the contract of ss_bank_scatter_rows_f32; below).  Both give the same bits for the same rows.
+ * ss_bank_scatter_rows16_f32 (staged rows, the contract of ss_bank_scatter_rows_f32; below) and its one-pass form
+ * ss_bank_scatter_rows16_max_f32 (the rows' maxima given).  All give the same bits for the same rows.
  * Consumers (k_conv<.., HALF>: only the loads in front of the first FFT pass differ, so the results equal those of the fp32
  * entries fed float(q) * rscale):
  *   ss_fftconv_binaural_rir16_f32   every shape ss_fftconv_binaural_f32 serves on a planar bank without SS_FLAG_CROSSFADE;
@@ -256,8 +257,9 @@ int ss_audio_obs_logmel_rows_spec16_f32(const float* spec, const void* hspec16, 
  *                                   graph (the note on ss_audio_obs_rows_f32).
  *                                   The results of both equal those of ss_audio_obs_logmel_f32 / _rows_f32 fed float(q) * rscale.
  * Length buckets: the section "Half-precision time-domain rows in length buckets" below (entries of their own).
- * Not served, by any entry: SS_FLAG_CROSSFADE (log-mel included), k_conv_rows, the wide form and the 512-thread core, the in-call
- * loaders, the TORCH_LIBRARY ops; no default selects the form, its row kernels or its log-mel forms.
+ * Not served, by any entry: SS_FLAG_CROSSFADE (log-mel included), k_conv_rows, the wide form and the 512-thread core, the
+ * TORCH_LIBRARY ops; no default selects the form, its row kernels or its log-mel forms.  The in-call loaders serve the two
+ * single-allocation bindings (ss_ctx_set_rir_bank16 / _rows, given ss_miss_loader.stage_max), not the length-bucketed one.
  * SS_EINVAL before a device is touched: NULL halves or scales, a base that is not 4-byte aligned, odd rir_cap or rir_cap < 2, more
  * than 16 partition blocks, SS_FLAG_CROSSFADE, out_len outside the entry's range, a bad pad_mode, a NULL required output, mel
  * arguments outside the limits of ss_audio_features_f32.
@@ -619,8 +621,13 @@ int ss_ctx_set_rir_spectra16_rows(ss_ctx* ctx, const void* hspec16, const float*
  * row (44.1 / 48 kHz) the half convolution into the caller's waveform buffer - or the context's hand-over buffer - and the
  * spectrogram kernel over it; log-mel steps render into the context's waveform scratch unless ss_ctx_set_logmel_rir16_policy
  * admits them to the one-launch form (one-block rows on this binding).  A cross-faded step is SS_EINVAL and
- * leaves no keys behind.  The in-call loaders do not serve this form: ss_ctx_load_rir_files returns 1,
- * ss_ctx_observe_requests_load reports the misses (the caller scatters with ss_bank_scatter_rows16_f32 and calls again).  The pose
+ * leaves no keys behind.  The in-call loaders (ss_ctx_load_rir_files, ss_ctx_observe_requests_load) serve this binding when the
+ * ss_miss_loader lends no rows (bank = NULL), a pinned block for the rows' maxima (stage_max != NULL) and cap == rir_cap: the files'
+ * maxima are taken by the reader, ONE launch (k_scatter_rows16_max) writes halves, scales and lengths of the new entries, and the
+ * books are kept exactly as for a bank of fp32 rows (free stack, LRU eviction, host_len, clipped, the reports, the order behind
+ * steps in flight in overlap mode).  Without stage_max, or with another cap, the answers are those of a form that is not served:
+ * ss_ctx_load_rir_files returns 1, ss_ctx_observe_requests_load reports the misses (the caller scatters with
+ * ss_bank_scatter_rows16_f32 and calls again); nothing is changed.  The pose
  * memo, the overlap mode and the column / request entries run on it unchanged.  SS_EINVAL, nothing changed: the bank refusals of
  * the stateless entries, rir_len == NULL. */
 int ss_ctx_set_rir_bank16(ss_ctx* ctx, const void* rir16, const float* rscale, const int* rir_len, int rir_cap);
@@ -892,6 +899,9 @@ typedef struct ss_miss_loader {
     int* loaded_slot;                /* ... the entry it went to, ...                                                            */
     int* loaded_frames;              /* ... frames in its file (kept = min(frames, keep))                                        */
     int n_loaded, loaded_cap;
+    float* stage_max;                /* optional, PINNED [stage_rows][2]: maxima of |v| per staged row and ear, written by the reader.
+                                      * With it (and bank = NULL, cap = the bound rir_cap) a context bound by ss_ctx_set_rir_bank16 /
+                                      * _rows is served: halves + scales through k_scatter_rows16_max.  NULL: that form is not served  */
 } ss_miss_loader;
 int ss_ctx_observe_requests_load(ss_ctx* ctx, const long long* recs, int n, ss_request_tables* tables, ss_miss_loader* loader,
                                  float* audiogoal, float* spectrogram, int* miss_out, int* n_miss, void* stream);
@@ -996,6 +1006,12 @@ int ss_ctx_sims_memo_plan(ss_ctx* ctx, const ss_sim_columns* cols, int n, int po
  * status are zero-filled.  Returns 0 / SS_EINVAL. */
 int ss_wav_read_rirs_f32(const char* const* paths, int n, float* dst, long long row_stride, int cap, int keep, int planar,
                          int* kept_out, int* frames_out, int* status_out, int n_threads);
+/* The same read in wav layout (planar = 0) with the rows' maxima: max_out [n][2] (host memory) receives, per row and ear, the
+ * maximum of |v| over the frames KEPT - taken with fmax in one pass on the reader's thread, right behind the row's read(); frames
+ * of the file behind `keep` do not count; 0, 0 for every non-zero status.  What ss_bank_scatter_rows16_max_f32 takes as row_max.
+ * Rows, kept_out, frames_out and status_out are those of ss_wav_read_rirs_f32.  Returns 0 / SS_EINVAL (also max_out == NULL). */
+int ss_wav_read_rirs_max_f32(const char* const* paths, int n, float* dst, long long row_stride, int cap, int keep,
+                             int* kept_out, int* frames_out, int* status_out, int n_threads, float* max_out);
 /* The miss path's last hop: n staged rows in wav layout - row i = frames j < lens[i] as (L, R) pairs at
  * staged[i*staged_row_stride + 2*j + c] - into the planar bank rows bank[slots[i]*unit_stride + c*chan_stride + j], zeros
  * behind each row's length up to `cap`, and lens[i] into bank_len[slots[i]] (bank_len may be NULL).  `staged`, `slots`
@@ -1027,6 +1043,15 @@ int ss_bank_scatter_spectra16_f32(const float* staged, long long staged_row_stri
  * ss_bank_scatter_rows_f32 would have written.  One launch; a row is read twice (maxima, then quantisation), never staged. */
 int ss_bank_scatter_rows16_f32(const float* staged, long long staged_row_stride, const int* slots, const int* lens, int n,
                                void* rir16, float* rscale, int cap, int* bank_len, void* stream);
+/* The same hop in ONE pass over each row, for callers that know the rows' maxima (ss_wav_read_rirs_max_f32 takes them while it
+ * reads): row_max is [n][2] fp32 in pinned host or device memory (pageable: SS_EINVAL), row_max[i][c] = the maximum of |v| over
+ * ear c of the frames j < clamp(lens[i], 0, cap), 0 for an empty row.  k_scatter_rows16_max: a row is spread over ceil(cap / 512)
+ * workgroups and every kept frame is read once, frames at or behind the length never.  Same bits as ss_bank_scatter_rows16_f32 on
+ * the same samples: halves, scales, lengths.  A row_max that is not the rows' maxima gives unspecified values in the entries
+ * named and touches nothing else.  The refusals of ss_bank_scatter_rows16_f32, and row_max == NULL or not 4-byte aligned;
+ * n == 0 returns 0 without a launch. */
+int ss_bank_scatter_rows16_max_f32(const float* staged, long long staged_row_stride, const int* slots, const int* lens,
+                                   const float* row_max, int n, void* rir16, float* rscale, int cap, int* bank_len, void* stream);
 /* n HOST arrays -> n rows of a (pinned) staging block: row i = src[i][0 .. n_floats[i]) followed by zeros up to row_floats,
  * rows row_stride floats apart, on up to n_threads plain threads.  The live RIRs of a SoundSpaces 2.0 step (one new RIR per
  * env and step from the ray tracer, soundspaces/continuous_simulator.py:419) travel to the bank this way: one block, one

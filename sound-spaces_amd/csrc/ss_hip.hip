@@ -2551,12 +2551,21 @@ int ss_ctx_observe_requests(ss_ctx* h, const long long* recs, int n, const ss_re
 // k files -> k bank entries of the lent store (ss_miss_loader): entries off the free stack, then - with the recency arrays lent -
 // the least recently used occupied ones (never one stamped with `tick`); files read into the pinned block, ONE scatter launch,
 // the new rows' block spectra when `spectral`; loaded_slot / loaded_frames / evicted_slot report.  1 = not served, nothing changed.
+// A third bank kind beside "rows" and "spectral-only": half-precision time-domain rows in ONE allocation (ss_ctx_set_rir_bank16 /
+// _rows).  Served when the loader lends no rows (bank == NULL), a pinned block for the rows' maxima (stage_max) and the bound
+// capacity; never spectral.  Same books; the one launch is k_scatter_rows16_max on the context's halves and scales.
+static bool loader_rows16(const ssctx::Context& c, const ss_miss_loader* ld) {
+    return c.rir16 && c.rscale && ld && !ld->bank && ld->stage_max && ld->cap == c.rir_cap;
+}
+
 static int loader_load_paths(ssctx::Context& c, ss_miss_loader* ld, const char* const* cp, int k, long long* last_used, long long tick,
                              int n_slots, bool spectral, hipStream_t st) {
     const int hb = (ld->cap + ssk::kB - 1) / ssk::kB;
     if (k <= 0 || k > ld->stage_rows || k > ld->loaded_cap) return 1;
     // a spectral-only bank (no rows: ld->bank == NULL) takes its block spectra straight from the staged rows (k_stage_spectra)
-    const bool spec_only = !ld->bank;
+    const bool rows16 = loader_rows16(c, ld);
+    if (rows16 && spectral) return 1;
+    const bool spec_only = !ld->bank && !rows16;
     if (spec_only && (!spectral || c.rir)) return 1;
     if (spectral && ((!spec_only && !ld->stage_desc) || c.h_blocks != hb || !c.hspec)) return 1;
     // entries: free ones first, then - if the caller lent its recency arrays - the least recently used occupied ones
@@ -2590,7 +2599,7 @@ static int loader_load_paths(ssctx::Context& c, ss_miss_loader* ld, const char* 
     }
     std::vector<int> kept(k), frames(k), status(k);
     sswav::read_many(cp, k, ld->stage, 2LL * ld->cap, ld->cap, ld->keep, false, kept.data(), frames.data(), status.data(),
-                     ld->threads > 0 ? ld->threads : 1);
+                     ld->threads > 0 ? ld->threads : 1, rows16 ? ld->stage_max : nullptr);
     for (int i = 0; i < k; ++i)
         if (status[i] != sswav::kOk && status[i] != sswav::kEmpty) return 1;     // scipy's semantics are the caller's reader's
 #if !defined(SS_AB_NO_LOADER_LANE_ORDER)                       // (A/B builds: tests/test_wav_loader.py's write-after-read case fails without)
@@ -2613,7 +2622,10 @@ static int loader_load_paths(ssctx::Context& c, ss_miss_loader* ld, const char* 
     }
     ld->n_loaded = k;
     int rc = 0;
-    if (spec_only) {                                           // staged rows -> block spectra + lengths, one launch
+    if (rows16) {                                              // staged rows + their maxima -> halves, scales, lengths: one launch
+        rc = ss_bank_scatter_rows16_max_f32(ld->stage, 2LL * ld->cap, ld->stage_slot, ld->stage_len, ld->stage_max, k,
+                                            const_cast<void*>(c.rir16), const_cast<float*>(c.rscale), ld->cap, ld->dev_len, st);
+    } else if (spec_only) {                                    // staged rows -> block spectra + lengths, one launch
         // (a half bank, ss_ctx_set_rir_spectra16, through the half staging kernel: never fp32 spectra into its buffer)
         rc = c.hscale ? ss_bank_scatter_spectra16_f32(ld->stage, 2LL * ld->cap, 0, ld->stage_slot, ld->stage_len, k,
                                                       const_cast<float*>(c.hspec), const_cast<float*>(c.hscale), hb, ld->dev_len, st)
@@ -2663,8 +2675,9 @@ static int serve_pose_misses(ss_ctx* h, const long long* recs, int n, ss_request
     ssctx::Context& c = h->c;
     const int hb = (ld && ld->cap > 0) ? (ld->cap + ssk::kB - 1) / ssk::kB : 1;
     const bool spec_only = ld && !ld->bank && !c.rir && c.hspec && spectral;       // spectral-only bank: no rows, no descriptors
+    const bool rows16 = loader_rows16(c, ld) && !spectral;                        // half-precision time-domain rows
     if (spectral && (!ld || (!spec_only && !ld->stage_desc) || c.h_blocks != hb)) return 1;
-    if (!ld || !ld->table_dirs || !ld->pair_keys || !ld->pair_slots || !ld->free_slots || (!ld->bank && !spec_only) || !ld->dev_len ||
+    if (!ld || !ld->table_dirs || !ld->pair_keys || !ld->pair_slots || !ld->free_slots || (!ld->bank && !spec_only && !rows16) || !ld->dev_len ||
         !ld->host_len || !ld->clipped || !ld->stage || !ld->stage_slot || !ld->stage_len || !ld->loaded_key || !ld->loaded_slot ||
         !ld->loaded_frames || ld->cap < 2 || (ld->cap & 1) || tb->pair_keys != ld->pair_keys || tb->pair_slots != ld->pair_slots)
         return 1;
@@ -2738,9 +2751,11 @@ int ss_ctx_load_rir_files(ss_ctx* h, ss_miss_loader* ld, const char* const* path
     ld->n_loaded = 0; ld->n_evicted = 0;
     if (k == 0) return 0;
     ssctx::Context& c = h->c;
-    if (c.rir16 || !c.rir16_buckets.empty()) return 1;         // half rows: not served here (the caller's own path scatters them)
+    if (!c.rir16_buckets.empty()) return 1;                    // half rows in length buckets: not served here
+    const bool rows16 = loader_rows16(c, ld);                  // half rows, one allocation: the one-pass scatter (see loader_load_paths)
+    if (c.rir16 && !rows16) return 1;                          // ... without stage_max / with another capacity: the caller's own path
     const bool spec_only = !ld->bank && !c.rir && c.hspec && c.buckets.empty();     // spectral-only bank (see loader_load_paths)
-    if (!ld->free_slots || (!ld->bank && !spec_only) || !ld->dev_len || !ld->host_len || !ld->clipped || !ld->stage || !ld->stage_slot ||
+    if (!ld->free_slots || (!ld->bank && !spec_only && !rows16) || !ld->dev_len || !ld->host_len || !ld->clipped || !ld->stage || !ld->stage_slot ||
         !ld->stage_len || !ld->loaded_slot || !ld->loaded_frames || ld->cap < 2 || (ld->cap & 1) || c.rir != ld->bank)
         return 1;
     // (rows of a store that keeps the spectral form get their block spectra right away: whichever form the next launch reads)
@@ -2761,7 +2776,8 @@ int ss_ctx_observe_requests_load(ss_ctx* h, const long long* recs, int n, ss_req
         bool any_dis = false;
         for (int i = 0; i < n && !any_dis; ++i) any_dis = recs[static_cast<size_t>(i) * SS_REQ_WORDS] == 0 && recs[static_cast<size_t>(i) * SS_REQ_WORDS + 6] >= 0;
         const bool spectral = c.hspec && !(c.policy.spectral_max_units > 0 && c.rir && c.out_len <= ssk::kB && n > c.policy.spectral_max_units && !any_dis);
-        if (!ld || !miss_out || c.rir != ld->bank || c.rir16 || !c.rir16_buckets.empty()) return 0;     // (half rows: the misses are reported, never served here)
+        // (half rows: served through loader_rows16's form of the struct; otherwise, and in length buckets, the misses are reported)
+        if (!ld || !miss_out || c.rir != ld->bank || (c.rir16 && !loader_rows16(c, ld)) || !c.rir16_buckets.empty()) return 0;
         std::vector<int> miss(miss_out, miss_out + (*n_miss < n ? *n_miss : n));
         rc = serve_pose_misses(h, recs, n, tb, ld, miss.data(), static_cast<int>(miss.size()), static_cast<hipStream_t>(stream), spectral);
         if (rc == 1) return 0;                                 // reported as ss_ctx_observe_requests reports it
@@ -2991,6 +3007,16 @@ extern "C" int ss_wav_read_rirs_f32(const char* const* paths, int n, float* dst,
     return 0;
 }
 
+// ... with the maxima of |v| over each row's kept frames, per ear, taken on the reader's thread (wav layout only)
+extern "C" int ss_wav_read_rirs_max_f32(const char* const* paths, int n, float* dst, long long row_stride, int cap, int keep,
+                                        int* kept_out, int* frames_out, int* status_out, int n_threads, float* max_out) {
+    if (n == 0) return 0;
+    if (!paths || !dst || !kept_out || !frames_out || !status_out || !max_out || n < 0 || cap < 1 || row_stride < 2LL * cap)
+        return SS_EINVAL;
+    sswav::read_many(paths, n, dst, row_stride, cap, keep, false, kept_out, frames_out, status_out, n_threads, max_out);
+    return 0;
+}
+
 // Staged rows (wav layout, pinned host or device memory) -> planar bank rows + their lengths, one launch (k_scatter_rows)
 extern "C" int ss_bank_scatter_rows_f32(const float* staged, long long staged_row_stride, const int* slots, const int* lens,
                                         int n, float* bank, long long unit_stride, int chan_stride, int cap, int* bank_len,
@@ -3150,5 +3176,28 @@ extern "C" int ss_bank_scatter_rows16_f32(const float* staged, long long staged_
     p.staged = staged; p.slots = slots; p.lens = lens; p.rir16 = static_cast<ssk::h16x2*>(rir16); p.rscale = rscale;
     p.bank_len = bank_len; p.staged_stride = staged_row_stride; p.cap = cap;
     hipLaunchKernelGGL(ssk::k_scatter_rows16, dim3(n), dim3(256), 0, static_cast<hipStream_t>(stream), p);
+    return hip_err(hipGetLastError());
+}
+
+// The same hop in one pass over each row, the rows' maxima given (k_scatter_rows16_max; ss_wav_read_rirs_max_f32 supplies them)
+extern "C" int ss_bank_scatter_rows16_max_f32(const float* staged, long long staged_row_stride, const int* slots, const int* lens,
+                                              const float* row_max, int n, void* rir16, float* rscale, int cap, int* bank_len,
+                                              void* stream) {
+    if (n == 0) return 0;
+    if (!staged || !slots || !lens || !row_max || n < 0 || !rows16_bank_ok(rir16, rscale, cap) || staged_row_stride < 2LL * cap)
+        return SS_EINVAL;
+    if ((reinterpret_cast<size_t>(staged) & 7) || (staged_row_stride & 1) || (reinterpret_cast<size_t>(row_max) & 3)) return SS_EINVAL;
+    for (const void* ptr : {static_cast<const void*>(staged), static_cast<const void*>(slots), static_cast<const void*>(lens),
+                            static_cast<const void*>(row_max)})
+        if (!device_accessible(ptr)) return SS_EINVAL;
+    ssk::ScatterRows16MaxParams p;
+    p.staged = staged; p.slots = slots; p.lens = lens; p.row_max = row_max; p.rir16 = static_cast<ssk::h16x2*>(rir16); p.rscale = rscale;
+    p.bank_len = bank_len; p.staged_stride = staged_row_stride; p.cap = cap;
+    for (int lo = 0; lo < n; lo += 65535) {                    // (grid.y limit)
+        const int m = n - lo < 65535 ? n - lo : 65535;
+        ssk::ScatterRows16MaxParams q = p;
+        q.staged += static_cast<size_t>(lo) * staged_row_stride; q.slots += lo; q.lens += lo; q.row_max += 2 * static_cast<size_t>(lo);
+        hipLaunchKernelGGL(ssk::k_scatter_rows16_max, dim3((cap + 511) / 512, m), dim3(256), 0, static_cast<hipStream_t>(stream), q);
+    }
     return hip_err(hipGetLastError());
 }

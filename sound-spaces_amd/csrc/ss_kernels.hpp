@@ -3351,6 +3351,54 @@ __global__ __launch_bounds__(256) void k_scatter_rows16(ScatterRows16Params p) {
     }
 }
 
+// k_scatter_rows16_max: the same hop in ONE pass over the row, for callers that already know the two maxima (the file reader
+// takes them on its own thread while the row is still in the host's cache: ss_wavio.hpp).  row_max[i][c] = max |v| over ear c of
+// the frames j < clamp(lens[i], 0, cap), taken with fmaxf, 0 for an empty row; pinned host or device memory like the other staged
+// arrays.  Grid (chunks of 512 frames, n) as k_scatter_rows, 256 threads: thread t of chunk x owns the half pair m = 256 x + t =
+// frames 2m and 2m + 1 of both ears - one 16-byte load (two 8-byte loads when the base or the stride does not allow it), one
+// 8-byte load when only frame 2m lies inside the length, none behind it; one 4-byte store per ear.  Exponent and quantisation are
+// k_scatter_rows16's own functions, so the two kernels agree bit for bit on the same samples.  A wrong row_max gives unspecified
+// values in the row's own entry and touches nothing else.  No LDS, no communication between workgroups.
+struct ScatterRows16MaxParams {
+    const float* staged;       // [n][staged_stride] floats, row i = frames j < lens[i] as (L, R) pairs; 8-byte aligned, stride even
+    const int* slots;
+    const int* lens;
+    const float* row_max;      // [n][2]
+    h16x2* rir16;              // [entries][2][cap / 2]
+    float* rscale;             // [entries][2]
+    int* bank_len;             // may be nullptr
+    long long staged_stride;
+    int cap;                   // even
+};
+__global__ __launch_bounds__(256) void k_scatter_rows16_max(ScatterRows16MaxParams p) {
+    const int t = threadIdx.x, i = blockIdx.y;
+    const size_t slot = (size_t)p.slots[i];
+    const int len = min(max(p.lens[i], 0), p.cap);
+    const float ml = p.row_max[2 * i], mr = p.row_max[2 * i + 1];
+    const int el = row16_exponent(ml), er = row16_exponent(mr);
+    if (blockIdx.x == 0 && t == 0) {
+        p.rscale[slot * 2] = ldexpf(1.0f, el - 15); p.rscale[slot * 2 + 1] = ldexpf(1.0f, er - 15);
+        if (p.bank_len) p.bank_len[slot] = len;
+    }
+    const int m = blockIdx.x * 256 + t;
+    if (m >= (p.cap >> 1)) return;
+    const float* src = p.staged + (size_t)i * p.staged_stride + 4 * (size_t)m;     // frames 2m, 2m + 1 = (L, R, L, R)
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (2 * m + 1 < len) {
+        if (((p.staged_stride & 3) | (reinterpret_cast<size_t>(p.staged) & 15)) == 0) v = *reinterpret_cast<const f32x4*>(src);
+        else {
+            const c32 f0 = *reinterpret_cast<const c32*>(src), f1 = *reinterpret_cast<const c32*>(src + 2);
+            v.x = f0.x; v.y = f0.y; v.z = f1.x; v.w = f1.y;
+        }
+    } else if (2 * m < len) {
+        const c32 f0 = *reinterpret_cast<const c32*>(src);
+        v.x = f0.x; v.y = f0.y;
+    }
+    h16x2* ol = p.rir16 + slot * 2 * (size_t)(p.cap >> 1);
+    ol[m] = row16_quantise(v.x, v.z, ml, el);
+    ol[(p.cap >> 1) + m] = row16_quantise(v.y, v.w, mr, er);
+}
+
 // ---------------------------------------------------------------------------------------------
 // k_memo_rows: the row copies of the pose memo (ss_memo.hpp; reference: the per-pose caches of soundspaces/simulator.py:678-701).
 // One launch moves observation rows between a step's output arrays and device-side pools, for up to kMemoArrays (output, pool)

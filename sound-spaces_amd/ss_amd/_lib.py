@@ -32,7 +32,8 @@ EXPORTS = ("ss_block_len", "ss_spec_floats", "ss_version", "ss_init", "ss_source
            "ss_ctx_set_rir_bank16", "ss_audio_obs_rows_rir16_f32", "ss_ctx_set_rir_bank16_rows",
            "ss_fftconv_binaural_rir16_buckets_f32", "ss_audio_obs_rir16_buckets_f32", "ss_ctx_set_rir16_buckets",
            "ss_audio_obs_logmel_rir16_f32", "ss_audio_obs_logmel_rows_rir16_f32", "ss_audio_obs_logmel_rir16_buckets_f32",
-           "ss_ctx_set_logmel_rir16_policy")
+           "ss_ctx_set_logmel_rir16_policy",
+           "ss_bank_scatter_rows16_max_f32", "ss_wav_read_rirs_max_f32")
 # entries that return a size_t, not a status (EXPORTS: every `int ss_*` of include/ss_hip.h)
 EXPORTS_SIZE = ("ss_ctx_wave_scratch_bytes",)
 
@@ -68,7 +69,7 @@ class SsMissLoader(ctypes.Structure):
                 ("used", ctypes.c_void_p), ("use_seq", ctypes.c_void_p), ("evicted_slot", ctypes.c_void_p),
                 ("n_evicted", ctypes.c_int), ("evict_cap", ctypes.c_int),
                 ("loaded_key", ctypes.c_void_p), ("loaded_slot", ctypes.c_void_p), ("loaded_frames", ctypes.c_void_p),
-                ("n_loaded", ctypes.c_int), ("loaded_cap", ctypes.c_int)]
+                ("n_loaded", ctypes.c_int), ("loaded_cap", ctypes.c_int), ("stage_max", ctypes.c_void_p)]
 
 
 class SsMemoIo(ctypes.Structure):
@@ -226,6 +227,9 @@ def load() -> ctypes.CDLL:
     lib.ss_audio_obs_logmel_rows_rir16_f32.argtypes = lib.ss_audio_obs_logmel_rir16_f32.argtypes
     lib.ss_audio_obs_logmel_rir16_buckets_f32.argtypes = lib.ss_audio_obs_logmel_buckets_f32.argtypes
     lib.ss_ctx_set_logmel_rir16_policy.argtypes = [vp, c_int, c_int]
+    # ... their one-pass scatter (the rows' maxima given) and the reader that takes the maxima
+    lib.ss_bank_scatter_rows16_max_f32.argtypes = [vp, c_ll, vp, vp, vp, c_int, vp, vp, c_int, vp, vp]
+    lib.ss_wav_read_rirs_max_f32.argtypes = [vp, c_int, vp, c_ll, c_int, c_int, vp, vp, vp, c_int, vp]
     # pose memo of the column path
     lib.ss_memo_rows_f32.argtypes = [vp, c_int, vp, c_int, c_int, vp]
     lib.ss_ctx_memo_enable.argtypes = [vp, c_int]

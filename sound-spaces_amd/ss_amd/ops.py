@@ -392,6 +392,29 @@ def scatter_rows16_into(staged: torch.Tensor, slots: torch.Tensor, lens: torch.T
                                                           _stream(rir16)), "ss_bank_scatter_rows16_f32")
 
 
+def scatter_rows16_max_into(staged: torch.Tensor, slots: torch.Tensor, lens: torch.Tensor, row_max: torch.Tensor, n: int,
+                            rir16: torch.Tensor, rscale: torch.Tensor, bank_len: torch.Tensor) -> None:
+    """``scatter_rows16_into`` in one pass over each row, the rows' maxima given (``ss_bank_scatter_rows16_max_f32``,
+    k_scatter_rows16_max): row_max float32 [*, 2], pinned host or device memory, row_max[i, c] = max |v| over ear c of the frames
+    of row i in front of its (clamped) length, 0 for an empty row - what ``ss_wav_read_rirs_max_f32`` reports.  Same bits as
+    ``scatter_rows16_into`` on the same samples."""
+    cap = _chk_rows16(rir16, rscale); _chk(bank_len, torch.int32, "bank_len")
+    for t, dt, name in ((staged, torch.float32, "staged"), (slots, torch.int32, "slots"), (lens, torch.int32, "lens"),
+                        (row_max, torch.float32, "row_max")):
+        if not (t.is_cuda or t.is_pinned()):
+            raise ValueError(f"{name}: pinned host or device memory expected (the kernel reads it in place)")
+        if t.dtype != dt or not t.is_contiguous():
+            raise ValueError(f"{name}: expected contiguous {dt}, got {t.dtype} contiguous={t.is_contiguous()}")
+    assert staged.dim() == 3 and staged.shape[2] == 2 and staged.shape[1] >= cap and staged.shape[0] >= n
+    assert row_max.dim() == 2 and row_max.shape[1] == 2 and row_max.shape[0] >= n
+    if n == 0:
+        return
+    with torch.cuda.device(rir16.device):
+        _lib.check(_lib.load().ss_bank_scatter_rows16_max_f32(staged.data_ptr(), staged[0].numel(), slots.data_ptr(), lens.data_ptr(),
+                                                              row_max.data_ptr(), n, rir16.data_ptr(), rscale.data_ptr(), cap,
+                                                              bank_len.data_ptr(), _stream(rir16)), "ss_bank_scatter_rows16_max_f32")
+
+
 def fftconv_binaural_rir16_into(spec, rir16, rscale, rir_len, unit_desc, out, n_valid: int, flags: int = 0) -> None:
     """``fftconv_binaural_into`` from a bank of half rows (``ss_fftconv_binaural_rir16_f32``); no cross-fade."""
     _chk(spec, torch.float32, "spec"); cap = _chk_rows16(rir16, rscale); _chk(rir_len, torch.int32, "rir_len")

@@ -1103,9 +1103,13 @@ class RirStore:
                     d["stage_desc"] = torch.zeros((L.stage_rows * 2 * P.ceil_div(self.cap, P.KB) * 5,), dtype=torch.int32,
                                                   pin_memory=True)
                     L.stage_desc = d["stage_desc"].data_ptr() if self.spectral else None
+                if self.rows_half:                               # (half rows: the reader's maxima per staged row and ear - with them
+                    d["stage_max"] = torch.zeros((L.stage_rows, 2), dtype=torch.float32, pin_memory=True)     # the library serves the form)
+                    L.stage_max = d["stage_max"].data_ptr()
+                else:
+                    d["stage_max"], L.stage_max = None, None
             d["bank"], d["cap"] = bank.data, self.cap
-            if self._staged_only:                                # ss_miss_loader.bank = NULL: the context's spectra are written
-                # (half rows: the library's loaders do not serve them - they answer "not served" and load_files does the work)
+            if self._staged_only:                                # ss_miss_loader.bank = NULL: the context's spectra / halves are written
                 L.bank, L.bank_unit_stride, L.bank_chan_stride, L.cap = None, 0, 0, self.cap
             else:
                 L.bank, L.bank_unit_stride, L.bank_chan_stride, L.cap = (bank.data.data_ptr(), bank.data.stride(0),
