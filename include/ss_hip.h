@@ -62,10 +62,37 @@ int ss_version(void);
 /* Build (idempotent) the constant tables for the current HIP device. */
 int ss_init(void);
 /* Rows longer than kB (44.1 kHz) make the library keep a scratch per (device, stream) for the block spectra of the rows in
- * flight (96 MiB per stream at 44.1 kHz without distractors), allocated by the stream's first such call (not inside a
- * hipGraph capture: warm the stream up first).  This frees all of them (after a device synchronise), and the contexts'
- * waveform scratches of ss_ctx_observe_features (which grow again on demand). */
+ * flight (96 MiB per stream at 44.1 kHz without distractors), allocated by the stream's first such call (inside a
+ * hipGraph capture that call is refused with SS_EINVAL: see "Captured steps" below).  This frees all of them (after a device
+ * synchronise), and the contexts' waveform scratches of ss_ctx_observe_features (which grow again on demand).  A graph
+ * captured before this call holds pointers to what it freed: capture again. */
 int ss_release_scratch(void);
+
+/* ---- Captured steps (hipGraph / torch.cuda.graph) ------------------------------------------------------------------------
+ * The stateless entries (everything that is not ss_ctx_*) may be captured into a graph and replayed, on every route, on a
+ * stream that was RESERVED (ss_stream_reserve) or WARMED UP (one eager call of the same shape on that stream).  What a first
+ * call allocates cannot be allocated inside a capture: the scratch and the hand-off area of rows longer than kB - a call that
+ * would have to allocate or grow one while its stream is being captured is refused with SS_EINVAL, nothing is allocated,
+ * nothing is enqueued - and the device's constant tables (ss_init, ss_stream_reserve or any earlier call has built them: the
+ * library does not check this one).  The scratches belong to the (device, stream) pair, so capture on the stream that was prepared, and as ONE linear
+ * chain on that ONE stream: a graph whose branches could run two of these launches at once would share one scratch between
+ * them.  Replays and eager calls may alternate on the stream.
+ * Small steps of rows longer than kB (k_obs_blocks, see ss_audio_obs_f32) hand samples between workgroups through flags that
+ * carry the launch's epoch.  An eager launch gets a positive epoch from a host counter as a kernel argument; a captured launch
+ * is enqueued as TWO kernels, k_sync_next and k_obs_blocks: the first moves a word of the hand-off area on to the next replay
+ * epoch (-1, -2, ...), the second reads its epoch from that word - so every replay has an epoch of its own, and the two kinds
+ * never meet.
+ * The context entries (ss_ctx_*) are NOT part of this: their descriptor ring waits on events on the host.
+ *
+ * ss_stream_reserve allocates what the rows entries (ss_audio_obs_f32 and its siblings on rows of out_len samples, kB <
+ * out_len <= 3 kB) would allocate on their first use on `stream` for banks of up to rir_cap samples per row and n_terms terms
+ * per unit (1: every launch carries SS_FLAG_NO_DISTRACTOR; 2 otherwise): the hand-off area and the scratch at its largest
+ * size for that shape, and the constant tables.  SS_EINVAL, before a device is touched: hipStreamPerThread, out_len outside
+ * (kB, 3 kB], rir_cap < 1, n_terms outside {1, 2}.  SS_EINVAL on a stream that is being captured. */
+int ss_stream_reserve(void* stream, int out_len, int rir_cap, int n_terms);
+/* Synchronises the stream and returns the replay epoch word of its hand-off area: 0 = no replay yet, -k after the k-th replay
+ * of a captured k_obs_blocks launch.  SS_EINVAL when the stream has no hand-off area.  For tests and diagnostics. */
+int ss_stream_replay_epoch(void* stream, int* out);
 
 /* Source-window spectra.  win_desc[w] = {src_offset, src_len, start, wrap} (int32 x4):
  * window w holds samples src[src_offset + start + n], n in [0, 2*kB), zero outside [0, src_len)
@@ -109,8 +136,8 @@ int ss_spectrogram_f32(const float* x, float* out, int n_units, int len, int pad
  * the rows in flight (<= 2 x ceil(rir_cap/kB) x 128 KiB per CU), allocated on the stream's first such call.
  * Small steps of such rows (rows x output blocks <= the launch's share of the CUs: <= 42 units at 44.1 kHz) are rendered by one
  * workgroup per OUTPUT BLOCK (k_obs_blocks): the samples in front of a block boundary are handed to the next block's workgroup
- * through a per-(device, stream) area of 1.3 MB whose flags carry a launch counter - such a launch must not be replayed from a
- * captured hipGraph (the counter would repeat; the library itself never captures).
+ * through a per-(device, stream) area of 1.3 MB whose flags carry the launch's epoch - a host counter for an eager launch, a
+ * word of the area for a launch captured into a hipGraph, so that such a launch may be replayed ("Captured steps" above).
  * out_len >= 257 (SS_EINVAL below, here and in the *_spec_ / *_buckets_ / 32 forms): the fused kernels reflect the centre
  * padding once.  Shorter rows: ss_fftconv_binaural_f32, then ss_spectrogram_f32 (any length). */
 int ss_audio_obs_f32(const float* spec, const float* rir, const int* rir_len, const int* unit_desc,
@@ -242,8 +269,8 @@ int ss_audio_obs_logmel_rows_spec16_f32(const float* spec, const void* hspec16, 
  *                                   passes and the STFT phases are the fp32 time-domain form's.  `audiogoal` may be NULL.  Given a
  *                                   waveform buffer and n_valid <= kB (one rendered block) the step takes the half convolution +
  *                                   k_spectrogram, as the fp32 entry does (obs_rows_ok); that shape needs `audiogoal`.  Small steps
- *                                   run k_obs_blocks, whose hand-off flags carry a launch counter: do not replay this entry from
- *                                   a captured graph (the note on ss_audio_obs_rows_f32).
+ *                                   run k_obs_blocks; captured into a graph on a reserved or warmed-up stream they may be
+ *                                   replayed ("Captured steps").
  *   ss_audio_obs_logmel_rir16_f32   ss_audio_obs_logmel_f32 from half rows (k_conv<.., MEL, HALF>: loop-free when
  *                                   SS_FLAG_NO_DISTRACTOR and rir_cap <= kB, else the loop kernel): 257 <= out_len <= kB, the mel
  *                                   arguments and their limits as there; `audiogoal` and `spectrogram` may each be NULL, any
@@ -253,8 +280,7 @@ int ss_audio_obs_logmel_rows_spec16_f32(const float* spec, const void* hspec16, 
  *   ss_audio_obs_logmel_rows_rir16_f32  the same for rows of 2 or 3 partition blocks (kB < out_len <= 3 kB, at most 16 RIR
  *                                   blocks): k_obs_blocks / k_obs_rows<.., MEL, .., ROWS16>, chosen by the rule of
  *                                   ss_audio_obs_rows_rir16_f32 (same stash, same hand-off area); a waveform buffer is written as
- *                                   that entry writes it.  A launch that takes k_obs_blocks must not be replayed from a captured
- *                                   graph (the note on ss_audio_obs_rows_f32).
+ *                                   that entry writes it.  Capture and replay: as that entry ("Captured steps").
  *                                   The results of both equal those of ss_audio_obs_logmel_f32 / _rows_f32 fed float(q) * rscale.
  * Length buckets: the section "Half-precision time-domain rows in length buckets" below (entries of their own).
  * Not served, by any entry: SS_FLAG_CROSSFADE (log-mel included), k_conv_rows, the wide form and the 512-thread core, the
@@ -294,8 +320,8 @@ int ss_audio_obs_logmel_rows_rir16_f32(const float* spec, const void* rir16, con
  * (rir_cap <= 16 kB / 1 <= h_blocks <= 16), no SS_FLAG_CROSSFADE, mel arguments under the limits above.  Everything else is
  * SS_EINVAL from the argument checks, before a device is touched.  The choice between the two kernels, the per-stream stash and
  * hand-off area are those of ss_audio_obs_f32 on such rows; like there, a launch that takes the one-workgroup-per-output-block
- * kernel (small steps: the whole grid fits the chip) must NOT be replayed from a captured graph - its hand-off flags carry the
- * launch's epoch. */
+ * kernel (small steps: the whole grid fits the chip) may be captured on a reserved or warmed-up stream and replayed - its
+ * hand-off flags then carry the replay's epoch ("Captured steps"). */
 int ss_audio_obs_logmel_rows_f32(const float* spec, const float* rir, const int* rir_len, const int* unit_desc,
                                  float* audiogoal, float* spectrogram, float* logmel, const int* mel_start,
                                  const float* mel_w, int n_mels, int max_len, float mel_eps, int n_units,
@@ -429,8 +455,8 @@ int ss_audio_obs_logmel_spec_buckets_f32(const float* spec, const ss_spec_bucket
  * Launches with one bucket or SS_FLAG_FIRST_BUCKET are single-allocation launches on bucket 0: bit for bit what the siblings
  * give on its arrays.  Values: those of the fp32 spectral buckets fed float(q) * hscale, to the rounding of the products' order.
  * SS_EINVAL before a device is touched: fp32 or mixed buckets, every refusal of ss_spec_bucket, SS_FLAG_CROSSFADE, out_len <= kB
- * or > 3 kB, n_valid outside [0, out_len], a bad pad_mode, a NULL required output.  n_units == 0 returns 0.  A k_obs_blocks
- * launch must not be replayed from a captured graph (see ss_audio_obs_rows_spec16_f32). */
+ * or > 3 kB, n_valid outside [0, out_len], a bad pad_mode, a NULL required output.  n_units == 0 returns 0.  Capture and
+ * replay: "Captured steps" (see ss_audio_obs_rows_spec16_f32). */
 int ss_audio_obs_rows_spec16_buckets_f32(const float* spec, const ss_spec_bucket* buckets, int n_buckets, const int* rir_len,
                                          const int* unit_desc, float* audiogoal, float* spectrogram, int n_units, int n_valid,
                                          int out_len, int pad_mode, int flags, void* stream);

@@ -271,6 +271,16 @@ void fill_rir16_buckets(ssk::ConvParams& p, ssk::RowScale<true, true>& rs, const
 struct StashBuf { float* ptr = nullptr; size_t bytes = 0; };
 std::map<std::pair<int, hipStream_t>, StashBuf> g_stash;
 
+// is `st` being captured into a graph?  (a stream that cannot be asked counts as refused: SS_EINVAL)
+int stream_capturing(hipStream_t st, bool* capturing) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cap) != hipSuccess) { (void)hipGetLastError(); return SS_EINVAL; }
+    *capturing = cap != hipStreamCaptureStatusNone;
+    return 0;
+}
+
+// A growth needed while the stream is being captured is refused (an allocation cannot be part of a capture: ss_stream_reserve,
+// or one eager call of the shape, prepares the stream) - sslaunch::scratch_decision, as get_wave_scratch.
 int get_stash(hipStream_t st, size_t bytes, float** out) {
     // one handle for a different stream on every thread: two concurrent launches would share one stash
     if (st == hipStreamPerThread) return SS_EINVAL;
@@ -278,7 +288,15 @@ int get_stash(hipStream_t st, size_t bytes, float** out) {
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return hip_err(e);
     std::lock_guard<std::mutex> lk(g_mu);
-    StashBuf& b = g_stash[std::make_pair(dev, st)];
+    const auto key = std::make_pair(dev, st);
+    const auto found = g_stash.find(key);
+    if ((found == g_stash.end() ? 0 : found->second.bytes) < bytes) {      // (asked only where the answer matters)
+        bool capturing = false;
+        if (stream_capturing(st, &capturing)) return SS_EINVAL;
+        if (sslaunch::scratch_decision(capturing, found == g_stash.end() ? 0 : found->second.bytes, bytes) == sslaunch::Scratch::kRefuse)
+            return SS_EINVAL;
+    }
+    StashBuf& b = g_stash[key];
     if (b.bytes < bytes) {
         if (b.ptr) {
             e = hipStreamSynchronize(st);                       // earlier launches of this stream still use the old one
@@ -295,32 +313,55 @@ int get_stash(hipStream_t st, size_t bytes, float** out) {
 }
 
 // k_obs_blocks' hand-off area per (device, stream): [sslaunch::kSyncRows][2] tails of kTailFloats floats + as many flag words, zeroed once;
-// `epoch` counts the launches that used it (a flag holds the epoch of the launch that set it: nothing is reset in between -
-// which is also why such a launch cannot be replayed from a captured graph: the library never captures)
-struct SyncBuf { float* tails = nullptr; int* flags = nullptr; int epoch = 0; };
+// + the replay epoch word behind the flags (sslaunch::handoff_bytes).  `epoch` counts the EAGER launches that used the area (a
+// flag holds the epoch of the launch that set it: nothing is reset in between) and travels as a kernel argument.  A launch that
+// is being captured into a graph cannot do that - every replay would repeat the argument - so it leaves the host counter alone
+// and reads its epoch from the word, which k_sync_next, captured in front of it, moves on at every replay (*epoch_word != null:
+// the caller enqueues that pair; the two kinds of epoch never meet, see k_sync_next).  The area cannot be allocated inside a
+// capture: without one such a launch is refused (ss_stream_reserve, or one eager call, prepares the stream).
+struct SyncBuf { float* tails = nullptr; int* flags = nullptr; int* word = nullptr; int epoch = 0; };
 std::map<std::pair<int, hipStream_t>, SyncBuf> g_sync;
 
-int get_block_sync(hipStream_t st, float** tails, int** flags, int* epoch) {
-    if (st == hipStreamPerThread) return SS_EINVAL;
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return hip_err(e);
-    std::lock_guard<std::mutex> lk(g_mu);
+// the hand-off area of (dev, st), allocated and zeroed (stream-ordered) where absent; g_mu held; the stream is not capturing
+int make_block_sync(int dev, hipStream_t st, SyncBuf** out) {
     SyncBuf& b = g_sync[std::make_pair(dev, st)];
     if (!b.tails) {
         const size_t n_hand = sslaunch::handoff_flags(sslaunch::kSyncRows);
-        const size_t bytes = n_hand * ssk::kTailFloats * sizeof(float) + n_hand * sizeof(int);
+        const size_t bytes = sslaunch::handoff_bytes(sslaunch::kSyncRows);
         void* ptr = nullptr;
-        e = hipMalloc(&ptr, bytes);
+        hipError_t e = hipMalloc(&ptr, bytes);
         if (e != hipSuccess) return hip_err(e);
         e = hipMemsetAsync(ptr, 0, bytes, st);                  // (stream-ordered in front of the first launch that reads it)
         if (e != hipSuccess) { (void)hipFree(ptr); return hip_err(e); }
         b.tails = static_cast<float*>(ptr);
         b.flags = reinterpret_cast<int*>(b.tails + n_hand * ssk::kTailFloats);
+        b.word = b.flags + n_hand;
         b.epoch = 0;
     }
-    b.epoch = b.epoch == 0x7fffffff ? 1 : b.epoch + 1;
-    *tails = b.tails; *flags = b.flags; *epoch = b.epoch;
+    *out = &b;
+    return 0;
+}
+
+int get_block_sync(hipStream_t st, float** tails, int** flags, int* epoch, int** epoch_word) {
+    if (st == hipStreamPerThread) return SS_EINVAL;
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return hip_err(e);
+    bool capturing = false;
+    if (stream_capturing(st, &capturing)) return SS_EINVAL;
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (capturing) {
+        const auto it = g_sync.find(std::make_pair(dev, st));
+        const size_t have = it != g_sync.end() && it->second.tails ? sslaunch::handoff_bytes(sslaunch::kSyncRows) : 0;
+        if (sslaunch::scratch_decision(true, have, sslaunch::handoff_bytes(sslaunch::kSyncRows)) != sslaunch::Scratch::kUse) return SS_EINVAL;
+        *tails = it->second.tails; *flags = it->second.flags; *epoch = 0; *epoch_word = it->second.word;
+        return 0;
+    }
+    SyncBuf* b = nullptr;
+    const int rc = make_block_sync(dev, st, &b);
+    if (rc) return rc;
+    b->epoch = b->epoch == 0x7fffffff ? 1 : b->epoch + 1;
+    *tails = b->tails; *flags = b->flags; *epoch = b->epoch; *epoch_word = nullptr;
     return 0;
 }
 
@@ -370,16 +411,20 @@ int launch_obs_rows(ssk::ConvParams p, int n_units, int flags, int n_cus, const 
         float* tails = nullptr;
         int* fl = nullptr;
         int epoch = 0;
-        const int rc = get_block_sync(st, &tails, &fl, &epoch);
+        int* word = nullptr;                                    // a capturing stream: the epoch comes from the area's word
+        const int rc = get_block_sync(st, &tails, &fl, &epoch, &word);
         if (rc) return rc;
         sslaunch::apply(pb, p);
         const dim3 grid(pb.grid);
-        if constexpr (ROWS16)
-            hipLaunchKernelGGL((ssk::k_obs_blocks<false, MEL, false, false, true>), grid, block, 0, st, p, n_rows, tails, fl, epoch, mel, hs, rs);
-        else if constexpr (HBK) hipLaunchKernelGGL((ssk::k_obs_blocks<SPECTRAL, MEL, true, true>), grid, block, 0, st, p, n_rows, tails, fl, epoch, mel, hs);
-        else if constexpr (HALF) hipLaunchKernelGGL((ssk::k_obs_blocks<SPECTRAL, MEL, true>), grid, block, 0, st, p, n_rows, tails, fl, epoch, mel, hs);
-        else if constexpr (MEL) hipLaunchKernelGGL((ssk::k_obs_blocks<SPECTRAL, true>), grid, block, 0, st, p, n_rows, tails, fl, epoch, mel);
-        else hipLaunchKernelGGL((ssk::k_obs_blocks<SPECTRAL>), grid, block, 0, st, p, n_rows, tails, fl, epoch);
+        if (word) {                                             // ... which k_sync_next moves on first, at every replay
+            hipLaunchKernelGGL(ssk::k_sync_next, dim3(1), dim3(64), 0, st, word);
+            const int rc2 = hip_err(hipGetLastError());
+            if (rc2) return rc2;
+        }
+        const int* epoch_word = word;
+        // (the instantiations the forms had before: the defaulted arguments written out)
+        hipLaunchKernelGGL((ssk::k_obs_blocks<SPECTRAL, MEL, HALF, HBK, ROWS16>), grid, block, 0, st, p, n_rows, tails, fl, epoch, mel, hs, rs,
+                           epoch_word);
         return hip_err(hipGetLastError());
     }
     sslaunch::apply(pr, p);
@@ -912,6 +957,56 @@ int ss_release_scratch(void) {
     for (auto it = g_wave_scratch.begin(); it != g_wave_scratch.end();) it = it->second.ptr ? std::next(it) : g_wave_scratch.erase(it);
     (void)hipSetDevice(cur);
     return rc;
+}
+
+// What the rows entries would allocate on their first use for this shape on this stream, now: the device's constant tables,
+// k_obs_blocks' hand-off area and k_obs_rows' stash at the largest size a launch of (rir_cap, n_terms) can ask for (one
+// workgroup per CU).  Afterwards such launches may be captured on the stream without a warm-up call.
+int ss_stream_reserve(void* stream, int out_len, int rir_cap, int n_terms) {
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!sslaunch::reserve_args_ok(st != hipStreamPerThread, out_len, rir_cap, n_terms)) return SS_EINVAL;
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return hip_err(e);
+    bool capturing = false;
+    if (stream_capturing(st, &capturing) || capturing) return SS_EINVAL;
+    ssk::Tables tb;
+    int n_cus = 1;
+    int rc = get_tables(&tb, &n_cus);
+    if (rc) return rc;
+    // (the runtime loads the library's device code on first use: asked for here, not by a first launch inside a capture)
+    hipFuncAttributes attr;
+    e = hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&ssk::k_sync_next));
+    if (e != hipSuccess) return hip_err(e);
+    const sslaunch::ObsRowsPlan pr = sslaunch::plan_obs_rows(false, false, false, n_terms == 1 ? SS_FLAG_NO_DISTRACTOR : 0, out_len, 1,
+                                                             ssroute::ceil_div(rir_cap, ssk::kB), n_cus, n_cus, 1, launch_switches());
+    if (pr.rc) return pr.rc;
+    float* stash = nullptr;
+    rc = get_stash(st, pr.stash_bytes, &stash);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(g_mu);
+    SyncBuf* b = nullptr;
+    return make_block_sync(dev, st, &b);
+}
+
+// The replay epoch word of the stream's hand-off area, after a synchronise of the stream: 0 = no replay yet, -k after replay k
+// of captured k_obs_blocks launches (k_sync_next).  For tests and diagnostics.
+int ss_stream_replay_epoch(void* stream, int* out) {
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!out || st == hipStreamPerThread) return SS_EINVAL;
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return hip_err(e);
+    const int* word = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(g_mu);
+        const auto it = g_sync.find(std::make_pair(dev, st));
+        if (it == g_sync.end() || !it->second.tails) return SS_EINVAL;
+        word = it->second.word;
+    }
+    e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return hip_err(e);
+    return hip_err(hipMemcpy(out, word, sizeof(int), hipMemcpyDeviceToHost));
 }
 
 int ss_init(void) {

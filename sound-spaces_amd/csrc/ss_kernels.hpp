@@ -3027,14 +3027,20 @@ __global__ __launch_bounds__(1024) void k_obs_rows(ConvParams p, int n_rows, Uni
 // HALF (a half bank, see k_conv_spec<.., HALF>): the spectral branch reads fp16 block spectra and their scales.
 // HBK (a half bank in length buckets, see k_conv_spec<.., HBK>): the term's bucket gives the fp16 base, the scale base and the depth.
 // ROWS16 (half-precision time-domain rows, see k_obs_rows<.., ROWS16>): the time-domain branch transforms a BankRow16.
+// epoch_word (may be null: `epoch` as given): a launch that is REPLAYED from a captured graph cannot carry its epoch in the
+// kernel arguments - every replay would repeat it and a consumer would accept the flag its producer left in the previous
+// replay.  Such a launch reads the epoch from a word of the hand-off area instead, once, here at the top; k_sync_next, captured
+// in front of it on the same stream, has moved the word on (see there for the two number ranges).
 template <bool SPECTRAL, bool MEL = false, bool HALF = false, bool HBK = false, bool ROWS16 = false>
 __global__ __launch_bounds__(1024) void k_obs_blocks(ConvParams p, int n_rows, float* tails, int* flags, int epoch,
                                                      UnitTab<false, MEL> ut = UnitTab<false, MEL>(),
                                                      SpecScale<HALF, HBK> hs = SpecScale<HALF, HBK>(),
-                                                     RowScale<ROWS16> rs = RowScale<ROWS16>()) {
+                                                     RowScale<ROWS16> rs = RowScale<ROWS16>(),
+                                                     const int* epoch_word = nullptr) {
     static_assert(!HALF || SPECTRAL, "half bank: the spectral form");
     static_assert(!ROWS16 || (!SPECTRAL && !HALF && !HBK), "half rows: plain rows of one time-domain allocation");
     static_assert(!HBK || HALF, "bucketed half bank: a half form");
+    if (epoch_word) epoch = uniform_load(epoch_word);     // (workgroup-uniform; written by an earlier kernel of the stream)
     __shared__ c32 lds[16 * kWaveScratch > kLdsComplex ? 16 * kWaveScratch : kLdsComplex];
     __shared__ float s_win[kNfft];
     __shared__ c32 s_tw512[kTw512Lds];
@@ -3152,6 +3158,20 @@ __global__ __launch_bounds__(1024) void k_obs_blocks(ConvParams p, int n_rows, f
         rows_stft_phase<true>(lds, p, t, unit, ch, j, b0, b1, last, y, s_win, s_tw512, s_wq, s_res,
                               j > 0 ? tails + (hand + (j - 1)) * kTailFloats : nullptr,
                               (!last && part == 0) ? tails + (hand + j) * kTailFloats : nullptr, part, sync);
+}
+
+// k_sync_next: moves the epoch word of a hand-off area on to the next REPLAY epoch; captured in front of every k_obs_blocks
+// launch that reads its epoch from the word (one wave, one store).  The two kinds of launch draw their epochs from disjoint
+// ranges, so a flag left by one kind can never equal the epoch of the other:
+//   eager launches   the host's counter as a kernel argument: 1, 2, ..., 0x7fffffff, then 1 again     (positive)
+//   replays          this word: -1, -2, ..., -0x7fffffff, then -1 again                               (negative)
+//   0                the area as it was zeroed: never an epoch of either kind.
+// Within a kind a flag only repeats after 2^31 - 1 launches of that kind on the stream.  A plain store: the kernel boundary
+// orders it in front of the k_obs_blocks launch that follows on the stream.
+constexpr int kReplayEpochLast = -0x7fffffff;
+__host__ __device__ inline int next_replay_epoch(int e) { return (e >= 0 || e == kReplayEpochLast) ? -1 : e - 1; }
+__global__ __launch_bounds__(64) void k_sync_next(int* epoch_word) {
+    if (threadIdx.x == 0) *epoch_word = next_replay_epoch(*epoch_word);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -108,11 +108,31 @@ inline ConvPlan plan_conv(Form form, bool fuse, bool wide, int flags, int rir_ca
     return pl;
 }
 
+// ---- per-stream scratch (the k_obs_rows stash, the k_obs_blocks hand-off area) under a graph capture ----------------------------
+// An allocation cannot be part of a capture: a launch that finds its scratch large enough uses it, capturing or not; one that
+// would have to allocate (or grow) does so on a plain stream and is refused on a capturing one - ss_stream_reserve, or one
+// eager call of the same shape, prepares the stream beforehand.
+enum class Scratch { kUse, kAllocate, kRefuse };
+inline Scratch scratch_decision(bool capturing, size_t have_bytes, size_t need_bytes) {
+    if (have_bytes >= need_bytes) return Scratch::kUse;
+    return capturing ? Scratch::kRefuse : Scratch::kAllocate;
+}
+
 // ---- k_obs_blocks: one workgroup per OUTPUT BLOCK of a row ---------------------------------------------------------------------
 constexpr int kSyncRows = 512;        // (unit, ear) rows a k_obs_blocks launch may have: more than CUs / 2
 // the hand-off area of `rows` rows: [rows][2] tails of kTailFloats floats + as many flag words
 inline size_t handoff_floats(int rows) { return static_cast<size_t>(rows) * 2 * ssk::kTailFloats; }
 inline size_t handoff_flags(int rows) { return static_cast<size_t>(rows) * 2; }
+// ... in bytes, with the replay epoch word behind the flags (k_sync_next)
+inline size_t handoff_bytes(int rows) {
+    return handoff_floats(rows) * sizeof(float) + handoff_flags(rows) * sizeof(int) + sizeof(int);
+}
+
+// ss_stream_reserve's argument rule (before a device is touched): a row of 2 or 3 partition blocks, a bank capacity, one or two
+// terms per unit.  stream_ok: not the per-thread stream (it can own no scratch).
+inline bool reserve_args_ok(bool stream_ok, int out_len, int rir_cap, int n_terms) {
+    return stream_ok && out_len > kB && out_len <= 3 * kB && rir_cap >= 1 && (n_terms == 1 || n_terms == 2);
+}
 
 struct ObsBlocksPlan {
     bool ok = false;                  // false: the launch does not qualify (the caller falls through to k_obs_rows)

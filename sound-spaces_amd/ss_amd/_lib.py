@@ -33,7 +33,8 @@ EXPORTS = ("ss_block_len", "ss_spec_floats", "ss_version", "ss_init", "ss_source
            "ss_fftconv_binaural_rir16_buckets_f32", "ss_audio_obs_rir16_buckets_f32", "ss_ctx_set_rir16_buckets",
            "ss_audio_obs_logmel_rir16_f32", "ss_audio_obs_logmel_rows_rir16_f32", "ss_audio_obs_logmel_rir16_buckets_f32",
            "ss_ctx_set_logmel_rir16_policy",
-           "ss_bank_scatter_rows16_max_f32", "ss_wav_read_rirs_max_f32")
+           "ss_bank_scatter_rows16_max_f32", "ss_wav_read_rirs_max_f32",
+           "ss_stream_reserve", "ss_stream_replay_epoch")
 # entries that return a size_t, not a status (EXPORTS: every `int ss_*` of include/ss_hip.h)
 EXPORTS_SIZE = ("ss_ctx_wave_scratch_bytes",)
 
@@ -230,6 +231,9 @@ def load() -> ctypes.CDLL:
     # ... their one-pass scatter (the rows' maxima given) and the reader that takes the maxima
     lib.ss_bank_scatter_rows16_max_f32.argtypes = [vp, c_ll, vp, vp, vp, c_int, vp, vp, c_int, vp, vp]
     lib.ss_wav_read_rirs_max_f32.argtypes = [vp, c_int, vp, c_ll, c_int, c_int, vp, vp, vp, c_int, vp]
+    # captured steps: what a stream's first rows launches would allocate, and the replay epoch of its hand-off area
+    lib.ss_stream_reserve.argtypes = [vp, c_int, c_int, c_int]
+    lib.ss_stream_replay_epoch.argtypes = [vp, vp]
     # pose memo of the column path
     lib.ss_memo_rows_f32.argtypes = [vp, c_int, vp, c_int, c_int, vp]
     lib.ss_ctx_memo_enable.argtypes = [vp, c_int]

@@ -450,8 +450,8 @@ def audio_obs_rows_rir16_into(spec, rir16, rscale, rir_len, unit_desc, audiogoal
                               pad_mode="reflect", flags: int = 0) -> None:
     """The fused observation of rows of 2 or 3 partition blocks (KB < out_len <= 3 KB: 44.1 / 48 kHz) from a bank of half rows
     (``ss_audio_obs_rows_rir16_f32``: k_obs_blocks for small steps, k_obs_rows beyond); ``audiogoal`` may be None - except with
-    n_valid <= KB, which the library serves in two launches when it is given one and in one when it is not.  Small steps must
-    not be replayed from a captured graph (include/ss_hip.h)."""
+    n_valid <= KB, which the library serves in two launches when it is given one and in one when it is not.  Captured into a
+    graph: ``ss_amd.graphs.capture`` (include/ss_hip.h "Captured steps")."""
     _chk(spec, torch.float32, "spec"); cap = _chk_rows16(rir16, rscale); _chk(rir_len, torch.int32, "rir_len")
     _chk(unit_desc, torch.int32, "unit_desc"); _chk(spectrogram_out, torch.float32, "spectrogram_out")
     N = unit_desc.shape[0]
@@ -493,7 +493,7 @@ def audio_obs_logmel_rows_rir16_into(spec, rir16, rscale, rir_len, unit_desc, au
                                      flags: int = 0) -> None:
     """``audio_obs_logmel_rows_into`` from a bank of half rows (``ss_audio_obs_logmel_rows_rir16_f32``): rows of 2 or 3 partition
     blocks (KB < out_len <= 3 KB), at most 16 RIR blocks, no cross-fade.  Small steps run the one-workgroup-per-output-block
-    kernel, whose launch must not be replayed from a captured graph."""
+    kernel; captured into a graph: ``ss_amd.graphs.capture``."""
     _obs_logmel_rir16("ss_audio_obs_logmel_rows_rir16_f32", spec, rir16, rscale, rir_len, unit_desc, audiogoal, spectrogram_out,
                       logmel_out, mel_start, mel_w, n_valid, out_len, mel_eps, pad_mode, flags)
 
@@ -564,7 +564,7 @@ def audio_obs_logmel_rows_into(spec, rir_bank, rir_len, unit_desc, audiogoal, sp
     """``audio_obs_logmel_into`` for rows of 2 or 3 partition blocks (KB < out_len <= 3 KB: 44.1 / 48 kHz;
     ``ss_audio_obs_logmel_rows_f32``): ONE launch of the log-mel form of the fused row kernels, whichever outputs are asked for
     next to ``logmel_out``.  No cross-fade, at most 16 RIR blocks; anything else is refused (invalid argument).  Small steps run
-    the one-workgroup-per-output-block kernel, whose launch must not be replayed from a captured graph."""
+    the one-workgroup-per-output-block kernel; captured into a graph: ``ss_amd.graphs.capture``."""
     _chk(spec, torch.float32, "spec"); _chk(rir_bank, torch.float32, "rir_bank"); _chk(rir_len, torch.int32, "rir_len")
     N, n_mels, max_len, ag_ptr, sg_ptr = _obs_logmel_args(unit_desc, audiogoal, spectrogram_out, logmel_out, mel_start, mel_w, out_len)
     us, cs, es, cap = _bank_strides(rir_bank, interleaved)
