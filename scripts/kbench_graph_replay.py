@@ -182,6 +182,8 @@ for sr, n_units in ((44100, 5), (44100, 10), (16000, 16)):
             tn.append(events(obs, a.launches, side))
         emit(f"# eager ss_audio_obs_f32 (k_obs_blocks), 5 units of 44.1 kHz, events on the stream: parent {fmt(tp)}  this tree {fmt(tn)}  "
              f"this / parent = {np.median(tn) / np.median(tp):.3f}")
+        emit(f"#   the rounds: parent {min(tp):.1f} .. {max(tp):.1f} (spread {(max(tp) - min(tp)) / np.median(tp):.3f} of its median)  "
+             f"this tree {min(tn):.1f} .. {max(tn):.1f}")
 if a.out:
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:

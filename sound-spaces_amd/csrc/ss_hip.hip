@@ -1,4 +1,7 @@
 // ss_hip.hip — host side of libss_hip.so: table construction and kernel launches (gfx950 only).
+// A launch of the four hot kernel families is three steps: plan (ss_route.hpp decides which launch, ss_launch.hpp its geometry),
+// acquire the resources the plan sizes (unit table, stash, hand-off area), dispatch (ss_dispatch.hpp decides which instantiation
+// and hands it to StreamLaunch below) - no instantiation of those families is named in this file.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -18,6 +21,7 @@
 #include "ss_kernels32.hpp"
 #include "ss_route.hpp"
 #include "ss_launch.hpp"
+#include "ss_dispatch.hpp"
 #include "ss_features.hpp"
 #include "ss_tables.hpp"
 #include "ss_wavio.hpp"
@@ -160,22 +164,22 @@ inline const sslaunch::Switches& launch_switches() {
     return sw;
 }
 
+// The launcher ss_dispatch.hpp hands its kernel choice to: the instantiation onto the stream, workgroups of ssk::kT threads
+struct StreamLaunch {
+    hipStream_t st;
+    template <class... A, class... B>
+    int operator()(void (*kernel)(A...), dim3 grid, const B&... args) const {
+        hipLaunchKernelGGL(kernel, grid, dim3(ssk::kT), 0, st, args...);
+        return hip_err(hipGetLastError());
+    }
+};
+
 // The convolution of whichever bank form the launch reads, fused with the STFT (FUSE) or not: sslaunch::plan_conv decides
-// refusal, kernel variant, parts and grid; here the unit table is filled where the plan allows one and the variant picks the
+// refusal, kernel variant, parts and grid; here the unit table is filled where the plan allows one; ssdispatch::conv picks the
 // instantiation.  hs: the scales of a half spectral bank (Form::kSpec16 / kSpec16Buckets), rs: those of half rows (Form::kRows16).
-// Half rows in length buckets (Form::kRows16 with p.n_buckets > 1): launches that only touch bucket 0 are single-allocation launches
-// on bucket 0's arrays (the HALF kernels, the loop-free ones included); everything else: k_conv<.., HALF, RBK>.
-// Half-precision time-domain rows (include/ss_hip.h "Half-precision time-domain rows"): k_conv<.., HALF> for every launch - no
-// cross-fade, no wide form, no persistent row kernel.  Half bank (include/ss_hip.h "Half-precision spectral bank"): k_conv_spec
-// <.., HALF> for every launch (more rows than CUs included: the persistent k_conv_spec_rows has no half form).  Half buckets:
-// launches that only touch bucket 0 (one bucket, or SS_FLAG_FIRST_BUCKET) are single-allocation launches on bucket 0's arrays:
-// the HALF kernels, the loop-free ones included; everything else: k_conv_spec<.., HALF, HBK>.
 template <bool FUSE>
 int launch_conv(sslaunch::Form form, ssk::ConvParams p, int n_units, int nb_y, int flags, int n_cus, const LaunchEnv& env,
                 bool wide = false, const ssk::SpecScale<true, true>* hs = nullptr, const ssk::RowScale<true, true>* rs = nullptr) {
-    using sslaunch::Form;
-    using V = sslaunch::Variant;
-    const hipStream_t st = env.st;
     const bool planar = p.rir_elem_stride == 1 && !(p.rir_cap & 1) && !(reinterpret_cast<size_t>(p.rir) & 7) &&
                         !(p.rir_unit_stride & 1) && !(p.rir_chan_stride & 1) && p.rir_cap >= 2;
     const sslaunch::ConvPlan pl = sslaunch::plan_conv(form, FUSE, wide, flags, p.rir_cap, p.h_blocks, p.n_buckets, p.fade_len, planar,
@@ -183,52 +187,10 @@ int launch_conv(sslaunch::Form form, ssk::ConvParams p, int n_units, int nb_y, i
                                                       launch_switches());
     if (pl.rc) return pl.rc;
     sslaunch::apply(pl, p);
-    const dim3 grid(pl.grid_x, pl.grid_y), block(ssk::kT);
-    const ssk::UnitTab<false> nt;
     ssk::UnitTab<true> ut;
-    const bool simple = pl.variant == V::kSimple;
     const bool tab = pl.tab_ok && fill_unit_tab(ut, env, n_units);
-    if (form == Form::kRows) {
-        switch (pl.variant) {
-            case V::kPersistRows:
-                if constexpr (!FUSE) hipLaunchKernelGGL(ssk::k_conv_rows, grid, block, 0, st, p, 2 * n_units);
-                break;
-            case V::kWide:
-                if constexpr (FUSE) hipLaunchKernelGGL((ssk::k_conv<true, false, false, false, true>), grid, block, 0, st, p, nt);
-                break;
-            case V::kWideXfade:
-                if constexpr (FUSE) hipLaunchKernelGGL((ssk::k_conv<true, false, true, false, true>), grid, block, 0, st, p, nt);
-                break;
-            case V::kXfade: hipLaunchKernelGGL((ssk::k_conv<FUSE, false, true>), grid, block, 0, st, p, nt); break;
-            case V::kSimple:
-                if (tab) hipLaunchKernelGGL((ssk::k_conv<FUSE, true, false, true>), grid, block, 0, st, p, ut);
-                else hipLaunchKernelGGL((ssk::k_conv<FUSE, true>), grid, block, 0, st, p, nt);
-                break;
-            case V::kLoop: hipLaunchKernelGGL((ssk::k_conv<FUSE, false>), grid, block, 0, st, p, nt); break;
-        }
-    } else if (form == Form::kRows16) {
-        const ssk::RowScale<true> rs1{rs->rir16, rs->rscale};
-        if (!pl.bucket0) hipLaunchKernelGGL((ssk::k_conv<FUSE, false, false, false, false, false, true, true>), grid, block, 0, st, p, nt, *rs);
-        else if (tab) hipLaunchKernelGGL((ssk::k_conv<FUSE, true, false, true, false, false, true>), grid, block, 0, st, p, ut, rs1);
-        else if (simple) hipLaunchKernelGGL((ssk::k_conv<FUSE, true, false, false, false, false, true>), grid, block, 0, st, p, nt, rs1);
-        else hipLaunchKernelGGL((ssk::k_conv<FUSE, false, false, false, false, false, true>), grid, block, 0, st, p, nt, rs1);
-    } else if (form == Form::kSpec) {
-        if (pl.variant == V::kPersistRows) {
-            if constexpr (!FUSE) hipLaunchKernelGGL(ssk::k_conv_spec_rows, grid, block, 0, st, p, 2 * n_units);
-        } else if (tab) hipLaunchKernelGGL((ssk::k_conv_spec<FUSE, true, true>), grid, block, 0, st, p, ut);
-        else if (simple) hipLaunchKernelGGL((ssk::k_conv_spec<FUSE, true>), grid, block, 0, st, p, nt);
-        else hipLaunchKernelGGL((ssk::k_conv_spec<FUSE, false>), grid, block, 0, st, p, nt);
-    } else if (form == Form::kSpec16 || pl.bucket0) {
-        const ssk::SpecScale<true> hs1{hs->hscale};
-        if (tab) hipLaunchKernelGGL((ssk::k_conv_spec<FUSE, true, true, false, true>), grid, block, 0, st, p, ut, hs1);
-        else if (simple) hipLaunchKernelGGL((ssk::k_conv_spec<FUSE, true, false, false, true>), grid, block, 0, st, p, nt, hs1);
-        else hipLaunchKernelGGL((ssk::k_conv_spec<FUSE, false, false, false, true>), grid, block, 0, st, p, nt, hs1);
-    } else {
-        hipLaunchKernelGGL((ssk::k_conv_spec<FUSE, false, false, false, true, true>), grid, block, 0, st, p, nt, *hs);
-    }
-    return hip_err(hipGetLastError());
+    return ssdispatch::conv<FUSE>(StreamLaunch{env.st}, form, pl, p, n_units, tab ? &ut : nullptr, hs, rs);
 }
-
 
 // the arguments every half-rows entry refuses before a device is touched
 inline bool rows16_bank_ok(const void* rir16, const float* rscale, int cap) {
@@ -384,25 +346,21 @@ void drop_stash(hipStream_t st) {
 
 // k_obs_blocks / k_obs_rows behind one launcher: sslaunch::plan_obs_rows gives the refusals and the row kernel's shape,
 // sslaunch::plan_obs_blocks says whether the step is small enough for one workgroup per OUTPUT BLOCK of a row (k_obs_blocks:
-// the hand-off area of the stream) - else k_obs_rows with its stash.
-// MEL: the log-mel instantiations (ss_audio_obs_logmel_rows_f32 / _spec_f32), same rule, same hand-off area.
-// HALF: the half-bank instantiations (ss_audio_obs_rows_spec16_f32 / ss_audio_obs_logmel_rows_spec16_f32), likewise.
-// HBK: a half bank in length buckets (ss_audio_obs_rows_spec16_buckets_f32 / ss_audio_obs_logmel_rows_spec16_buckets_f32), likewise.
-// ROWS16: half-precision time-domain rows (ss_audio_obs_rows_rir16_f32; with MEL: ss_audio_obs_logmel_rows_rir16_f32), likewise.
-template <bool SPECTRAL, bool MEL = false, bool HALF = false, bool HBK = false, bool ROWS16 = false>
-int launch_obs_rows(ssk::ConvParams p, int n_units, int flags, int n_cus, const LaunchEnv& env,
-                    const ssk::UnitTab<false, MEL>& mel = ssk::UnitTab<false, MEL>(),
-                    const ssk::SpecScale<HALF, HBK>& hs = ssk::SpecScale<HALF, HBK>(),
-                    const ssk::RowScale<ROWS16>& rs = ssk::RowScale<ROWS16>()) {
+// the hand-off area of the stream) - else k_obs_rows with its stash.  Plan, scratch, then ssdispatch picks the instantiation.
+// form: sslaunch::rows_form's; mel: the log-mel instantiations, same rule, same hand-off area; hs: the scales of the half spectral
+// forms; rs: those of half-precision time-domain rows (Form::kRows16).
+int launch_obs_rows(sslaunch::Form form, ssk::ConvParams p, int n_units, int flags, int n_cus, const LaunchEnv& env,
+                    const ssk::MelArgs* mel = nullptr, const ssk::SpecScale<true, true>* hs = nullptr,
+                    const ssk::RowScale<true>* rs = nullptr) {
+    using sslaunch::Form;
     const hipStream_t st = env.st;
-    static_assert(!HALF || SPECTRAL, "half bank: the spectral form");
-    static_assert(!HBK || HALF, "bucketed half bank: a half form");
-    static_assert(!ROWS16 || (!SPECTRAL && !HALF), "half rows: plain rows of one time-domain allocation");
+    const bool spectral = form != Form::kRows && form != Form::kRows16;
+    const bool half = form == Form::kSpec16 || form == Form::kSpec16Buckets, rows16 = form == Form::kRows16;
     const int n_rows = 2 * n_units;
-    const dim3 block(ssk::kT);
-    // (the log-mel and half forms: plain rows; half: one allocation, or the HBK form)
-    const sslaunch::ObsRowsPlan pr = sslaunch::plan_obs_rows(SPECTRAL, MEL || HALF || ROWS16, (HALF && !HBK) || ROWS16, flags, p.n_valid,
-                                                             p.n_buckets, sslaunch::rows_nbh_max(p), n_units, n_cus, env.share,
+    if (form == Form::kSpec16) p.n_buckets = 1;                 // (a bucket-0 launch of half buckets: bucket 0's arrays alone)
+    // (the log-mel and half forms: plain rows; half: one allocation, or the bucketed form)
+    const sslaunch::ObsRowsPlan pr = sslaunch::plan_obs_rows(spectral, mel || half || rows16, form == Form::kSpec16 || rows16, flags,
+                                                             p.n_valid, p.n_buckets, sslaunch::rows_nbh_max(p), n_units, n_cus, env.share,
                                                              launch_switches());
     if (pr.rc) return pr.rc;
     const sslaunch::ObsBlocksPlan pb = sslaunch::plan_obs_blocks(flags, p.out_len, p.n_valid, n_units, n_cus, env.share,
@@ -415,43 +373,21 @@ int launch_obs_rows(ssk::ConvParams p, int n_units, int flags, int n_cus, const 
         const int rc = get_block_sync(st, &tails, &fl, &epoch, &word);
         if (rc) return rc;
         sslaunch::apply(pb, p);
-        const dim3 grid(pb.grid);
         if (word) {                                             // ... which k_sync_next moves on first, at every replay
             hipLaunchKernelGGL(ssk::k_sync_next, dim3(1), dim3(64), 0, st, word);
             const int rc2 = hip_err(hipGetLastError());
             if (rc2) return rc2;
         }
-        const int* epoch_word = word;
-        // (the instantiations the forms had before: the defaulted arguments written out)
-        hipLaunchKernelGGL((ssk::k_obs_blocks<SPECTRAL, MEL, HALF, HBK, ROWS16>), grid, block, 0, st, p, n_rows, tails, fl, epoch, mel, hs, rs,
-                           epoch_word);
-        return hip_err(hipGetLastError());
+        return ssdispatch::obs_blocks(StreamLaunch{st}, form, pb.grid, p, n_rows, tails, fl, epoch, mel, hs, rs, word);
     }
     sslaunch::apply(pr, p);
-    if constexpr (!SPECTRAL) {                                  // (sized from the deepest bucket and n_terms - half rows as fp32 rows)
+    if (!spectral) {                                            // (sized from the deepest bucket and n_terms - half rows as fp32 rows)
         float* buf = nullptr;
         const int rc = get_stash(st, pr.stash_bytes, &buf);
         if (rc) return rc;
         p.stash = reinterpret_cast<ssk::f32x4*>(buf);
     }
-    const dim3 grid(pr.grid);
-    if constexpr (ROWS16) hipLaunchKernelGGL((ssk::k_obs_rows<false, false, false, MEL, false, true>), grid, block, 0, st, p, n_rows, mel, hs, rs);
-    else if constexpr (HBK) hipLaunchKernelGGL((ssk::k_obs_rows<true, false, true, MEL, true>), grid, block, 0, st, p, n_rows, mel, hs);
-    else if constexpr (HALF) hipLaunchKernelGGL((ssk::k_obs_rows<true, false, false, MEL, true>), grid, block, 0, st, p, n_rows, mel, hs);
-    else if constexpr (MEL) {                                   // (length buckets: the instantiation that resolves them)
-        if (p.n_buckets == 1) hipLaunchKernelGGL((ssk::k_obs_rows<SPECTRAL, false, false, true>), grid, block, 0, st, p, n_rows, mel);
-        else hipLaunchKernelGGL((ssk::k_obs_rows<SPECTRAL, false, true, true>), grid, block, 0, st, p, n_rows, mel);
-    } else {
-        bool xfade = false;
-        if constexpr (!SPECTRAL) xfade = (flags & SS_FLAG_CROSSFADE) != 0;
-        if (xfade) {
-            if constexpr (!SPECTRAL) hipLaunchKernelGGL((ssk::k_obs_rows<false, true>), grid, block, 0, st, p, n_rows);
-        }
-        // one bank allocation (every launch but those of a length-bucketed store): the instantiation without the bucket descriptors
-        else if (p.n_buckets == 1) hipLaunchKernelGGL((ssk::k_obs_rows<SPECTRAL, false, false>), grid, block, 0, st, p, n_rows);
-        else hipLaunchKernelGGL((ssk::k_obs_rows<SPECTRAL>), grid, block, 0, st, p, n_rows);
-    }
-    return hip_err(hipGetLastError());
+    return ssdispatch::obs_rows(StreamLaunch{st}, form, (flags & SS_FLAG_CROSSFADE) != 0, pr.grid, p, n_rows, mel, hs, rs);
 }
 
 // ---- log-mel form of the fused one-block kernels (k_conv / k_conv_spec <.., MEL>): one workgroup per row, no unit table ----
@@ -461,57 +397,13 @@ inline bool mel_args_ok(const float* logmel, const int* mel_start, const float* 
            max_len <= ssk::kFeatMaxLen && !(max_len & 3) && n_mels * max_len <= ssk::kFeatMelTable && eps > 0.f &&
            !(reinterpret_cast<size_t>(mel_w) & 15);
 }
-int launch_conv_mel(ssk::ConvParams p, const ssk::MelArgs& m, int n_units, int flags, hipStream_t st) {
-    const bool simple = (flags & SS_FLAG_NO_DISTRACTOR) && p.rir_cap <= ssk::kB && p.n_buckets == 1;
-    const dim3 grid(2 * n_units), block(ssk::kT);
-    if (simple) hipLaunchKernelGGL((ssk::k_conv<true, true, false, false, false, true>), grid, block, 0, st, p, m);
-    else hipLaunchKernelGGL((ssk::k_conv<true, false, false, false, false, true>), grid, block, 0, st, p, m);
-    return hip_err(hipGetLastError());
-}
-
-// ... from half-precision time-domain rows (k_conv<.., MEL, HALF>; ssk::RowScale): the convention of launch_conv_mel - one
-// workgroup per row, parts_log2 = 0.  Launches that only touch bucket 0 (one allocation, one bucket, or SS_FLAG_FIRST_BUCKET)
-// run the single-allocation kernels on bucket 0's arrays, the loop-free one included; everything else bucketed: k_conv<.., RBK>.
-int launch_conv16_mel(ssk::ConvParams p, const ssk::MelArgs& m, const ssk::RowScale<true, true>& rs, int n_units, int flags,
-                      hipStream_t st) {
-    const bool bucket0 = p.n_buckets == 1 || (flags & SS_FLAG_FIRST_BUCKET);
-    const bool simple = (flags & SS_FLAG_NO_DISTRACTOR) && p.rir_cap <= ssk::kB && bucket0;
-    const dim3 grid(2 * n_units), block(ssk::kT);
-    const ssk::RowScale<true> rs1{rs.rir16, rs.rscale};
-    if (!bucket0) hipLaunchKernelGGL((ssk::k_conv<true, false, false, false, false, true, true, true>), grid, block, 0, st, p, m, rs);
-    else if (simple) hipLaunchKernelGGL((ssk::k_conv<true, true, false, false, false, true, true>), grid, block, 0, st, p, m, rs1);
-    else hipLaunchKernelGGL((ssk::k_conv<true, false, false, false, false, true, true>), grid, block, 0, st, p, m, rs1);
-    return hip_err(hipGetLastError());
-}
-
-// SoundSpaces 2.0 steps (ss_audio_obs_logmel_ss2_f32): the cross-faded one-block row and the WIDE row (block 0 of a longer row,
-// with or without the cross-fade) in their log-mel forms - the loop kernel, one workgroup per (unit, ear) row
-int launch_conv_mel_ss2(ssk::ConvParams p, const ssk::MelArgs& m, int n_units, int flags, bool wide, hipStream_t st) {
-    const bool xfade = (flags & SS_FLAG_CROSSFADE) != 0;
-    if (xfade && (p.fade_len < 1 || p.fade_len > 2 * ssk::kPrevPairs - 2)) return SS_EINVAL;
-    const dim3 grid(2 * n_units), block(ssk::kT);
-    if (!wide) hipLaunchKernelGGL((ssk::k_conv<true, false, true, false, false, true>), grid, block, 0, st, p, m);
-    else if (xfade) hipLaunchKernelGGL((ssk::k_conv<true, false, true, false, true, true>), grid, block, 0, st, p, m);
-    else hipLaunchKernelGGL((ssk::k_conv<true, false, false, false, true, true>), grid, block, 0, st, p, m);
-    return hip_err(hipGetLastError());
-}
-
-int launch_conv_spec_mel(ssk::ConvParams p, const ssk::MelArgs& m, int n_units, int flags, hipStream_t st) {
-    const bool simple = (flags & SS_FLAG_NO_DISTRACTOR) && p.h_blocks == 1 && p.n_buckets == 1;
-    const dim3 grid(2 * n_units), block(ssk::kT);
-    if (simple) hipLaunchKernelGGL((ssk::k_conv_spec<true, true, false, true>), grid, block, 0, st, p, m);
-    else hipLaunchKernelGGL((ssk::k_conv_spec<true, false, false, true>), grid, block, 0, st, p, m);
-    return hip_err(hipGetLastError());
-}
-
-// ... from a half bank (fp16 block spectra + one scale per block: ssk::SpecScale)
-int launch_conv_spec16_mel(ssk::ConvParams p, const ssk::MelArgs& m, const float* hscale, int n_units, int flags, hipStream_t st) {
-    const bool simple = (flags & SS_FLAG_NO_DISTRACTOR) && p.h_blocks == 1;
-    const dim3 grid(2 * n_units), block(ssk::kT);
-    const ssk::SpecScale<true> hs{hscale};
-    if (simple) hipLaunchKernelGGL((ssk::k_conv_spec<true, true, false, true, true>), grid, block, 0, st, p, m, hs);
-    else hipLaunchKernelGGL((ssk::k_conv_spec<true, false, false, true, true>), grid, block, 0, st, p, m, hs);
-    return hip_err(hipGetLastError());
+// ss2: 0 = the one-block row; SoundSpaces 2.0 steps (ss_audio_obs_logmel_ss2_f32): ssroute::obs_logmel_ss2_shape's answer
+int launch_conv_mel(sslaunch::Form form, ssk::ConvParams p, const ssk::MelArgs& m, int ss2, int n_units, int flags, hipStream_t st,
+                    const ssk::SpecScale<true, true>* hs = nullptr, const ssk::RowScale<true, true>* rs = nullptr) {
+    const sslaunch::ConvPlan pl = sslaunch::plan_conv_mel(form, ss2, flags, p.rir_cap, p.h_blocks, p.n_buckets, p.fade_len, n_units);
+    if (pl.rc) return pl.rc;
+    sslaunch::apply(pl, p);
+    return ssdispatch::conv_mel(StreamLaunch{st}, form, pl, p, m, hs, rs);
 }
 
 // Waveform scratch of the contexts: ss_ctx_observe_features without an audiogoal buffer, on the shapes the log-mel form does
@@ -749,19 +641,11 @@ int launch_conv_any(const ssk::ConvParams& p, const ssk::SpecScale<true, true>& 
     return launch_conv<FUSE>(hs.hscale ? sslaunch::Form::kSpec16Buckets : sslaunch::Form::kSpec, p, n_units, nb_y, flags, n_cus, env, false, &hs);
 }
 
-// ... and k_obs_blocks / k_obs_rows likewise (launch_obs_rows' own choice, hand-off area and stash)
-template <bool MEL>
+// ... and k_obs_blocks / k_obs_rows likewise (sslaunch::rows_form: half buckets whose launch only touches bucket 0 as one allocation)
 int launch_rows_any(const ssk::ConvParams& p, const ssk::SpecScale<true, true>& hs, bool spectral, int n_units, int flags, int n_cus,
-                    const LaunchEnv& env, const ssk::UnitTab<false, MEL>& mel = ssk::UnitTab<false, MEL>()) {
-    if (!spectral) return launch_obs_rows<false, MEL>(p, n_units, flags, n_cus, env, mel);
-    // half buckets: launches that only touch bucket 0 (one bucket, or SS_FLAG_FIRST_BUCKET) are single-allocation launches on its arrays
-    if (hs.hscale && p.n_buckets > 1 && !(flags & SS_FLAG_FIRST_BUCKET)) return launch_obs_rows<true, MEL, true, true>(p, n_units, flags, n_cus, env, mel, hs);
-    if (hs.hscale) {
-        ssk::ConvParams p1 = p;
-        p1.n_buckets = 1;
-        return launch_obs_rows<true, MEL, true>(p1, n_units, flags, n_cus, env, mel, ssk::SpecScale<true>{hs.hscale});
-    }
-    return launch_obs_rows<true, MEL>(p, n_units, flags, n_cus, env, mel);
+                    const LaunchEnv& env, const ssk::MelArgs* mel = nullptr) {
+    return launch_obs_rows(sslaunch::rows_form(spectral, hs.hscale != nullptr, false, p.n_buckets, flags), p, n_units, flags, n_cus, env,
+                           mel, &hs);
 }
 
 // One step from bank `b`: the body of every ss_fftconv_binaural_* (want = kConv: the waveform alone), ss_audio_obs_* (kObs: the
@@ -864,15 +748,15 @@ int render(const Bank& b, bool spectral, ssroute::Launch want, const float* spec
         if (want == Launch::kObs && chain == Chain::kRows) {
             p.pad_mode = pad_mode;
             p.sgram = spectrogram;
-            return launch_obs_rows<false, false, false, false, true>(p, n_units, flags, n_cus, env, ssk::UnitTab<false, false>(),
-                                                                     ssk::SpecScale<false, false>(), ssk::RowScale<true>{rs.rir16, rs.rscale});
+            const ssk::RowScale<true> rs1 = ssdispatch::first_bucket(rs);
+            return launch_obs_rows(Form::kRows16, p, n_units, flags, n_cus, env, nullptr, nullptr, &rs1);
         }
         if (want == Launch::kMelOneBlock || want == Launch::kMelRows) {
             p.pad_mode = pad_mode;
             p.sgram = spectrogram;
-            if (want == Launch::kMelOneBlock) return launch_conv16_mel(p, *mel, rs, n_units, flags, env.st);
-            return launch_obs_rows<false, true, false, false, true>(p, n_units, flags, n_cus, env, *mel, ssk::SpecScale<false, false>(),
-                                                                    ssk::RowScale<true>{rs.rir16, rs.rscale});
+            if (want == Launch::kMelOneBlock) return launch_conv_mel(Form::kRows16, p, *mel, 0, n_units, flags, env.st, nullptr, &rs);
+            const ssk::RowScale<true> rs1 = ssdispatch::first_bucket(rs);
+            return launch_obs_rows(Form::kRows16, p, n_units, flags, n_cus, env, mel, nullptr, &rs1);
         }
         rc = launch_conv<false>(Form::kRows16, p, n_units, nb_y, flags, n_cus, env, false, nullptr, &rs);
         if (rc || want == Launch::kConv) return rc;
@@ -889,18 +773,14 @@ int render(const Bank& b, bool spectral, ssroute::Launch want, const float* spec
     if (want == Launch::kObs) {
         if (chain == Chain::kFused) return launch_conv_any<true>(p, hs, spectral, n_units, 1, flags, n_cus, env);
         if (chain == Chain::kWide) return launch_conv<true>(Form::kRows, p, n_units, 1, flags, n_cus, env, true);
-        return launch_rows_any<false>(p, hs, spectral, n_units, flags, n_cus, env);
+        return launch_rows_any(p, hs, spectral, n_units, flags, n_cus, env);
     }
     // the log-mel forms.  Launches that only touch bucket 0 (one bucket, or SS_FLAG_FIRST_BUCKET) are single-allocation launches
     // on bucket 0's arrays: the single-bank log-mel launchers, loop-free kernels included.
     if (flags & SS_FLAG_FIRST_BUCKET) p.n_buckets = 1;
-    if (want == Launch::kMelSs2) return launch_conv_mel_ss2(p, *mel, n_units, flags, ss2_shape == 2, env.st);
-    if (want == Launch::kMelRows) return launch_rows_any<true>(p, hs, spectral, n_units, flags, n_cus, env, *mel);
-    if (!spectral) return launch_conv_mel(p, *mel, n_units, flags, env.st);
-    if (!half) return launch_conv_spec_mel(p, *mel, n_units, flags, env.st);
-    if (p.n_buckets == 1) return launch_conv_spec16_mel(p, *mel, hs.hscale, n_units, flags, env.st);
-    hipLaunchKernelGGL((ssk::k_conv_spec<true, false, false, true, true, true>), dim3(2 * n_units), dim3(ssk::kT), 0, env.st, p, *mel, hs);
-    return hip_err(hipGetLastError());
+    if (want == Launch::kMelRows) return launch_rows_any(p, hs, spectral, n_units, flags, n_cus, env, mel);
+    const Form form = !spectral ? Form::kRows : half ? Form::kSpec16Buckets : Form::kSpec;
+    return launch_conv_mel(form, p, *mel, want == Launch::kMelSs2 ? ss2_shape : 0, n_units, flags, env.st, &hs);
 }
 
 // the stateless entries: device pointers only, the whole chip

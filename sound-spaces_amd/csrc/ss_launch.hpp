@@ -1,11 +1,11 @@
 // ss_launch.hpp — how a launch is shaped: output blocks, parts, grids, kernel variant, stash and hand-off sizes, and the shape
-// fields of ConvParams.  ss_route.hpp decides WHICH launch serves a step; this header decides its geometry; ss_hip.hip acquires
-// the resources at the sizes given here and dispatches to the kernel instantiation.
+// fields of ConvParams.  Three layers: ss_route.hpp decides WHICH launch serves a step; this header decides its geometry;
+// ss_dispatch.hpp decides which kernel instantiation runs it.  ss_hip.hip acquires the resources at the sizes given here in between.
 //
 // Pure host C++, no HIP runtime, no environment, no statics, no pointers to device memory: tests/launch_host.cpp compiles this
-// header on its own and prints the plan of every case of a fixed grid (tests/golden/launch_table.txt pins it), and the host
-// simulator (tests/hostsim/hostsim.cpp and the drivers around it) shapes its launches with the same functions - so the CPU tests
-// of the kernels run the library's own geometry.  The A/B switches of -DSS_AB builds are read in ss_hip.hip and arrive here as
+// header on its own and prints the plan of every case of a fixed grid (tests/golden/launch_table.txt and launch_mel_table.txt pin
+// it), and the host simulator (tests/hostsim/hostsim.cpp and the drivers around it) shapes its launches with the same functions
+// and dispatches them through ss_dispatch.hpp - so the CPU tests of the kernels run the library's own geometry and kernel choice.  The A/B switches of -DSS_AB builds are read in ss_hip.hip and arrive here as
 // plain values (Switches).
 #pragma once
 
@@ -108,6 +108,25 @@ inline ConvPlan plan_conv(Form form, bool fuse, bool wide, int flags, int rir_ca
     return pl;
 }
 
+// ---- the one-block log-mel launches (k_conv / k_conv_spec <.., MEL>): one workgroup per (unit, ear) row, no parts, no unit table ---
+// ss2: 0 = the one-block row of ssroute::obs_logmel_shape_ok; SoundSpaces 2.0 steps (ssroute::obs_logmel_ss2_shape, fp32 rows of
+// one allocation): 1 = the cross-faded one-block row, 2 = the WIDE row (block 0 of a longer row, with or without the cross-fade).
+// n_buckets: the launch's (ConvParams::n_buckets).  The loop-free kernel: one term, one RIR block, bucket 0 only.
+inline ConvPlan plan_conv_mel(Form form, int ss2, int flags, int rir_cap, int h_blocks, int n_buckets, int fade_len, int n_units) {
+    ConvPlan pl;
+    const bool time = form == Form::kRows || form == Form::kRows16;
+    const bool xfade = (flags & SS_FLAG_CROSSFADE) != 0;
+    if (ss2 && (form != Form::kRows || (xfade && (fade_len < 1 || fade_len > 2 * ssk::kPrevPairs - 2)))) {
+        pl.rc = SS_EINVAL;
+        return pl;
+    }
+    pl.grid_x = 2 * n_units;
+    pl.bucket0 = n_buckets == 1 || (flags & SS_FLAG_FIRST_BUCKET);
+    const bool simple = (flags & SS_FLAG_NO_DISTRACTOR) && (time ? rir_cap <= kB : h_blocks == 1) && pl.bucket0;
+    pl.variant = ss2 == 2 ? (xfade ? Variant::kWideXfade : Variant::kWide) : ss2 ? Variant::kXfade : simple ? Variant::kSimple : Variant::kLoop;
+    return pl;
+}
+
 // ---- per-stream scratch (the k_obs_rows stash, the k_obs_blocks hand-off area) under a graph capture ----------------------------
 // An allocation cannot be part of a capture: a launch that finds its scratch large enough uses it, capturing or not; one that
 // would have to allocate (or grow) does so on a plain stream and is refused on a capturing one - ss_stream_reserve, or one
@@ -163,6 +182,15 @@ inline ObsBlocksPlan plan_obs_blocks(int flags, int out_len, int n_valid, int n_
     pl.handoff_floats = handoff_floats(n_rows);
     pl.handoff_flags = handoff_flags(n_rows);
     return pl;
+}
+
+// ---- the row kernels (k_obs_blocks / k_obs_rows): the bank form a launch reads ---------------------------------------------------
+// half: a half spectral bank.  Half buckets: a launch that only touches bucket 0 (one bucket, or SS_FLAG_FIRST_BUCKET) is a
+// single-allocation launch on bucket 0's arrays (Form::kSpec16: the caller sets ConvParams::n_buckets = 1).
+inline Form rows_form(bool spectral, bool half, bool rows16, int n_buckets, int flags) {
+    if (!spectral) return rows16 ? Form::kRows16 : Form::kRows;
+    if (!half) return Form::kSpec;
+    return n_buckets > 1 && !(flags & SS_FLAG_FIRST_BUCKET) ? Form::kSpec16Buckets : Form::kSpec16;
 }
 
 // ---- k_obs_rows: persistent workgroups walk the (unit, ear) rows ---------------------------------------------------------------

@@ -38,11 +38,8 @@ extern "C" int hs_obs_blocks_replay(int mode, int epoch, const float* spec, cons
     set_spectra(p, hspec, h_blocks);
     p.fade_len = 0;
     const int n_rows = 2 * n_units;
-    if (mode == 0)
-        return run_obs_blocks(p, n_units, 0, 0, [&](float* tails, int* fl) {
-            if (hspec) ssk::k_obs_blocks<true>(p, n_rows, tails, fl, epoch);
-            else ssk::k_obs_blocks<false>(p, n_rows, tails, fl, epoch);
-        });
+    const Form form = hspec ? Form::kSpec : Form::kRows;
+    if (mode == 0) return run_obs_blocks(p, form, n_units, 0, 0, nullptr, nullptr, nullptr, epoch);
     const sslaunch::ObsBlocksPlan pl = sslaunch::plan_obs_blocks(0, p.out_len, p.n_valid, n_units, n_rows * ssroute::ceil_div(out_len, ssk::kB), 1,
                                                                  true, sslaunch::Switches());
     if (!pl.ok || pl.parts_log2 != 0) return -3;
@@ -58,13 +55,7 @@ extern "C" int hs_obs_blocks_replay(int mode, int epoch, const float* spec, cons
     }
     const int* epoch_word = mode == 1 ? word : nullptr;
     const int arg = mode == 1 ? 0 : epoch;
-    const ssk::UnitTab<false> nt;
-    const ssk::SpecScale<false> ns;
-    const ssk::RowScale<false> nr;
-    return run_grid(pl.grid, 1, ssk::kT, [&] {
-        if (hspec) ssk::k_obs_blocks<true>(p, n_rows, tails, fl, arg, nt, ns, nr, epoch_word);
-        else ssk::k_obs_blocks<false>(p, n_rows, tails, fl, arg, nt, ns, nr, epoch_word);
-    });
+    return ssdispatch::obs_blocks(HostLaunch{}, form, pl.grid, p, n_rows, tails, fl, arg, nullptr, nullptr, nullptr, epoch_word);
 }
 
 // next_replay_epoch at the ends of its range (the wrap cannot be reached by running replays)

@@ -13,6 +13,7 @@
 #include "../../sound-spaces_amd/csrc/ss_features.hpp"
 #include "../../sound-spaces_amd/csrc/ss_tables.hpp"
 #include "../../sound-spaces_amd/csrc/ss_launch.hpp"
+#include "../../sound-spaces_amd/csrc/ss_dispatch.hpp"
 
 dim3 threadIdx, blockIdx, blockDim, gridDim;
 
@@ -159,31 +160,65 @@ void fill_tab_reversed(ssk::UnitTab<true>& ut, const int* desc, int n_units) {
     }
 }
 
+// The kernel choice is the library's too (sound-spaces_amd/csrc/ss_dispatch.hpp).  Its launcher here: the grid on the fibers, one
+// workgroup after the other (reversed: the last first) - under the shim __global__ is empty, a kernel is an ordinary function.
+struct HostLaunch {
+    bool reversed = false;
+    template <class... A, class... B>
+    int operator()(void (*kernel)(A...), dim3 grid, const B&... args) const {
+        return run_grid(static_cast<int>(grid.x), static_cast<int>(grid.y), ssk::kT, [&] { kernel(args...); }, reversed);
+    }
+};
+using sslaunch::Form;
+// ssdispatch::conv with FUSE as a value; ut != nullptr: the unit table, where the plan allows one
+int dispatch_conv(bool fuse, Form form, const sslaunch::ConvPlan& pl, const ssk::ConvParams& p, int n_units,
+                  const ssk::UnitTab<true>* ut = nullptr, const ssk::SpecScale<true, true>* hs = nullptr,
+                  const ssk::RowScale<true, true>* rs = nullptr) {
+    if (ut && !pl.tab_ok) return -8;
+    return fuse ? ssdispatch::conv<true>(HostLaunch{}, form, pl, p, n_units, ut, hs, rs)
+                : ssdispatch::conv<false>(HostLaunch{}, form, pl, p, n_units, ut, hs, rs);
+}
+// the one-block log-mel launch as the library shapes and dispatches it (launch_conv_mel of ss_hip.hip); *plan_out: the plan it ran;
+// -4: the plan refuses the launch
+int run_conv_mel(Form form, ssk::ConvParams& p, const ssk::MelArgs& m, int ss2, int n_units, int flags,
+                 const ssk::SpecScale<true, true>* hs = nullptr, const ssk::RowScale<true, true>* rs = nullptr,
+                 sslaunch::ConvPlan* plan_out = nullptr) {
+    const sslaunch::ConvPlan pl = sslaunch::plan_conv_mel(form, ss2, flags, p.rir_cap, p.h_blocks, p.n_buckets, p.fade_len, n_units);
+    if (plan_out) *plan_out = pl;
+    if (pl.rc) return -4;
+    sslaunch::apply(pl, p);
+    return ssdispatch::conv_mel(HostLaunch{}, form, pl, p, m, hs, rs);
+}
+
 // k_obs_blocks as sslaunch::plan_obs_blocks shapes it: the plan sees a chip of exactly the (row, block, part) workgroups the
 // test wants, so that its own rule arrives at `parts_log2`; the hand-off area at the plan's sizes; the workgroups run in
 // blockIdx order with xcd_map = 0 - (row, j - 1) before (row, j): producers before consumers - or reversed.
-// body(tails, flags) runs the kernel; -3: the plan does not take the launch (a cross-fade, n_valid < out_len).
-template <class Body>
-int run_obs_blocks(ssk::ConvParams& p, int n_units, int flags, int parts_log2, Body body, bool reversed = false,
-                   std::vector<int>* flags_out = nullptr) {
+// The instantiation: ssdispatch::obs_blocks for `form` (mel / hs / rs: as there).  -3: the plan does not take the launch (a
+// cross-fade, n_valid < out_len).
+int run_obs_blocks(ssk::ConvParams& p, Form form, int n_units, int flags, int parts_log2, const ssk::MelArgs* mel = nullptr,
+                   const ssk::SpecScale<true, true>* hs = nullptr, const ssk::RowScale<true>* rs = nullptr, int epoch = 7,
+                   bool reversed = false, std::vector<int>* flags_out = nullptr) {
     const int wanted = (2 * n_units * ssroute::ceil_div(p.out_len, ssk::kB)) << parts_log2;
     const sslaunch::ObsBlocksPlan pl = sslaunch::plan_obs_blocks(flags, p.out_len, p.n_valid, n_units, wanted, 1, true, sslaunch::Switches());
     if (!pl.ok) return -3;
+    if (form == Form::kSpec16) p.n_buckets = 1;
     sslaunch::apply(pl, p);
     p.xcd_map = 0;
     std::vector<float> tails(pl.handoff_floats, 12345.0f);
     std::vector<int> fl(pl.handoff_flags, 0);
-    const int rc = run_grid(pl.grid, 1, ssk::kT, [&] { body(tails.data(), fl.data()); }, reversed);
+    const int rc = ssdispatch::obs_blocks(HostLaunch{reversed}, form, pl.grid, p, 2 * n_units, tails.data(), fl.data(), epoch, mel, hs, rs, nullptr);
     if (flags_out) flags_out->swap(fl);
     return rc;
 }
 
 // k_obs_rows as sslaunch::plan_obs_rows shapes it: `wgs` persistent workgroups are the plan's CUs (parts_log2 > 0: one workgroup
 // per (row, part), whatever `wgs` says), the stash of a time-domain bank at the plan's size, filled with `fill`.
-// -2: the plan refuses the launch.
-template <class Body>
-int run_obs_rows(ssk::ConvParams& p, bool spectral, int n_units, int flags, int wgs, int parts_log2, float fill, Body body,
+// The instantiation: ssdispatch::obs_rows for `form`.  -2: the plan refuses the launch.
+int run_obs_rows(ssk::ConvParams& p, Form form, int n_units, int flags, int wgs, int parts_log2, float fill,
+                 const ssk::MelArgs* mel = nullptr, const ssk::SpecScale<true, true>* hs = nullptr, const ssk::RowScale<true>* rs = nullptr,
                  int xcd_map = -1) {
+    const bool spectral = form != Form::kRows && form != Form::kRows16;
+    if (form == Form::kSpec16) p.n_buckets = 1;
     const sslaunch::ObsRowsPlan pl = sslaunch::plan_obs_rows(spectral, false, false, flags, p.n_valid, p.n_buckets, sslaunch::rows_nbh_max(p),
                                                              n_units, parts_log2 ? (2 * n_units) << parts_log2 : wgs, 1,
                                                              forced_parts(parts_log2));
@@ -192,7 +227,7 @@ int run_obs_rows(ssk::ConvParams& p, bool spectral, int n_units, int flags, int 
     p.xcd_map = xcd_map >= 0 ? xcd_map : pl.grid >= 8;
     std::vector<float> stash(pl.stash_bytes / sizeof(float), fill);
     if (!spectral) p.stash = reinterpret_cast<ssk::f32x4*>(stash.data());
-    return run_grid(pl.grid, 1, ssk::kT, body);
+    return ssdispatch::obs_rows(HostLaunch{}, form, (flags & SS_FLAG_CROSSFADE) != 0, pl.grid, p, 2 * n_units, mel, hs, rs);
 }
 }  // namespace
 
@@ -267,14 +302,9 @@ int hs_conv(int fuse, int simple, const float* spec, const float* rir, const int
     if (pl.rc) return -1;
     g_parts_log2 = 0;
     sslaunch::apply(pl, p);
-    if (persist > 0)            // (forced where the plan would not take it - no more rows than workgroups: one workgroup per row)
-        return run_grid(pl.variant == V::kPersistRows ? pl.grid_x : 2 * n_units, 1, ssk::kT, [&] { ssk::k_conv_rows(p, 2 * n_units); });
-    return run_grid(pl.grid_x, pl.grid_y, ssk::kT, [&] {
-        if (wide) { if (xfade) ssk::k_conv<true, false, true, false, true>(p); else ssk::k_conv<true, false, false, false, true>(p); }
-        else if (xfade) { if (fuse) ssk::k_conv<true, false, true>(p); else ssk::k_conv<false, false, true>(p); }
-        else if (fuse) { if (simple) ssk::k_conv<true, true>(p); else ssk::k_conv<true, false>(p); }
-        else { if (simple) ssk::k_conv<false, true>(p); else ssk::k_conv<false, false>(p); }
-    });
+    if (persist > 0 && pl.variant != V::kPersistRows)   // not the plan's choice (no more rows than workgroups): the test's, one workgroup per row
+        return run_grid(2 * n_units, 1, ssk::kT, [&] { ssk::k_conv_rows(p, 2 * n_units); });
+    return dispatch_conv(fuse, Form::kRows, pl, p, n_units);
 }
 
 // ---- 512-thread core (ss_kernels32.hpp): window spectra in ITS order + the loop-free row kernel
@@ -338,13 +368,10 @@ int hs_conv_spec(int fuse, int simple, const float* spec, const float* hspec, co
                                                       forced_parts(fuse ? g_parts_log2 : 0));
     if (pl.rc) return -1;
     sslaunch::apply(pl, p);
-    if (persist > 0)            // (forced where the plan would not take it - no more units than workgroups: one workgroup per unit)
-        return run_grid(pl.variant == V::kPersistRows ? pl.grid_x : n_units, 1, ssk::kT, [&] { ssk::k_conv_spec_rows(p, 2 * n_units); });
-    g_parts_log2 = 0;
-    return run_grid(pl.grid_x, pl.grid_y, ssk::kT, [&] {
-        if (fuse) { if (simple) ssk::k_conv_spec<true, true>(p); else ssk::k_conv_spec<true, false>(p); }
-        else { if (simple) ssk::k_conv_spec<false, true>(p); else ssk::k_conv_spec<false, false>(p); }
-    });
+    if (persist > 0 && pl.variant != V::kPersistRows)   // not the plan's choice (no more units than workgroups): the test's, one workgroup per unit
+        return run_grid(n_units, 1, ssk::kT, [&] { ssk::k_conv_spec_rows(p, 2 * n_units); });
+    if (persist <= 0) g_parts_log2 = 0;
+    return dispatch_conv(fuse, Form::kSpec, pl, p, n_units);
 }
 
 // k_obs_rows: `wgs` persistent workgroups walk the (unit, ear) rows; hspec != nullptr selects the spectral-bank variant
@@ -361,26 +388,20 @@ int hs_obs_rows(const float* spec, const float* rir, const float* hspec, const i
     const int parts_log2 = g_parts_log2;                // split rows: one workgroup per (row, part), whatever `wgs` says
     g_parts_log2 = 0;
     const int n_rows = 2 * n_units;
+    const Form form = hspec ? Form::kSpec : Form::kRows;
     (void)use_stash;                                    // (the time-domain path always has its stash)
     if (g_obs_blocks) {
         const bool reversed = g_obs_blocks == 2;        // consumers BEFORE producers: every hand-off wait runs out (poisoned frames)
         g_obs_blocks = 0;
         std::vector<int> fl;
-        const int rc = run_obs_blocks(p, n_units, flags, parts_log2, [&](float* tails, int* flag) {
-            if (hspec) ssk::k_obs_blocks<true>(p, n_rows, tails, flag, 7);
-            else ssk::k_obs_blocks<false>(p, n_rows, tails, flag, 7);
-        }, reversed, &fl);
+        const int rc = run_obs_blocks(p, form, n_units, flags, parts_log2, nullptr, nullptr, nullptr, 7, reversed, &fl);
         if (rc) return rc;
         for (int r = 0; r < n_rows; ++r)                // every hand-off of a non-silent row was released exactly once
             for (int j = 0; j + 1 < p.nb_y; ++j)
                 if (fl[static_cast<size_t>(r) * (p.nb_y - 1) + j] != 7 && fl[static_cast<size_t>(r) * (p.nb_y - 1) + j] != 0) return -4;
         return 0;
     }
-    return run_obs_rows(p, hspec != nullptr, n_units, flags, wgs, parts_log2, 12345.0f, [&] {
-        if (hspec) ssk::k_obs_rows<true>(p, n_rows);
-        else if (crossfade) ssk::k_obs_rows<false, true>(p, n_rows);
-        else ssk::k_obs_rows<false>(p, n_rows);
-    }, wgs >= 8);
+    return run_obs_rows(p, form, n_units, flags, wgs, parts_log2, 12345.0f, nullptr, nullptr, nullptr, wgs >= 8);
 }
 
 // the stand-alone feature kernels: gpw = the groups one workgroup should walk (sslaunch::plan_frames clamps it)

@@ -16,6 +16,10 @@
 //          plan: <n_frames>/<t4>/<live>/<groups>/<gpw>/<chunks>/<grid>
 //     features <len>                                         | per units, max workgroups (512, 16, 1): the grid
 //     params <out_len> <n_valid>                             | the shape fields and defaults init_conv_params sets
+// and, with the argument `mel`, the one-block log-mel plan alone (plan_conv_mel; tests/golden/launch_mel_table.txt):
+//     mel <form> <ss2 shape 0 1 2> <RIR blocks 1, 1 + a sample / 2> | per buckets (1, 2), flags (0, NO_DISTRACTOR, NO_DISTRACTOR +
+//          FIRST_BUCKET, CROSSFADE), fade_len (0, 1, 2 kPrevPairs - 2, one beyond), units (1, 5, 257)
+//          plan: <variant SLXWY>/<bucket 0>/<grid>, E: refused; grid y, parts and nb_y are fixed (1, 0, 1: anything else prints ?)
 //
 // units: 1 2 5 16 32 33 64 128 129 256 257.  The values of every input are the smallest at which a rule flips; each launcher is
 // walked over the inputs it reads.  tests/test_launch_host.py builds this with -fsanitize=address,undefined, runs it and compares
@@ -82,7 +86,34 @@ void rows(bool spectral, const int (&shape)[2], int flags, int depth, int n_buck
 
 }  // namespace
 
-int main() {
+// ---- plan_conv_mel: `launch_host mel` prints this table alone (tests/golden/launch_mel_table.txt)
+int mel_table() {
+    const int kMelFlags[4] = {0, SS_FLAG_NO_DISTRACTOR, SS_FLAG_NO_DISTRACTOR | SS_FLAG_FIRST_BUCKET, SS_FLAG_CROSSFADE};
+    const int kFades[4] = {0, 1, 2 * ssk::kPrevPairs - 2, 2 * ssk::kPrevPairs - 1};
+    char buf[64];
+    for (int f = 0; f < 5; ++f)
+        for (int ss2 = 0; ss2 < 3; ++ss2)
+            for (int depth = 1; depth <= 2; ++depth) {
+                const bool time = kForms[f] == Form::kRows || kForms[f] == Form::kRows16;
+                std::printf("mel %s %d %d |", kFormNames[f], ss2, depth);
+                for (int n_buckets = 1; n_buckets <= 2; ++n_buckets)
+                    for (int flags : kMelFlags)
+                        for (int fade : kFades)
+                            for (int n_units : {1, 5, 257}) {
+                                const ConvPlan pl = plan_conv_mel(kForms[f], ss2, flags, time ? (depth == 1 ? kB : kB + 1) : 0, time ? 0 : depth,
+                                                                  n_buckets, fade, n_units);
+                                if (pl.rc) std::snprintf(buf, sizeof buf, "E");
+                                else if (pl.grid_y != 1 || pl.parts_log2 != 0 || pl.nb_y != 1 || pl.tab_ok) std::snprintf(buf, sizeof buf, "?");
+                                else std::snprintf(buf, sizeof buf, "%c/%d/%d", "SLXWYP"[static_cast<int>(pl.variant)], pl.bucket0, pl.grid_x);
+                                add(buf);
+                            }
+                end_line();
+            }
+    return 0;
+}
+
+int main(int argc, char** argv) {
+    if (argc > 1 && std::string(argv[1]) == "mel") return mel_table();
     char buf[128];
     // ---- plan_conv
     for (int f = 0; f < 5; ++f)

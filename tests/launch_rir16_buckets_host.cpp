@@ -13,7 +13,7 @@
 #include <cstring>
 
 int main(int argc, char** argv) {
-    if (argc == 2 && !std::strcmp(argv[1], "table")) return launch_host_main();
+    if (argc == 2 && !std::strcmp(argv[1], "table")) return launch_host_main(1, argv);
     if (argc != 2 || std::strcmp(argv[1], "rows16bk")) return 2;
     const int shapes[3] = {1, 4, 5};                    // 16000 / 16000, 44100 / 44100, 44100 / 11025
     for (int fuse = 0; fuse < 2; ++fuse)

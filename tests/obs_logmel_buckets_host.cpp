@@ -30,27 +30,12 @@ extern "C" int hs_obs_logmel_buckets(int kernel, int form, const float* spec, co
     set_buckets(p, rows ? reinterpret_cast<const float* const*>(bank) : nullptr, rows ? nullptr : bank, first, cap, n_buckets);
     const ssk::SpecScale<true, true> hs = bucket_scales(form == 2 ? hscale : nullptr, n_buckets);
     const ssk::MelArgs m{logmel, mel_start, mel_w, n_mels, max_len, mel_eps};
-    const int n_rows = 2 * n_units, flags = no_distractor ? SS_FLAG_NO_DISTRACTOR : 0;
+    const int flags = no_distractor ? SS_FLAG_NO_DISTRACTOR : 0;
     if (kernel == 0) {
         p.n_terms = no_distractor ? 1 : 2;
-        return run_grid(n_rows, 1, ssk::kT, [&] {
-            if (form == 2) ssk::k_conv_spec<true, false, false, true, true, true>(p, m, hs);
-            else if (form == 1) ssk::k_conv_spec<true, false, false, true>(p, m);
-            else ssk::k_conv<true, false, false, false, false, true>(p, m);
-        });
+        return run_conv_mel(form == 2 ? Form::kSpec16Buckets : form == 1 ? Form::kSpec : Form::kRows, p, m, 0, n_units, flags, &hs);
     }
-    if (kernel == 2)
-        return run_obs_blocks(p, n_units, flags, parts_log2, [&](float* tails, int* fl) {
-            if (form == 1) ssk::k_obs_blocks<true, true>(p, n_rows, tails, fl, 7, m);
-            else ssk::k_obs_blocks<false, true>(p, n_rows, tails, fl, 7, m);
-        });
-    return run_obs_rows(p, !rows, n_units, flags, wgs, parts_log2, 12345.0f, [&] {  // (the stash: the deepest bucket's blocks per term)
-        if (n_buckets == 1) {
-            if (form == 1) ssk::k_obs_rows<true, false, false, true>(p, n_rows, m);
-            else ssk::k_obs_rows<false, false, false, true>(p, n_rows, m);
-        } else {
-            if (form == 1) ssk::k_obs_rows<true, false, true, true>(p, n_rows, m);
-            else ssk::k_obs_rows<false, false, true, true>(p, n_rows, m);
-        }
-    });
+    const Form f = rows ? Form::kRows : Form::kSpec;
+    if (kernel == 2) return run_obs_blocks(p, f, n_units, flags, parts_log2, &m);
+    return run_obs_rows(p, f, n_units, flags, wgs, parts_log2, 12345.0f, &m);       // (the stash: the deepest bucket's blocks per term)
 }

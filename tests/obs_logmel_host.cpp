@@ -17,13 +17,6 @@ extern "C" int hs_obs_logmel(int spectral, int simple, const float* spec, const 
     p.fade_len = 0;
     apply_bucket2(p);
     const ssk::MelArgs m{logmel, mel_start, mel_w, n_mels, max_len, mel_eps};
-    return run_grid(2 * n_units, 1, ssk::kT, [&] {
-        if (spectral) {
-            if (simple) ssk::k_conv_spec<true, true, false, true>(p, m);
-            else ssk::k_conv_spec<true, false, false, true>(p, m);
-        } else {
-            if (simple) ssk::k_conv<true, true, false, false, false, true>(p, m);
-            else ssk::k_conv<true, false, false, false, false, true>(p, m);
-        }
-    });
+    // the caller chooses the kernel; the flags under which the library's plan chooses the same one
+    return run_conv_mel(spectral ? Form::kSpec : Form::kRows, p, m, 0, n_units, simple ? SS_FLAG_NO_DISTRACTOR | SS_FLAG_FIRST_BUCKET : 0);
 }

@@ -2,8 +2,8 @@
 // TIME-DOMAIN ROWS (ss_kernels.hpp: k_conv<.., MEL, HALF>, k_conv<.., MEL, HALF, RBK>, k_obs_rows<.., MEL, .., ROWS16>,
 // k_obs_blocks<.., MEL, .., ROWS16>) compiled for the host on the fibers of tests/hostsim/hostsim.cpp (included whole: its runner
 // and tables are file-local), so tests/test_obs_logmel_rir16_host.py can compare each with its fp32 log-mel sibling fed the
-// dequantised rows and with the float64 model.  The kernel choice is the library's (launch_conv16_mel / launch_conv_mel of
-// ss_hip.hip, restated here), the row kernels' shape is its plan (run_obs_rows / run_obs_blocks).  Never part of the product.
+// dequantised rows and with the float64 model.  The kernel choice is the library's (sslaunch::plan_conv_mel and ssdispatch of
+// sound-spaces_amd/csrc, through run_conv_mel / run_obs_rows / run_obs_blocks of hostsim.cpp).  Never part of the product.
 #include "hostsim/hostsim.cpp"
 
 #include <limits>
@@ -37,38 +37,22 @@ extern "C" int hs_obs_logmel_rir16(int half, int kernel, const float* spec, cons
     set_buckets(p, rows, nullptr, first, cap, n_buckets);
     ssk::RowScale<true, true> rs{static_cast<const ssk::h16x2*>(bank[0]), half ? rscale[0] : nullptr, {nullptr, nullptr, nullptr}};
     for (int b = 1; half && b < n_buckets; ++b) rs.bk[b - 1] = rscale[b];
-    const ssk::RowScale<true> rs1{rs.rir16, rs.rscale};
+    const ssk::RowScale<true> rs1 = ssdispatch::first_bucket(rs);
     const ssk::MelArgs m{logmel, mel_start, mel_w, n_mels, max_len, mel_eps};
-    const ssk::SpecScale<false> ns;
-    const int n_rows = 2 * n_units;
+    const Form form = half ? Form::kRows16 : Form::kRows;
     int dummy = 0;
     if (!taken) taken = &dummy;
     if (kernel == 0) {
-        const bool bucket0 = n_buckets == 1 || (flags & SS_FLAG_FIRST_BUCKET);
-        const bool simple = (flags & SS_FLAG_NO_DISTRACTOR) && cap[0] <= ssk::kB && bucket0;
-        if (bucket0) p.n_buckets = 1;                   // (the fp32 entries' own rule for such launches)
-        *taken = !bucket0 ? 2 : simple ? 0 : 1;
-        return run_grid(n_rows, 1, ssk::kT, [&] {       // (the log-mel launchers' fixed grid: parts_log2 = 0)
-            if (half) {
-                if (!bucket0) ssk::k_conv<true, false, false, false, false, true, true, true>(p, m, rs);
-                else if (simple) ssk::k_conv<true, true, false, false, false, true, true>(p, m, rs1);
-                else ssk::k_conv<true, false, false, false, false, true, true>(p, m, rs1);
-            } else {
-                if (simple) ssk::k_conv<true, true, false, false, false, true>(p, m);
-                else ssk::k_conv<true, false, false, false, false, true>(p, m);
-            }
-        });
+        if (!half && (flags & SS_FLAG_FIRST_BUCKET)) p.n_buckets = 1;      // (the fp32 entries' own rule for such launches)
+        sslaunch::ConvPlan pl;
+        const int rc = run_conv_mel(form, p, m, 0, n_units, flags, nullptr, &rs, &pl);
+        *taken = !pl.bucket0 ? 2 : pl.variant == sslaunch::Variant::kSimple ? 0 : 1;
+        return rc;
     }
     if (kernel == 2) {
         *taken = 4;
-        return run_obs_blocks(p, n_units, flags, parts_log2, [&](float* tails, int* fl) {
-            if (half) ssk::k_obs_blocks<false, true, false, false, true>(p, n_rows, tails, fl, 7, m, ns, rs1);
-            else ssk::k_obs_blocks<false, true>(p, n_rows, tails, fl, 7, m);
-        });
+        return run_obs_blocks(p, form, n_units, flags, parts_log2, &m, nullptr, &rs1);
     }
     *taken = 3;
-    return run_obs_rows(p, false, n_units, flags, wgs, parts_log2, std::numeric_limits<float>::quiet_NaN(), [&] {
-        if (half) ssk::k_obs_rows<false, false, false, true, false, true>(p, n_rows, m, ns, rs1);
-        else ssk::k_obs_rows<false, false, false, true>(p, n_rows, m);
-    });
+    return run_obs_rows(p, form, n_units, flags, wgs, parts_log2, std::numeric_limits<float>::quiet_NaN(), &m, nullptr, &rs1);
 }

@@ -17,11 +17,7 @@ extern "C" int hs_obs_logmel_ss2(int xfade, const float* spec, const float* bank
     const bool wide = out_len > ssk::kB;
     if (wide && !ssroute::wide_one_block_ok(out_len, n_valid, 0, false, ssroute::Switches())) return -2;      // (the shape alone)
     if (!wide && !xfade) return -3;
-    if (xfade && (p.fade_len < 1 || p.fade_len > 2 * ssk::kPrevPairs - 2)) return -4;
     const ssk::MelArgs m{logmel, mel_start, mel_w, n_mels, max_len, mel_eps};
-    return run_grid(2 * n_units, 1, ssk::kT, [&] {
-        if (!wide) ssk::k_conv<true, false, true, false, false, true>(p, m);
-        else if (xfade) ssk::k_conv<true, false, true, false, true, true>(p, m);
-        else ssk::k_conv<true, false, false, false, true, true>(p, m);
-    });
+    // (-4: a cross-fade ramp the kernels cannot keep - the plan's refusal)
+    return run_conv_mel(Form::kRows, p, m, wide ? 2 : 1, n_units, xfade ? SS_FLAG_CROSSFADE : 0);
 }

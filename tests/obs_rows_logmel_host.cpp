@@ -21,14 +21,8 @@ extern "C" int hs_obs_rows_logmel(int blocks, int spectral, const float* spec, c
     p.fade_len = 0;
     apply_bucket2(p);
     const ssk::MelArgs m{logmel, mel_start, mel_w, n_mels, max_len, mel_eps};
-    const int n_rows = 2 * n_units, flags = no_distractor ? SS_FLAG_NO_DISTRACTOR : 0;
-    if (blocks)
-        return run_obs_blocks(p, n_units, flags, parts_log2, [&](float* tails, int* fl) {
-            if (spectral) ssk::k_obs_blocks<true, true>(p, n_rows, tails, fl, 7, m);
-            else ssk::k_obs_blocks<false, true>(p, n_rows, tails, fl, 7, m);
-        });
-    return run_obs_rows(p, spectral != 0, n_units, flags, wgs, parts_log2, 12345.0f, [&] {
-        if (spectral) ssk::k_obs_rows<true, false, false, true>(p, n_rows, m);
-        else ssk::k_obs_rows<false, false, false, true>(p, n_rows, m);
-    });
+    const int flags = no_distractor ? SS_FLAG_NO_DISTRACTOR : 0;
+    const Form form = spectral ? Form::kSpec : Form::kRows;
+    if (blocks) return run_obs_blocks(p, form, n_units, flags, parts_log2, &m);
+    return run_obs_rows(p, form, n_units, flags, wgs, parts_log2, 12345.0f, &m);
 }

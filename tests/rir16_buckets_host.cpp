@@ -35,31 +35,9 @@ extern "C" int hs_conv_rir16_buckets(int half, int fuse, int bucket0, const floa
     if (pl.rc) return -5;
     if (pl.bucket0 != (bucket0 != 0 || n_buckets == 1)) return -6;
     sslaunch::apply(pl, p);
-    const bool simple = pl.variant == sslaunch::Variant::kSimple;
-    if (!simple && pl.variant != sslaunch::Variant::kLoop) return -7;
-    const bool tab = bucket0 == 2 && pl.tab_ok;
-    if (bucket0 == 2 && !tab) return -8;
-    const ssk::RowScale<true> rs1{rs.rir16, rs.rscale};
+    if (pl.variant != sslaunch::Variant::kSimple && pl.variant != sslaunch::Variant::kLoop) return -7;
     ssk::UnitTab<true> ut;
-    if (tab) fill_tab_reversed(ut, desc, n_units);
-    const ssk::UnitTab<false> nt;
-    return run_grid(pl.grid_x, pl.grid_y, ssk::kT, [&] {
-        if (!half) {                                    // the fp32 length-bucketed launch (the loop kernel resolves bank_row per term)
-            if (simple) { if (fuse) ssk::k_conv<true, true>(p); else ssk::k_conv<false, true>(p); }
-            else if (fuse) ssk::k_conv<true, false>(p);
-            else ssk::k_conv<false, false>(p);
-        } else if (!pl.bucket0) {                       // the new instantiation
-            if (fuse) ssk::k_conv<true, false, false, false, false, false, true, true>(p, nt, rs);
-            else ssk::k_conv<false, false, false, false, false, false, true, true>(p, nt, rs);
-        } else if (tab) {                               // bucket-0 launches: the single-allocation half kernels on bucket 0's arrays
-            if (fuse) ssk::k_conv<true, true, false, true, false, false, true>(p, ut, rs1);
-            else ssk::k_conv<false, true, false, true, false, false, true>(p, ut, rs1);
-        } else if (simple) {
-            if (fuse) ssk::k_conv<true, true, false, false, false, false, true>(p, nt, rs1);
-            else ssk::k_conv<false, true, false, false, false, false, true>(p, nt, rs1);
-        } else {
-            if (fuse) ssk::k_conv<true, false, false, false, false, false, true>(p, nt, rs1);
-            else ssk::k_conv<false, false, false, false, false, false, true>(p, nt, rs1);
-        }
-    });
+    if (bucket0 == 2) fill_tab_reversed(ut, desc, n_units);
+    // (-8: the unit table where the plan allows none)
+    return dispatch_conv(fuse, half ? Form::kRows16 : Form::kRows, pl, p, n_units, bucket0 == 2 ? &ut : nullptr, nullptr, &rs);
 }

@@ -45,19 +45,8 @@ extern "C" int hs_conv_rir16_ab(int half, int fuse, int simple, int use_tab, con
                                                       false, false, n_units, nb_y, kBigChip, 1, forced_parts(parts_log2));
     if (pl.rc) return -5;
     sslaunch::apply(pl, p);
-    const ssk::RowScale<true> rs{static_cast<const ssk::h16x2*>(bank), rscale};
+    const ssk::RowScale<true, true> rs{static_cast<const ssk::h16x2*>(bank), rscale, {nullptr, nullptr, nullptr}};
     ssk::UnitTab<true> ut;
     if (use_tab) fill_tab_reversed(ut, desc, n_units);
-    const ssk::UnitTab<false> nt;
-    return run_grid(pl.grid_x, pl.grid_y, ssk::kT, [&] {
-        if (half) {
-            if (use_tab) { if (fuse) ssk::k_conv<true, true, false, true, false, false, true>(p, ut, rs); else ssk::k_conv<false, true, false, true, false, false, true>(p, ut, rs); }
-            else if (fuse) { if (simple) ssk::k_conv<true, true, false, false, false, false, true>(p, nt, rs); else ssk::k_conv<true, false, false, false, false, false, true>(p, nt, rs); }
-            else { if (simple) ssk::k_conv<false, true, false, false, false, false, true>(p, nt, rs); else ssk::k_conv<false, false, false, false, false, false, true>(p, nt, rs); }
-        } else {
-            if (use_tab) { if (fuse) ssk::k_conv<true, true, false, true>(p, ut); else ssk::k_conv<false, true, false, true>(p, ut); }
-            else if (fuse) { if (simple) ssk::k_conv<true, true>(p); else ssk::k_conv<true, false>(p); }
-            else { if (simple) ssk::k_conv<false, true>(p); else ssk::k_conv<false, false>(p); }
-        }
-    });
+    return dispatch_conv(fuse, half ? Form::kRows16 : Form::kRows, pl, p, n_units, use_tab ? &ut : nullptr, nullptr, &rs);
 }

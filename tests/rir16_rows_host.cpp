@@ -26,17 +26,9 @@ extern "C" int hs_obs_rows_rir16_ab(int half, int blocks, const float* spec, con
     else set_rows(p, static_cast<const float*>(bank), 2LL * cap, cap, 1, cap);
     p.fade_len = 0;
     apply_bucket2(p);
-    const ssk::UnitTab<false> nt;
-    const ssk::SpecScale<false> ns;
     const ssk::RowScale<true> rs{static_cast<const ssk::h16x2*>(bank), rscale};
-    const int n_rows = 2 * n_units, flags = no_distractor ? SS_FLAG_NO_DISTRACTOR : 0;
-    if (blocks)
-        return run_obs_blocks(p, n_units, flags, parts_log2, [&](float* tails, int* fl) {
-            if (half) ssk::k_obs_blocks<false, false, false, false, true>(p, n_rows, tails, fl, 7, nt, ns, rs);
-            else ssk::k_obs_blocks<false>(p, n_rows, tails, fl, 7);
-        });
-    return run_obs_rows(p, false, n_units, flags, wgs, parts_log2, std::numeric_limits<float>::quiet_NaN(), [&] {
-        if (half) ssk::k_obs_rows<false, false, false, false, false, true>(p, n_rows, nt, ns, rs);
-        else ssk::k_obs_rows<false, false, false>(p, n_rows);
-    });
+    const Form form = half ? Form::kRows16 : Form::kRows;
+    const int flags = no_distractor ? SS_FLAG_NO_DISTRACTOR : 0;
+    if (blocks) return run_obs_blocks(p, form, n_units, flags, parts_log2, nullptr, nullptr, &rs);
+    return run_obs_rows(p, form, n_units, flags, wgs, parts_log2, std::numeric_limits<float>::quiet_NaN(), nullptr, nullptr, &rs);
 }

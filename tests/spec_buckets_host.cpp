@@ -27,14 +27,5 @@ extern "C" int hs_conv_spec_buckets(int half, int fuse, const float* spec, const
                                                       p.h_blocks, n_buckets, p.fade_len, false, false, n_units, nb_y, kBigChip, 1, forced_parts(0));
     if (pl.rc) return -1;
     sslaunch::apply(pl, p);
-    const ssk::UnitTab<false> nt;
-    return run_grid(pl.grid_x, pl.grid_y, ssk::kT, [&] {
-        if (half) {
-            if (fuse) ssk::k_conv_spec<true, false, false, false, true, true>(p, nt, hs);
-            else ssk::k_conv_spec<false, false, false, false, true, true>(p, nt, hs);
-        } else {
-            if (fuse) ssk::k_conv_spec<true, false>(p);
-            else ssk::k_conv_spec<false, false>(p);
-        }
-    });
+    return dispatch_conv(fuse, half ? Form::kSpec16Buckets : Form::kSpec, pl, p, n_units, nullptr, &hs);
 }

@@ -30,33 +30,11 @@ extern "C" int hs_obs_rows_half_buckets(int form, int blocks, int mel, const flo
     p.fade_len = 0;
     set_buckets(p, nullptr, bank, first, cap, n_buckets);
     const ssk::SpecScale<true, true> hs = bucket_scales(form ? hscale : nullptr, n_buckets);
-    const ssk::SpecScale<true> hs1{hs.hscale};
     const ssk::MelArgs m{logmel, mel_start, mel_w, n_mels, max_len, mel_eps};
-    const ssk::UnitTab<false> nt;
-    const int n_rows = 2 * n_units, flags = no_distractor ? SS_FLAG_NO_DISTRACTOR : 0;
-    if (blocks)
-        return run_obs_blocks(p, n_units, flags, parts_log2, [&](float* tails, int* fl) {
-            if (form == 1) {
-                if (mel) ssk::k_obs_blocks<true, true, true, true>(p, n_rows, tails, fl, 7, m, hs);
-                else ssk::k_obs_blocks<true, false, true, true>(p, n_rows, tails, fl, 7, nt, hs);
-            } else if (form == 2) {
-                if (mel) ssk::k_obs_blocks<true, true, true>(p, n_rows, tails, fl, 7, m, hs1);
-                else ssk::k_obs_blocks<true, false, true>(p, n_rows, tails, fl, 7, nt, hs1);
-            } else {
-                if (mel) ssk::k_obs_blocks<true, true>(p, n_rows, tails, fl, 7, m);
-                else ssk::k_obs_blocks<true>(p, n_rows, tails, fl, 7);
-            }
-        });
-    return run_obs_rows(p, true, n_units, flags, wgs, parts_log2, 12345.0f, [&] {
-        if (form == 1) {
-            if (mel) ssk::k_obs_rows<true, false, true, true, true>(p, n_rows, m, hs);
-            else ssk::k_obs_rows<true, false, true, false, true>(p, n_rows, nt, hs);
-        } else if (form == 2) {
-            if (mel) ssk::k_obs_rows<true, false, false, true, true>(p, n_rows, m, hs1);
-            else ssk::k_obs_rows<true, false, false, false, true>(p, n_rows, nt, hs1);
-        } else {
-            if (mel) ssk::k_obs_rows<true, false, true, true>(p, n_rows, m);
-            else ssk::k_obs_rows<true, false, true>(p, n_rows);
-        }
-    });
+    const int flags = no_distractor ? SS_FLAG_NO_DISTRACTOR : 0;
+    // form 1 over ONE bucket is not the library's choice (rows_form: a single allocation, form 2): the bucketed half instantiations
+    // all the same - the test compares the two on the same bank
+    const Form f = form == 0 ? Form::kSpec : form == 1 ? Form::kSpec16Buckets : sslaunch::rows_form(true, true, false, n_buckets, flags);
+    if (blocks) return run_obs_blocks(p, f, n_units, flags, parts_log2, mel ? &m : nullptr, &hs);
+    return run_obs_rows(p, f, n_units, flags, wgs, parts_log2, 12345.0f, mel ? &m : nullptr, &hs);
 }

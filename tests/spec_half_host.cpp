@@ -50,21 +50,10 @@ extern "C" int hs_conv_spec_ab(int half, int fuse, int simple, int mel, int use_
     if (pl.rc) return -1;
     sslaunch::apply(pl, p);
     const ssk::MelArgs m{logmel, mel_start, mel_w, n_mels, max_len, mel_eps};
-    const ssk::SpecScale<true> hs{hscale};
+    const ssk::SpecScale<true, true> hs{hscale, {nullptr, nullptr, nullptr}};
+    const Form form = half ? Form::kSpec16 : Form::kSpec;
+    if (mel) return run_conv_mel(form, p, m, 0, n_units, simple ? SS_FLAG_NO_DISTRACTOR | SS_FLAG_FIRST_BUCKET : 0, &hs);
     ssk::UnitTab<true> ut;
     if (use_tab) fill_tab_reversed(ut, desc, n_units);
-    const ssk::UnitTab<false> nt;
-    return run_grid(pl.grid_x, pl.grid_y, ssk::kT, [&] {
-        if (half) {
-            if (mel) { if (simple) ssk::k_conv_spec<true, true, false, true, true>(p, m, hs); else ssk::k_conv_spec<true, false, false, true, true>(p, m, hs); }
-            else if (use_tab) { if (fuse) ssk::k_conv_spec<true, true, true, false, true>(p, ut, hs); else ssk::k_conv_spec<false, true, true, false, true>(p, ut, hs); }
-            else if (fuse) { if (simple) ssk::k_conv_spec<true, true, false, false, true>(p, nt, hs); else ssk::k_conv_spec<true, false, false, false, true>(p, nt, hs); }
-            else { if (simple) ssk::k_conv_spec<false, true, false, false, true>(p, nt, hs); else ssk::k_conv_spec<false, false, false, false, true>(p, nt, hs); }
-        } else {
-            if (mel) { if (simple) ssk::k_conv_spec<true, true, false, true>(p, m); else ssk::k_conv_spec<true, false, false, true>(p, m); }
-            else if (use_tab) { if (fuse) ssk::k_conv_spec<true, true, true>(p, ut); else ssk::k_conv_spec<false, true, true>(p, ut); }
-            else if (fuse) { if (simple) ssk::k_conv_spec<true, true>(p); else ssk::k_conv_spec<true, false>(p); }
-            else { if (simple) ssk::k_conv_spec<false, true>(p); else ssk::k_conv_spec<false, false>(p); }
-        }
-    });
+    return dispatch_conv(fuse, form, pl, p, n_units, use_tab ? &ut : nullptr, &hs);
 }

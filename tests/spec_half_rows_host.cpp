@@ -23,26 +23,9 @@ extern "C" int hs_obs_rows_spec_ab(int half, int blocks, int mel, const float* s
     p.fade_len = 0;
     apply_bucket2(p);
     const ssk::MelArgs m{logmel, mel_start, mel_w, n_mels, max_len, mel_eps};
-    const ssk::UnitTab<false> nt;
-    const ssk::SpecScale<true> hs{hscale};
-    const int n_rows = 2 * n_units, flags = no_distractor ? SS_FLAG_NO_DISTRACTOR : 0;
-    if (blocks)
-        return run_obs_blocks(p, n_units, flags, parts_log2, [&](float* tails, int* fl) {
-            if (half) {
-                if (mel) ssk::k_obs_blocks<true, true, true>(p, n_rows, tails, fl, 7, m, hs);
-                else ssk::k_obs_blocks<true, false, true>(p, n_rows, tails, fl, 7, nt, hs);
-            } else {
-                if (mel) ssk::k_obs_blocks<true, true>(p, n_rows, tails, fl, 7, m);
-                else ssk::k_obs_blocks<true>(p, n_rows, tails, fl, 7);
-            }
-        });
-    return run_obs_rows(p, true, n_units, flags, wgs, parts_log2, 12345.0f, [&] {
-        if (half) {
-            if (mel) ssk::k_obs_rows<true, false, false, true, true>(p, n_rows, m, hs);
-            else ssk::k_obs_rows<true, false, false, false, true>(p, n_rows, nt, hs);
-        } else {
-            if (mel) ssk::k_obs_rows<true, false, false, true>(p, n_rows, m);
-            else ssk::k_obs_rows<true, false, false>(p, n_rows);
-        }
-    });
+    const ssk::SpecScale<true, true> hs{hscale, {nullptr, nullptr, nullptr}};
+    const Form form = half ? Form::kSpec16 : Form::kSpec;
+    const int flags = no_distractor ? SS_FLAG_NO_DISTRACTOR : 0;
+    if (blocks) return run_obs_blocks(p, form, n_units, flags, parts_log2, mel ? &m : nullptr, &hs);
+    return run_obs_rows(p, form, n_units, flags, wgs, parts_log2, 12345.0f, mel ? &m : nullptr, &hs);
 }

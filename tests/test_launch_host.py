@@ -14,19 +14,40 @@ KB, SPEC_COMPLEX, TAIL_FLOATS = 16384, 16384, 640
 
 
 @pytest.fixture(scope="module")
-def table(tmp_path_factory):
+def program(tmp_path_factory):
     cxx = shutil.which("g++") or shutil.which("clang++") or "/opt/rocm/lib/llvm/bin/clang++"
     out = str(tmp_path_factory.mktemp("launch") / "launch_host")
     subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined",
                            "-fno-sanitize-recover=undefined", os.path.join(HERE, "launch_host.cpp"), "-o", out])
-    r = subprocess.run([out], capture_output=True, text=True)
+    return out
+
+
+def _run(program, *args):
+    r = subprocess.run([program] + list(args), capture_output=True, text=True)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     return r.stdout.splitlines()
 
 
-def _golden():
-    with open(os.path.join(HERE, "golden", "launch_table.txt")) as f:
+@pytest.fixture(scope="module")
+def table(program):
+    return _run(program)
+
+
+def _golden(name="launch_table.txt"):
+    with open(os.path.join(HERE, "golden", name)) as f:
         return [ln for ln in f.read().splitlines() if not ln.startswith("#")]
+
+
+def test_every_log_mel_plan_is_the_recorded_one(program):
+    """plan_conv_mel over every bank form, flags, one RIR block and beyond, one and two buckets, the SoundSpaces 2.0 shapes and the
+    cross-fade ramp at its limits: tests/golden/launch_mel_table.txt, recorded from the inline rules of the five log-mel launchers
+    (and the tail of render()) of ss_hip.hip before they became this plan."""
+    got, golden = _run(program, "mel"), _golden("launch_mel_table.txt")
+    assert got == golden, [(a, b) for a, b in zip(golden, got) if a != b][:3]
+    assert len(got) == 30 and not any("?" in ln for ln in got)
+    plans = [p for ln in got for p in _plans(ln)[1]]
+    assert {p[0] for p in plans} == set("SLXWYE")                  # every variant and the refusal occur
+    assert all(p == ["E"] or (p[1] in "01" and int(p[2]) in (2, 10, 514)) for p in plans)
 
 
 UNITS = [1, 2, 5, 16, 32, 33, 64, 128, 129, 256, 257]
